@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the cWGAN-GP training iteration on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR] [--full]
 
 A "step" is one training iteration of the reference's loop body (gan_train_cwgangp_pixelnorm.py:468-482) on synthetic
 24 x nd x nd tiles: n_critic critic updates + 1 generator update.  Configurations (SURVEY 8d numbering = BASELINE.json
@@ -18,6 +18,11 @@ is unset, this script starts N fresh child processes itself BEFORE it touches th
 minibatch dimension is sharded; gradient slabs are summed by RCCL (torch.distributed backend "nccl"), one all-reduce per
 optimizer update, on a communication stream beside the next generator forward.  Inputs are resident in HBM before the
 timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (samples/s, ms_per_step).  --full adds what takes
+extra work or extra iterations: HIP events around every timed step and around the dominant kernel (`iteration_ms`, `roofline`),
+the time per kernel class and the per-launch table of a few iterations after the timed ones, and the torch-CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (loss tails, updated weights) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -135,6 +140,26 @@ def cpu_baseline(nd=16, n_critic=1, batch=256, reps=3, small_batch=32):
                                                          "(example.py), median of 5 after 1 warm-up"}}
 
 
+DUMP_MAX_ELEMENTS = 4 << 20        # per array (16 MB of float32): a larger output is written as a fixed, seeded sample
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each named tensor / array as out_dir/<name>.npy in float32 (float64 stays float64).  An array of more than
+    DUMP_MAX_ELEMENTS elements is written as the flat elements at DUMP_MAX_ELEMENTS sorted positions drawn with a fixed seed
+    (the same positions for the same size, so two runs compare element for element)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        t = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, t.numel(), size=DUMP_MAX_ELEMENTS))
+            t = t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device))
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def launch_children(args, argv):
     """--gpus N without a launcher: N fresh processes, one per GPU, started before this process makes any GPU call (it
     never does); rank 0's JSON line is relayed, the others' output goes to stderr."""
@@ -196,7 +221,12 @@ def main():
     ap.add_argument("--ndomain", type=int, default=None)
     ap.add_argument("--scaling", choices=("weak", "strong"), default=None,
                     help="weak: --batch per GPU; strong: the configuration's global batch divided over the GPUs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-step and dominant-kernel HIP events (iteration_ms, "
+                         "roofline), time per kernel class and per launch over extra iterations, the torch-CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss tails and updated weights as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the torch-CPU baseline")
     ap.add_argument("--no-overlap", action="store_true", help="exchange + Adam on the compute stream (A/B)")
     ap.add_argument("--grad-transport", choices=("fp32", "bf16"), default="fp32",
                     help="sharded exchange: gradients on the wire as fp32 (default) or rounded to bf16 for the reduce-scatter (optional "
@@ -309,27 +339,39 @@ def main():
         if k == 0:
             check_replicas(dl_w, gl_w, "after the first iteration")
     sync()
-    eng.profile(1 << _lib.TAG_GCONV3_FWD)            # HIP events around the dominant kernel, on the launch stream
-    eng.flop_count(reset=True)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    sync()
+    ev = None
+    if args.full:
+        eng.profile(1 << _lib.TAG_GCONV3_FWD)        # HIP events around the dominant kernel, on the launch stream
+        eng.flop_count(reset=True)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        sync()
     t0 = time.perf_counter()
     for k in range(args.steps):
         crit, gen = data[k % nbuf]
-        ev[k][0].record()
+        if ev:
+            ev[k][0].record()
         dl, gl = trainer.iteration_raw(crit, gen)         # loss tails stay on the device; looked at once, below
-        ev[k][1].record()
+        if ev:
+            ev[k][1].record()
     sync()
     dt = time.perf_counter() - t0
-    flops_iter = eng.flop_count() / max(args.steps, 1)
-    kern_ms, kern_n = eng.profile_read(_lib.TAG_GCONV3_FWD)
-    eng.profile(0)
-    it_ms = np.array([a.elapsed_time(b) for a, b in ev]) if args.steps else np.zeros(1)
+    if args.full:
+        flops_iter = eng.flop_count() / max(args.steps, 1)
+        kern_ms, kern_n = eng.profile_read(_lib.TAG_GCONV3_FWD)
+        eng.profile(0)
+        it_ms = np.array([a.elapsed_time(b) for a, b in ev])
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     check_replicas(dl, gl, "after the timed iterations")
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the loss tails [total, valid, fake, gp, nonfinite] of
+        # the last critic update and of the generator update, and both models' weights after them (before --full's extra
+        # iterations change the weights again)
+        trainer.join()
+        dump_outputs(args.dump_outputs, {"critic_loss_tail": dl, "generator_loss_tail": gl,
+                                         "generator_weights": trainer.gparams, "critic_weights": trainer.dparams})
     # (a non-finite value anywhere poisons the weights for good, so the last iteration's flags and losses tell)
     dl, gl = dl.cpu().numpy(), gl.cpu().numpy()
     nonfinite = float(max(dl[4], gl[4]))
@@ -337,54 +379,54 @@ def main():
     if nonfinite != 0 or not (np.isfinite(d_loss) and np.isfinite(g_loss)):
         raise SystemExit(f"non-finite loss encountered (d_loss={d_loss}, g_loss={g_loss})")   # reference :487-488
 
-    # time per kernel class over a few extra iterations (HIP events around every launch of the class; outside the timed
-    # region because the extra events perturb it)
+    # --full: time per kernel class over a few extra iterations (HIP events around every launch of the class; outside the
+    # timed region because the extra events perturb it)
     classes = None
-    if rank == 0:
-        names = {_lib.TAG_GCONV_FWD: "gen_conv_fwd", _lib.TAG_GCONV_DGRAD: "gen_conv_dgrad", _lib.TAG_GCONV_WGRAD: "gen_conv_wgrad",
-                 _lib.TAG_CRITIC_GEMM: "critic_gemm", _lib.TAG_ELEMENTWISE: "elementwise"}
-    sync()
-    nprof = 3
-    eng.profile(sum(1 << t for t in (_lib.TAG_GCONV_FWD, _lib.TAG_GCONV_DGRAD, _lib.TAG_GCONV_WGRAD, _lib.TAG_CRITIC_GEMM,
-                                     _lib.TAG_ELEMENTWISE)))
-    for k in range(nprof):
-        crit, gen = data[k % nbuf]
-        trainer.iteration_raw(crit, gen)
-    sync()
-    if rank == 0:
-        classes = {}
-        for t, nm in names.items():
-            ms, n = eng.profile_read(t)
-            classes[nm] = {"ms_per_iteration": round(ms / nprof, 4), "launches_per_iteration": n // nprof}
-    eng.profile(0)
-
-    # per-launch table: HIP events around every GEMM launch of a few more iterations (outside the timed region)
     launches = None
-    sync()
-    eng.profile_launches(True)
-    for k in range(nprof):
-        crit, gen = data[k % nbuf]
-        trainer.iteration_raw(crit, gen)
-    sync()
-    if rank == 0:
-        rows = eng.launch_table()
-        pk = BF16_MFMA_PEAK_TFLOPS if bf16 else FP32_MFMA_PEAK_TFLOPS
-        launches = []
-        for r in sorted(rows, key=lambda r: -r["ms"]):
-            n = max(r["launches"], 1)
-            # the fp32-pipe GEMMs of the bf16 storage mode (Dense, the 64 -> 1 conv's weight gradient) are priced against the fp32 peak
-            on_bf16_pipe = bf16 and ("bf16" in r["kernel"] or "ws16" in r["kernel"]) and "g9_wgrad" not in r["kernel"]
-            peak_r = pk if on_bf16_pipe else FP32_MFMA_PEAK_TFLOPS
-            tf = r["gflop"] / max(r["ms"], 1e-9)
-            launches.append({"what": r["name"], "kind": r["kind"], "kernel": r["kernel"], "samples": r["batch"],
-                             "launches_per_iteration": round(r["launches"] / nprof, 2), "gflop_per_launch": round(r["gflop"] / n, 3),
-                             "ms_per_launch": round(r["ms"] / n, 4), "ms_per_iteration": round(r["ms"] / nprof, 4),
-                             "tflops": round(tf, 1), "peak": peak_r, "frac": round(tf / peak_r, 4)})
-    eng.profile_launches(False)
+    nprof = 3
+    if args.full:
+        if rank == 0:
+            names = {_lib.TAG_GCONV_FWD: "gen_conv_fwd", _lib.TAG_GCONV_DGRAD: "gen_conv_dgrad", _lib.TAG_GCONV_WGRAD: "gen_conv_wgrad",
+                     _lib.TAG_CRITIC_GEMM: "critic_gemm", _lib.TAG_ELEMENTWISE: "elementwise"}
+        sync()
+        eng.profile(sum(1 << t for t in (_lib.TAG_GCONV_FWD, _lib.TAG_GCONV_DGRAD, _lib.TAG_GCONV_WGRAD, _lib.TAG_CRITIC_GEMM,
+                                         _lib.TAG_ELEMENTWISE)))
+        for k in range(nprof):
+            crit, gen = data[k % nbuf]
+            trainer.iteration_raw(crit, gen)
+        sync()
+        if rank == 0:
+            classes = {}
+            for t, nm in names.items():
+                ms, n = eng.profile_read(t)
+                classes[nm] = {"ms_per_iteration": round(ms / nprof, 4), "launches_per_iteration": n // nprof}
+        eng.profile(0)
+
+        # per-launch table: HIP events around every GEMM launch of a few more iterations (outside the timed region)
+        sync()
+        eng.profile_launches(True)
+        for k in range(nprof):
+            crit, gen = data[k % nbuf]
+            trainer.iteration_raw(crit, gen)
+        sync()
+        if rank == 0:
+            rows = eng.launch_table()
+            pk = BF16_MFMA_PEAK_TFLOPS if bf16 else FP32_MFMA_PEAK_TFLOPS
+            launches = []
+            for r in sorted(rows, key=lambda r: -r["ms"]):
+                n = max(r["launches"], 1)
+                # the fp32-pipe GEMMs of the bf16 storage mode (Dense, the 64 -> 1 conv's weight gradient) are priced against the fp32 peak
+                on_bf16_pipe = bf16 and ("bf16" in r["kernel"] or "ws16" in r["kernel"]) and "g9_wgrad" not in r["kernel"]
+                peak_r = pk if on_bf16_pipe else FP32_MFMA_PEAK_TFLOPS
+                tf = r["gflop"] / max(r["ms"], 1e-9)
+                launches.append({"what": r["name"], "kind": r["kind"], "kernel": r["kernel"], "samples": r["batch"],
+                                 "launches_per_iteration": round(r["launches"] / nprof, 2), "gflop_per_launch": round(r["gflop"] / n, 3),
+                                 "ms_per_launch": round(r["ms"] / n, 4), "ms_per_iteration": round(r["ms"] / nprof, 4),
+                                 "tflops": round(tf, 1), "peak": peak_r, "frac": round(tf / peak_r, 4)})
+        eng.profile_launches(False)
 
     if rank == 0:
         value = world * B * args.steps / dt
-        avg_ms = kern_ms / max(kern_n, 1)
         # tap products per output position of the tagged launch (generator block 3 forward): direct 27, collapsed 8, or the
         # difference part of the shared-centre form 4 (fp32 default); the bf16 storage mode defaults to the collapsed form
         fast_fwd = opts.get("fast_fwd", "0" if bf16 else "1")
@@ -393,14 +435,6 @@ def main():
         # operands split three ways in registers, six partial products per fp32 product -> priced against a sixth of the bf16 peak
         split3 = int(opts.get("split3", 0)) != 0 and not bf16
         peak = BF16_MFMA_PEAK_TFLOPS if bf16 else (BF16_MFMA_PEAK_TFLOPS / 6 if split3 else FP32_MFMA_PEAK_TFLOPS)
-        achieved = gconv3_flops(B, ND, taps) / (avg_ms * 1e-3) / 1e12 if kern_n else None
-        med = float(np.median(it_ms))
-        direct_equiv = None
-        if ND in DIRECT_GF_PER_SAMPLE:
-            gf = n_critic * DIRECT_GF_PER_SAMPLE[ND]["critic_step"] + DIRECT_GF_PER_SAMPLE[ND]["gen_step"]
-            direct_equiv = gf * 1e9 * B / (med * 1e-3) / 1e12          # per GPU
-        it_tflops = flops_iter / (med * 1e-3) / 1e12
-        traffic, traffic_src = dominant_traffic(bf16, ND, B) if taps == (8 if bf16 else 4) else (None, None)
         is_metric = (args.config, ND, B, n_critic, bf16, split3) == (2, 16, 256, 1, False, False)
         dtype = ("bf16 activations / gradients in HBM and bf16 MFMA operands, f32 accumulation, f32 master weights, "
                  "PixelNorm / softmax / penalty / Adam in f32") if bf16 else "f32"
@@ -429,43 +463,51 @@ def main():
                        "grad_transport": None if world == 1 else trainer.grad_transport,
                        "rccl_verified": None if world == 1 else (args.backend == "nccl"),
                        "weights": "random init (RandomNormal 0.02 / glorot_uniform), dropout 0.25 active"},
-            "iteration_ms": {"median": round(med, 4), "p10": round(float(np.percentile(it_ms, 10)), 4),
-                             "p90": round(float(np.percentile(it_ms, 90)), 4), "n": int(args.steps),
-                             "clock": "HIP events on the compute stream around each iteration"},
-            "roofline": {"bound": "mfma", "kernel": ((("k_upconv_slab16<1, true, *> (last conv's tap products in its epilogue, their FLOPs not counted; critic steps do not store the output)"
-                                                      if opts.get("g9_fused", "1") != "0" and opts.get("tapgather", "1") != "0" else "k_upconv_slab16<1>")
-                                                     if (bf16 and taps == 8 and ND == 16 and opts.get("upconv_slab", "1") != "0") else
-                                                     ("k_upconv_slab_t16<*, *> (8 x 8 tiles with their halo resident; last conv's tap products in its epilogue, "
-                                                      "their FLOPs not counted)"
-                                                      if (bf16 and taps == 8 and ND > 16 and ND % 16 == 0 and opts.get("upconv_slab_t", "1") != "0") else
-                                                      "k_conv_gemm_ws<256, 64, 4, 1, %d, %s, 1>" % (8 if taps == 8 else 4, "true" if bf16 else "false"))))
-                                                    + " (own symbol: this launch only), generator block 3 forward, "
-                                                    + ("collapsed form (8 parity phases x 8 taps + bias + PixelNorm + LeakyReLU in the epilogue)"
-                                                       if taps == 8 else
-                                                       "difference part (E x U over 8 parity phases x 4 taps + shared part T + bias + "
-                                                       "PixelNorm + LeakyReLU in the epilogue)"),
-                         "achieved": None if achieved is None else round(achieved, 2), "peak": peak,
-                         "unit": "TFLOP/s", "frac": None if achieved is None else round(achieved / peak, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "launches": int(kern_n), "avg_launch_ms": round(avg_ms, 4),
-                         "flops_per_launch": gconv3_flops(B, ND, taps),
-                         "iteration": {"executed_gflop": round(flops_iter / 1e9, 2), "tflops": round(it_tflops, 2),
-                                       "frac": round(it_tflops / peak, 4),
-                                       "note": "algorithmic FLOPs of every GEMM of one iteration in the forms actually run "
-                                               "(rdgan_flop_count) / median iteration time / the same MFMA peak; includes all "
-                                               "elementwise kernels' time"},
-                         "iteration_direct_equiv_tflops": None if direct_equiv is None else round(direct_equiv, 2),
-                         "kernel_classes": classes,
-                         "launches": launches,
-                         "launches_note": "every GEMM launch of an iteration (HIP events on the launch stream, %d extra iterations outside "
-                                          "the timed region): algorithmic GFLOP of the form run / mean duration / the dense MFMA peak of "
-                                          "the launch's operand type; a split-K launch includes its finish kernel, a weight gradient "
-                                          "its partial-slab fold" % nprof},
         }
-        out.update({
-            "final_losses": {"d_loss": round(d_loss, 5), "g_loss": round(g_loss, 5)},
-        })
-        if world == 1 and not args.no_cpu_baseline and ND == 16:
+        if args.full:
+            avg_ms = kern_ms / max(kern_n, 1)
+            achieved = gconv3_flops(B, ND, taps) / (avg_ms * 1e-3) / 1e12 if kern_n else None
+            med = float(np.median(it_ms))
+            direct_equiv = None
+            if ND in DIRECT_GF_PER_SAMPLE:
+                gf = n_critic * DIRECT_GF_PER_SAMPLE[ND]["critic_step"] + DIRECT_GF_PER_SAMPLE[ND]["gen_step"]
+                direct_equiv = gf * 1e9 * B / (med * 1e-3) / 1e12          # per GPU
+            it_tflops = flops_iter / (med * 1e-3) / 1e12
+            traffic, traffic_src = dominant_traffic(bf16, ND, B) if taps == (8 if bf16 else 4) else (None, None)
+            out["iteration_ms"] = {"median": round(med, 4), "p10": round(float(np.percentile(it_ms, 10)), 4),
+                                   "p90": round(float(np.percentile(it_ms, 90)), 4), "n": int(args.steps),
+                                   "clock": "HIP events on the compute stream around each iteration"}
+            out["roofline"] = {"bound": "mfma", "kernel": ((("k_upconv_slab16<1, true, *> (last conv's tap products in its epilogue, their FLOPs not counted; critic steps do not store the output)"
+                                                            if opts.get("g9_fused", "1") != "0" and opts.get("tapgather", "1") != "0" else "k_upconv_slab16<1>")
+                                                           if (bf16 and taps == 8 and ND == 16 and opts.get("upconv_slab", "1") != "0") else
+                                                           ("k_upconv_slab_t16<*, *> (8 x 8 tiles with their halo resident; last conv's tap products in its epilogue, "
+                                                            "their FLOPs not counted)"
+                                                            if (bf16 and taps == 8 and ND > 16 and ND % 16 == 0 and opts.get("upconv_slab_t", "1") != "0") else
+                                                            "k_conv_gemm_ws<256, 64, 4, 1, %d, %s, 1>" % (8 if taps == 8 else 4, "true" if bf16 else "false"))))
+                                                          + " (own symbol: this launch only), generator block 3 forward, "
+                                                          + ("collapsed form (8 parity phases x 8 taps + bias + PixelNorm + LeakyReLU in the epilogue)"
+                                                             if taps == 8 else
+                                                             "difference part (E x U over 8 parity phases x 4 taps + shared part T + bias + "
+                                                             "PixelNorm + LeakyReLU in the epilogue)"),
+                               "achieved": None if achieved is None else round(achieved, 2), "peak": peak,
+                               "unit": "TFLOP/s", "frac": None if achieved is None else round(achieved / peak, 4),
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "launches": int(kern_n), "avg_launch_ms": round(avg_ms, 4),
+                               "flops_per_launch": gconv3_flops(B, ND, taps),
+                               "iteration": {"executed_gflop": round(flops_iter / 1e9, 2), "tflops": round(it_tflops, 2),
+                                             "frac": round(it_tflops / peak, 4),
+                                             "note": "algorithmic FLOPs of every GEMM of one iteration in the forms actually run "
+                                                     "(rdgan_flop_count) / median iteration time / the same MFMA peak; includes all "
+                                                     "elementwise kernels' time"},
+                               "iteration_direct_equiv_tflops": None if direct_equiv is None else round(direct_equiv, 2),
+                               "kernel_classes": classes,
+                               "launches": launches,
+                               "launches_note": "every GEMM launch of an iteration (HIP events on the launch stream, %d extra iterations outside "
+                                                "the timed region): algorithmic GFLOP of the form run / mean duration / the dense MFMA peak of "
+                                                "the launch's operand type; a split-K launch includes its finish kernel, a weight gradient "
+                                                "its partial-slab fold" % nprof}
+        out["final_losses"] = {"d_loss": round(d_loss, 5), "g_loss": round(g_loss, 5)}
+        if args.full and world == 1 and not args.no_cpu_baseline and ND == 16:
             # bounded sample: the default configuration's iteration at the GPU line's batch (~6 s per CPU iteration);
             # n_critic = 5 configurations at bs 64 so that the default run still ends within minutes
             out["cpu_baseline"] = cpu_baseline(ND, n_critic, batch=256 if n_critic == 1 else 64)

@@ -9,7 +9,7 @@ rc=$?
 tail -n 15 $O/tests.log
 [ $rc -ne 0 ] && exit $rc
 for v in 0 1; do
-  timeout -k 10 300 python bench.py --config 5 --batch 64 --steps 10 --warmup 3 --no-cpu-baseline --opt upconv_slab_t=$v > $O/cfg5_t$v.json 2> $O/cfg5_t$v.err || { tail -5 $O/cfg5_t$v.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --config 5 --batch 64 --steps 10 --warmup 3 --no-cpu-baseline --opt upconv_slab_t=$v > $O/cfg5_t$v.json 2> $O/cfg5_t$v.err || { tail -5 $O/cfg5_t$v.err; exit 1; }
   python - "$O/cfg5_t$v.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

@@ -8,7 +8,7 @@ timeout -k 10 600 python -m pytest tests/test_hip_bf16.py tests/test_hip_fullsiz
 rc=$?
 tail -n 8 $O/tests.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python bench.py --config 5 --batch 64 --steps 10 --warmup 3 --no-cpu-baseline > $O/cfg5.json 2> $O/cfg5.err || { tail -5 $O/cfg5.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config 5 --batch 64 --steps 10 --warmup 3 --no-cpu-baseline > $O/cfg5.json 2> $O/cfg5.err || { tail -5 $O/cfg5.err; exit 1; }
 python - "$O/cfg5.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

@@ -8,8 +8,8 @@ timeout -k 10 600 python -m pytest tests/test_hip_step.py tests/test_hip_condcha
 rc=$?
 tail -n 6 $O/tests.log | cut -c1-300
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python bench.py --config 3 --steps 5 --warmup 2 --no-cpu-baseline > $O/cfg3.json 2> $O/cfg3.err || { tail -5 $O/cfg3.err; exit 1; }
-timeout -k 10 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline > $O/fp32.json 2> $O/fp32.err || { tail -5 $O/fp32.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config 3 --steps 5 --warmup 2 --no-cpu-baseline > $O/cfg3.json 2> $O/cfg3.err || { tail -5 $O/cfg3.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > $O/fp32.json 2> $O/fp32.err || { tail -5 $O/fp32.err; exit 1; }
 python - $O/cfg3.json $O/fp32.json <<'PY'
 import json, sys
 for f in sys.argv[1:]:

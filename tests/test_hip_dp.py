@@ -151,7 +151,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher: the script starts two fresh rank processes itself (here both on
     cuda:0 with gloo: a one-GPU rehearsal of the RCCL path) and prints ONE JSON line from rank 0."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-device", "--backend", "gloo", "--steps", "3",
-           "--warmup", "1", "--batch", "8", "--no-cpu-baseline"]
+           "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, timeout=900)
     assert p.returncode == 0
