@@ -170,6 +170,42 @@ def gen_step_grads(dp, gp, z, cond, seed, gates=None, return_intermediates=False
     return loss.detach(), [gg.detach() for gg in grads]
 
 
+def gate_stats(gates, acts, masks=None, into=None):
+    """The per-layer counts behind check_gates, in a form that adds up over sample ranges of one batch: for each layer
+    [disagreements, live elements, sum of squares of the live LeakyReLU inputs, largest |input| at a disagreement].
+    into: the list of an earlier range of the same batch, accumulated in place."""
+    out = [[0, 0, 0.0, 0.0] for _ in gates] if into is None else into
+    for li, (g, a) in enumerate(zip(gates, acts)):
+        live = torch.ones_like(g) if masks is None else (masks[li] != 0)
+        pre = a / torch.where(g, torch.ones((), dtype=a.dtype, device=a.device), torch.full((), LRELU, dtype=a.dtype, device=a.device))
+        if masks is not None:
+            pre = pre / torch.where(live, masks[li], torch.ones((), dtype=a.dtype, device=a.device))
+        bad = (g != (pre > 0)) & live
+        nbad = int(bad.sum())
+        out[li][0] += nbad
+        out[li][1] += int(live.sum())
+        out[li][2] += float(torch.where(live, pre * pre, torch.zeros((), dtype=a.dtype, device=a.device)).sum())
+        if nbad:
+            out[li][3] = max(out[li][3], float(pre[bad].abs().max()))
+    return out
+
+
+def check_gate_stats(stats, max_margin=1e-3, max_fraction=1e-3, observed=None):
+    """check_gates on the counts of gate_stats (pooled over all sample ranges of the batch before max_fraction applies)."""
+    worst, worst_frac = 0.0, 0.0
+    for li, (nbad, nlive, sumsq, maxbad) in enumerate(stats):
+        if nbad:
+            frac = nbad / max(1, nlive)
+            margin = maxbad / float(np.sqrt(sumsq / nlive))
+            worst, worst_frac = max(worst, margin), max(worst_frac, frac)
+            if observed is not None:
+                observed["margin"] = max(observed.get("margin", 0.0), margin)
+                observed["fraction"] = max(observed.get("fraction", 0.0), frac)
+            assert frac <= max_fraction, f"layer {li}: {nbad} slope disagreements ({frac:.2e} of the layer)"
+            assert margin <= max_margin, f"layer {li}: slope disagreement {margin:.2e} RMS away from the kink"
+    return worst, worst_frac
+
+
 def check_gates(gates, acts, masks=None, max_margin=1e-3, max_fraction=1e-3, observed=None):
     """Guard for the ``gates=`` mechanism: an externally supplied slope pattern may differ from this oracle's own decision
     only where the oracle's LeakyReLU input is within rounding of zero.  gates / acts: matching lists of bool patterns and of
@@ -179,26 +215,115 @@ def check_gates(gates, acts, masks=None, max_margin=1e-3, max_fraction=1e-3, obs
     rare (max_fraction of the layer) and all sit within max_margin of the kink, measured as |LeakyReLU input| / RMS of the
     layer.  Returns (worst margin, worst fraction) met over the layers; with `observed` (a dict) the maxima are also
     accumulated there (keys "margin", "fraction"), so that a test run can report the guard's headroom."""
-    worst, worst_frac = 0.0, 0.0
-    for li, (g, a) in enumerate(zip(gates, acts)):
-        live = torch.ones_like(g) if masks is None else (masks[li] != 0)
-        pre = a / torch.where(g, torch.ones((), dtype=a.dtype), torch.full((), LRELU, dtype=a.dtype))
-        if masks is not None:
-            pre = pre / torch.where(live, masks[li], torch.ones((), dtype=a.dtype))
-        own = pre > 0
-        rms = float(pre[live].pow(2).mean().sqrt())
-        bad = (g != own) & live
-        nbad = int(bad.sum())
-        if nbad:
-            frac = nbad / max(1, int(live.sum()))
-            margin = float(pre[bad].abs().max()) / rms
-            worst, worst_frac = max(worst, margin), max(worst_frac, frac)
-            if observed is not None:
-                observed["margin"] = max(observed.get("margin", 0.0), margin)
-                observed["fraction"] = max(observed.get("fraction", 0.0), frac)
-            assert frac <= max_fraction, f"layer {li}: {nbad} slope disagreements ({frac:.2e} of the layer)"
-            assert margin <= max_margin, f"layer {li}: slope disagreement {margin:.2e} RMS away from the kink"
-    return worst, worst_frac
+    return check_gate_stats(gate_stats(gates, acts, masks), max_margin, max_fraction, observed)
+
+
+def sample_ranges(B, chunk):
+    """[lo, hi) ranges covering 0..B-1: chunk = the largest range length (int) or the list of range lengths"""
+    sizes = [chunk] * (-(-B // chunk)) if isinstance(chunk, int) else list(chunk)
+    out, lo = [], 0
+    for n in sizes:
+        hi = min(B, lo + n)
+        out.append((lo, hi))
+        lo = hi
+    assert lo == B and all(hi > lo for lo, hi in out), (B, chunk)
+    return out
+
+
+def critic_masks_rows(seed, ndomain, rows, device=None, dtype=torch.float64):
+    """critic_masks for the sample ranges `rows` ([(lo, hi), ...], concatenated) of a larger critic pass, generated on
+    `device`: the flat indices stay those of the whole pass.  seed == 0 -> None."""
+    if seed == 0:
+        return None
+    geo = onp.critic_geometry(ndomain)
+    chans = (64, 128, 256, 256)
+    out = []
+    for li in range(4):
+        shp = tuple(geo[li][1]) + (chans[li],)
+        per = int(np.prod(shp))
+        out.append(torch.cat([orng.dropout_scale_mask_t(seed, orng.STREAM_D1 + li, (hi - lo,) + shp, start=lo * per,
+                                                        device=device, dtype=dtype) for lo, hi in rows], 0))
+    return out
+
+
+def _grads_or_zeros(out, params):
+    return [torch.zeros_like(p) if g is None else g.detach() for p, g in zip(params, out)]
+
+
+def critic_step_grads_chunked(dp, gp, x_real, cond, z, seed, chunk, alpha_offset=0, gates=None, fake=None, device="cpu"):
+    """critic_step_grads in fp64 on `device`, evaluated over the sample ranges of sample_ranges(B, chunk), so that the
+    benchmarked batch sizes fit: every critic pass is per sample, so the ranges' gradients add up to the whole batch's.
+    Rows lo..hi of the real, fake and interpolated thirds keep their dropout indices k, B + k, 2B + k of the 3B pass, alpha
+    of sample k stays uniform(alpha_offset + k); loss parts are summed and divided by the global B.  Inputs may be numpy
+    arrays or tensors on any device; gates (3B samples) and fake are sliced per range.
+    Returns (losses, grads, parts, stats): parts[i] = range i's contribution to grads (sum(parts) = grads); stats = the
+    gate_stats of the whole batch (None without gates), for check_gate_stats."""
+    put = lambda t: torch.as_tensor(t).to(device=device, dtype=torch.float64)
+    B = x_real.shape[0]
+    nd = cond.shape[1]
+    dp = [put(t).detach().requires_grad_(True) for t in dp]
+    gp = [put(t) for t in gp]
+    alpha_all = torch.from_numpy(orng.uniform(seed, orng.STREAM_ALPHA, B, start=alpha_offset))
+    sums = torch.zeros(3, dtype=torch.float64, device=device)
+    grads, parts, stats = None, [], None
+    for lo, hi in sample_ranges(B, chunk):
+        n = hi - lo
+        xr, c = put(x_real[lo:hi]), put(cond[lo:hi])
+        if fake is None:
+            with torch.no_grad():
+                fk = generator_forward(gp, put(z[lo:hi]), c)
+        else:
+            fk = put(fake[lo:hi])
+        alpha = put(alpha_all[lo:hi]).reshape(n, 1, 1, 1, 1)
+        xhat = (alpha * xr + (1 - alpha) * fk).detach().requires_grad_(True)
+        rows = [(lo, hi), (B + lo, B + hi), (2 * B + lo, 2 * B + hi)]
+        masks = critic_masks_rows(seed, nd, rows, device)
+        gch = None if gates is None else [torch.cat([g[a:b] for a, b in rows], 0).to(device) for g in gates]
+        v, inter = critic_forward(dp, torch.cat([xr, fk, xhat], 0), torch.cat([c, c, c], 0), masks, True, gates=gch)
+        v_real, v_fake, v_hat = v[:n], v[n:2 * n], v[2 * n:]
+        g, = torch.autograd.grad(v_hat.sum(), xhat, create_graph=True)
+        gpen = torch.sqrt((g * g).reshape(n, -1).sum(1, keepdim=True)) - 1     # per sample: range-local
+        part = torch.stack([(-1.0 * v_real).sum(), v_fake.sum(), (gpen * gpen).sum()])
+        total = (part[0] + part[1] + onp.GP_WEIGHT * part[2]) / B
+        pg = _grads_or_zeros(torch.autograd.grad(total, dp, allow_unused=True), dp)
+        parts.append(pg)
+        grads = pg if grads is None else [a + b for a, b in zip(grads, pg)]
+        sums += part.detach()
+        if gates is not None:
+            stats = gate_stats(gch, [h.detach() for h in inter["h"]], masks, stats)
+        del v, inter, g, gpen, total
+    l_valid, l_fake, l_gp = sums / B
+    losses = torch.stack([l_valid + l_fake + onp.GP_WEIGHT * l_gp, l_valid, l_fake, l_gp])
+    return losses, grads, parts, stats
+
+
+def gen_step_grads_chunked(dp, gp, z, cond, seed, chunk, gates=None, device="cpu"):
+    """gen_step_grads in fp64 on `device` over the sample ranges of sample_ranges(B, chunk) (see
+    critic_step_grads_chunked).  gates: optional (generator [h0..h3], critic [4 layers]) patterns over the B samples.
+    Returns (loss, grads, parts, (generator stats, critic stats)) -- stats None without gates."""
+    put = lambda t: torch.as_tensor(t).to(device=device, dtype=torch.float64)
+    B = z.shape[0]
+    nd = cond.shape[1]
+    gp = [put(t).detach().requires_grad_(True) for t in gp]
+    dp = [put(t) for t in dp]
+    lsum = torch.zeros((), dtype=torch.float64, device=device)
+    grads, parts, gstats, dstats = None, [], None, None
+    for lo, hi in sample_ranges(B, chunk):
+        gg = None if gates is None else [t[lo:hi].to(device) for t in gates[0]]
+        dg = None if gates is None else [t[lo:hi].to(device) for t in gates[1]]
+        img, gi = generator_forward(gp, put(z[lo:hi]), put(cond[lo:hi]), True, gates=gg)
+        masks = critic_masks_rows(seed, nd, [(lo, hi)], device)
+        v, di = critic_forward(dp, img, put(cond[lo:hi]), masks, True, gates=dg)
+        s = (-1.0 * v).sum()
+        pg = [t.detach() for t in torch.autograd.grad(s / B, gp)]
+        parts.append(pg)
+        grads = pg if grads is None else [a + b for a, b in zip(grads, pg)]
+        lsum += s.detach()
+        if gates is not None:
+            gstats = gate_stats(gg, [gi[k].detach() for k in ("h0", "h1", "h2", "h3")], None, gstats)
+            dstats = gate_stats(dg, [h.detach() for h in di["h"]], masks, dstats)
+        del img, gi, v, di, s
+    return lsum / B, grads, parts, (None if gates is None else (gstats, dstats))
 
 
 def adam_update(params, grads, vs, t, lr=1e-4, beta2=0.9, eps=1e-7):

@@ -53,13 +53,52 @@ def uniform(seed, stream, n, start=0):
     return (bits(seed, stream, n, start) >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
 
 
-def dropout_scale_mask(seed, stream, shape):
+def dropout_scale_mask(seed, stream, shape, start=0):
     """float32 mask holding 0 or 1/0.75 (inverted dropout, rate 0.25) of the given shape.
-    seed == 0 means dropout off (all ones) -- the ``predict`` path of the reference."""
+    seed == 0 means dropout off (all ones) -- the ``predict`` path of the reference.
+    start: flat index of the mask's first element in the whole tensor (a sample range of a larger batch)."""
     n = int(np.prod(shape))
     if seed == 0:
         return np.ones(shape, np.float32)
-    words = np.repeat(bits(seed, stream, (n + 3) // 4), 4)[:n]
-    byte = (words >> (np.uint32(8) * (np.arange(n, dtype=np.uint32) & np.uint32(3)))) & np.uint32(0xFF)
+    idx = np.arange(start, start + n, dtype=np.uint64)
+    w0 = int(start) >> 2
+    words = bits(seed, stream, ((int(start) + n + 3) >> 2) - w0, start=w0)[(idx >> np.uint64(2)).astype(np.int64) - w0]
+    byte = (words >> (np.uint32(8) * (idx & np.uint64(3)).astype(np.uint32))) & np.uint32(0xFF)
     keep = byte >= np.uint32(DROP_THRESHOLD)
     return np.where(keep, DROP_SCALE, np.float32(0)).astype(np.float32).reshape(shape)
+
+
+# The same definitions in torch int64 arithmetic, for masks generated on a GPU (the fp64 device oracle at the benchmarked
+# batch sizes).  Every product is split so that no intermediate leaves the int64 range; bit-equal to the numpy form
+# (tests/test_oracle_chunked.py).
+def _mul32_t(x, c):
+    return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & 0xFFFFFFFF
+
+
+def mix32_t(x):
+    """mix32 of an int64 torch tensor holding uint32 values"""
+    x = x ^ (x >> 16)
+    x = _mul32_t(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32_t(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def bits_t(seed, stream, n, start=0, device=None):
+    import torch
+    idx = torch.arange(start, start + n, dtype=torch.int64, device=device) & 0xFFFFFFFF
+    return mix32_t(mix32_t(idx) ^ int(make_key(seed, stream)))
+
+
+def dropout_scale_mask_t(seed, stream, shape, start=0, device=None, dtype=None):
+    """dropout_scale_mask as a torch tensor generated on `device` (default dtype float32)"""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    n = int(np.prod(shape))
+    if seed == 0:
+        return torch.ones(shape, dtype=dtype, device=device)
+    idx = torch.arange(start, start + n, dtype=torch.int64, device=device)
+    words = mix32_t(mix32_t((idx >> 2) & 0xFFFFFFFF) ^ int(make_key(seed, stream)))
+    keep = ((words >> (8 * (idx & 3))) & 0xFF) >= DROP_THRESHOLD
+    return torch.where(keep, torch.tensor(float(DROP_SCALE), dtype=torch.float32, device=device),
+                       torch.zeros((), dtype=torch.float32, device=device)).to(dtype).reshape(shape)

@@ -30,29 +30,32 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
 
 
-def hip_gates(eng, B):
+def hip_gates(eng, B, on_device=False):
     """LeakyReLU slope pattern (True = slope 1) of the engine's last generator-step forward: generator h0..h3 and critic
     layers 1..4 over B samples, from the activations left in the workspace (rdgan_debug_activation).  A dropped critic
-    activation reads 0 -> False, which is immaterial: its gradient is multiplied by the zero mask anyway."""
+    activation reads 0 -> False, which is immaterial: its gradient is multiplied by the zero mask anyway.
+    on_device: leave the patterns on the GPU (production batch sizes: h3 alone is 805 M elements at bs 2048)."""
     from oracle import rdgan_np as onp
     nd = eng.ndomain
     s = nd // 8
     gshape = [(B, 3, s, s, 256), (B, 6, 2 * s, 2 * s, 256), (B, 12, 4 * s, 4 * s, 128), (B, 24, 8 * s, 8 * s, 64)]
     geo = onp.critic_geometry(nd)
     chans = (64, 128, 256, 256)
-    g = [eng.debug_activation(i, shp).cpu() > 0 for i, shp in enumerate(gshape)]
-    d = [eng.debug_activation(4 + li, (B,) + tuple(geo[li][1]) + (chans[li],)).cpu() > 0 for li in range(4)]
+    put = (lambda t: t > 0) if on_device else (lambda t: t.cpu() > 0)
+    g = [put(eng.debug_activation(i, shp)) for i, shp in enumerate(gshape)]
+    d = [put(eng.debug_activation(4 + li, (B,) + tuple(geo[li][1]) + (chans[li],))) for li in range(4)]
     return g, d
 
 
-def hip_critic_gates(eng, B):
+def hip_critic_gates(eng, B, on_device=False):
     """The same for the engine's last CRITIC step: the four critic layers over the 3B batch [real; fake; interpolated].
     Needs the option "keep_gates" set before the step (the penalty's second sweep overwrites the interpolated third of the
     activations in place; the option keeps a copy)."""
     from oracle import rdgan_np as onp
     geo = onp.critic_geometry(eng.ndomain)
     chans = (64, 128, 256, 256)
-    return [eng.debug_activation(4 + li, (3 * B,) + tuple(geo[li][1]) + (chans[li],)).cpu() > 0 for li in range(4)]
+    put = (lambda t: t > 0) if on_device else (lambda t: t.cpu() > 0)
+    return [put(eng.debug_activation(4 + li, (3 * B,) + tuple(geo[li][1]) + (chans[li],))) for li in range(4)]
 
 
 # how far from a LeakyReLU kink (in RMS of the layer's inputs) the engine's slope decision may differ from the fp64 oracle's,
@@ -107,3 +110,46 @@ def critic_step_on_engine_branch(eng, ds, gs, d, g, x, cond, z, seed, mode="f32"
     ot.check_gates(gates, dh, ot.critic_masks(seed, 3 * B, eng.ndomain, torch.float64), observed=GATE_OBSERVED[mode], **GATE_TOL[mode])
     _gate_report(mode, f"critic step nd{eng.ndomain} B{B}")
     return slab, losses, grads
+
+
+# Production batch sizes (tests/test_hip_fullsize.py): the same comparisons against the fp64 oracle run ON THE GPU over sample
+# ranges of `chunk` samples (oracle/rdgan_torch.py: *_step_grads_chunked); inputs stay on the device, the gate guard pools its
+# counts over the ranges.  Each returns (slab, loss(es), grads, last): last = the last range's share of grads, for the tests'
+# drop-the-last-range sensitivity control.
+
+def gen_step_on_engine_branch_chunked(eng, ds, gs, d, g, z, cond, seed, chunk, mode="f32", gate_tol=None):
+    """gate_tol: the guard's limits (default GATE_TOL[mode])"""
+    from oracle import rdgan_torch as ot
+    tol = GATE_TOL[mode] if gate_tol is None else gate_tol
+    B = z.shape[0]
+    zd, cd = dev(z), dev(cond)
+    slab = eng.gen_grad(ds, gs, zd, cd, seed).cpu().numpy()
+    gates = hip_gates(eng, B, on_device=True)
+    loss, grads, parts, (gst, dst) = ot.gen_step_grads_chunked(d, g, zd, cd, seed, chunk, gates=gates, device=eng.device)
+    del gates
+    ot.check_gate_stats(gst, observed=GATE_OBSERVED[mode], **tol)
+    ot.check_gate_stats(dst, observed=GATE_OBSERVED[mode], **tol)
+    _gate_report(mode, f"generator step nd{eng.ndomain} B{B} (device oracle, {len(parts)} ranges)")
+    return slab, loss.cpu(), [t.cpu() for t in grads], [t.cpu() for t in parts[-1]]
+
+
+def critic_step_on_engine_branch_chunked(eng, ds, gs, d, g, x, cond, z, seed, chunk, mode="f32", fake=None, alpha_offset=0,
+                                         gate_tol=None):
+    """fake: the generator output the engine fed its critic (a tensor may stay on the device); alpha_offset: the engine's
+    "sample_offset", which the caller sets; gate_tol: the guard's limits (default GATE_TOL[mode])"""
+    from oracle import rdgan_torch as ot
+    tol = GATE_TOL[mode] if gate_tol is None else gate_tol
+    B = x.shape[0]
+    xd, cd, zd = dev(x), dev(cond), dev(z)
+    eng.set_option("keep_gates", 1)
+    try:
+        slab = eng.critic_grad(ds, gs, xd, cd, zd, seed).cpu().numpy()
+        gates = hip_critic_gates(eng, B, on_device=True)
+    finally:
+        eng.set_option("keep_gates", 0)
+    losses, grads, parts, stats = ot.critic_step_grads_chunked(d, g, xd, cd, zd, seed, chunk, alpha_offset=alpha_offset,
+                                                               gates=gates, fake=fake, device=eng.device)
+    del gates
+    ot.check_gate_stats(stats, observed=GATE_OBSERVED[mode], **tol)
+    _gate_report(mode, f"critic step nd{eng.ndomain} B{B} (device oracle, {len(parts)} ranges)")
+    return slab, losses.cpu(), [t.cpu() for t in grads], [t.cpu() for t in parts[-1]]

@@ -515,12 +515,13 @@ def test_d2_wgrad_slab_tiled_kernel_vs_definition(B, OH, OW):
         assert np.array_equal(o1.cpu().numpy(), want), (id_, ih, iw)
 
 
-@pytest.mark.parametrize("B", [1, 3, 520])
+@pytest.mark.parametrize("B", [1, 3, 520, 2048])
 def test_upconv2_slab_kernel_vs_oracle(B):
     """k_upconv2_slab16 alone (rdgan_op_upconv2_slab16): generator block 2 of the bf16 storage mode -- UpSampling3D(2) + Conv3D(256
     -> 128, 3x3x3, 'same') + bias + PixelNorm + LeakyReLU(0.2) (T:335-338) on a 6 x 4 x 4 x 256 input -- against the fp64 oracle on
     the bf16-rounded input.  The kernel rounds the COLLAPSED weights (sums of up to 8 taps) and its output to bf16: 2^-8 each, so
-    2e-2 of the largest output; the per-pixel 1/l2 at 1e-2.  B = 520: persistent workgroups walk two samples."""
+    2e-2 of the largest output; the per-pixel 1/l2 at 1e-2.  B = 520: persistent workgroups walk two samples; B = 2048: the launch
+    of BASELINE configs[2] (the oracle checks the first, middle and last sample)."""
     g = torch.Generator(); g.manual_seed(500 + B)
     nref = min(B, 3)
     x = torch.randn((B, 6, 4, 4, 256), generator=g)
@@ -598,3 +599,113 @@ def test_d3_wgrad_slab_kernel_vs_definition(B):
     out2 = torch.empty_like(out)
     assert lib().rdgan_op_d3_wgrad_slab16(ptr(xd), ptr(dyd), ptr(out2), B, stream()) == 0
     assert torch.equal(out, out2)
+
+
+# ---- The bf16 slab kernels alone at the sizes the engine launches them with: BASELINE configs[2] (the critic's 3B = 6144 rows, the
+# generator's B = 2048) and configs[4]'s ndomain-64 shard (3B = 192).  References in fp64 ON THE DEVICE,
+# on the bf16-rounded operands, with the tolerances of the small-batch rows above.  Every rdgan_op_* wrapper used here allocates its own
+# bf16 copies and partial-slab workspace, sized for its B, and picks the group count G the engine picks for the same B (rdgan_api.hip);
+# none caps B.  The engine's own workspace at these sizes is covered by the oracle comparisons of tests/test_hip_fullsize.py.
+
+def _randn_dev(shape, seed, scale=1.0):
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    return scale * torch.randn(shape, generator=g, device="cuda")
+
+
+_PROD_WGRAD = [
+    # (kernel, B, x dims, Cin, Cout, output dims, stride, pad)
+    ("d2_wgrad_slab16", 6144, (11, 7, 7), 64, 128, (6, 4, 4), 2, (1, 1, 1)),          # configs[2] critic layer 2, 64 groups
+    ("d3_wgrad_slab16", 6144, (6, 4, 4), 128, 256, (3, 2, 2), 2, (0, 0, 0)),          # configs[2] critic layer 3, 16 groups
+    ("d2_wgrad_slab_t16", 192, (11, 31, 31), 64, 128, (6, 16, 16), 2, (1, 1, 1)),     # configs[4] shard critic layer 2
+    ("conv3d_wgrad_bf16", 6144, (3, 2, 2), 256, 256, (2, 1, 1), 2, (1, 0, 0)),        # configs[2] critic layer 4
+    ("conv3d_wgrad_bf16", 192, (6, 16, 16), 128, 256, (3, 8, 8), 2, (0, 0, 0)),       # configs[4] shard critic layer 3
+    ("conv3d_wgrad_bf16", 192, (3, 8, 8), 256, 256, (2, 4, 4), 2, (1, 0, 0)),         # configs[4] shard critic layer 4
+]
+
+
+@pytest.mark.parametrize("g", _PROD_WGRAD, ids=[f"{g[0]}-B{g[1]}-{g[2][1]}" for g in _PROD_WGRAD])
+def test_bf16_wgrad_kernels_at_production_sizes(g):
+    """weight gradients at the engine's production launch sizes: 2e-5 of the largest entry per tap (fp32 accumulation of exact bf16
+    products; conv3d_wgrad_bf16: 1e-5 of the largest entry overall, as its small rows), deterministic"""
+    kernel, B, dims, cin, cout, od, stride, pad = g
+    x = _randn_dev((B,) + dims + (cin,), 800 + B)
+    dy = _randn_dev((B,) + od + (cout,), 900 + B)
+    w = torch.zeros((3, 3, 3, cin, cout), dtype=torch.float64, device="cuda", requires_grad=True)
+    (ref,) = torch.autograd.grad(ot._conv3d_tf(x.bfloat16().double(), w, None, stride, pad, od), w, dy.bfloat16().double())
+
+    def run():
+        out = torch.full((3, 3, 3, cin, cout), float("nan"), device="cuda")
+        if kernel == "conv3d_wgrad_bf16":
+            rc = lib().rdgan_op_conv3d_wgrad_bf16(ptr(x), ptr(dy), ptr(out), B, *dims, cin, cout, *od, stride, *pad, stream())
+        elif kernel == "d2_wgrad_slab_t16":
+            rc = lib().rdgan_op_d2_wgrad_slab_t16(ptr(x), ptr(dy), ptr(out), B, od[1], od[2], stream())
+        else:
+            rc = getattr(lib(), "rdgan_op_" + kernel)(ptr(x), ptr(dy), ptr(out), B, stream())
+        assert rc == 0
+        return out
+
+    out = run()
+    assert bool(torch.isfinite(out).all())
+    scale = float(ref.abs().max())
+    if kernel == "conv3d_wgrad_bf16":
+        err = float((out.double() - ref).abs().max()) / scale
+        assert err < 1e-5, err
+    else:
+        err = ((out.double() - ref).abs().amax(dim=(3, 4)) / scale).cpu().numpy()
+        assert err.max() < 2e-5, err
+    assert torch.equal(out, run())                                   # deterministic
+
+
+@pytest.mark.parametrize("B,OH,OW", [(6144, 4, 4), (192, 16, 16)])
+def test_d2_dgrad_slab_kernels_at_production_sizes(B, OH, OW):
+    """k_d2_dgrad_slab16 (ndomain 16, configs[2]: 3B = 6144, persistent workgroups walk six items) and k_d2_dgrad_slab_t16
+    (ndomain 64, configs[4]'s shard: 3B = 192) at the engine's launch sizes: the critic's layer-2 input gradient times the layer-1
+    LeakyReLU' / dropout gate, per element within 2^-8 (one bf16 rounding of the output), with and without dropout"""
+    IH, IW = 2 * OH - 1, 2 * OW - 1
+    gy = _randn_dev((B, 6, OH, OW, 128), 1000 + B)
+    w = _randn_dev((3, 3, 3, 64, 128), 1001 + B, 0.05)
+    aux = _randn_dev((B, 11, IH, IW, 64), 1002 + B)
+    xz = torch.zeros((B, 11, IH, IW, 64), dtype=torch.float64, device="cuda", requires_grad=True)
+    (gx_ref,) = torch.autograd.grad(ot._conv3d_tf(xz, w.bfloat16().double(), None, 2, (1, 1, 1), (6, OH, OW)), xz, gy.bfloat16().double())
+    del xz
+    for seed in (0, 0x5DEECE66D):
+        a = aux.clone()
+        a[a == 0] = -0.0                  # the engine stores a kept exact zero as -0.0 (torch.randn on the GPU draws exact zeros)
+        m = orng.dropout_scale_mask_t(seed, orng.STREAM_D1, a.shape, device="cuda")
+        a[m == 0] = 0.0                                                # dropped: +0.0
+        want = gx_ref * torch.where(a.bfloat16() > 0, 1.0, 0.2).double() * m.double()
+        gx = torch.full((B, 11, IH, IW, 64), float("nan"), device="cuda")
+        if OH == 4:
+            rc = lib().rdgan_op_d2_dgrad_slab16(ptr(gy), ptr(w), ptr(a), ptr(gx), B, int(seed != 0), stream())
+        else:
+            rc = lib().rdgan_op_d2_dgrad_slab_t16(ptr(gy), ptr(w), ptr(a), ptr(gx), B, OH, OW, int(seed != 0), stream())
+        assert rc == 0
+        assert bool(torch.isfinite(gx).all())
+        bad = (gx.double() - want).abs() > (2.0 ** -8 + 1e-5) * want.abs() + 1e-5 * float(want.abs().max())
+        assert not bool(bad.any()), int(bad.sum())
+        del want, gx, bad
+
+
+def test_upconv_wgrad_slab_kernel_at_production_size():
+    """k_upconv_wgrad_slab16 at configs[2]'s B = 2048 (32 groups, each walking 384 items): the collapsed weight gradient of generator
+    block 3 against its definition (test_upconv_wgrad_slab_kernel_vs_definition) in fp64 on the device, 2e-5 of the largest entry"""
+    B = 2048
+    x = _randn_dev((B, 12, 8, 8, 128), 1100)
+    dy = _randn_dev((B, 24, 16, 16, 64), 1101)
+    xp = torch.nn.functional.pad(x.bfloat16().double(), (0, 0, 1, 1, 1, 1, 1, 1))
+    dyr = dy.bfloat16().double()
+    ref = torch.zeros((64, 128, 64), dtype=torch.float64, device="cuda")
+    for p in range(8):
+        par = (p >> 2, (p >> 1) & 1, p & 1)
+        dyp = dyr[:, par[0]::2, par[1]::2, par[2]::2].reshape(-1, 64)
+        for t in range(8):
+            o = [par[a] - 1 + ((t >> (2 - a)) & 1) for a in range(3)]
+            xs = xp[:, 1 + o[0]:13 + o[0], 1 + o[1]:9 + o[1], 1 + o[2]:9 + o[2]].reshape(-1, 128)
+            ref[p * 8 + t] = xs.T @ dyp
+    del xp, dyr
+    out = torch.full((64, 128, 64), float("nan"), device="cuda")
+    assert lib().rdgan_op_upconv_wgrad_slab16(ptr(x), ptr(dy), ptr(out), B, stream()) == 0
+    assert bool(torch.isfinite(out).all())
+    err = float((out.double() - ref).abs().max() / ref.abs().max())
+    assert err < 2e-5, err
