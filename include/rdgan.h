@@ -302,6 +302,28 @@ int rdgan_data_valid_tiles(const float* data, int n_days, int ny, int nx, int nd
 int rdgan_crps_ensemble(const float* ens, const float* obs, const float* scale, float* crps_out, int n, long npix,
                         void* stream);
 
+/* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
+ * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
+ * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->
+ * out [n][K] = mean of |fftshift(fft2(x))|^2 over the integer radial bins 1..K about the centre ((nd-1)/2, (nd-1)/2) (bin 0,
+ * which holds DC, and the corner bin are dropped, as the reference's bookkeeping drops them); log_out != 0 writes
+ * 10 log10 of it (dB; -inf for an empty bin).  An all-zero or constant field gives 0 (-inf dB) in every kept bin. */
+int rdgan_spectra_bins(int nd);
+int rdgan_radial_spectra(const float* fields, float* out, long n, int nd, int log_out, void* stream);
+/* rdgan_lsd_pairwise: log_spectral_distance (:68-77) for every ordered pair of compute_dists (:104-118), reduced on the device.
+ * spec_a [n][k], spec_b [m][k] are log-spectra in dB (spec_b may equal spec_a); d(i, j) = sqrt(sum (a_i - b_j)^2) * (1/k) in
+ * fp32, NaN for two empty spectra and +inf for one (log10(0/0), log10(p/0) of the reference).  Outputs, NULL to skip, not
+ * all NULL: dist [n][m] fp32; hist [nbins + 4] uint64 = counts per bin b = (int)floorf((d - lo) * scale), scale = (float)nbins
+ * / (hi - lo), all fp32, clamped to nbins - 1, then d < lo, d >= hi, NaN, +inf; moments [5] = count, sum, sum of squares
+ * (fp64), min, max of the finite d, which needs workspace of rdgan_lsd_workspace_bytes(n, m).  exclude_diagonal != 0
+ * leaves the pairs i == j out of hist and moments and writes 0 there in dist (:112 never writes them, :123-130 removes them).
+ * hist and moments are the same bit for bit on every call.  n, m <= 2^22; 1024 k + 4 (nbins + 4) <= 57344 with hist
+ * (512 bins at any k; 2048 at k <= 47); k <= 48. */
+long rdgan_lsd_workspace_bytes(long n, long m);
+int rdgan_lsd_pairwise(const float* spec_a, const float* spec_b, long n, long m, int k, int exclude_diagonal, float* dist,
+                       unsigned long long* hist, int nbins, float lo, float hi, double* moments, void* workspace,
+                       long workspace_bytes, void* stream);
+
 /* Op-level entry points used by the parity tests (tests/test_hip_ops.py). */
 /* Conv3D forward, TF semantics.  x [B,D,H,W,Cin] -> y [B,Do,Ho,Wo,Cout]; upsample=1 folds
  * UpSampling3D(2) in front (T:330-331); pad = zero padding before each axis; Cin%4==0,

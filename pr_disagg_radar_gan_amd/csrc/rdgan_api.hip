@@ -32,6 +32,7 @@
 #include "rdgan_d3wgrad16.hip.h"
 #include "rdgan_d1fwd16.hip.h"
 #include "rdgan_g9bwd16.hip.h"
+#include "rdgan_spectral.hip.h"
 static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
 // k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
 static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
@@ -3004,6 +3005,90 @@ extern "C" int rdgan_crps_ensemble(const float* ens, const float* obs, const flo
   while (npow2 < n) npow2 <<= 1;
   hipLaunchKernelGGL(k_crps_ensemble, dim3((unsigned)npix), dim3(256), npow2 * sizeof(float), (hipStream_t)stream, ens, obs,
                      scale, crps_out, n, npow2, npix);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// log-spectral distance (rdgan_spectral.hip.h)
+// ------------------------------------------------------------------------------------
+extern "C" int rdgan_spectra_bins(int nd) {
+  if (nd < 8 || nd > RD_SPEC_MAXND || nd % 2) return -2;
+  return rd_spec_bin(nd - 1, nd - 1) - 1;               // bins 1 .. max - 1: the first and the last group are dropped
+}
+
+extern "C" int rdgan_radial_spectra(const float* fields, float* out, long n, int nd, int log_out, void* stream) {
+  const int K = rdgan_spectra_bins(nd);
+  if (!fields || !out || n < 1 || n > (1L << 26) || K < 1) return -2;
+  rd_spec_args a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < nd; ++j) {
+    const double th = -2.0 * M_PI * (double)j / (double)nd;
+    a.tw_re[j] = (float)cos(th);
+    a.tw_im[j] = (float)sin(th);
+  }
+  for (int i = 0; i < nd; ++i)
+    for (int j = 0; j < nd; ++j) {
+      const int b = rd_spec_bin(2 * j - (nd - 1), 2 * i - (nd - 1));
+      if (b >= 1 && b <= K) a.cnt[b - 1]++;
+    }
+  for (int b = 0; b < K; ++b)
+    if (a.cnt[b] == 0) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  const int lo = log_out ? 1 : 0;
+  switch (nd) {
+#define RD_SPEC_CASE(ND)                                                                                                     \
+  case ND: {                                                                                                                 \
+    constexpr int FPB = ND * ND >= 256 ? 1 : 256 / (ND * ND);                                                                \
+    hipLaunchKernelGGL(k_radial_spectra<ND>, dim3((unsigned)((n + FPB - 1) / FPB)), dim3(256), 0, st, fields, out, (int)n, K, \
+                       lo, a);                                                                                               \
+    break;                                                                                                                   \
+  }
+    RD_SPEC_CASE(8) RD_SPEC_CASE(16) RD_SPEC_CASE(24) RD_SPEC_CASE(32) RD_SPEC_CASE(48) RD_SPEC_CASE(64)
+#undef RD_SPEC_CASE
+    default: return -2;
+  }
+  return (int)hipGetLastError();
+}
+
+static void rd_lsd_grid(long n, long m, int* gx, int* gy) {
+  const long nti = (n + RD_LSD_TILE - 1) / RD_LSD_TILE, ntj = (m + RD_LSD_TILE - 1) / RD_LSD_TILE;
+  *gy = (int)nti;
+  *gx = (int)std::max(1L, std::min(ntj, (2048 + nti - 1) / nti));     // ~2048 workgroups; a function of (n, m) alone
+}
+
+extern "C" long rdgan_lsd_workspace_bytes(long n, long m) {
+  if (n < 1 || m < 1 || n > RD_LSD_MAXROWS || m > RD_LSD_MAXROWS) return -2;
+  int gx, gy;
+  rd_lsd_grid(n, m, &gx, &gy);
+  return (long)gx * gy * (long)sizeof(rd_lsd_partial);
+}
+
+extern "C" int rdgan_lsd_pairwise(const float* spec_a, const float* spec_b, long n, long m, int k, int exclude_diagonal,
+                                  float* dist, unsigned long long* hist, int nbins, float lo, float hi, double* moments,
+                                  void* workspace, long workspace_bytes, void* stream) {
+  if (!spec_a || !spec_b || n < 1 || m < 1 || n > RD_LSD_MAXROWS || m > RD_LSD_MAXROWS || k < 1 || k > RD_SPEC_MAXK) return -2;
+  if (!dist && !hist && !moments) return -2;
+  long lds = 2L * k * RD_LSD_TILE * (long)sizeof(float);
+  float scale = 0.f;
+  if (hist) {
+    if (nbins < 1 || !(lo < hi) || !std::isfinite(lo) || !std::isfinite(hi)) return -2;
+    scale = (float)nbins / (hi - lo);
+    if (!std::isfinite(scale)) return -2;
+    lds += 4L * (nbins + 4);
+  }
+  if (lds > RD_LSD_MAX_DYN_LDS) return -2;
+  int gx, gy;
+  rd_lsd_grid(n, m, &gx, &gy);
+  if (moments && (!workspace || workspace_bytes < rdgan_lsd_workspace_bytes(n, m))) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  if (hist) {
+    hipError_t e = hipMemsetAsync(hist, 0, sizeof(unsigned long long) * (nbins + 4), st);
+    if (e != hipSuccess) return (int)e;
+  }
+  rd_lsd_partial* part = moments ? (rd_lsd_partial*)workspace : nullptr;
+  hipLaunchKernelGGL(k_lsd_pairwise, dim3(gx, gy), dim3(256), (size_t)lds, st, spec_a, spec_b, (int)n, (int)m, k,
+                     exclude_diagonal ? 1 : 0, dist, hist, nbins, lo, hi, scale, part);
+  if (moments) hipLaunchKernelGGL(k_lsd_reduce, dim3(1), dim3(256), 0, st, part, gx * gy, moments);
   return (int)hipGetLastError();
 }
 

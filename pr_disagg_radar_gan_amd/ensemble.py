@@ -81,3 +81,44 @@ def crps_for_day(gen, real_precip, n_fake_per_real=1000, norm_scale=W.NORM_SCALE
     scale = scale.unsqueeze(0).expand(W.NHOURS, -1, -1).contiguous()
     crps = crps_ensemble_device(ens, real.to(dev), scale)
     return crps.mean(dim=(1, 2)).cpu().numpy()                    # crps_areamean, :190
+
+
+def generate_one_per_condition(gen, real_precip, seed=None, latent=None, chunk=1024, norm_scale=W.NORM_SCALE):
+    """The evaluation loop of generate_and_evaluate.py:403-417: one generated day per real day, each under that day's own
+    condition (daily sum / norm_scale), batched through the engine in chunks of its max_batch.  real_precip (n,24,nd,nd) mm/h.
+    Latent noise (n, 100) from the global numpy RNG as the reference draws it (:406), from a device generator when a seed is
+    given, or `latent`.  Returns (precip, ameans): precip (n,24,nd,nd) on the device = fractions * cond * norm_scale (:416-417),
+    the layout spectral.lsd_evaluation takes; ameans the hourly area means (:412-415), numpy (n,24), keys fraction_gen,
+    fraction_real, gen, real."""
+    real = torch.as_tensor(np.ascontiguousarray(real_precip, dtype=np.float32) if not isinstance(real_precip, torch.Tensor)
+                           else real_precip, dtype=torch.float32)
+    nd = gen.ndomain
+    if real.dim() != 4 or tuple(real.shape[1:]) != (W.NHOURS, nd, nd):
+        raise ValueError(f"real_precip must have shape (n, {W.NHOURS}, {nd}, {nd}), got {tuple(real.shape)}")
+    n = real.shape[0]
+    eng = models.get_engine(nd, min(chunk, n))
+    real = real.to(eng.device).contiguous()
+    if latent is not None:
+        z_all = torch.as_tensor(latent, dtype=torch.float32)
+        if tuple(z_all.shape) != (n, W.LATENT_DIM):
+            raise ValueError(f"latent must have shape ({n}, {W.LATENT_DIM}), got {tuple(z_all.shape)}")
+        z_all = z_all.to(eng.device)
+    elif seed is None:
+        z_all = torch.from_numpy(np.random.normal(size=(n, W.LATENT_DIM)).astype(np.float32)).to(eng.device)
+    else:
+        g = torch.Generator(device=eng.device); g.manual_seed(int(seed))
+        z_all = torch.randn((n, W.LATENT_DIM), generator=g, device=eng.device)
+    cond = real.sum(1) / norm_scale                                   # (n, nd, nd), normalised condition
+    slab = gen.device_slab(eng)
+    frac = torch.empty((n, W.NHOURS, nd, nd, 1), dtype=torch.float32, device=eng.device)
+    for i in range(0, n, eng.max_batch):
+        m = min(eng.max_batch, n - i)
+        eng.gen_forward(slab, z_all[i:i + m].contiguous(), cond[i:i + m].reshape(m, nd, nd, 1).contiguous(), out=frac[i:i + m])
+        eng.check_numerics()                     # reference T:349-350
+    frac = frac.view(n, W.NHOURS, nd, nd)
+    precip = frac * cond[:, None] * norm_scale
+    dsum = real.sum(1, keepdim=True)
+    real_frac = torch.where(dsum > 0, real / torch.where(dsum > 0, dsum, torch.ones_like(dsum)), torch.zeros_like(real))
+    ameans = {"fraction_gen": frac.mean(dim=(2, 3)).cpu().numpy(), "fraction_real": real_frac.mean(dim=(2, 3)).cpu().numpy(),
+              "gen": precip.mean(dim=(2, 3)).cpu().numpy(), "real": real.mean(dim=(2, 3)).cpu().numpy()}
+    return precip, ameans
