@@ -324,6 +324,30 @@ int rdgan_lsd_pairwise(const float* spec_a, const float* spec_b, long n, long m,
                        unsigned long long* hist, int nbins, float lo, float hi, double* moments, void* workspace,
                        long workspace_bytes, void* stream);
 
+/* RainFARM baseline, rainfarm/rainfarm_temporal_downscaling.py (R below); nd 8/16/24/32/48/64, 24 hours; -2 for any other nd.
+ * rdgan_rainfarm_classes: C = (nd/2 + 1)^2 + 13, the length of the class arrays of rdgan_rainfarm_slope_stats.
+ * rdgan_rainfarm_slope_stats: the statistics behind estimate_alpha (R:54-81) and estimate_beta (R:22-51), in fp64 arithmetic, for
+ * samples [n][24][nd][nd] fp32 (16-byte aligned): per frequency class, the number of kept points (counts, uint64) and the sum of
+ * log(|F|^2) over them (sums, fp64).  Classes 0 .. (nd/2+1)^2 - 1: the 2-D DFT of every hour plane, class |a| (nd/2 + 1) + |b| for
+ * the integer fftfreq indices (a, b) of the point; then 13 classes |m| = 0 .. 12 of the 24-point DFT of every pixel series.  A point
+ * is kept when its power is > 0 and its frequency is not 0.  Repeated calls agree bit for bit.  n <= 2^24; workspace of
+ * rdgan_rainfarm_stats_workspace_bytes(n, nd).  The fit (_log_slope, R:6-19) runs on the host over the classes. */
+int rdgan_rainfarm_classes(int nd);
+long rdgan_rainfarm_stats_workspace_bytes(long n, int nd);
+int rdgan_rainfarm_slope_stats(const float* samples, long n, int nd, unsigned long long* counts, double* sums, void* workspace,
+                               long workspace_bytes, void* stream);
+/* rdgan_rainfarm_generate: downscale_spatiotemporal (R:84-125) for n members in fp32.  amplitudes [24][nd][nd] complex (re, im fp32
+ * pairs) = R's sqrt(om^-beta k^-alpha) with its zeroing (R:103-113, built on the host); precip [nd][nd] for every member
+ * (precip_per_member = 0) or [n][nd][nd]; phases u from uniforms [n][24][nd][nd] (fp32, or fp64 when uniforms_fp64; R:103's
+ * np.random.rand) or, when uniforms is NULL, from the counter RNG: u = rd_uniform(rd_member_key(rd_make_key(seed,
+ * RD_STREAM_RAINFARM), first_member + i), e) for member i and element e = (t nd + y) nd + x (rdgan_rng.h).
+ * out [n][24][nd][nd] = r precip / sum_t r, r = exp(g / std(g)), g = Re ifftn(amplitudes e^{2 pi i u}) (R:114-122); exact 0 where
+ * precip is 0.  n <= 2^24; workspace of rdgan_rainfarm_gen_workspace_bytes(n). */
+long rdgan_rainfarm_gen_workspace_bytes(long n);
+int rdgan_rainfarm_generate(const float* amplitudes, const float* precip, int precip_per_member, const void* uniforms,
+                            int uniforms_fp64, uint64_t seed, long first_member, float* out, long n, int nd,
+                            void* workspace, long workspace_bytes, void* stream);
+
 /* Op-level entry points used by the parity tests (tests/test_hip_ops.py). */
 /* Conv3D forward, TF semantics.  x [B,D,H,W,Cin] -> y [B,Do,Ho,Wo,Cout]; upsample=1 folds
  * UpSampling3D(2) in front (T:330-331); pad = zero padding before each axis; Cin%4==0,

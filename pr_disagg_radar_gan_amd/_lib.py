@@ -62,6 +62,14 @@ SIGNATURES = {
     "rdgan_lsd_pairwise": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_f32p,
                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_long, c_stream]),
+    "rdgan_rainfarm_classes": (ctypes.c_int, [ctypes.c_int]),
+    "rdgan_rainfarm_stats_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_int]),
+    "rdgan_rainfarm_slope_stats": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_long, c_stream]),
+    "rdgan_rainfarm_gen_workspace_bytes": (ctypes.c_long, [ctypes.c_long]),
+    "rdgan_rainfarm_generate": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64,
+                                               ctypes.c_long, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
+                                               c_stream]),
     "rdgan_op_conv3d": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p] + [ctypes.c_int] * 14 + [c_stream]),
     "rdgan_op_conv3d_bf16": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p] + [ctypes.c_int] * 14 + [c_stream]),
     "rdgan_op_conv3d_dgrad": (ctypes.c_int, [c_f32p, c_f32p, c_f32p] + [ctypes.c_int] * 13 + [c_stream]),

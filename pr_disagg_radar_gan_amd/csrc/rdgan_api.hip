@@ -33,6 +33,7 @@
 #include "rdgan_d1fwd16.hip.h"
 #include "rdgan_g9bwd16.hip.h"
 #include "rdgan_spectral.hip.h"
+#include "rdgan_rainfarm.hip.h"
 static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
 // k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
 static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
@@ -3089,6 +3090,115 @@ extern "C" int rdgan_lsd_pairwise(const float* spec_a, const float* spec_b, long
   hipLaunchKernelGGL(k_lsd_pairwise, dim3(gx, gy), dim3(256), (size_t)lds, st, spec_a, spec_b, (int)n, (int)m, k,
                      exclude_diagonal ? 1 : 0, dist, hist, nbins, lo, hi, scale, part);
   if (moments) hipLaunchKernelGGL(k_lsd_reduce, dim3(1), dim3(256), 0, st, part, gx * gy, moments);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// RainFARM baseline (rdgan_rainfarm.hip.h)
+// ------------------------------------------------------------------------------------
+extern "C" int rdgan_rainfarm_classes(int nd) {
+  if (!rd_rf_nd_ok(nd)) return -2;
+  return (nd / 2 + 1) * (nd / 2 + 1) + RD_RF_TCLASS;
+}
+
+static void rd_rf_stat_grid(long n, int* gs, int* gt) {
+  *gs = (int)std::min((long)RD_RF_STAT_WG, n * RD_RF_NT);
+  *gt = (int)std::min((long)RD_RF_STAT_WG, n);
+}
+
+extern "C" long rdgan_rainfarm_stats_workspace_bytes(long n, int nd) {
+  if (!rd_rf_nd_ok(nd) || n < 1 || n > RD_RF_MAXN) return -2;
+  int gs, gt;
+  rd_rf_stat_grid(n, &gs, &gt);
+  const long nc = (long)(nd / 2 + 1) * (nd / 2 + 1);
+  return ((long)gs * nc + (long)gt * RD_RF_TCLASS) * (long)sizeof(rd_rf_stat);
+}
+
+extern "C" int rdgan_rainfarm_slope_stats(const float* samples, long n, int nd, unsigned long long* counts, double* sums,
+                                          void* workspace, long workspace_bytes, void* stream) {
+  if (!samples || !counts || !sums || !workspace || ((uintptr_t)samples & 15)) return -2;
+  const long need = rdgan_rainfarm_stats_workspace_bytes(n, nd);
+  if (need < 0 || workspace_bytes < need) return -2;
+  rd_rf_slope_args a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < nd; ++j) {
+    const double th = -2.0 * M_PI * (double)j / (double)nd;
+    a.tw_re[j] = cos(th);
+    a.tw_im[j] = sin(th);
+  }
+  for (int j = 0; j < RD_RF_NT; ++j) {
+    const double th = -2.0 * M_PI * (double)j / (double)RD_RF_NT;
+    a.t24_re[j] = cos(th);
+    a.t24_im[j] = sin(th);
+  }
+  int gs, gt;
+  rd_rf_stat_grid(n, &gs, &gt);
+  const int nc = (nd / 2 + 1) * (nd / 2 + 1);
+  rd_rf_stat* ps = (rd_rf_stat*)workspace;
+  rd_rf_stat* pt = ps + (long)gs * nc;
+  hipStream_t st = (hipStream_t)stream;
+  const long nplanes = n * RD_RF_NT;
+  switch (nd) {
+#define RD_RF_STATS_CASE(ND)                                                                                                 \
+  case ND:                                                                                                                   \
+    hipLaunchKernelGGL(k_rf_spatial_stats<ND>, dim3(gs), dim3(256), 0, st, samples, nplanes, ps, a);                        \
+    hipLaunchKernelGGL(k_rf_temporal_stats<ND>, dim3(gt), dim3(256), 0, st, samples, n, pt, a);                             \
+    break;
+    RD_RF_STATS_CASE(8) RD_RF_STATS_CASE(16) RD_RF_STATS_CASE(24) RD_RF_STATS_CASE(32) RD_RF_STATS_CASE(48) RD_RF_STATS_CASE(64)
+#undef RD_RF_STATS_CASE
+    default: return -2;
+  }
+  hipLaunchKernelGGL(k_rf_stats_reduce, dim3((nc + 255) / 256), dim3(256), 0, st, ps, gs, nc, counts, sums);
+  hipLaunchKernelGGL(k_rf_stats_reduce, dim3(1), dim3(256), 0, st, pt, gt, RD_RF_TCLASS, counts + nc, sums + nc);
+  return (int)hipGetLastError();
+}
+
+extern "C" long rdgan_rainfarm_gen_workspace_bytes(long n) {
+  if (n < 1 || n > RD_RF_MAXN) return -2;
+  return n * RD_RF_NT * (long)sizeof(float2);
+}
+
+extern "C" int rdgan_rainfarm_generate(const float* amplitudes, const float* precip, int precip_per_member, const void* uniforms,
+                                       int uniforms_fp64, uint64_t seed, long first_member, float* out, long n, int nd,
+                                       void* workspace, long workspace_bytes, void* stream) {
+  if (!rd_rf_nd_ok(nd) || !amplitudes || !precip || !out || !workspace || first_member < 0) return -2;
+  const long need = rdgan_rainfarm_gen_workspace_bytes(n);
+  if (need < 0 || workspace_bytes < need || ((uintptr_t)amplitudes & 7)) return -2;
+  rd_rf_gen_args a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < nd; ++j) {
+    const double th = 2.0 * M_PI * (double)j / (double)nd;
+    a.tw_re[j] = (float)cos(th);
+    a.tw_im[j] = (float)sin(th);
+  }
+  for (int j = 0; j < RD_RF_NT; ++j) {
+    const double th = 2.0 * M_PI * (double)j / (double)RD_RF_NT;
+    a.t24_re[j] = (float)cos(th);
+    a.t24_im[j] = (float)sin(th);
+  }
+  const int usrc = uniforms ? (uniforms_fp64 ? 2 : 1) : 0;
+  const uint32_t key = rd_make_key(seed, RD_STREAM_RAINFARM);
+  const float2* amp = (const float2*)amplitudes;
+  float2* stats = (float2*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned nb = (unsigned)(n * RD_RF_NT);
+  switch (nd) {
+#define RD_RF_GEN_CASE(ND)                                                                                                   \
+  case ND: {                                                                                                                 \
+    constexpr int NT = rd_rf_gen_shape<ND>::NT;                                                                              \
+    if (usrc == 0)                                                                                                           \
+      hipLaunchKernelGGL((k_rf_gen_planes<ND, 0>), dim3(nb), dim3(NT), 0, st, amp, uniforms, key, first_member, out, stats, a); \
+    else if (usrc == 1)                                                                                                      \
+      hipLaunchKernelGGL((k_rf_gen_planes<ND, 1>), dim3(nb), dim3(NT), 0, st, amp, uniforms, key, first_member, out, stats, a); \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((k_rf_gen_planes<ND, 2>), dim3(nb), dim3(NT), 0, st, amp, uniforms, key, first_member, out, stats, a); \
+    hipLaunchKernelGGL(k_rf_gen_finish<ND>, dim3((unsigned)n), dim3(NT), 0, st, out, precip, precip_per_member ? 1 : 0, stats); \
+    break;                                                                                                                   \
+  }
+    RD_RF_GEN_CASE(8) RD_RF_GEN_CASE(16) RD_RF_GEN_CASE(24) RD_RF_GEN_CASE(32) RD_RF_GEN_CASE(48) RD_RF_GEN_CASE(64)
+#undef RD_RF_GEN_CASE
+    default: return -2;
+  }
   return (int)hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 
 #define RD_STREAM_D1 1u
 #define RD_STREAM_ALPHA 5u
+#define RD_STREAM_RAINFARM 6u       // phases of the RainFARM generation (rdgan_rainfarm.hip.h)
 #define RD_DROP_THRESHOLD 64u          // 0.25 * 2^8: a byte of the hash word decides one element
 
 #if defined(__HIPCC__)
@@ -33,4 +34,12 @@ RD_HD static inline uint32_t rd_drop_word(uint32_t key, uint32_t idx) { return r
 RD_HD static inline int rd_drop_keep(uint32_t word, uint32_t e) { return ((word >> (8u * (e & 3u))) & 0xFFu) >= RD_DROP_THRESHOLD; }
 RD_HD static inline float rd_drop_scale(uint32_t key, uint32_t idx) {
   return rd_drop_keep(rd_drop_word(key, idx), idx) ? (1.0f / 0.75f) : 0.0f;
+}
+// Per-member keys (the RainFARM phases): member m of a seeded ensemble draws u(m, e) = rd_uniform(rd_member_key(base, m), e) with
+// base = rd_make_key(seed, RD_STREAM_RAINFARM) and e the element's index inside the member ((t nd + i) nd + j for a (24, nd, nd)
+// day).  A value depends on (seed, m, e) only -- not on how members are split into launches or calls -- and m is 64-bit, so
+// ensembles far beyond 2^32 elements in all never reuse a counter.
+//     rd_member_key(base, m) = mix(base ^ mix(lo32(m) ^ mix(hi32(m) ^ 0x9E3779B9)))
+RD_HD static inline uint32_t rd_member_key(uint32_t base, uint64_t member) {
+  return rd_mix32(base ^ rd_mix32((uint32_t)member ^ rd_mix32((uint32_t)(member >> 32) ^ 0x9E3779B9u)));
 }
