@@ -74,6 +74,19 @@ int rdgan_critic_grad_after(rdgan_handle* h, const float* critic_params, const f
                             const float* x_real, const float* cond, const float* z, uint64_t seed,
                             float* grad_out, int B, void* critic_ready_event, void* stream);
 
+/* rdgan_critic_grad_after for the LAST critic step of an iteration, told the batch of the generator step that follows it
+ * (gen_z [gen_B,100], gen_cond [gen_B,nd,nd,1]; both NULL = rdgan_critic_grad_after).  With option "gen_fwd_ahead" on
+ * (the default with fp32 storage) the call also issues that step's generator forward (gen_params), on a stream of the handle's own, forked right after the
+ * critic input is built, so that it runs beside the rest of the critic step and whatever the caller issues next (its Adam).
+ * The next rdgan_gen_grad(_after) on the handle with the same gen_params pointer and content version, z, cond pointers and
+ * batch size skips its own forward and waits for that one instead: same kernels on the same data, results bit-identical to
+ * the option off.  A different batch, pointer or version, or any other call on the handle first, drops it (the generator step
+ * then runs its own forward).  The caller keeps gen_params, gen_z and gen_cond valid and unchanged until that generator step. */
+int rdgan_critic_grad_ahead(rdgan_handle* h, const float* critic_params, const float* gen_params,
+                            const float* x_real, const float* cond, const float* z, uint64_t seed,
+                            float* grad_out, int B, void* critic_ready_event, const float* gen_z, const float* gen_cond,
+                            int gen_B, void* stream);
+
 /* Gradient half of generator_model.train_on_batch([latent, cond], valid) (T:482; graph T:395-408):
  * loss = mean(-D(G(z,c))), critic frozen, its dropout active.
  * grad_out[0:n_gen_params], grad_out[n .. n+8) = {loss, 0, 0, 0, nonfinite_flag, 0, 0, 0}. */
@@ -240,6 +253,9 @@ int rdgan_critic_param_layout(const rdgan_handle* h, long* offsets, long* sizes)
  * caller's stream and ordered against it by events (fork at entry, joins in front of the first reader / at the end of the
  * call): ~50 launches of 5-30 us per iteration leave the critical path.  The call's contract is unchanged (everything is
  * complete when `stream` is); same kernels on the same data, results bit-identical to 0.
+ * "gen_fwd_ahead" (default -1 = by storage mode: on with fp32 storage, off in the bf16 mode): rdgan_critic_grad_ahead issues the
+ * next generator step's forward beside the critic step's tail (see there); 0 = that call is rdgan_critic_grad_after, the schedule
+ * of the entries without the generator batch; 1 = on in both modes.
  * "sample_offset" (default 0): global index of this rank's first sample.  RandomWeightedAverage's alpha (T:222-223) of
  * local sample k is uniform(key(seed, ALPHA), sample_offset + k), so ranks that share a seed draw the alphas of the
  * global batch (used by the data-parallel equivalence tests; the dropout masks stay keyed by the local element index).

@@ -36,6 +36,8 @@ SIGNATURES = {
                                       ctypes.c_int, c_stream]),
     "rdgan_critic_grad_after": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_uint64,
                                                c_f32p, ctypes.c_int, ctypes.c_void_p, c_stream]),
+    "rdgan_critic_grad_ahead": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_uint64,
+                                               c_f32p, ctypes.c_int, ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, c_stream]),
     "rdgan_gen_grad_after": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_uint64, c_f32p,
                                             ctypes.c_int, ctypes.c_void_p, c_stream]),
     "rdgan_adam": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_float, ctypes.c_float,

@@ -141,6 +141,30 @@ struct rdgan_handle : RdGeom {     // geometry + parameter layout: rdgan_hostpla
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_cw = nullptr, ev_g[4] = {nullptr, nullptr, nullptr, nullptr};
   int* d_flag;
+  // Generator forward ahead (option "gen_fwd_ahead", default on with fp32 storage; rdgan_critic_grad_ahead): the last critic
+  // step of an iteration issues the NEXT generator step's forward on a stream of its own, forked right after the critic input
+  // is built (from there
+  // on the critic step reads neither h->fake nor any generator activation), beside the critic step's tail and the caller's
+  // Adam.  The generator step then skips its forward and waits for ev_ahead_done in front of its critic forward.  Same kernels,
+  // same plans and splits: results are bit-identical to the option off.  What the early forward writes, against what the rest
+  // of the critic step touches (compute stream st, side stream for the column sums):
+  //   buffer                                   early forward (stream `ahead`)   critic step tail (st / side)
+  //   xcat, xcat16, h0..h3, r1..r3, fE, fgS, P9, fake   written                  not touched (fake read only by the build, before the fork)
+  //   generator weight forms (uncached only)    written                          not touched
+  //   kpartial (split-K partials)               kpartial_ahead (own copy)        kpartial
+  //   non-finite flag                           flag_ahead (own copy)            d_flag (read by k_critic_losses)
+  //   cin, dh, du, v, P1, g0, gpv, gp_part, wpartial, cpartial, dW1P, dw6_part, g1bits, critic forms: tail only
+  // Every other entry that uses the workspace first waits for a forward still pending (ahead_drain).
+  int fwd_ahead = -1;             // 1 on, 0 off, -1 by storage mode: on with fp32 storage (the metric: 11.03 -> 10.77 ms), off in the
+                                  // bf16 mode, whose critic tail leaves no CUs idle (BASELINE configs[2] / [4] shard 0.3-0.6 % slower)
+  hipStream_t ahead = nullptr;
+  hipEvent_t ev_ahead_fork = nullptr, ev_ahead_done = nullptr;
+  float* kpartial_ahead = nullptr;
+  int* flag_ahead = nullptr;
+  bool ahead_pending = false;     // a forward has been issued and not yet consumed / waited for
+  const float *ahead_gp = nullptr, *ahead_z = nullptr, *ahead_cond = nullptr;
+  int ahead_B = 0;
+  uint64_t ahead_gver = 0;
   // kernels whose dynamic-LDS limit has been raised on THIS handle's device (hipFuncSetAttribute is per device; keeping the
   // record per handle rather than per process makes two handles on two devices, or on two threads, independent)
   std::unordered_set<const void*> lds_attr_done;
@@ -910,6 +934,7 @@ extern "C" int rdgan_create(rdgan_handle** out, int ndomain, int n_cond_channels
     carve(h->wpartial, h->wpartial_cap);
     carve(h->cpartial, h->cpartial_cap);
     carve(h->kpartial, h->kpartial_cap);
+    carve(h->kpartial_ahead, h->kpartial_cap);       // (same capacity: the split-K choice tests against kpartial_cap)
     h->DWT[0] = h->DWT[1] = nullptr;
     for (int l = 2; l <= 4; ++l) carve(h->DWT[l], 27L * dch[l - 1] * dch[l]);
     carve(h->W1T, 64 * h->ldp1);
@@ -968,7 +993,7 @@ extern "C" int rdgan_create(rdgan_handle** out, int ndomain, int n_cond_channels
       }
       carve(h->fdU, 48L * 256 * 256); carve(h->fUT, 48L * 256 * 256);
     }
-    { float* f = nullptr; carve(f, 64); if (pass == 1) h->d_flag = (int*)f; }
+    { float* f = nullptr; carve(f, 64); if (pass == 1) { h->d_flag = (int*)f; h->flag_ahead = (int*)f + 32; } }
     carve(h->g9b_tmp, 64);
     carve(h->ubias_part, 32 * 8 * 64);
     carve(h->gp_part, (size_t)MB * 64);
@@ -986,6 +1011,12 @@ extern "C" int rdgan_create(rdgan_handle** out, int ndomain, int n_cond_channels
     hipEvent_t* evs[] = {&h->ev_fork, &h->ev_join, &h->ev_cw, &h->ev_g[1], &h->ev_g[2], &h->ev_g[3]};
     for (hipEvent_t* e2 : evs) ok = ok && hipEventCreateWithFlags(e2, hipEventDisableTiming) == hipSuccess;
     if (!ok) { h->side_on = 0; (void)hipGetLastError(); }
+    // the early generator forward's stream: a compute stream of its own (not the side stream, whose weight forms and column
+    // sums must not queue behind a 2 ms forward)
+    bool ok2 = hipStreamCreateWithFlags(&h->ahead, hipStreamNonBlocking) == hipSuccess;
+    ok2 = ok2 && hipEventCreateWithFlags(&h->ev_ahead_fork, hipEventDisableTiming) == hipSuccess;
+    ok2 = ok2 && hipEventCreateWithFlags(&h->ev_ahead_done, hipEventDisableTiming) == hipSuccess;
+    if (!ok2) { h->ahead = nullptr; (void)hipGetLastError(); }
   }
   *out = h;
   return 0;
@@ -994,7 +1025,9 @@ extern "C" int rdgan_create(rdgan_handle** out, int ndomain, int n_cond_channels
 extern "C" void rdgan_destroy(rdgan_handle* h) {
   if (!h) return;
   if (h->side) { (void)hipStreamSynchronize(h->side); (void)hipStreamDestroy(h->side); }
-  for (hipEvent_t e2 : {h->ev_fork, h->ev_join, h->ev_cw, h->ev_g[1], h->ev_g[2], h->ev_g[3]}) if (e2) (void)hipEventDestroy(e2);
+  if (h->ahead) { (void)hipStreamSynchronize(h->ahead); (void)hipStreamDestroy(h->ahead); }
+  for (hipEvent_t e2 : {h->ev_fork, h->ev_join, h->ev_cw, h->ev_g[1], h->ev_g[2], h->ev_g[3], h->ev_ahead_fork, h->ev_ahead_done})
+    if (e2) (void)hipEventDestroy(e2);
   for (auto& r : h->launch_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
   for (int t = 0; t < RDGAN_NUM_TAGS; ++t) {
     for (auto e : h->ev_start[t]) (void)hipEventDestroy(e);
@@ -1065,6 +1098,7 @@ extern "C" int rdgan_set_option(rdgan_handle* h, const char* name, int value) {
   }
   if (!strcmp(name, "split3")) { h->split3 = value ? 1 : 0; return 0; }
   if (!strcmp(name, "side_stream")) { h->side_on = (value && h->side) ? 1 : 0; return 0; }
+  if (!strcmp(name, "gen_fwd_ahead")) { h->fwd_ahead = value < 0 ? -1 : (value ? 1 : 0); return 0; }     // -1 = by storage mode
   if (!strcmp(name, "edge_kernels")) { h->edge_kernels = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }
   if (!strcmp(name, "sample_offset")) { if (value < 0) return bad_arg(h, "set_option: sample_offset < 0"); h->sample_offset = value; return 0; }
   if (!strcmp(name, "ws_ksplit")) { h->ws_ksplit = value < 0 ? 0 : (value > 8 ? 8 : value); return 0; }   // > 1 = force (tests)
@@ -1592,10 +1626,39 @@ static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, co
   return 0;
 }
 
+static bool fwd_ahead_on(const rdgan_handle* h) { return h->ahead && h->ev_ahead_done && (h->fwd_ahead < 0 ? !h->a16 : h->fwd_ahead); }
+
+// `st` waits for an early generator forward still in flight, which is then dropped: every entry that uses the workspace
+// calls this first, except the generator step that consumes the forward
+static int ahead_drain(rdgan_handle* h, hipStream_t st) {
+  if (!h->ahead_pending) return 0;
+  h->ahead_pending = false;
+  RD_CHECK(h, hipStreamWaitEvent(st, h->ev_ahead_done, 0));
+  return 0;
+}
+
+// the early generator forward (see the handle): forked from `st` behind everything issued there so far, on the handle's own
+// stream, with its own split-K slab and non-finite flag.  The arithmetic is that of the forward in rdgan_gen_grad_after.
+static int ahead_issue(rdgan_handle* h, const float* gp, const float* z, const float* cond, int B, hipStream_t st) {
+  RD_CHECK(h, hipEventRecord(h->ev_ahead_fork, st));
+  RD_CHECK(h, hipStreamWaitEvent(h->ahead, h->ev_ahead_fork, 0));
+  std::swap(h->kpartial, h->kpartial_ahead);
+  std::swap(h->d_flag, h->flag_ahead);
+  const int rc = gen_forward_impl(h, gp, z, cond, h->fake, B, h->ahead, h->ahead);
+  std::swap(h->kpartial, h->kpartial_ahead);
+  std::swap(h->d_flag, h->flag_ahead);
+  RD_TRY(rc);
+  RD_CHECK(h, hipEventRecord(h->ev_ahead_done, h->ahead));
+  h->ahead_pending = true;
+  h->ahead_gp = gp; h->ahead_z = z; h->ahead_cond = cond; h->ahead_B = B; h->ahead_gver = h->gver_in;
+  return 0;
+}
+
 extern "C" int rdgan_gen_forward(rdgan_handle* h, const float* gen_params, const float* z, const float* cond,
                                  float* out, int B, void* stream) {
   if (!h || !gen_params || !z || !cond || !out) return bad_arg(h, "gen_forward: null pointer");
   if (B < 1 || B > h->MB) return bad_arg(h, "gen_forward: B outside [1, max_batch]");
+  RD_TRY(ahead_drain(h, (hipStream_t)stream));
   return gen_forward_impl(h, gen_params, z, cond, out, B, (hipStream_t)stream, side_fork(h, (hipStream_t)stream));
 }
 
@@ -1888,6 +1951,7 @@ extern "C" int rdgan_critic_forward(rdgan_handle* h, const float* critic_params,
   if (!h || !critic_params || !sample || !cond || !out) return bad_arg(h, "critic_forward: null pointer");
   if (B < 1 || B > h->NB) return bad_arg(h, "critic_forward: B outside [1, 3*max_batch]");
   hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ahead_drain(h, st));
   h->gate_keep_B = 0;
   RD_TRY(a16_check(h));
   if (h->a16) RD_TRY(prep_critic_weights(h, critic_params, st));      // (also makes the bf16 kernels of layers 2-4)
@@ -1911,9 +1975,19 @@ extern "C" int rdgan_critic_grad(rdgan_handle* h, const float* dp, const float* 
 extern "C" int rdgan_critic_grad_after(rdgan_handle* h, const float* dp, const float* gp, const float* x_real,
                                        const float* cond, const float* z, uint64_t seed, float* grad, int B,
                                        void* critic_ready_event, void* stream) {
+  return rdgan_critic_grad_ahead(h, dp, gp, x_real, cond, z, seed, grad, B, critic_ready_event, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int rdgan_critic_grad_ahead(rdgan_handle* h, const float* dp, const float* gp, const float* x_real,
+                                       const float* cond, const float* z, uint64_t seed, float* grad, int B,
+                                       void* critic_ready_event, const float* gen_z, const float* gen_cond, int gen_B,
+                                       void* stream) {
   if (!h || !dp || !gp || !x_real || !cond || !z || !grad) return bad_arg(h, "critic_grad: null pointer");
   if (B < 1 || B > h->MB) return bad_arg(h, "critic_grad: B outside [1, max_batch]");
+  if ((gen_z != nullptr) != (gen_cond != nullptr)) return bad_arg(h, "critic_grad: gen_z and gen_cond go together");
+  if (gen_z && (gen_B < 1 || gen_B > h->MB)) return bad_arg(h, "critic_grad: gen_B outside [1, max_batch]");
   hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ahead_drain(h, st));
   const int NBt = 3 * B;
   const int use_drop = seed != 0;
   // fake = G(z, cond), generator frozen (T:363,370): reads no critic weight, so it is issued in front of the wait for
@@ -1931,6 +2005,8 @@ extern "C" int rdgan_critic_grad_after(rdgan_handle* h, const float* dp, const f
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
     launch_build_critic_input(h, x_real, h->fake, cond, B, 0, rd_make_key(seed, RD_STREAM_ALPHA), (uint32_t)h->sample_offset, st);
   }
+  // the next generator step's forward, beside everything below (nothing below reads a generator buffer)
+  if (gen_z && fwd_ahead_on(h)) RD_TRY(ahead_issue(h, gp, gen_z, gen_cond, gen_B, st));
   RD_TRY(critic_forward_impl(h, dp, NBt, seed, st));           // T:372,373,379 as one batch
   RD_TRY(critic_dgrad_chain(h, dp, NBt, B, 0, seed, st));       // dL/dh for real|fake, dD/dh for x_hat
   // bias gradients: only the real|fake passes reach the loss through the bias (the penalty term does not).  Column sums of
@@ -2077,6 +2153,12 @@ extern "C" int rdgan_gen_grad_after(rdgan_handle* h, const float* dp, const floa
   if (B < 1 || B > h->MB) return bad_arg(h, "gen_grad: B outside [1, max_batch]");
   hipStream_t st = (hipStream_t)stream;
   const int nd = h->nd;
+  // the forward issued by the last critic step (rdgan_critic_grad_ahead) is this step's when it was made from the same
+  // generator slab (pointer and content version), latent and condition buffers and batch size; otherwise it is dropped
+  const bool ahead = h->ahead_pending && gp == h->ahead_gp && z == h->ahead_z && cond == h->ahead_cond && B == h->ahead_B &&
+                     h->gver_in == h->ahead_gver;
+  if (!ahead) RD_TRY(ahead_drain(h, st));
+  h->ahead_pending = false;
   h->gate_keep_B = 0;
   if (!h->collapse)
     for (int l = 1; l <= 3; ++l)
@@ -2084,10 +2166,14 @@ extern "C" int rdgan_gen_grad_after(rdgan_handle* h, const float* dp, const floa
   // the generator forward reads no critic weight: the last critic update (all-reduce + Adam on the caller's other
   // stream) hides behind it; everything below the wait reads them
   hipStream_t ws = side_fork(h, st);                    // weight-only kernels beside the generator forward (see rdgan_critic_grad_after)
-  RD_TRY(gen_forward_impl(h, gp, z, cond, h->fake, B, st, ws));
+  if (!ahead) RD_TRY(gen_forward_impl(h, gp, z, cond, h->fake, B, st, ws));
   if (critic_ready_event) RD_CHECK(h, hipStreamWaitEvent(ws, (hipEvent_t)critic_ready_event, 0));
   RD_TRY(prep_critic_weights(h, dp, ws));
   RD_TRY(side_join(h, st, h->ev_cw));
+  if (ahead) {      // the early forward's outputs, and its non-finite flag as this call's
+    RD_CHECK(h, hipStreamWaitEvent(st, h->ev_ahead_done, 0));
+    std::swap(h->d_flag, h->flag_ahead);
+  }
   {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
     launch_build_critic_input(h, nullptr, h->fake, cond, B, 1, 0u, 0u, st);
@@ -2925,6 +3011,7 @@ __global__ void k_bytes_to_f32(const unsigned char* in, float* out, long n) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = (float)in[i];
 }
 extern "C" int rdgan_debug_activation(rdgan_handle* h, int which, float* out, long n, void* stream) {
+  if (h) RD_TRY(ahead_drain(h, (hipStream_t)stream));
   if (h && out && which == 8 && n >= 1) {      // test hook: layer 1's packed gate bytes (16 per row) as floats
     if (!h->g1bits || n > (long)h->NB * h->dL[1] * 16) return bad_arg(h, "debug_activation: no gate bytes");
     hipLaunchKernelGGL(k_bytes_to_f32, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, h->g1bits, out, n);

@@ -140,10 +140,15 @@ class Engine:
         """hipEvent_t of a recorded torch.cuda.Event (None -> NULL)"""
         return ctypes.c_void_p(ev.cuda_event if ev is not None else 0)
 
+    forward_ahead = True        # critic_grad takes gen_batch (WGANGPTrainer passes it to the last critic step of an iteration)
+
     def critic_grad(self, critic_params, gen_params, x_real, cond, z, seed, grad_out=None, critic_ready=None,
-                    gen_version=0, critic_version=0):
+                    gen_version=0, critic_version=0, gen_batch=None):
         """critic_ready: torch.cuda.Event recorded (on another stream) behind the last update of critic_params; the
-        current stream waits for it after the generator forward (rdgan_critic_grad_after)."""
+        current stream waits for it after the generator forward (rdgan_critic_grad_after).
+        gen_batch: (z, cond) of the generator step that follows this critic step with the same gen_params: with option
+        "gen_fwd_ahead" on (the default with fp32 storage) its generator forward runs beside this step's tail
+        (rdgan_critic_grad_ahead); keep both tensors unchanged until that gen_grad call."""
         B = x_real.shape[0]
         nd = self.ndomain
         self._check_batch(B, self.max_batch)
@@ -155,10 +160,20 @@ class Engine:
         if grad_out is None:
             grad_out = torch.empty(self.n_critic + LOSS_SLOTS, dtype=torch.float32, device=self.device)
         _chk_tensor(grad_out, (self.n_critic + LOSS_SLOTS,), "grad_out")
+        gz = gc = None
+        gB = 0
+        if gen_batch is not None:
+            gz, gc = gen_batch
+            gB = gz.shape[0]
+            self._check_batch(gB, self.max_batch)
+            _chk_tensor(gz, (gB, W.LATENT_DIM), "gen_batch z")
+            _chk_tensor(gc, (gB, nd, nd, self.n_cond_channels), "gen_batch cond")
         self._versions(gen_version, critic_version)
-        _lib.check(self.lib.rdgan_critic_grad_after(self._h, _ptr(critic_params), _ptr(gen_params), _ptr(x_real), _ptr(cond),
+        _lib.check(self.lib.rdgan_critic_grad_ahead(self._h, _ptr(critic_params), _ptr(gen_params), _ptr(x_real), _ptr(cond),
                                                     _ptr(z), ctypes.c_uint64(seed), _ptr(grad_out), B,
-                                                    self._event_handle(critic_ready), self._stream()),
+                                                    self._event_handle(critic_ready),
+                                                    ctypes.c_void_p(gz.data_ptr() if gz is not None else 0),
+                                                    ctypes.c_void_p(gc.data_ptr() if gc is not None else 0), gB, self._stream()),
                    self._h, "rdgan_critic_grad")
         return grad_out
 

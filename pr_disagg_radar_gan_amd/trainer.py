@@ -96,6 +96,7 @@ class WGANGPTrainer:
         self.g_ready = None
         self._native_collectives = None
         self._native_verified = set()   # slabs whose first native sharded exchange has been checked against an all-reduce
+        self._gen_batch_next = None     # iteration(): the generator batch for the last critic step (critic_step's gen_batch)
 
     def weights_changed(self, which="gd"):
         """Call after writing a weight slab from outside (set_weights, a checkpoint load): its forms are rebuilt on next use."""
@@ -292,19 +293,26 @@ class WGANGPTrainer:
         """the gradient slab the engine writes: n gradients + 8 loss slots (the first n + 8 floats of the padded buffer)"""
         return getattr(self, which + "grad")[:self._pad[which][0] + LOSS_SLOTS]
 
-    def critic_step(self, x_real, cond, z, seed=None):
+    def critic_step(self, x_real, cond, z, seed=None, gen_batch=None):
         """critic_model.train_on_batch([X_real, cond_real, latent], [valid, fake, dummy]) (reference :472).
-        Returns the device tensor [total, valid, fake, gp, nonfinite] averaged over ranks."""
+        Returns the device tensor [total, valid, fake, gp, nonfinite] averaged over ranks.
+        gen_batch: (z, cond) of the gen_step that comes next (the last critic step of an iteration): an engine that can
+        (Engine.forward_ahead) runs that step's generator forward beside this step's tail; results are unchanged."""
         seed = self._next_seed() if seed is None else seed
+        if gen_batch is None:
+            gen_batch, self._gen_batch_next = self._gen_batch_next, None
+        kw = self._ver()
+        if gen_batch is not None and getattr(self.eng, "forward_ahead", False):
+            kw["gen_batch"] = tuple(gen_batch)
         if not self.overlap:
-            self.eng.critic_grad(self.dparams, self.gparams, x_real, cond, z, seed, grad_out=self._slab("d"), **self._ver())
+            self.eng.critic_grad(self.dparams, self.gparams, x_real, cond, z, seed, grad_out=self._slab("d"), **kw)
             return self._update("d")
         cur = torch.cuda.current_stream(self.dparams.device)
         if self.g_ready is not None:
             cur.wait_event(self.g_ready)               # the generator forward reads the generator weights at once
         # critic weights, their Adam state and the gradient slab are touched only behind the wait for d_ready
         self.eng.critic_grad(self.dparams, self.gparams, x_real, cond, z, seed, grad_out=self._slab("d"), critic_ready=self.d_ready,
-                             **self._ver())
+                             **kw)
         return self._update_overlapped("d")
 
     def gen_step(self, z, cond, seed=None):
@@ -333,8 +341,11 @@ class WGANGPTrainer:
         [total, valid, fake, gp, nonfinite] as left by the LAST critic step / the generator step (views into the gradient
         slabs at world 1: read them before the next iteration).  For loops that look at the losses only now and then."""
         assert len(critic_batches) == self.n_disc
-        for (x, c, z) in critic_batches:
+        for k, (x, c, z) in enumerate(critic_batches):
+            # (handed over through the trainer, not as an argument: critic_step keeps its signature for callers that wrap it)
+            self._gen_batch_next = gen_batch if k == self.n_disc - 1 else None
             dl = self.critic_step(x, c, z)
+        self._gen_batch_next = None
         gl = self.gen_step(*gen_batch)
         self.join()
         return dl, gl
@@ -344,8 +355,11 @@ class WGANGPTrainer:
         device scalars with the reference's reporting: d_loss = mean(valid_loss, fake_loss) of the LAST
         critic step (reference :475), g_loss = generator loss."""
         assert len(critic_batches) == self.n_disc
-        for (x, c, z) in critic_batches:
+        for k, (x, c, z) in enumerate(critic_batches):
+            # (handed over through the trainer, not as an argument: critic_step keeps its signature for callers that wrap it)
+            self._gen_batch_next = gen_batch if k == self.n_disc - 1 else None
             dl = self.critic_step(x, c, z)
+        self._gen_batch_next = None
         gl = self.gen_step(*gen_batch)
         self.join()         # the returned scalars (and the weights) are safe to read on the current stream; the next
         #                     iteration's first kernel needs the new generator weights anyway
