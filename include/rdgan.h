@@ -318,6 +318,24 @@ int rdgan_data_valid_tiles(const float* data, int n_days, int ny, int nx, int nd
 int rdgan_crps_ensemble(const float* ens, const float* obs, const float* scale, float* crps_out, int n, long npix,
                         void* stream);
 
+/* The "random" climatological baseline of generate_and_evaluate_crps.py:164, 193-194: properscoring.crps_ensemble(real_precip,
+ * baseline, axis=0) for MANY days against ONE ensemble.  ens [n][24][nd][nd] (finite values), obs [n_days][24][nd][nd];
+ * crps_out [n_days][24][nd][nd] = mean|x_i - y| - 0.5 mean|x_i - x_j| per grid point, hourly_out [n_days][24] its area mean
+ * (:194); either may be NULL, not both.  The members of a grid point are sorted once per call and every day costs a binary search
+ * (fp64 prefix sums, results rounded to fp32); the area mean is an fp64 sum in a fixed order: repeated calls agree bit for bit.
+ * A NaN observation gives NaN at its grid point and in its hour's mean.  1 <= n <= 8192, n_days * 24 nd^2 < 2^31. */
+int rdgan_crps_fixed_ensemble(const float* ens, const float* obs, float* crps_out, float* hourly_out, int n, long n_days, int nd,
+                              void* stream);
+/* analyze_crps_results.py:25-35, the resampled means of bootstrapped_difference_onesample: means_out [n_resamples], entry j the
+ * mean of n draws x[idx] for resample r = first_resample + j, idx = (uint64(rd_bits(rd_member_key(rd_make_key(seed,
+ * RD_STREAM_BOOTSTRAP), r), i)) * n) >> 32 for draw i = 0 .. n - 1 (rdgan_rng.h; the reference draws np.random.choice).  A value
+ * depends on (seed, r) only; fp64 sums in a fixed order.  n < 2^32, n_resamples < 2^31. */
+int rdgan_bootstrap_means(const double* x, long n, uint64_t seed, long first_resample, long n_resamples, double* means_out,
+                          void* stream);
+/* The moments behind scipy.stats.ttest_1samp of analyze_crps_results.py:14: out3 = { n, mean, variance with ddof = 1 } of x [n] in
+ * fp64, two passes, fixed order. */
+int rdgan_moments_f64(const double* x, long n, double* out3, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

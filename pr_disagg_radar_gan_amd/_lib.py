@@ -58,6 +58,11 @@ SIGNATURES = {
     "rdgan_data_valid_tiles": (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_float, ctypes.c_int, ctypes.c_void_p, c_stream]),
     "rdgan_crps_ensemble": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_long, c_stream]),
+    "rdgan_crps_fixed_ensemble": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_long, ctypes.c_int,
+                                                 c_stream]),
+    "rdgan_bootstrap_means": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_uint64, ctypes.c_long, ctypes.c_long,
+                                             ctypes.c_void_p, c_stream]),
+    "rdgan_moments_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_stream]),
     "rdgan_spectra_bins": (ctypes.c_int, [ctypes.c_int]),
     "rdgan_radial_spectra": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_stream]),
     "rdgan_lsd_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long]),

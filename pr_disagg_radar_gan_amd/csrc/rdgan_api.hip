@@ -34,6 +34,7 @@
 #include "rdgan_g9bwd16.hip.h"
 #include "rdgan_spectral.hip.h"
 #include "rdgan_rainfarm.hip.h"
+#include "rdgan_crps.hip.h"
 static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
 // k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
 static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
@@ -3093,6 +3094,50 @@ extern "C" int rdgan_crps_ensemble(const float* ens, const float* obs, const flo
   while (npow2 < n) npow2 <<= 1;
   hipLaunchKernelGGL(k_crps_ensemble, dim3((unsigned)npix), dim3(256), npow2 * sizeof(float), (hipStream_t)stream, ens, obs,
                      scale, crps_out, n, npow2, npix);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// CRPS experiment (rdgan_crps.hip.h): fixed-ensemble CRPS, bootstrapped means, moments
+// ------------------------------------------------------------------------------------
+extern "C" int rdgan_crps_fixed_ensemble(const float* ens, const float* obs, float* crps_out, float* hourly_out, int n,
+                                         long n_days, int nd, void* stream) {
+  if (!ens || !obs || (!crps_out && !hourly_out) || n < 1 || n > RD_CRPS_MAXN || n_days < 1 || nd < 1 || nd > 1024) return -2;
+  const long npos = (long)RDGAN_NHOURS * nd * nd;
+  if (npos > 0x7FFFFFFFL || n_days > 0x7FFFFFFFL / npos) return -2;       // D * npos < 2^31, and the grids below fit
+  hipStream_t st = (hipStream_t)stream;
+  int npow2 = 2;
+  while (npow2 < n) npow2 <<= 1;
+  const size_t lds = (size_t)(n + 1 + RD_CRPS_THREADS) * sizeof(double) + (size_t)npow2 * sizeof(float);
+  RD_TRY(ensure_lds(nullptr, (const void*)k_crps_fixed, lds));
+  // the hourly means are taken over the per-position values: without a caller's buffer they live in a stream-ordered temporary
+  float* per_pos = crps_out;
+  if (!per_pos) {
+    hipError_t e = hipMallocAsync((void**)&per_pos, (size_t)n_days * npos * sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(k_crps_fixed, dim3((unsigned)npos), dim3(RD_CRPS_THREADS), lds, st, ens, obs, per_pos, n, npow2, n_days, npos);
+  if (hourly_out)
+    hipLaunchKernelGGL(k_crps_hourly, dim3((unsigned)(n_days * RDGAN_NHOURS)), dim3(256), 0, st, per_pos, hourly_out, nd * nd);
+  hipError_t e = hipGetLastError();
+  if (!crps_out) {
+    hipError_t f = hipFreeAsync(per_pos, st);
+    if (e == hipSuccess) e = f;
+  }
+  return (int)e;
+}
+
+extern "C" int rdgan_bootstrap_means(const double* x, long n, uint64_t seed, long first_resample, long n_resamples,
+                                     double* means_out, void* stream) {
+  if (!x || !means_out || n < 1 || n > 0xFFFFFFFFL || first_resample < 0 || n_resamples < 1 || n_resamples > 0x7FFFFFFFL) return -2;
+  hipLaunchKernelGGL(k_bootstrap_means, dim3((unsigned)n_resamples), dim3(RD_CRPS_THREADS), 0, (hipStream_t)stream, x, (uint32_t)n,
+                     rd_make_key(seed, RD_STREAM_BOOTSTRAP), (uint64_t)first_resample, means_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_moments_f64(const double* x, long n, double* out3, void* stream) {
+  if (!x || !out3 || n < 1) return -2;
+  hipLaunchKernelGGL(k_moments_f64, dim3(1), dim3(RD_CRPS_THREADS), 0, (hipStream_t)stream, x, n, out3);
   return (int)hipGetLastError();
 }
 

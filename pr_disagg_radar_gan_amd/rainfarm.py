@@ -168,24 +168,30 @@ def estimate_beta(p_samples):
     return slope_statistics(p_samples).beta
 
 
-def calibrate(dataset, n_calib=5000, n_repeat=10):
-    """rainfarm_calibrate.py:67-93 on a DeviceDataset: n_repeat times, n_calib indices drawn with
-    np.random.randint(n_samples, size=n_calib) (:76, the global numpy RNG), their raw mm/h tiles (n_calib, 24, nd, nd) gathered
-    from dataset.data on the device (:80-81), and (alpha, beta) estimated.  Returns the list of (alpha, beta)."""
+def random_tiles(dataset, n):
+    """rainfarm_calibrate.py:76-81 on a DeviceDataset: n indices drawn with np.random.randint(n_samples, size=n) (:76, the global
+    numpy RNG) and their raw mm/h tiles (n, 24, nd, nd) gathered from dataset.data on the device (:80-81)."""
     if dataset.indices is None:
         raise ValueError("dataset has no valid-tile indices (set_indices)")
     nd = _check_nd(dataset.ndomain)
     dev = dataset.data.device
     ar = torch.arange(nd, device=dev)
     hours = torch.arange(NHOURS, device=dev)
-    out = []
-    for _ in range(n_repeat):
-        ixs = np.random.randint(dataset.n_samples, size=n_calib)
-        idx = dataset.indices[torch.from_numpy(ixs).to(dev)].long()
-        days, ys, xs = idx[:, 0], idx[:, 1:2] + ar, idx[:, 2:3] + ar
-        batch = dataset.data[days[:, None, None, None], hours[None, :, None, None], ys[:, None, :, None], xs[:, None, None, :]]
-        out.append(estimate_slopes(batch.contiguous()))
-    return out
+    ixs = np.random.randint(dataset.n_samples, size=n)
+    idx = dataset.indices[torch.from_numpy(ixs).to(dev)].long()
+    days, ys, xs = idx[:, 0], idx[:, 1:2] + ar, idx[:, 2:3] + ar
+    batch = dataset.data[days[:, None, None, None], hours[None, :, None, None], ys[:, None, :, None], xs[:, None, None, :]]
+    return batch.contiguous()
+
+
+def calibrate(dataset, n_calib=5000, n_repeat=10):
+    """rainfarm_calibrate.py:67-93 on a DeviceDataset: n_repeat times, n_calib indices drawn with
+    np.random.randint(n_samples, size=n_calib) (:76, the global numpy RNG), their raw mm/h tiles (n_calib, 24, nd, nd) gathered
+    from dataset.data on the device (:80-81), and (alpha, beta) estimated.  Returns the list of (alpha, beta)."""
+    if dataset.indices is None:
+        raise ValueError("dataset has no valid-tile indices (set_indices)")
+    _check_nd(dataset.ndomain)
+    return [estimate_slopes(random_tiles(dataset, n_calib)) for _ in range(n_repeat)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
