@@ -336,6 +336,35 @@ int rdgan_bootstrap_means(const double* x, long n, uint64_t seed, long first_res
  * fp64, two passes, fixed order. */
 int rdgan_moments_f64(const double* x, long n, double* out3, void* stream);
 
+/* Distribution checks, generate_and_evaluate.py:431-604.  Samples lie as the reference holds them: x [batch][n][ncol], a column
+ * being the n values of one (batch, col) (ncol = 24 hours in every reference use).  One workgroup per column; the column is sorted
+ * once in LDS, hence 1 <= n <= 16384 (-2 beyond).  All three are asynchronous on `stream`, allocate nothing, take fp64 sums in a
+ * fixed order and use no floating-point atomics: repeated calls agree bit for bit.
+ *
+ * rdgan_ks_2samp: the statistic of scipy.stats.ks_2samp(a_col, b_col) of :583, two-sided.  a [batch][n][ncol], b [batch][m][ncol];
+ * counts_out [batch][ncol][2] = (i, j) = (#{a <= v}, #{b <= v}) at the first data value v where |i / n - j / m| is largest (both
+ * ECDFs counted with <=, so equal values within or across the samples are all consumed before the difference is taken; "largest"
+ * is decided on the integer |i m - j n|), d_out [batch][ncol] = fabs((double)i / n - (double)j / m); for n = m, |i - j| / n
+ * exactly.  A column holding a NaN in either sample: counts (-1, -1), d NaN.  1 <= n, m <= 16384, batch * ncol < 2^31. */
+int rdgan_ks_2samp(const float* a, const float* b, int n, int m, int ncol, long batch, int* counts_out, double* d_out,
+                   void* stream);
+/* matplotlib.cbook.boxplot_stats(x_col, whis=1.5), what sns.boxplot draws at :495, :499 and :600.  stats_out [batch][ncol][12]
+ * doubles: n, mean, q1, med, q3, iqr, whislo, whishi, cilo, cihi, n_fliers_lo, n_fliers_hi.  Quartiles as np.percentile(x, [25,
+ * 50, 75]) (linear, numpy's lerp, fp64, not contracted); whishi the largest datum <= q3 + 1.5 iqr (q3 if none at or above q3),
+ * whislo the smallest >= q1 - 1.5 iqr (q1 likewise); cilo / cihi = med -/+ 1.57 iqr / sqrt(n); the fliers are the data outside
+ * [whislo, whishi].  sorted_out (may be NULL) [batch][n][ncol]: the ascending column, whose first n_fliers_lo and last n_fliers_hi
+ * entries are the fliers.  A column holding a NaN: n, then NaN in the other eleven slots and throughout its sorted column. */
+int rdgan_box_stats(const float* x, int n, int ncol, long batch, double* stats_out, float* sorted_out, void* stream);
+/* The ECDF of :431-435, :451-452 counted on thresholds, for any number of values in one pass.  grid [n_grid] ascending,
+ * 1 <= n_grid <= 4096 (an unsorted grid is the caller's error and is not detected); x [n_values], 4-byte aligned,
+ * 1 <= n_values <= 2^40.  counts_out [n_grid + 2] 64-bit integers: counts[j] = #{x <= grid[j]} exactly for j < n_grid, then the
+ * number of values above the last threshold, then the number of NaNs (which belong to no threshold).  workspace: at least
+ * rdgan_ecdf_workspace_bytes(n_grid) bytes of device memory (-2 for an n_grid outside 1..4096), cleared by the call.  Integer
+ * atomics only, so the counts do not depend on the order of execution. */
+long rdgan_ecdf_workspace_bytes(int n_grid);
+int rdgan_ecdf_grid(const float* x, long n_values, const float* grid, int n_grid, long long* counts_out, void* workspace,
+                    long workspace_bytes, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

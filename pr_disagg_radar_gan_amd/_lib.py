@@ -63,6 +63,12 @@ SIGNATURES = {
     "rdgan_bootstrap_means": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_uint64, ctypes.c_long, ctypes.c_long,
                                              ctypes.c_void_p, c_stream]),
     "rdgan_moments_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_stream]),
+    "rdgan_ks_2samp": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_void_p,
+                                      ctypes.c_void_p, c_stream]),
+    "rdgan_box_stats": (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_void_p, c_f32p, c_stream]),
+    "rdgan_ecdf_workspace_bytes": (ctypes.c_long, [ctypes.c_int]),
+    "rdgan_ecdf_grid": (ctypes.c_int, [c_f32p, ctypes.c_long, c_f32p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
+                                       c_stream]),
     "rdgan_spectra_bins": (ctypes.c_int, [ctypes.c_int]),
     "rdgan_radial_spectra": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_stream]),
     "rdgan_lsd_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long]),

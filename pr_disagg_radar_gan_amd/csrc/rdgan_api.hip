@@ -35,6 +35,7 @@
 #include "rdgan_spectral.hip.h"
 #include "rdgan_rainfarm.hip.h"
 #include "rdgan_crps.hip.h"
+#include "rdgan_dist.hip.h"
 static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
 // k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
 static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
@@ -3138,6 +3139,58 @@ extern "C" int rdgan_bootstrap_means(const double* x, long n, uint64_t seed, lon
 extern "C" int rdgan_moments_f64(const double* x, long n, double* out3, void* stream) {
   if (!x || !out3 || n < 1) return -2;
   hipLaunchKernelGGL(k_moments_f64, dim3(1), dim3(RD_CRPS_THREADS), 0, (hipStream_t)stream, x, n, out3);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// distribution checks (rdgan_dist.hip.h): two-sample KS, box-plot statistics, ECDF on a grid
+// ------------------------------------------------------------------------------------
+static int rd_pow2_at_least(int n) {
+  int p = 2;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+extern "C" int rdgan_ks_2samp(const float* a, const float* b, int n, int m, int ncol, long batch, int* counts_out, double* d_out,
+                              void* stream) {
+  if (!a || !b || !counts_out || !d_out || n < 1 || n > RD_DIST_MAXN || m < 1 || m > RD_DIST_MAXN || ncol < 1 || batch < 1) return -2;
+  if (batch > 0x7FFFFFFFL / ncol) return -2;
+  const int npa = rd_pow2_at_least(n), npb = rd_pow2_at_least(m);
+  RD_TRY(ensure_lds(nullptr, (const void*)k_ks_2samp, RD_KS_LDS_MAX));
+  hipLaunchKernelGGL(k_ks_2samp, dim3((unsigned)(batch * ncol)), dim3(RD_DIST_THREADS),
+                     RD_KS_LDS_HEAD + (size_t)(npa + npb) * sizeof(float), (hipStream_t)stream, a, b, n, m, npa, npb, ncol, counts_out,
+                     d_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_box_stats(const float* x, int n, int ncol, long batch, double* stats_out, float* sorted_out, void* stream) {
+  if (!x || !stats_out || n < 1 || n > RD_DIST_MAXN || ncol < 1 || batch < 1) return -2;
+  if (batch > 0x7FFFFFFFL / ncol) return -2;
+  const int npow2 = rd_pow2_at_least(n);
+  RD_TRY(ensure_lds(nullptr, (const void*)k_box_stats, RD_BOX_LDS_MAX));
+  hipLaunchKernelGGL(k_box_stats, dim3((unsigned)(batch * ncol)), dim3(RD_DIST_THREADS), RD_BOX_LDS_HEAD + (size_t)npow2 * sizeof(float),
+                     (hipStream_t)stream, x, n, npow2, ncol, stats_out, sorted_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" long rdgan_ecdf_workspace_bytes(int n_grid) {
+  if (n_grid < 1 || n_grid > RD_ECDF_MAXT) return -2;
+  return (long)(n_grid + 2) * (long)sizeof(unsigned long long);
+}
+
+extern "C" int rdgan_ecdf_grid(const float* x, long n_values, const float* grid, int n_grid, long long* counts_out, void* workspace,
+                               long workspace_bytes, void* stream) {
+  if (!x || !grid || !counts_out || !workspace || n_values < 1 || n_values > (1L << 40) || n_grid < 1 || n_grid > RD_ECDF_MAXT) return -2;
+  if (((unsigned long long)x & 3) || workspace_bytes < rdgan_ecdf_workspace_bytes(n_grid)) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* hist = (unsigned long long*)workspace;
+  hipError_t e = hipMemsetAsync(hist, 0, (size_t)(n_grid + 2) * sizeof(unsigned long long), st);
+  if (e != hipSuccess) return (int)e;
+  const long per_block = (long)RD_ECDF_THREADS * 16;                     // four float4 per thread
+  const long blocks = std::max<long>(1, std::min<long>(RD_ECDF_MAXBLOCKS, (n_values + per_block - 1) / per_block));
+  hipLaunchKernelGGL(k_ecdf_grid, dim3((unsigned)blocks), dim3(RD_ECDF_THREADS), (size_t)(2 * n_grid + 2) * sizeof(float), st, x,
+                     n_values, grid, n_grid, hist);
+  hipLaunchKernelGGL(k_ecdf_scan, dim3(1), dim3(RD_DIST_THREADS), 0, st, hist, n_grid, counts_out);
   return (int)hipGetLastError();
 }
 
