@@ -29,7 +29,9 @@ typedef struct rdgan_handle rdgan_handle;
 
 /* Build the per-(ndomain, max_batch) plans and allocate the activation workspace.
  * Replaces model construction at T:361-362 (create_generator / create_discriminator).
- * ndomain must be a multiple of 8 (L:324); n_cond_channels = 1 (T:129: the daily sum), 2 (+ longitude index,
+ * ndomain must be a multiple of 8 (L:324) from 8 to 120 -- fp32 storage runs all of them (the Dense kernel passes 4 GiB from
+ * ndomain 104 on); the bf16 storage mode (rdgan_set_option "bf16") supports ndomain <= 72 and is refused above, with a message
+ * in rdgan_last_error, when the option is set; n_cond_channels = 1 (T:129: the daily sum), 2 (+ longitude index,
  * revision1/additional_inputs/gan_train_cwgangp_pixelnorm_lon.py:136) or 3 (+ sin/cos day of year, …_doy.py:135):
  * every `cond` below is then [B,nd,nd,n_cond_channels], the generator's Dense has 100 + nd*nd*n_cond_channels
  * inputs and the critic's first Conv3D 1 + n_cond_channels input channels. */

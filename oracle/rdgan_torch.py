@@ -53,15 +53,21 @@ def _lrelu(x, gate=None):
     return x * torch.where(gate, torch.ones((), dtype=x.dtype), torch.full((), LRELU, dtype=x.dtype))
 
 
-def generator_forward(p, z, cond, return_intermediates=False, gates=None):
-    """T:312-357.  gates: optional [h0, h1, h2, h3] slope patterns for _lrelu."""
+def generator_forward(p, z, cond, return_intermediates=False, gates=None, dense_cols=None):
+    """T:312-357.  gates: optional [h0, h1, h2, h3] slope patterns for _lrelu.  dense_cols: take the Dense product over
+    column ranges of that many columns, each range of the kernel converted to the input's dtype on its own (the same sums:
+    for a kernel kept in fp32 whose fp64 copy would not fit, ndomain 120 with three condition channels)."""
     Wd, bd, W1, b1, W2, b2, W3, b3, W4, b4 = p
     B = z.shape[0]
     nd = cond.shape[1]
     s = nd // 8
     x = torch.cat([z, cond.reshape(B, -1)], dim=1)
     gt = gates if gates is not None else [None] * 4
-    h0 = _lrelu((x @ Wd + bd).reshape(B, 3, s, s, 256), gt[0])
+    if dense_cols is None:
+        pre = x @ Wd
+    else:
+        pre = torch.cat([x @ Wd[:, c:c + dense_cols].to(x.dtype) for c in range(0, Wd.shape[1], dense_cols)], dim=1)
+    h0 = _lrelu((pre + bd).reshape(B, 3, s, s, 256), gt[0])
     hs = [h0]
     h = h0
     for li, (W, b) in enumerate(((W1, b1), (W2, b2), (W3, b3))):

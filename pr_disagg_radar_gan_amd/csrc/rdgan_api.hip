@@ -1057,11 +1057,18 @@ extern "C" int rdgan_critic_param_layout(const rdgan_handle* h, long* offsets, l
   return 10;
 }
 
+// bf16 storage mode: its last conv exists only as the direct kernel, which keeps 4 (ndomain + 2)^2 floats in LDS -- ndomain <= 72
+static bool a16_geometry_ok(int nd) { return 4 * (size_t)(nd + 2) * (nd + 2) * sizeof(float) <= 96 * 1024; }
+#define RD_A16_TOO_LARGE "bf16 storage mode: ndomain too large (the mode supports ndomain <= 72; fp32 storage runs every accepted ndomain)"
+
 extern "C" int rdgan_set_option(rdgan_handle* h, const char* name, int value) {
   if (!h || !name) return -2;
   if (!strcmp(name, "collapse")) { h->collapse = value ? 1 : 0; return 0; }
   if (!strcmp(name, "wave_specialized")) { h->wave_spec = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }   // 2 = also for small problems (tests)
-  if (!strcmp(name, "bf16") || !strcmp(name, "mfma_bf16")) { h->a16 = value ? 1 : 0; return 0; }   // ("mfma_bf16": round-1 name)
+  if (!strcmp(name, "bf16") || !strcmp(name, "mfma_bf16")) {      // ("mfma_bf16": round-1 name)
+    if (value && !a16_geometry_ok(h->nd)) return bad_arg(h, RD_A16_TOO_LARGE);       // (refused here, not at the first step: the mode stays off)
+    h->a16 = value ? 1 : 0; return 0;
+  }
   if (!strcmp(name, "g9_direct")) { h->g9_direct = value ? 1 : 0; return 0; }
   if (!strcmp(name, "fast_fwd")) { h->fast_fwd = value < 0 ? -1 : (value ? 1 : 0); return 0; }     // -1 = by storage mode
   if (!strcmp(name, "fast_bwd")) { h->fast_bwd = value < 0 ? -1 : (value ? 1 : 0); return 0; }
@@ -1230,7 +1237,7 @@ static int a16_check(rdgan_handle* h) {
   if (!h->a16) return 0;
   if (!h->collapse || !h->g9_direct)
     return bad_arg(h, "bf16 storage mode needs the options collapse and g9_direct at 1");
-  if (4 * (size_t)(h->nd + 2) * (h->nd + 2) * sizeof(float) > 96 * 1024) return bad_arg(h, "bf16 storage mode: ndomain too large");
+  if (!a16_geometry_ok(h->nd)) return bad_arg(h, RD_A16_TOO_LARGE);
   return 0;
 }
 

@@ -231,7 +231,9 @@ k_conv_gemm(const RdPlan* __restrict__ plan, int B, const float* __restrict__ sr
   const int ntaps = P.ntaps;
   const RdRowTab tab = rd_row_tab(plan, P.tab);
   const __amdgpu_buffer_rsrc_t rsA = rd_make_rsrc((const float*)((const char*)src + (long)b0 * plan->src_sample * AESZ));
-  const __amdgpu_buffer_rsrc_t rsB = rd_make_rsrc(W + P.w_off);
+  // the weight descriptor is rebased at every K chunk (issue_loads): the generator's Dense kernel passes 4 GiB from ndomain 104
+  // on (80 with three condition channels), which neither a descriptor nor a 32-bit byte offset spans
+  const float* const Wp = W + P.w_off;
 
   // ---- per-thread A rows: byte offset relative to sample b0 (incl. this thread's channel group), validity bits
   // (branch-free: the A_P row-table loads are issued back to back and waited for once)
@@ -289,7 +291,7 @@ k_conv_gemm(const RdPlan* __restrict__ plan, int B, const float* __restrict__ sr
     for (int t = 0; t < TG; ++t) {
       const int tap = min(g * TG + t, ntaps - 1);
       const RdTap ti = P.tap[tap];
-      tapw[t] = ti.w * wrpt * ldw * 4;
+      tapw[t] = ti.w * wrpt;                    // first weight row of the tap
       const int sd = ti.code & 255, sh_ = (ti.code >> 8) & 255, sw = ti.code >> 16;
 #pragma unroll
       for (int i = 0; i < A_P; ++i) {
@@ -330,13 +332,13 @@ k_conv_gemm(const RdPlan* __restrict__ plan, int B, const float* __restrict__ sr
       }
       ra[i] = v;
     }
-    const int sB = tapw[t] + ld_cc * BK * ldw * 4;
+    const __amdgpu_buffer_rsrc_t rsB = rd_make_rsrc(Wp + (long)(tapw[t] + ld_cc * BK) * ldw);      // (wave-uniform)
 #pragma unroll
     for (int i = 0; i < B_P; ++i) {
       const int kk = b_kk + i * B_RPP;
       unsigned voff = (unsigned)boff[i];
       if ((BK % B_RPP != 0 && kk >= BK) || (tail && ld_cc * BK + kk >= SC)) voff = RD_OOB;
-      rw[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)voff, sB, 0));
+      rw[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)voff, 0, 0));
     }
   };
   auto load_chunk = [&]() {

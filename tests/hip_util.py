@@ -117,33 +117,40 @@ def critic_step_on_engine_branch(eng, ds, gs, d, g, x, cond, z, seed, mode="f32"
 # counts over the ranges.  Each returns (slab, loss(es), grads, last): last = the last range's share of grads, for the tests'
 # drop-the-last-range sensitivity control.
 
-def gen_step_on_engine_branch_chunked(eng, ds, gs, d, g, z, cond, seed, chunk, mode="f32", gate_tol=None):
-    """gate_tol: the guard's limits (default GATE_TOL[mode])"""
+def gen_step_on_engine_branch_chunked(eng, ds, gs, d, g, z, cond, seed, chunk, mode="f32", gate_tol=None, on_device=False):
+    """gate_tol: the guard's limits (default GATE_TOL[mode]); on_device: everything returned stays on the GPU (slab as a
+    tensor): geometries whose Dense kernel alone is gigabytes (tests/test_hip_geometry.py)"""
     from oracle import rdgan_torch as ot
     tol = GATE_TOL[mode] if gate_tol is None else gate_tol
     B = z.shape[0]
     zd, cd = dev(z), dev(cond)
-    slab = eng.gen_grad(ds, gs, zd, cd, seed).cpu().numpy()
+    slab = eng.gen_grad(ds, gs, zd, cd, seed)
+    if not on_device:
+        slab = slab.cpu().numpy()
     gates = hip_gates(eng, B, on_device=True)
     loss, grads, parts, (gst, dst) = ot.gen_step_grads_chunked(d, g, zd, cd, seed, chunk, gates=gates, device=eng.device)
     del gates
     ot.check_gate_stats(gst, observed=GATE_OBSERVED[mode], **tol)
     ot.check_gate_stats(dst, observed=GATE_OBSERVED[mode], **tol)
     _gate_report(mode, f"generator step nd{eng.ndomain} B{B} (device oracle, {len(parts)} ranges)")
+    if on_device:
+        return slab, loss, grads, parts[-1]
     return slab, loss.cpu(), [t.cpu() for t in grads], [t.cpu() for t in parts[-1]]
 
 
 def critic_step_on_engine_branch_chunked(eng, ds, gs, d, g, x, cond, z, seed, chunk, mode="f32", fake=None, alpha_offset=0,
-                                         gate_tol=None):
+                                         gate_tol=None, on_device=False):
     """fake: the generator output the engine fed its critic (a tensor may stay on the device); alpha_offset: the engine's
-    "sample_offset", which the caller sets; gate_tol: the guard's limits (default GATE_TOL[mode])"""
+    "sample_offset", which the caller sets; gate_tol: the guard's limits (default GATE_TOL[mode]); on_device: as above"""
     from oracle import rdgan_torch as ot
     tol = GATE_TOL[mode] if gate_tol is None else gate_tol
     B = x.shape[0]
     xd, cd, zd = dev(x), dev(cond), dev(z)
     eng.set_option("keep_gates", 1)
     try:
-        slab = eng.critic_grad(ds, gs, xd, cd, zd, seed).cpu().numpy()
+        slab = eng.critic_grad(ds, gs, xd, cd, zd, seed)
+        if not on_device:
+            slab = slab.cpu().numpy()
         gates = hip_critic_gates(eng, B, on_device=True)
     finally:
         eng.set_option("keep_gates", 0)
@@ -152,4 +159,6 @@ def critic_step_on_engine_branch_chunked(eng, ds, gs, d, g, x, cond, z, seed, ch
     del gates
     ot.check_gate_stats(stats, observed=GATE_OBSERVED[mode], **tol)
     _gate_report(mode, f"critic step nd{eng.ndomain} B{B} (device oracle, {len(parts)} ranges)")
+    if on_device:
+        return slab, losses, grads, parts[-1]
     return slab, losses.cpu(), [t.cpu() for t in grads], [t.cpu() for t in parts[-1]]

@@ -1,7 +1,8 @@
 """The host planner of librdgan_hip.so (csrc/rdgan_hostplan.h: geometry, gather plans, row tables, border-class boxes,
 weight-gradient tilings, partial-slab workspace bound) compiled WITHOUT HIP by g++ under AddressSanitizer + UBSan and run on
-the CPU: tests/host/plan_check.cpp builds every plan for ndomain {8,16,24,32,64,120} x {1,2,3} condition channels x max_batch
-{1,9,96,256,2048} and checks that (1) every product the validity mask lets through reads and writes inside its tensors and
+the CPU: tests/host/plan_check.cpp builds every plan for every accepted ndomain {8,16,...,120} x {1,2,3} condition channels
+(45 geometries) x max_batch {1,9,96,256,2048} (the nine ndomains other than 8, 16, 24, 32, 64, 120 with a coarser stride over
+the batch sizes below max_batch) and checks that (1) every product the validity mask lets through reads and writes inside its tensors and
 every destination row is written exactly once, (2) a border-class box plan computes exactly the parent plan's products,
 (3) the tap lookup tables agree with the phases, (4) the box kernels' workgroup decode covers every partial slab, and the slab
 need of EVERY batch size up to max_batch stays inside the bound the workspace is sized with."""
