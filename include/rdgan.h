@@ -308,11 +308,33 @@ int rdgan_launch_table(rdgan_handle* h, rdgan_launch_stat* out, int cap, int* n_
  * *flags |= 1 for a non-finite value (the reference asserts none, T:169-170), |= 2 for a fraction outside [0,1].
  * rdgan_data_valid_tiles: compute_valid_indices.py:74-92 -- valid_out[day][ii/stride][jj/stride] (int32 0/1) for the
  * boxes ii in range(0, ny-ndomain, stride), jj in range(0, nx-ndomain, stride): no NaN in the daily sum and at
- * least n_thresh points above tp_thresh_daily.  Bit-identical to the numpy forms. */
+ * least n_thresh points above tp_thresh_daily.  Bit-identical to the numpy forms.  rdgan_data_valid_tiles takes at most 2^24 - 1
+ * boxes per call (-2 beyond: one workgroup per box; rdgan_data_valid_tiles_daily has no such limit). */
 int rdgan_data_gather(const float* data, int n_days, int ny, int nx, const int* indices, int n, int ndomain,
                       float norm_scale, float* batch_out, float* cond_out, int* flags, void* stream);
 int rdgan_data_valid_tiles(const float* data, int n_days, int ny, int nx, int ndomain, int stride,
                            float tp_thresh_daily, int n_thresh, int* valid_out, void* stream);
+
+/* Training set from raw radar frames: the host scripts in front of everything above, on the device.
+ * rdgan_data_radar_hourly: convert_smhi_radardata.py:38-44 and reformat_data.py:72-91.  codes [n_days][24 * frames_per_hour][ny][nx]
+ * uint8 radar codes (device, contiguous); lut256 [256] floats (device): the value of each code per frame, NaN at the missing code
+ * (data_pipeline.radar_lut evaluates the reference's formula in its operation order).  hourly_out [n_days][24][ny][nx] =
+ * ((lut[c0] + lut[c1]) + lut[c2]) + ... over the frames of the hour in order, fp32 -- one missing frame makes the hour NaN
+ * (skipna=False); daily_out [n_days][ny][nx] (NULL: not wanted) = the sequential fp32 sum of the 24 rounded hourly values;
+ * *missing_out (NULL: not wanted) is INCREASED by the number of NaN values written to hourly_out: the caller zeroes it, calls over
+ * ranges of days add up.  frames_per_hour is one of 1, 2, 3, 4, 6, 12.  Any alignment of codes is accepted (16 codes per lane when
+ * ny * nx is a multiple of 16 and the pointers are 16-byte aligned, 4 when a multiple of 4, else bytes); indexing is 64-bit.
+ * rdgan_data_daily_sum: daily_out [n_days][ny][nx] of an hourly array that came from elsewhere, the same sequential sum
+ * (np.sum(data[tidx], axis=0) of compute_valid_indices.py:81).
+ * rdgan_data_valid_tiles_daily: the box test of compute_valid_indices.py:83-91 on that plane -- valid_out as
+ * rdgan_data_valid_tiles writes it, for any stride >= 1, reading 1 float per pixel of a box instead of 24.
+ * All three: asynchronous on the stream, 0 = success, -2 = bad argument (frames_per_hour not in the list, non-positive extents,
+ * ndomain > ny or > nx). */
+int rdgan_data_radar_hourly(const unsigned char* codes, const float* lut256, long n_days, int frames_per_hour, int ny, int nx,
+                            float* hourly_out, float* daily_out, unsigned long long* missing_out, void* stream);
+int rdgan_data_daily_sum(const float* hourly, long n_days, int ny, int nx, float* daily_out, void* stream);
+int rdgan_data_valid_tiles_daily(const float* daily, long n_days, int ny, int nx, int ndomain, int stride, float tp_thresh_daily,
+                                 int n_thresh, int* valid_out, void* stream);
 
 /* Ensemble CRPS per grid point, properscoring.crps_ensemble(obs, ens, axis=0) of generate_and_evaluate_crps.py:188:
  * ens [n][npix] (member-major), obs [npix], optional scale [npix] applied to the members first (fractions -> mm/h,

@@ -57,6 +57,11 @@ SIGNATURES = {
                                          ctypes.c_int, ctypes.c_float, c_f32p, c_f32p, ctypes.c_void_p, c_stream]),
     "rdgan_data_valid_tiles": (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_float, ctypes.c_int, ctypes.c_void_p, c_stream]),
+    "rdgan_data_radar_hourly": (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               c_f32p, c_f32p, ctypes.c_void_p, c_stream]),
+    "rdgan_data_daily_sum": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_f32p, c_stream]),
+    "rdgan_data_valid_tiles_daily": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_float, ctypes.c_int, ctypes.c_void_p, c_stream]),
     "rdgan_crps_ensemble": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_long, c_stream]),
     "rdgan_crps_fixed_ensemble": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_long, ctypes.c_int,
                                                  c_stream]),

@@ -36,6 +36,7 @@
 #include "rdgan_rainfarm.hip.h"
 #include "rdgan_crps.hip.h"
 #include "rdgan_dist.hip.h"
+#include "rdgan_radar.hip.h"
 static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
 // k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
 static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
@@ -3089,9 +3090,69 @@ extern "C" int rdgan_data_valid_tiles(const float* data, int n_days, int ny, int
   const int nbi = (ny - ndomain + stride - 1) / stride, nbj = (nx - ndomain + stride - 1) / stride;   // len(range(0, ny-nd, stride))
   if (nbi < 1 || nbj < 1) return 0;
   const long blocks = (long)n_days * nbi * nbj;
-  if (blocks > 0x7FFFFFFFL) return -2;
+  if (blocks > 0xFFFFFFL) return -2;       // one 256-thread block per box and no loop: a launch holds fewer than 2^32 threads
   hipLaunchKernelGGL(k_valid_tiles, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, data, RDGAN_NHOURS, ny, nx,
                      ndomain, stride, nbi, nbj, tp_thresh_daily, n_thresh, valid_out);
+  return (int)hipGetLastError();
+}
+
+// training set from raw radar frames (rdgan_radar.hip.h)
+template <int W, int FPH>
+static void launch_radar_hourly(const unsigned char* codes, const float* lut, long n_days, long plane, float* hourly, float* daily,
+                                unsigned long long* missing, hipStream_t st) {
+  const long groups = (plane + W - 1) / W;
+  // (a launch holds fewer than 2^32 threads; the kernel's grid-stride loop takes what lies beyond)
+  const long blocks = std::min<long>((n_days * groups + RD_RADAR_THREADS - 1) / RD_RADAR_THREADS, 0xFFFFFFL);
+  hipLaunchKernelGGL((k_radar_hourly<W, FPH>), dim3((unsigned)blocks), dim3(RD_RADAR_THREADS), 0, st, codes, lut, n_days, plane, groups,
+                     hourly, daily, missing);
+}
+template <int W>
+static void launch_radar_hourly_w(int fph, const unsigned char* codes, const float* lut, long n_days, long plane, float* hourly,
+                                  float* daily, unsigned long long* missing, hipStream_t st) {
+  switch (fph) {
+    case 1: launch_radar_hourly<W, 1>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+    case 2: launch_radar_hourly<W, 2>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+    case 3: launch_radar_hourly<W, 3>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+    case 4: launch_radar_hourly<W, 4>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+    case 6: launch_radar_hourly<W, 6>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+    default: launch_radar_hourly<W, 12>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+  }
+}
+
+extern "C" int rdgan_data_radar_hourly(const unsigned char* codes, const float* lut256, long n_days, int frames_per_hour, int ny, int nx,
+                                       float* hourly_out, float* daily_out, unsigned long long* missing_out, void* stream) {
+  const int f = frames_per_hour;
+  if (!codes || !lut256 || !hourly_out || n_days < 1 || ny < 1 || nx < 1) return -2;
+  if (f != 1 && f != 2 && f != 3 && f != 4 && f != 6 && f != 12) return -2;
+  const long plane = (long)ny * nx;
+  hipStream_t st = (hipStream_t)stream;
+  // 16 codes per lane: every frame and every output row group starts on a 16-byte boundary; 4 per lane: dword loads, float4 stores
+  const uintptr_t out_bits = (uintptr_t)hourly_out | (uintptr_t)daily_out;
+  if (plane % 16 == 0 && (((uintptr_t)codes | out_bits) & 15) == 0)
+    launch_radar_hourly_w<16>(f, codes, lut256, n_days, plane, hourly_out, daily_out, missing_out, st);
+  else if (plane % 4 == 0 && ((uintptr_t)codes & 3) == 0 && (out_bits & 15) == 0)
+    launch_radar_hourly_w<4>(f, codes, lut256, n_days, plane, hourly_out, daily_out, missing_out, st);
+  else
+    launch_radar_hourly_w<1>(f, codes, lut256, n_days, plane, hourly_out, daily_out, missing_out, st);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_data_daily_sum(const float* hourly, long n_days, int ny, int nx, float* daily_out, void* stream) {
+  if (!hourly || !daily_out || n_days < 1 || ny < 1 || nx < 1) return -2;
+  const long plane = (long)ny * nx;
+  hipLaunchKernelGGL(k_daily_sum, dim3(ew_blocks(n_days * plane)), dim3(256), 0, (hipStream_t)stream, hourly, n_days, plane, daily_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_data_valid_tiles_daily(const float* daily, long n_days, int ny, int nx, int ndomain, int stride,
+                                            float tp_thresh_daily, int n_thresh, int* valid_out, void* stream) {
+  if (!daily || !valid_out || n_days < 1 || ny < 1 || nx < 1 || stride < 1 || ndomain < 1 || ndomain > ny || ndomain > nx) return -2;
+  const int nbi = (ny - ndomain + stride - 1) / stride, nbj = (nx - ndomain + stride - 1) / stride;   // len(range(0, ny-nd, stride))
+  if (nbi < 1 || nbj < 1) return 0;
+  const long boxes = n_days * nbi * nbj;
+  const long blocks = std::min<long>((boxes + 3) / 4, 0xFFFFFFL);      // fewer than 2^32 threads per launch; the kernel loops over the rest
+  hipLaunchKernelGGL(k_valid_tiles_daily, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, daily, boxes, ny, nx, ndomain,
+                     stride, nbi, nbj, tp_thresh_daily, n_thresh, valid_out);
   return (int)hipGetLastError();
 }
 
