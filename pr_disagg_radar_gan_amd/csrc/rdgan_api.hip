@@ -264,6 +264,7 @@ struct LaunchScope {
   }
 };
 #define RD_KNAME(h, ...) do { if ((h) && (h)->prof_launches) snprintf((h)->cur_kernel, sizeof((h)->cur_kernel), __VA_ARGS__); } while (0)
+#include "rdgan_slab_launch.h"      // one launcher per slab kernel of the bf16 storage mode
 
 // ------------------------------------------------------------------------------------
 // launch helpers
@@ -890,13 +891,13 @@ extern "C" int rdgan_create(rdgan_handle** out, int ndomain, int n_cond_channels
   const long MB = h->MB, NB = h->NB;
   // partial slabs of the streaming weight-gradient kernels: the worst case over every batch size up to max_batch
   size_t wneed = rd_wgrad_workspace_floats(h, h->plans);
-  wneed = std::max(wneed, (size_t)MB * (RDGAN_NHOURS / 2) * 1728);        // k_g9_wgrad_pairs: [27][64] per (sample, plane pair)
+  wneed = std::max(wneed, g9w_partial_floats((int)MB * (RDGAN_NHOURS / 2)));      // k_g9_wgrad_pairs: [27][64] per (sample, plane pair)
   if (g9w_mfma_ok(nd, (long)MB * h->gpix[3]))                              // k_g9_wgrad_mfma: [27][64] per persistent workgroup
-    wneed = std::max(wneed, (size_t)std::min<long>(((long)MB * h->gpix[3] + 127) / 128, 768) * 1728);
-  if (nd == 16) wneed = std::max(wneed, (size_t)16 * 27 * RD_D3W_TILE);    // k_d3_wgrad_slab16: [16 groups][27][128][256]
-  if (nd % 16 == 0) wneed = std::max(wneed, (size_t)64 * 27 * RD_D2W_TILE);    // k_d2_wgrad_slab16 / _t16: [64 groups][27][64][128]
-  if (nd == 16) wneed = std::max(wneed, (size_t)8 * 64 * RD_UW2_TILE);      // k_upconv2_wgrad_slab16: [8 groups][64][256][128]
-  if (nd == 16) wneed = std::max(wneed, (size_t)32 * 64 * RD_UWG_TILE);     // k_upconv_wgrad_slab16: [32 groups][64][128][64]
+    wneed = std::max(wneed, g9w_partial_floats(g9w_groups(true, (int)MB, nd)));
+  if (nd == 16) wneed = std::max(wneed, d3w_partial_floats(RD_D3W_GMAX));          // k_d3_wgrad_slab16: [16 groups][27][128][256]
+  if (nd % 16 == 0) wneed = std::max(wneed, d2w_partial_floats(RD_D2W_GMAX));      // k_d2_wgrad_slab16 / _t16: [64 groups][27][64][128]
+  if (nd == 16) wneed = std::max(wneed, upwgrad2_partial_floats());                // k_upconv2_wgrad_slab16: [8 groups][64][256][128]
+  if (nd == 16) wneed = std::max(wneed, upwgrad_partial_floats(RD_UWG_GMAX));      // k_upconv_wgrad_slab16: [32 groups][64][128][64]
   h->wpartial_cap = wneed;
   h->cpartial_cap = (size_t)1024 * std::max(h->n_nodes, 256);
   {  // split-K partials: up to 8 copies of the largest small-M destination (critic layers 3/4, Dense, generator block 1)
@@ -1356,9 +1357,9 @@ static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, co
       if (a16) RD_TRY(launch_weights_to_bf16_t(h, h->fU[l], h->bU[l], 48, h->gch[l - 1], h->gch[l], ws));
     } else if (h->collapse) {
       hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * cc)), dim3(256), 0, ws, Wl, h->GWC[l], (int)cc);
-      if (upconv_slab_on(h, l)) hipLaunchKernelGGL(k_upconv_wimg, dim3(256), dim3(256), 0, ws, h->GWC[l], (unsigned short*)h->bW3I);
-      else if (upconv_slab_t_on(h, l)) hipLaunchKernelGGL(k_upconv_wimg_t, dim3(256), dim3(256), 0, ws, h->GWC[l], (unsigned short*)h->bW3T);
-      else if (upconv2_slab_on(h, l)) hipLaunchKernelGGL(k_upconv2_wimg, dim3(RD_UP2_KSTEPS), dim3(256), 0, ws, h->GWC[l], (unsigned short*)h->bW2I);
+      if (upconv_slab_on(h, l)) launch_upconv_wimg(h->GWC[l], h->bW3I, ws);
+      else if (upconv_slab_t_on(h, l)) launch_upconv_wimg_t(h->GWC[l], h->bW3T, ws);
+      else if (upconv2_slab_on(h, l)) launch_upconv2_wimg(h->GWC[l], h->bW2I, ws);
       else if (a16) {
         RD_TRY(launch_weights_to_bf16_t(h, h->GWC[l], h->bG1F[l], 64, h->gch[l - 1], h->gch[l], ws, h->conv_f16 ? h->fG1F[l] : nullptr));
       }
@@ -1472,71 +1473,24 @@ static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, co
     ep.out16 = a16;
     ep.nametag = a16 && l == 3;
     if (upconv_slab_on(h, l)) {     // block 3, bf16 storage: source slab resident in LDS, weights streamed in fragment order
-      ProfScope ps(h, RDGAN_TAG_GCONV3_FWD, st);
-      // (with the fused last conv the launch also carries that layer's 2 * rows * 64 * 27 FLOPs)
-      const double fl3 = plan_flops(h->plans[pl], B) + (g9_fused_on(h) ? 2.0 * B * h->gpix[3] * 64 * 27 : 0.0);
-      LaunchScope ls(h, pl, RD_KIND_CONV, B, fl3, st);
-      RD_KNAME(h, g9_fused_on(h) ? "k_upconv_slab16<bf16, +conv 64->1>" : "k_upconv_slab16<bf16>");
-      h->flops_acc += fl3;
-      const dim3 ug((unsigned)std::min(6 * B, 512));
-      if (g9_fused_on(h)) {         // + the last conv's tap products (Q12 in P9) from the rows while they are in registers
-        float* nodbg = nullptr;
-        if (keep_h3) {
-          RD_TRY(ensure_lds(h, (const void*)k_upconv_slab16<1, true, true>, RD_UPC_LDS_G9));
-          hipLaunchKernelGGL((k_upconv_slab16<1, true, true>), ug, dim3(256), RD_UPC_LDS_G9, st, (const rd_bf16_t*)hs[l - 1],
-                             (const rd_bf16_t*)h->bW3I, gp + h->goff[2 * l + 1], (rd_bf16_t*)hs[l], rs[l], B, nodbg,
-                             (const unsigned short*)h->bW9I, h->P9);
-        } else {
-          RD_TRY(ensure_lds(h, (const void*)k_upconv_slab16<1, true, false>, RD_UPC_LDS_G9));
-          hipLaunchKernelGGL((k_upconv_slab16<1, true, false>), ug, dim3(256), RD_UPC_LDS_G9, st, (const rd_bf16_t*)hs[l - 1],
-                             (const rd_bf16_t*)h->bW3I, gp + h->goff[2 * l + 1], (rd_bf16_t*)hs[l], rs[l], B, nodbg,
-                             (const unsigned short*)h->bW9I, h->P9);
-        }
-        RD_CHECK(h, hipGetLastError());
-        continue;
-      }
-      RD_TRY(ensure_lds(h, (const void*)k_upconv_slab16<1>, RD_UPC_LDS));
-      hipLaunchKernelGGL(k_upconv_slab16<1>, ug, dim3(256), RD_UPC_LDS, st, (const rd_bf16_t*)hs[l - 1],
-                         (const rd_bf16_t*)h->bW3I, gp + h->goff[2 * l + 1], (rd_bf16_t*)hs[l], rs[l], B);
-      RD_CHECK(h, hipGetLastError());
+      // (with the fused last conv the launch also carries that layer's 2 * rows * 64 * 27 FLOPs, and its tap products (Q12 in P9)
+      // leave the kernel from the rows while they are in registers)
+      const bool g9 = g9_fused_on(h);
+      const double fl3 = plan_flops(h->plans[pl], B) + (g9 ? 2.0 * B * h->gpix[3] * 64 * 27 : 0.0);
+      RD_TRY(launch_upconv_slab<1>(h, {pl, fl3, RDGAN_TAG_GCONV3_FWD}, hs[l - 1], h->bW3I, gp + h->goff[2 * l + 1], hs[l], rs[l], B, nullptr,
+                                   g9 ? h->bW9I : nullptr, g9 ? h->P9 : nullptr, keep_h3, st));
       continue;
     }
     if (upconv_slab_t_on(h, l)) {   // block 3, bf16 storage, planes larger than 8 x 8: (h, w) tiles with their halo resident, K in two halves
-      ProfScope ps(h, RDGAN_TAG_GCONV3_FWD, st);
       const bool g9t = g9_fused_t_on(h);
       const double fl3 = plan_flops(h->plans[pl], B) + (g9t ? 2.0 * B * h->gpix[3] * 64 * 27 : 0.0);
-      LaunchScope ls(h, pl, RD_KIND_CONV, B, fl3, st);
-      RD_KNAME(h, g9t ? "k_upconv_slab_t16<bf16, +conv 64->1>" : "k_upconv_slab_t16<bf16>");
-      h->flops_acc += fl3;
-      const int Hs = h->gdim[2][1], Ws = h->gdim[2][2];
-      const long items = (long)B * 6 * (Hs / 8) * (Ws / 8);
-      const dim3 tg((unsigned)std::min<long>(items, 512));
-      float* nodbg = nullptr;
-      if (g9t && keep_h3) {
-        RD_TRY(ensure_lds(h, (const void*)k_upconv_slab_t16<true, true>, RD_UPT_LDS_G9));
-        hipLaunchKernelGGL((k_upconv_slab_t16<true, true>), tg, dim3(256), RD_UPT_LDS_G9, st, (const rd_bf16_t*)hs[l - 1], (const rd_bf16_t*)h->bW3T,
-                           gp + h->goff[2 * l + 1], (rd_bf16_t*)hs[l], rs[l], B, Hs, Ws, nodbg, (const unsigned short*)h->bW9I, h->P9);
-      } else if (g9t) {
-        RD_TRY(ensure_lds(h, (const void*)k_upconv_slab_t16<true, false>, RD_UPT_LDS_G9));
-        hipLaunchKernelGGL((k_upconv_slab_t16<true, false>), tg, dim3(256), RD_UPT_LDS_G9, st, (const rd_bf16_t*)hs[l - 1], (const rd_bf16_t*)h->bW3T,
-                           gp + h->goff[2 * l + 1], (rd_bf16_t*)hs[l], rs[l], B, Hs, Ws, nodbg, (const unsigned short*)h->bW9I, h->P9);
-      } else {
-        RD_TRY(ensure_lds(h, (const void*)k_upconv_slab_t16<false, true>, RD_UPT_LDS));
-        hipLaunchKernelGGL((k_upconv_slab_t16<false, true>), tg, dim3(256), RD_UPT_LDS, st, (const rd_bf16_t*)hs[l - 1], (const rd_bf16_t*)h->bW3T,
-                           gp + h->goff[2 * l + 1], (rd_bf16_t*)hs[l], rs[l], B, Hs, Ws, nodbg, (const unsigned short*)nullptr, (float*)nullptr);
-      }
-      RD_CHECK(h, hipGetLastError());
+      RD_TRY(launch_upconv_slab_t(h, {pl, fl3, RDGAN_TAG_GCONV3_FWD}, hs[l - 1], h->bW3T, gp + h->goff[2 * l + 1], hs[l], rs[l], B,
+                                  h->gdim[2][1], h->gdim[2][2], nullptr, g9t ? h->bW9I : nullptr, g9t ? h->P9 : nullptr, keep_h3, st));
       continue;
     }
     if (upconv2_slab_on(h, l)) {    // block 2, bf16 storage: a sample resident in LDS, the four waves split the 128 channels
-      ProfScope ps(h, RDGAN_TAG_GCONV_FWD, st);
-      LaunchScope ls(h, pl, RD_KIND_CONV, B, plan_flops(h->plans[pl], B), st);
-      RD_KNAME(h, "k_upconv2_slab16<bf16>");
-      h->flops_acc += plan_flops(h->plans[pl], B);
-      RD_TRY(ensure_lds(h, (const void*)k_upconv2_slab16, RD_UP2_LDS));
-      hipLaunchKernelGGL(k_upconv2_slab16, dim3((unsigned)std::min(B, 256 * RD_UP2_WGS)), dim3(256), RD_UP2_LDS, st, (const rd_bf16_t*)hs[l - 1],
-                         (const rd_bf16_t*)h->bW2I, gp + h->goff[2 * l + 1], (rd_bf16_t*)hs[l], rs[l], B);
-      RD_CHECK(h, hipGetLastError());
+      RD_TRY(launch_upconv2_slab(h, {pl, plan_flops(h->plans[pl], B), RDGAN_TAG_GCONV_FWD}, hs[l - 1], h->bW2I, gp + h->goff[2 * l + 1], hs[l],
+                                 rs[l], B, st));
       continue;
     }
     if (a16) {     // collapsed form (64 taps) on the bf16 matrix pipe
@@ -1719,9 +1673,8 @@ static int prep_critic_weights(rdgan_handle* h, const float* dp, hipStream_t st)
     }
     hipLaunchKernelGGL(k_weights3_to_bf16, dim3(8, 8, 3 * 27), dim3(256), 0, st, a);
     if (d2_fwd_slab_on(h))
-      hipLaunchKernelGGL(k_d2f_wimg, dim3(RD_D2F_KSTEPS), dim3(256), 0, st, dp + h->doff[2], (unsigned short*)h->bW2F);
-    if (d2_slab_on(h) || d2_slab_t_on(h))
-      hipLaunchKernelGGL(k_d2s_wimg, dim3((RD_D2S_KSTEPS * 2 * 64 + 255) / 256), dim3(256), 0, st, dp + h->doff[2], (unsigned short*)h->bW2S);
+      launch_d2f_wimg(dp + h->doff[2], h->bW2F, st);
+    if (d2_slab_on(h) || d2_slab_t_on(h)) launch_d2s_wimg(dp + h->doff[2], h->bW2S, st);
     hipLaunchKernelGGL(k_w1_to_bf16, dim3(ew_blocks(64L * h->ldp1)), dim3(256), 0, st, dp + h->doff[0], (rd_bf16_t*)h->bW1B,
                        27 * h->Cin, h->ldp1);
   }
@@ -1839,16 +1792,10 @@ static int critic_forward_impl(rdgan_handle* h, const float* dp, int NBt, uint64
     else if (a16 && l == 1)
       RD_TRY(launch_conv_a16(h, h->plans[pl], h->d_plans + pl, NBt, in, d1_weights(h, dp), h->dch[l], h->dh[l], ep, st,
                              RDGAN_TAG_CRITIC_GEMM, false, true));
-    else if (l == 2 && d2_fwd_slab_on(h)) {      // a sample's layer-1 output resident in LDS, the four waves split the 128 channels
-      ProfScope ps(h, RDGAN_TAG_CRITIC_GEMM, st);
-      LaunchScope ls(h, pl, RD_KIND_CONV, NBt, plan_flops(h->plans[pl], NBt), st);
-      RD_KNAME(h, "k_d2_fwd_slab16<bf16>");
-      h->flops_acc += plan_flops(h->plans[pl], NBt);
-      RD_TRY(ensure_lds(h, (const void*)k_d2_fwd_slab16, RD_D2F_LDS));
-      hipLaunchKernelGGL(k_d2_fwd_slab16, dim3((unsigned)std::min(NBt, 512)), dim3(256), RD_D2F_LDS, st, (const rd_bf16_t*)in,
-                         (const rd_bf16_t*)h->bW2F, dp + h->doff[3], (rd_bf16_t*)h->dh[2], NBt, use_drop, ep.key, 0u);
-      RD_CHECK(h, hipGetLastError());
-    } else if (a16)
+    else if (l == 2 && d2_fwd_slab_on(h))      // a sample's layer-1 output resident in LDS, the four waves split the 128 channels
+      RD_TRY(launch_d2_fwd_slab(h, {pl, plan_flops(h->plans[pl], NBt), RDGAN_TAG_CRITIC_GEMM}, in, h->bW2F, dp + h->doff[3], h->dh[2], NBt,
+                                use_drop, ep.key, st));
+    else if (a16)
       RD_TRY(launch_conv16(h, h->plans[pl], h->d_plans + pl, NBt, in, h->bWF[l], h->dh[l], ep, st, RDGAN_TAG_CRITIC_GEMM,
                            h->conv_f16 ? h->fWF[l] : nullptr));
     else
@@ -1881,31 +1828,16 @@ static int critic_dgrad_chain(rdgan_handle* h, const float* dp, int NBt, int B, 
     int pl = critic_dgrad_plan(h, l, NBt);
     RdEpi ep = epi_make(RD_EPI_GATE_AUX, nullptr, h->dh[l - 1], use_drop, rd_make_key(seed, RD_STREAM_D1 + l - 2), 0);
     ep.out16 = a16;
+    const unsigned char* gbits = d2_gate_bits_on(h) && d1_gemm_ok(h) ? h->g1bits : nullptr;
     if (l == 2 && d2_slab_on(h)) {      // two samples' output gradient resident in LDS, weights streamed in fragment order
-      ProfScope ps(h, RDGAN_TAG_CRITIC_GEMM, st);
-      LaunchScope ls(h, pl, RD_KIND_CONV, NBt, plan_flops(h->plans[pl], NBt), st);
-      RD_KNAME(h, "k_d2_dgrad_slab16<bf16>");
-      h->flops_acc += plan_flops(h->plans[pl], NBt);
-      RD_TRY(ensure_lds(h, (const void*)k_d2_dgrad_slab16, RD_D2S_LDS));
-      hipLaunchKernelGGL(k_d2_dgrad_slab16, dim3((unsigned)std::min((NBt + 1) / 2, 512)), dim3(256), RD_D2S_LDS, st,
-                         (const rd_bf16_t*)h->du[2], (const rd_bf16_t*)h->bW2S, (const rd_bf16_t*)h->dh[1], (rd_bf16_t*)h->du[1], NBt,
-                         use_drop, d2_gate_bits_on(h) && d1_gemm_ok(h) ? h->g1bits : nullptr);
-      RD_CHECK(h, hipGetLastError());
+      RD_TRY(launch_d2_dgrad_slab(h, {pl, plan_flops(h->plans[pl], NBt), RDGAN_TAG_CRITIC_GEMM}, h->du[2], h->bW2S, h->dh[1], h->du[1], NBt,
+                                  use_drop, gbits, st));
       continue;
     }
     if (l == 2 && d2_slab_t_on(h)) {    // the same on tiles: two samples' 6 x 5 x 5 output-gradient positions per tile resident
-      ProfScope ps(h, RDGAN_TAG_CRITIC_GEMM, st);
       const int one = PL_D2B;               // (FLOPs of the one-phase plan: the slab kernel multiplies every (position, tap) pair that lands inside)
-      LaunchScope ls(h, one, RD_KIND_CONV, NBt, plan_flops(h->plans[one], NBt), st);
-      RD_KNAME(h, "k_d2_dgrad_slab_t16<bf16>");
-      h->flops_acc += plan_flops(h->plans[one], NBt);
-      const int OH = h->ddim[2][1], OW = h->ddim[2][2];
-      const long items = (long)((NBt + 1) / 2) * (OH / 4) * (OW / 4);
-      RD_TRY(ensure_lds(h, (const void*)k_d2_dgrad_slab_t16, RD_D2T_LDS));
-      hipLaunchKernelGGL(k_d2_dgrad_slab_t16, dim3((unsigned)std::min<long>(items, 512)), dim3(256), RD_D2T_LDS, st,
-                         (const rd_bf16_t*)h->du[2], (const rd_bf16_t*)h->bW2S, (const rd_bf16_t*)h->dh[1], (rd_bf16_t*)h->du[1], NBt,
-                         OH, OW, use_drop, d2_gate_bits_on(h) && d1_gemm_ok(h) ? h->g1bits : nullptr);
-      RD_CHECK(h, hipGetLastError());
+      RD_TRY(launch_d2_dgrad_slab_t(h, {one, plan_flops(h->plans[one], NBt), RDGAN_TAG_CRITIC_GEMM}, h->du[2], h->bW2S, h->dh[1], h->du[1], NBt,
+                                    h->ddim[2][1], h->ddim[2][2], use_drop, gbits, st));
       continue;
     }
     if (a16)
@@ -2081,44 +2013,17 @@ extern "C" int rdgan_critic_grad_ahead(rdgan_handle* h, const float* dp, const f
       RD_TRY(launch_d1_wgrad(h, in, h->du[1], grad + h->doff[0], NBt, st, grad + h->doff[1], (long)2 * B * h->dL[1]));
     } else if (a16 && l == 2 && h->d2_wgrad_slab && h->nd == 16) {
       // a wave owns one tap: its [64 x 128] product stays in registers over the workgroup's share of the batch
-      ProfScope ps(h, RDGAN_TAG_CRITIC_GEMM, st);
-      LaunchScope ls(h, pl, RD_KIND_WGRAD, NBt, plan_flops(h->plans[pl], NBt), st);
-      RD_KNAME(h, "k_d2_wgrad_slab16<bf16>");
-      h->flops_acc += plan_flops(h->plans[pl], NBt);
-      const int G = NBt >= 64 ? 64 : 8;
-      if ((size_t)G * 27 * RD_D2W_TILE > h->wpartial_cap) return bad_arg(h, "d2 wgrad: partial workspace too small");
-      RD_TRY(ensure_lds(h, (const void*)k_d2_wgrad_slab16, RD_D2W_LDS));
-      hipLaunchKernelGGL(k_d2_wgrad_slab16, dim3(4 * G), dim3(512), RD_D2W_LDS, st, (const rd_bf16_t*)in, (const rd_bf16_t*)h->du[2],
-                         h->wpartial, NBt, G);
-      hipLaunchKernelGGL(k_d2_wgrad_fold, dim3((27 * RD_D2W_TILE / 4 + 255) / 256), dim3(256), 0, st, h->wpartial, G, grad + h->doff[2]);
-      RD_CHECK(h, hipGetLastError());
+      RD_TRY(launch_d2_wgrad_slab(h, {pl, plan_flops(h->plans[pl], NBt), RDGAN_TAG_CRITIC_GEMM}, in, h->du[2], h->wpartial, h->wpartial_cap,
+                                  grad + h->doff[2], NBt, nullptr, st));
     } else if (a16 && l == 2 && d2_wgrad_slab_t_on(h)) {
       // the same on (h, w) tiles of 4 x 4 output positions (ndomain 32 / 48 / 64)
-      ProfScope ps(h, RDGAN_TAG_CRITIC_GEMM, st);
-      LaunchScope ls(h, pl, RD_KIND_WGRAD, NBt, plan_flops(h->plans[pl], NBt), st);
-      RD_KNAME(h, "k_d2_wgrad_slab_t16<bf16>");
-      h->flops_acc += plan_flops(h->plans[pl], NBt);
       const RdD2wGeom geo = {h->ddim[1][1], h->ddim[1][2], h->ddim[2][1], h->ddim[2][2], h->ddim[2][1] / 4, h->ddim[2][2] / 4};
-      const int G = (long)NBt * geo.TH * geo.TW >= 64 ? 64 : 8;
-      if ((size_t)G * 27 * RD_D2W_TILE > h->wpartial_cap) return bad_arg(h, "d2 wgrad: partial workspace too small");
-      RD_TRY(ensure_lds(h, (const void*)k_d2_wgrad_slab_t16, RD_D2WT_LDS));
-      hipLaunchKernelGGL(k_d2_wgrad_slab_t16, dim3(4 * G), dim3(512), RD_D2WT_LDS, st, (const rd_bf16_t*)in, (const rd_bf16_t*)h->du[2],
-                         h->wpartial, NBt, G, geo);
-      hipLaunchKernelGGL(k_d2_wgrad_fold, dim3((27 * RD_D2W_TILE / 4 + 255) / 256), dim3(256), 0, st, h->wpartial, G, grad + h->doff[2]);
-      RD_CHECK(h, hipGetLastError());
+      RD_TRY(launch_d2_wgrad_slab(h, {pl, plan_flops(h->plans[pl], NBt), RDGAN_TAG_CRITIC_GEMM}, in, h->du[2], h->wpartial, h->wpartial_cap,
+                                  grad + h->doff[2], NBt, &geo, st));
     } else if (a16 && l == 3 && h->d3_wgrad_slab && h->nd == 16) {
       // a wave owns (tap, quarter of the output channels); items of four samples (12 output positions each)
-      ProfScope ps(h, RDGAN_TAG_CRITIC_GEMM, st);
-      LaunchScope ls(h, pl, RD_KIND_WGRAD, NBt, plan_flops(h->plans[pl], NBt), st);
-      RD_KNAME(h, "k_d3_wgrad_slab16<bf16>");
-      h->flops_acc += plan_flops(h->plans[pl], NBt);
-      const int G = NBt >= 256 ? 16 : 8;
-      if ((size_t)G * 27 * RD_D3W_TILE > h->wpartial_cap) return bad_arg(h, "d3 wgrad: partial workspace too small");
-      RD_TRY(ensure_lds(h, (const void*)k_d3_wgrad_slab16, RD_D3W_LDS));
-      hipLaunchKernelGGL(k_d3_wgrad_slab16, dim3(16 * G), dim3(512), RD_D3W_LDS, st, (const rd_bf16_t*)in, (const rd_bf16_t*)h->du[3],
-                         h->wpartial, NBt, G);
-      hipLaunchKernelGGL(k_d3_wgrad_fold, dim3((27 * RD_D3W_TILE / 4 + 255) / 256), dim3(256), 0, st, h->wpartial, G, grad + h->doff[4]);
-      RD_CHECK(h, hipGetLastError());
+      RD_TRY(launch_d3_wgrad_slab(h, {pl, plan_flops(h->plans[pl], NBt), RDGAN_TAG_CRITIC_GEMM}, in, h->du[3], h->wpartial, h->wpartial_cap,
+                                  grad + h->doff[4], NBt, st));
     } else if (a16 && l >= 2) {      // layers 2-4: bf16 activations against bf16 output gradients (on the border-class boxes)
       pl = critic_wgrad_plan(h, l, NBt);
       if (!wgrad16_ok(h->plans[pl], NBt)) return bad_arg(h, "bf16 storage mode: no bf16 weight-gradient tile for this critic layer");
@@ -2204,35 +2109,14 @@ extern "C" int rdgan_gen_grad_after(rdgan_handle* h, const float* dp, const floa
   // through block 3's PixelNorm+LeakyReLU backward in the same kernel (below); needs the planes to fit in LDS.
   const size_t g9_lds = 4 * (size_t)(nd + 2) * (nd + 2) * sizeof(float);
   const bool g9_direct = h->g9_direct && g9_lds <= 96 * 1024 &&
-                         (size_t)B * (RDGAN_NHOURS / 2) * 1728 <= h->wpartial_cap;
+                         g9w_partial_floats(B * (RDGAN_NHOURS / 2)) <= h->wpartial_cap;
   if (a16 && !g9_direct) return bad_arg(h, "bf16 storage mode needs the direct backward of the last conv (g9_direct)");
   if (g9_direct) {
-    ProfScope ps(h, RDGAN_TAG_GCONV_WGRAD, st);
-    const size_t lds = std::max<size_t>(g9_lds, 4 * 27 * 16 * sizeof(f32x4));
     RD_TRY(ensure_lds(h, a16 ? (const void*)k_g9_bwd_pairs<rd_bf16_t> : (const void*)k_g9_bwd_pairs<float>, 96 * 1024));
-    int nwg;
-    if (h->edge_kernels && g9w_mfma_ok(nd, npix3) && (size_t)std::min<long>((npix3 + 127) / 128, 768) * 1728 <= h->wpartial_cap) {
-      // weight gradient on the matrix pipe, the h3 tensor streamed once (rdgan_edge.hip.h)
-      const size_t lds_m = g9w_mfma_lds(a16);
-      RD_TRY(ensure_lds(h, a16 ? (const void*)k_g9_wgrad_mfma<rd_bf16_t> : (const void*)k_g9_wgrad_mfma<float>, lds_m));
-      nwg = (int)std::min<long>((npix3 + 127) / 128, 768);          // persistent: three workgroups per CU
-      LaunchScope ls(h, PL_G9B, RD_KIND_WGRAD, B, 2.0 * npix3 * 64 * 27, st);
-      RD_KNAME(h, "k_g9_wgrad_mfma<%s>", a16 ? "bf16" : "f32");
-      h->flops_acc += 2.0 * npix3 * 64 * 27;
-      if (a16) hipLaunchKernelGGL(k_g9_wgrad_mfma<rd_bf16_t>, dim3(nwg), dim3(256), lds_m, st, h->dl, (const rd_bf16_t*)h->h3, h->wpartial,
-                                  npix3, RDGAN_NHOURS, nd, nd, ilog2(nd));
-      else hipLaunchKernelGGL(k_g9_wgrad_mfma<float>, dim3(nwg), dim3(256), lds_m, st, h->dl, (const float*)h->h3, h->wpartial,
-                              npix3, RDGAN_NHOURS, nd, nd, ilog2(nd));
-    } else {
-      RD_TRY(ensure_lds(h, a16 ? (const void*)k_g9_wgrad_pairs<rd_bf16_t> : (const void*)k_g9_wgrad_pairs<float>, 96 * 1024));
-      const int nunits = B * (RDGAN_NHOURS / 2);
-      nwg = std::min(nunits, 3072);            // (bs 256: one unit per workgroup, as before)
-      if (a16) hipLaunchKernelGGL(k_g9_wgrad_pairs<rd_bf16_t>, dim3(nwg), dim3(256), lds, st, h->dl, (const rd_bf16_t*)h->h3, h->wpartial,
-                                  RDGAN_NHOURS, nd, nd, nunits);
-      else hipLaunchKernelGGL(k_g9_wgrad_pairs<float>, dim3(nwg), dim3(256), lds, st, h->dl, (const float*)h->h3, h->wpartial,
-                              RDGAN_NHOURS, nd, nd, nunits);
-    }
-    hipLaunchKernelGGL(k_reduce_partials, dim3((1728 + 15) / 16), dim3(rd_reduce_threads(nwg)), 0, st, h->wpartial, nwg, 1728, grad + h->goff[8]);
+    // weight gradient on the matrix pipe, the h3 tensor streamed once (rdgan_edge.hip.h), where its partial rows fit
+    const bool mfma = h->edge_kernels && g9w_mfma_ok(nd, npix3) && g9w_partial_floats(g9w_groups(true, B, nd)) <= h->wpartial_cap;
+    RD_TRY(launch_g9_wgrad(h, {PL_G9B, 2.0 * npix3 * 64 * 27, RDGAN_TAG_GCONV_WGRAD}, mfma, a16, h->dl, h->h3, h->wpartial, h->wpartial_cap,
+                           grad + h->goff[8], B, nd, st));
   } else {
     {
       ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
@@ -2382,34 +2266,14 @@ extern "C" int rdgan_gen_grad_after(rdgan_handle* h, const float* dp, const floa
       bool bias_done = false;         // (the slab kernel delivers the bias gradient too)
       if (a16 && l == 3 && h->upwgrad_slab && h->nd == 16) {
         // each workgroup owns one phase and keeps its eight tap products in registers over its share of the batch
-        ProfScope ps(h, RDGAN_TAG_GCONV_WGRAD, st);
-        LaunchScope ls(h, plf, RD_KIND_WGRAD, B, plan_flops(h->plans[plf], B), st);
-        RD_KNAME(h, "k_upconv_wgrad_slab16<bf16>");
-        h->flops_acc += plan_flops(h->plans[plf], B);
-        const int G = 6 * B >= 64 ? 32 : 8;
-        if ((size_t)G * 64 * RD_UWG_TILE > h->wpartial_cap) return bad_arg(h, "upconv wgrad: partial workspace too small");
-        RD_TRY(ensure_lds(h, (const void*)k_upconv_wgrad_slab16, RD_UWG_LDS));
-        hipLaunchKernelGGL(k_upconv_wgrad_slab16, dim3(8 * G), dim3(512), RD_UWG_LDS, st, (const rd_bf16_t*)hs[l - 1],
-                           (const rd_bf16_t*)dys[l], h->wpartial, B, G, h->ubias_part);
-        hipLaunchKernelGGL(k_upconv_wgrad_fold, dim3(64 * RD_UWG_TILE / 4 / 256), dim3(256), 0, st, h->wpartial, G, h->dWc);
-        hipLaunchKernelGGL(k_reduce_partials, dim3(64 / 16), dim3(rd_reduce_threads(8 * G)), 0, st, h->ubias_part, 8 * G, 64, grad + h->goff[2 * l + 1]);      // (a serial fold of the 256 partial rows took 61 us)
+        RD_TRY(launch_upconv_wgrad_slab(h, {plf, plan_flops(h->plans[plf], B), RDGAN_TAG_GCONV_WGRAD}, hs[l - 1], dys[l], h->wpartial,
+                                        h->wpartial_cap, h->dWc, h->ubias_part, grad + h->goff[2 * l + 1], B, st));
         bias_done = true;
-        RD_CHECK(h, hipGetLastError());
       } else if (a16 && l == 2 && h->upwgrad_slab && h->nd == 16) {
         // the same on block 2's geometry: a workgroup owns (phase, quarter of the 256 input channels)
-        ProfScope ps(h, RDGAN_TAG_GCONV_WGRAD, st);
-        LaunchScope ls(h, plf, RD_KIND_WGRAD, B, plan_flops(h->plans[plf], B), st);
-        RD_KNAME(h, "k_upconv2_wgrad_slab16<bf16>");
-        h->flops_acc += plan_flops(h->plans[plf], B);
-        const int G = 8;
-        if ((size_t)G * 64 * RD_UW2_TILE > h->wpartial_cap) return bad_arg(h, "upconv wgrad: partial workspace too small");
-        RD_TRY(ensure_lds(h, (const void*)k_upconv2_wgrad_slab16, RD_UW2_LDS));
-        hipLaunchKernelGGL(k_upconv2_wgrad_slab16, dim3(32 * G), dim3(512), RD_UW2_LDS, st, (const rd_bf16_t*)hs[l - 1],
-                           (const rd_bf16_t*)dys[l], h->wpartial, B, G, h->ubias_part);
-        hipLaunchKernelGGL(k_upconv2_wgrad_fold, dim3(64 * RD_UW2_TILE / 4 / 256), dim3(256), 0, st, h->wpartial, G, h->dWc);
-        hipLaunchKernelGGL(k_reduce_partials, dim3(128 / 16), dim3(rd_reduce_threads(8 * G)), 0, st, h->ubias_part, 8 * G, 128, grad + h->goff[2 * l + 1]);
+        RD_TRY(launch_upconv2_wgrad_slab(h, {plf, plan_flops(h->plans[plf], B), RDGAN_TAG_GCONV_WGRAD}, hs[l - 1], dys[l], h->wpartial,
+                                         h->wpartial_cap, h->dWc, h->ubias_part, grad + h->goff[2 * l + 1], B, st));
         bias_done = true;
-        RD_CHECK(h, hipGetLastError());
       } else if (a16) {
         if (wbox && wgrad16_ok(h->plans[plfx], B)) plf = plfx;
         if (!wgrad16_ok(h->plans[plf], B)) return bad_arg(h, "bf16 storage mode: no bf16 weight-gradient tile for this block");
@@ -2500,6 +2364,31 @@ struct TmpPlan {
   ~TmpPlan() { if (dev) (void)hipFree(dev); if (tab) (void)hipFree(tab); }
 };
 
+// The device buffers of one op-level call: freed when the call returns.  `rc` keeps the first failing HIP call; once it is set
+// the later requests do nothing and return nullptr, so an entry allocates all it needs and checks `rc` once.
+struct TmpBufs {
+  std::vector<void*> bufs; int rc = 0;
+  void* bytes(size_t n) {
+    void* p = nullptr;
+    if (rc == 0 && (rc = (int)hipMalloc(&p, n)) == 0) bufs.push_back(p);
+    return rc == 0 ? p : nullptr;
+  }
+  float* floats(size_t n) { return (float*)bytes(n * sizeof(float)); }
+  void* bf16(long n) { return bytes((size_t)n * 2); }
+  // a fresh bf16 buffer holding the fp32 array `in`, rounded to nearest even
+  void* to_bf16(const float* in, long n, hipStream_t st) {
+    void* p = bf16(n);
+    if (rc == 0) rc = launch_to_bf16(nullptr, in, p, n, st);
+    return p;
+  }
+  ~TmpBufs() { for (void* p : bufs) (void)hipFree(p); }
+};
+// widen a bf16 buffer into the caller's fp32 output
+static int launch_widen_bf16(const void* in, float* out, long n, hipStream_t st) {
+  hipLaunchKernelGGL(k_bf16_to_f32, dim3(ew_blocks(n)), dim3(256), 0, st, (const rd_bf16_t*)in, out, n);
+  return (int)hipGetLastError();
+}
+
 extern "C" int rdgan_op_conv3d(const float* x, const float* w, const float* bias, float* y, int B, int D, int H, int W,
                                int Cin, int Cout, int Do, int Ho, int Wo, int stride, int pad_d, int pad_h, int pad_w,
                                int upsample, void* stream) {
@@ -2523,21 +2412,14 @@ extern "C" int rdgan_op_conv3d_wgrad_bf16(const float* x, const float* gy, float
   tp.host = plan_conv_fwd(D, H, W, Cin, Cout, Do, Ho, Wo, stride, pad_d, pad_h, pad_w, 0);
   RD_TRY(tp.upload());
   if (!wgrad16_ok(tp.host, B)) return -2;
-  const long nx = (long)B * D * H * W * Cin, ng = (long)B * Do * Ho * Wo * Cout;
-  size_t need = std::max(wgrad_partial_need(tp.host, B), wgrad_partial_need(tp.host, B, true));
-  void *xb = nullptr, *gb = nullptr; float* partial = nullptr;
-  hipError_t e = hipMalloc(&xb, nx * 2);
-  if (e == hipSuccess) e = hipMalloc(&gb, ng * 2);
-  if (e == hipSuccess) e = hipMalloc((void**)&partial, need * sizeof(float));
-  int rc = (int)e;
-  if (rc == 0) rc = launch_to_bf16(nullptr, x, xb, nx, st);
-  if (rc == 0) rc = launch_to_bf16(nullptr, gy, gb, ng, st);
-  if (rc == 0) rc = launch_wgrad16(nullptr, tp.host, tp.dev, B, xb, gb, dw, partial, need, st, -1);
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  if (xb) (void)hipFree(xb);
-  if (gb) (void)hipFree(gb);
-  if (partial) (void)hipFree(partial);
-  return rc;
+  const size_t need = std::max(wgrad_partial_need(tp.host, B), wgrad_partial_need(tp.host, B, true));
+  TmpBufs t;
+  void* xb = t.to_bf16(x, (long)B * D * H * W * Cin, st);
+  void* gb = t.to_bf16(gy, (long)B * Do * Ho * Wo * Cout, st);
+  float* partial = t.floats(need);
+  RD_TRY(t.rc);
+  RD_TRY(launch_wgrad16(nullptr, tp.host, tp.dev, B, xb, gb, dw, partial, need, st, -1));
+  return (int)hipStreamSynchronize(st);
 }
 
 // bf16-operand variant of the above for stride-1/2 convs without folded upsample (tests): x and w are rounded to
@@ -2550,27 +2432,23 @@ extern "C" int rdgan_op_conv3d_bf16(const float* x, const float* w, const float*
   TmpPlan tp;
   tp.host = plan_conv_fwd(D, H, W, Cin, Cout, Do, Ho, Wo, stride, pad_d, pad_h, pad_w, 0);
   RD_TRY(tp.upload());
-  const long nx = (long)B * D * H * W * Cin, nw = 27L * Cin * Cout;
-  void *xb = nullptr, *wb = nullptr;
-  hipError_t e = hipMalloc(&xb, nx * 2);
-  if (e == hipSuccess) e = hipMalloc(&wb, nw * 2);
-  int rc = (int)e;
-  if (rc == 0) rc = launch_to_bf16(nullptr, x, xb, nx, st);
-  if (rc == 0) rc = launch_weights_to_bf16_t(nullptr, w, wb, 27, Cin, Cout, st);
+  const long nw = 27L * Cin * Cout;
+  TmpBufs t;
+  void* xb = t.to_bf16(x, (long)B * D * H * W * Cin, st);
+  void* wb = t.bf16(nw);
+  RD_TRY(t.rc);
+  RD_TRY(launch_weights_to_bf16_t(nullptr, w, wb, 27, Cin, Cout, st));
   RdEpi ep = epi_make(bias ? RD_EPI_BIAS : RD_EPI_PLAIN, bias);
   ep.out16 = out_bf16 ? 1 : 0;
   void* wf = nullptr;
   if (out_bf16 == 2) {       // the fragment kernel (k_conv_gemm_f16), which must accept the launch
-    if (!conv_f16_ok(nullptr, tp.host, B, ep)) rc = -2;
-    if (rc == 0) rc = (int)hipMalloc(&wf, nw * 2);
-    if (rc == 0) rc = launch_wfrag_image(nullptr, wb, wf, 27, Cout, Cin, st);
+    if (!conv_f16_ok(nullptr, tp.host, B, ep)) return -2;
+    wf = t.bf16(nw);
+    RD_TRY(t.rc);
+    RD_TRY(launch_wfrag_image(nullptr, wb, wf, 27, Cout, Cin, st));
   }
-  if (rc == 0) rc = launch_conv16(nullptr, tp.host, tp.dev, B, xb, wb, y, ep, st, -1, wf);
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  if (xb) (void)hipFree(xb);
-  if (wb) (void)hipFree(wb);
-  if (wf) (void)hipFree(wf);
-  return rc;
+  RD_TRY(launch_conv16(nullptr, tp.host, tp.dev, B, xb, wb, y, ep, st, -1, wf));
+  return (int)hipStreamSynchronize(st);
 }
 
 extern "C" int rdgan_op_conv3d_dgrad(const float* gy, const float* w, float* gx, int B, int D, int H, int W, int Cin,
@@ -2578,23 +2456,22 @@ extern "C" int rdgan_op_conv3d_dgrad(const float* gy, const float* w, float* gx,
                                      void* stream) {
   if (!gy || !w || !gx || Cout % 4 || Cin % 64) return -2;
   hipStream_t st = (hipStream_t)stream;
-  float* wt = nullptr;
-  hipError_t e = hipMalloc((void**)&wt, sizeof(float) * 27 * Cin * Cout);
-  if (e != hipSuccess) return (int)e;
-  int rc = launch_transpose(nullptr, w, wt, 27, Cin, Cout, Cin, st);
+  TmpBufs t;
+  float* wt = t.floats((size_t)27 * Cin * Cout);
+  RD_TRY(t.rc);
+  const int rc = launch_transpose(nullptr, w, wt, 27, Cin, Cout, Cin, st);
   TmpPlan tp;
   if (stride == 1) {
-    if (pad_d != 1 || pad_h != 1 || pad_w != 1 || Do != D || Ho != H || Wo != W) { (void)hipFree(wt); return -2; }
+    if (pad_d != 1 || pad_h != 1 || pad_w != 1 || Do != D || Ho != H || Wo != W) return -2;
     tp.host = plan_conv_dgrad_s1(D, H, W, Cin, Cout);
   } else {
     int pad[3] = {pad_d, pad_h, pad_w};
     tp.host = plan_conv_dgrad_s2(D, H, W, Cin, Do, Ho, Wo, Cout, pad);
   }
-  if (rc == 0) rc = tp.upload();
-  if (rc == 0) rc = launch_conv(nullptr, tp.host, tp.dev, B, gy, wt, Cin, gx, epi_make(RD_EPI_PLAIN), st, -1);
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  (void)hipFree(wt);
-  return rc;
+  RD_TRY(rc);
+  RD_TRY(tp.upload());
+  RD_TRY(launch_conv(nullptr, tp.host, tp.dev, B, gy, wt, Cin, gx, epi_make(RD_EPI_PLAIN), st, -1));
+  return (int)hipStreamSynchronize(st);
 }
 
 // input gradient with bf16 operands (tests): gy and w rounded to bf16, fp32 accumulation.  The [tap][Cin][Cout] kernel IS
@@ -2612,19 +2489,15 @@ extern "C" int rdgan_op_conv3d_dgrad_bf16(const float* gy, const float* w, float
     int pad[3] = {pad_d, pad_h, pad_w};
     tp.host = plan_conv_dgrad_s2(D, H, W, Cin, Do, Ho, Wo, Cout, pad);
   }
-  const long ng = (long)B * Do * Ho * Wo * Cout, nw = 27L * Cin * Cout;
-  void *gb = nullptr, *wb = nullptr;
-  hipError_t e = hipMalloc(&gb, ng * 2);
-  if (e == hipSuccess) e = hipMalloc(&wb, nw * 2);
-  int rc = (int)e;
-  if (rc == 0) rc = tp.upload();
-  if (rc == 0) rc = launch_to_bf16(nullptr, gy, gb, ng, st);
-  if (rc == 0) rc = launch_to_bf16(nullptr, w, wb, nw, st);
-  if (rc == 0) rc = launch_conv16(nullptr, tp.host, tp.dev, B, gb, wb, gx, epi_make(RD_EPI_PLAIN), st, -1);
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  if (gb) (void)hipFree(gb);
-  if (wb) (void)hipFree(wb);
-  return rc;
+  TmpBufs t;
+  void* gb = t.bf16((long)B * Do * Ho * Wo * Cout);
+  void* wb = t.bf16(27L * Cin * Cout);
+  RD_TRY(t.rc);
+  RD_TRY(tp.upload());
+  RD_TRY(launch_to_bf16(nullptr, gy, gb, (long)B * Do * Ho * Wo * Cout, st));
+  RD_TRY(launch_to_bf16(nullptr, w, wb, 27L * Cin * Cout, st));
+  RD_TRY(launch_conv16(nullptr, tp.host, tp.dev, B, gb, wb, gx, epi_make(RD_EPI_PLAIN), st, -1));
+  return (int)hipStreamSynchronize(st);
 }
 
 extern "C" int rdgan_op_conv3d_wgrad(const float* x, const float* gy, float* dw, int B, int D, int H, int W, int Cin,
@@ -2635,14 +2508,12 @@ extern "C" int rdgan_op_conv3d_wgrad(const float* x, const float* gy, float* dw,
   TmpPlan tp;
   tp.host = plan_conv_fwd(D, H, W, Cin, Cout, Do, Ho, Wo, stride, pad_d, pad_h, pad_w, upsample);
   RD_TRY(tp.upload());
-  size_t need = wgrad_partial_need(tp.host, B);
-  float* partial = nullptr;
-  hipError_t e = hipMalloc((void**)&partial, need * sizeof(float));
-  if (e != hipSuccess) return (int)e;
-  int rc = launch_wgrad(nullptr, tp.host, tp.dev, B, x, gy, dw, partial, need, st, -1);
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  (void)hipFree(partial);
-  return rc;
+  const size_t need = wgrad_partial_need(tp.host, B);
+  TmpBufs t;
+  float* partial = t.floats(need);
+  RD_TRY(t.rc);
+  RD_TRY(launch_wgrad(nullptr, tp.host, tp.dev, B, x, gy, dw, partial, need, st, -1));
+  return (int)hipStreamSynchronize(st);
 }
 
 // Weight gradient of one tap group of the shared-centre form through the production plan
@@ -2658,28 +2529,21 @@ extern "C" int rdgan_op_fastd_wgrad(const float* src, const float* dy, float* dU
   TmpPlan tp;
   tp.host = plan_fastd_wgrad(D, H, W, Cin, Cout, g);
   RD_TRY(tp.upload());
-  size_t need = std::max(wgrad_partial_need(tp.host, B), wgrad_partial_need(tp.host, B, true));
-  float* partial = nullptr;
-  void *xb = nullptr, *gb = nullptr;
-  hipError_t e = hipMalloc((void**)&partial, need * sizeof(float));
-  int rc = (int)e;
-  if (rc == 0 && bf16) {
-    if (!wgrad16_ok(tp.host, B)) rc = -2;
-    const long nx = (long)B * tp.host.src_sample, ng = (long)B * tp.host.dst_sample;
-    if (rc == 0) rc = (int)hipMalloc(&xb, nx * 2);
-    if (rc == 0) rc = (int)hipMalloc(&gb, ng * 2);
-    if (rc == 0) rc = launch_to_bf16(nullptr, src, xb, nx, st);
-    if (rc == 0) rc = launch_to_bf16(nullptr, dy, gb, ng, st);
-    if (rc == 0) rc = launch_wgrad16(nullptr, tp.host, tp.dev, B, xb, gb, dU, partial, need, st, -1);
-  } else if (rc == 0) {
+  const size_t need = std::max(wgrad_partial_need(tp.host, B), wgrad_partial_need(tp.host, B, true));
+  TmpBufs t;
+  float* partial = t.floats(need);
+  RD_TRY(t.rc);
+  if (bf16) {
+    if (!wgrad16_ok(tp.host, B)) return -2;
+    void* xb = t.to_bf16(src, (long)B * tp.host.src_sample, st);
+    void* gb = t.to_bf16(dy, (long)B * tp.host.dst_sample, st);
+    RD_TRY(t.rc);
+    RD_TRY(launch_wgrad16(nullptr, tp.host, tp.dev, B, xb, gb, dU, partial, need, st, -1));
+  } else {
     rdgan_handle fake_h;                   // (wave_spec = 1: the producer/consumer kernel, as in production)
-    rc = launch_wgrad(&fake_h, tp.host, tp.dev, B, src, dy, dU, partial, need, st, -1);
+    RD_TRY(launch_wgrad(&fake_h, tp.host, tp.dev, B, src, dy, dU, partial, need, st, -1));
   }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  if (partial) (void)hipFree(partial);
-  if (xb) (void)hipFree(xb);
-  if (gb) (void)hipFree(gb);
-  return rc;
+  return (int)hipStreamSynchronize(st);
 }
 
 // Weight gradient of the last generator conv (64 -> 1) alone, through the production kernels: kernel = 1 the matrix-pipe kernel
@@ -2687,44 +2551,16 @@ extern "C" int rdgan_op_fastd_wgrad(const float* src, const float* dy, float* dU
 extern "C" int rdgan_op_g9_wgrad(const float* dl, const float* h3, float* dW, int B, int nd, int bf16, int kernel, void* stream) {
   if (!dl || !h3 || !dW || B < 1 || nd < 1) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const int D = RDGAN_NHOURS;
-  const long npix = (long)B * D * nd * nd;
+  const long npix = (long)B * RDGAN_NHOURS * nd * nd;
   if (npix >= 0x7FFFFFFFL) return -2;
-  const int nunits = B * (D / 2);
   if (kernel && !g9w_mfma_ok(nd, npix)) return -2;
-  const int nwg = kernel ? (int)std::min<long>((npix + 127) / 128, 768) : std::min(nunits, 3072);
-  float* partial = nullptr;
-  void* hb = nullptr;
-  int rc = (int)hipMalloc((void**)&partial, (size_t)nwg * 1728 * sizeof(float));
-  if (rc == 0 && bf16) {
-    rc = (int)hipMalloc(&hb, npix * 64 * 2);
-    if (rc == 0) rc = launch_to_bf16(nullptr, h3, hb, npix * 64, st);
-  }
-  if (rc == 0 && kernel) {
-    const size_t lds = g9w_mfma_lds(bf16 != 0);
-    rc = ensure_lds(nullptr, bf16 ? (const void*)k_g9_wgrad_mfma<rd_bf16_t> : (const void*)k_g9_wgrad_mfma<float>, lds);
-    if (rc == 0) {
-      if (bf16) hipLaunchKernelGGL(k_g9_wgrad_mfma<rd_bf16_t>, dim3(nwg), dim3(256), lds, st, dl, (const rd_bf16_t*)hb, partial, npix, D, nd, nd, ilog2(nd));
-      else hipLaunchKernelGGL(k_g9_wgrad_mfma<float>, dim3(nwg), dim3(256), lds, st, dl, h3, partial, npix, D, nd, nd, ilog2(nd));
-    }
-  } else if (rc == 0) {
-    const size_t g9_lds = 4 * (size_t)(nd + 2) * (nd + 2) * sizeof(float);
-    const size_t lds = std::max<size_t>(g9_lds, 4 * 27 * 16 * sizeof(f32x4));
-    if (lds > 96 * 1024) rc = -2;
-    if (rc == 0) rc = ensure_lds(nullptr, bf16 ? (const void*)k_g9_wgrad_pairs<rd_bf16_t> : (const void*)k_g9_wgrad_pairs<float>, 96 * 1024);
-    if (rc == 0) {
-      if (bf16) hipLaunchKernelGGL(k_g9_wgrad_pairs<rd_bf16_t>, dim3(nwg), dim3(256), lds, st, dl, (const rd_bf16_t*)hb, partial, D, nd, nd, nunits);
-      else hipLaunchKernelGGL(k_g9_wgrad_pairs<float>, dim3(nwg), dim3(256), lds, st, dl, h3, partial, D, nd, nd, nunits);
-    }
-  }
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_reduce_partials, dim3((1728 + 15) / 16), dim3(rd_reduce_threads(nwg)), 0, st, partial, nwg, 1728, dW);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  if (partial) (void)hipFree(partial);
-  if (hb) (void)hipFree(hb);
-  return rc;
+  const size_t need = g9w_partial_floats(g9w_groups(kernel != 0, B, nd));
+  TmpBufs t;
+  float* partial = t.floats(need);
+  const void* hb = bf16 ? t.to_bf16(h3, npix * 64, st) : h3;
+  RD_TRY(t.rc);
+  RD_TRY(launch_g9_wgrad(nullptr, kOpRec, kernel != 0, bf16 != 0, dl, hb, partial, need, dW, B, nd, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 // Generator block 3 forward of the bf16 storage mode through the slab kernel alone (rdgan_upconv16.hip.h): x [B,12,8,8,128] and the
@@ -2735,27 +2571,18 @@ extern "C" int rdgan_op_upconv_slab16(const float* x, const float* w, const floa
                                       void* stream) {
   if (!x || !w || !bias || !y || !rinv || B < 1) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const long nx = (long)B * 12 * 64 * 128, ny = (long)B * 24 * 256 * 64;
-  void *xb = nullptr, *yb = nullptr, *wi = nullptr; float* wc = nullptr;
-  int rc = (int)hipMalloc(&xb, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&yb, ny * 2);
-  if (rc == 0) rc = (int)hipMalloc(&wi, 64L * 8 * 2 * 64 * 16);
-  if (rc == 0) rc = (int)hipMalloc((void**)&wc, 64L * 128 * 64 * sizeof(float));
-  if (rc == 0) rc = launch_to_bf16(nullptr, x, xb, nx, st);
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * 128 * 64)), dim3(256), 0, st, w, wc, 128 * 64);
-    hipLaunchKernelGGL(k_upconv_wimg, dim3(256), dim3(256), 0, st, wc, (unsigned short*)wi);
-    rc = ensure_lds(nullptr, (const void*)k_upconv_slab16<0>, RD_UPC_LDS);
-  }
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_upconv_slab16<0>, dim3((unsigned)std::min(6 * B, 512)), dim3(256), RD_UPC_LDS, st, (const rd_bf16_t*)xb,
-                       (const rd_bf16_t*)wi, bias, (rd_bf16_t*)yb, rinv, B, dbg);
-    hipLaunchKernelGGL(k_bf16_to_f32, dim3(ew_blocks(ny)), dim3(256), 0, st, (const rd_bf16_t*)yb, y, ny);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  for (void* p : {xb, yb, wi, (void*)wc}) if (p) (void)hipFree(p);
-  return rc;
+  const long ny = (long)B * 24 * 256 * 64;
+  TmpBufs t;
+  void* xb = t.to_bf16(x, (long)B * 12 * 64 * 128, st);
+  void* yb = t.bf16(ny);
+  void* wi = t.bytes(64L * 8 * 2 * 64 * 16);
+  float* wc = t.floats(64L * 128 * 64);
+  RD_TRY(t.rc);
+  hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * 128 * 64)), dim3(256), 0, st, w, wc, 128 * 64);
+  launch_upconv_wimg(wc, wi, st);
+  RD_TRY(launch_upconv_slab<0>(nullptr, kOpRec, xb, wi, bias, yb, rinv, B, dbg, nullptr, nullptr, true, st));
+  RD_TRY(launch_widen_bf16(yb, y, ny, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 // The same block on source planes of H x W positions (multiples of 8) through the TILED slab kernel alone (rdgan_upconv16t.hip.h):
@@ -2764,29 +2591,19 @@ extern "C" int rdgan_op_upconv_slab_t16(const float* x, const float* w, const fl
                                         int H, int W, void* stream) {
   if (!x || !w || !bias || !y || !rinv || B < 1 || H < 8 || W < 8 || (H & 7) || (W & 7)) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const long nx = (long)B * 12 * H * W * 128, ny = (long)B * 24 * 4 * H * W * 64;
+  const long ny = (long)B * 24 * 4 * H * W * 64;
   if (12L * H * W * 256 >= 0x7FFFFFF0L) return -2;
-  void *xb = nullptr, *yb = nullptr, *wi = nullptr; float* wc = nullptr;
-  int rc = (int)hipMalloc(&xb, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&yb, ny * 2);
-  if (rc == 0) rc = (int)hipMalloc(&wi, 64L * 8 * 2 * 64 * 16);
-  if (rc == 0) rc = (int)hipMalloc((void**)&wc, 64L * 128 * 64 * sizeof(float));
-  if (rc == 0) rc = launch_to_bf16(nullptr, x, xb, nx, st);
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * 128 * 64)), dim3(256), 0, st, w, wc, 128 * 64);
-    hipLaunchKernelGGL(k_upconv_wimg_t, dim3(256), dim3(256), 0, st, wc, (unsigned short*)wi);
-    rc = ensure_lds(nullptr, (const void*)k_upconv_slab_t16<false, true>, RD_UPT_LDS);
-  }
-  if (rc == 0) {
-    const long items = (long)B * 6 * (H / 8) * (W / 8);
-    hipLaunchKernelGGL((k_upconv_slab_t16<false, true>), dim3((unsigned)std::min<long>(items, 512)), dim3(256), RD_UPT_LDS, st, (const rd_bf16_t*)xb,
-                       (const rd_bf16_t*)wi, bias, (rd_bf16_t*)yb, rinv, B, H, W, dbg, (const unsigned short*)nullptr, (float*)nullptr);
-    hipLaunchKernelGGL(k_bf16_to_f32, dim3(ew_blocks(ny)), dim3(256), 0, st, (const rd_bf16_t*)yb, y, ny);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  for (void* p : {xb, yb, wi, (void*)wc}) if (p) (void)hipFree(p);
-  return rc;
+  TmpBufs t;
+  void* xb = t.to_bf16(x, (long)B * 12 * H * W * 128, st);
+  void* yb = t.bf16(ny);
+  void* wi = t.bytes(64L * 8 * 2 * 64 * 16);
+  float* wc = t.floats(64L * 128 * 64);
+  RD_TRY(t.rc);
+  hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * 128 * 64)), dim3(256), 0, st, w, wc, 128 * 64);
+  launch_upconv_wimg_t(wc, wi, st);
+  RD_TRY(launch_upconv_slab_t(nullptr, kOpRec, xb, wi, bias, yb, rinv, B, H, W, dbg, nullptr, nullptr, true, st));
+  RD_TRY(launch_widen_bf16(yb, y, ny, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 // Collapsed weight gradient of generator block 3 through the slab kernel alone (rdgan_upwgrad16.hip.h), ndomain 16: x [B,12,8,8,128]
@@ -2794,23 +2611,14 @@ extern "C" int rdgan_op_upconv_slab_t16(const float* x, const float* w, const fl
 extern "C" int rdgan_op_upconv_wgrad_slab16(const float* x, const float* dy, float* dWc, int B, void* stream) {
   if (!x || !dy || !dWc || B < 1) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const long nx = (long)B * 12 * 64 * 128, ny = (long)B * 24 * 256 * 64;
-  const int G = 6 * B >= 64 ? 32 : 8;
-  void *xb = nullptr, *yb = nullptr; float* part = nullptr;
-  int rc = (int)hipMalloc(&xb, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&yb, ny * 2);
-  if (rc == 0) rc = (int)hipMalloc((void**)&part, (size_t)G * 64 * RD_UWG_TILE * sizeof(float));
-  if (rc == 0) rc = launch_to_bf16(nullptr, x, xb, nx, st);
-  if (rc == 0) rc = launch_to_bf16(nullptr, dy, yb, ny, st);
-  if (rc == 0) rc = ensure_lds(nullptr, (const void*)k_upconv_wgrad_slab16, RD_UWG_LDS);
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_upconv_wgrad_slab16, dim3(8 * G), dim3(512), RD_UWG_LDS, st, (const rd_bf16_t*)xb, (const rd_bf16_t*)yb, part, B, G);
-    hipLaunchKernelGGL(k_upconv_wgrad_fold, dim3(64 * RD_UWG_TILE / 4 / 256), dim3(256), 0, st, part, G, dWc);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  for (void* p : {xb, yb, (void*)part}) if (p) (void)hipFree(p);
-  return rc;
+  const size_t need = upwgrad_partial_floats(upwgrad_groups(B));
+  TmpBufs t;
+  void* xb = t.to_bf16(x, (long)B * 12 * 64 * 128, st);
+  void* yb = t.to_bf16(dy, (long)B * 24 * 256 * 64, st);
+  float* part = t.floats(need);
+  RD_TRY(t.rc);
+  RD_TRY(launch_upconv_wgrad_slab(nullptr, kOpRec, xb, yb, part, need, dWc, nullptr, nullptr, B, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 // Forward of the critic's second layer through the slab kernel alone (rdgan_d2fwd16.hip.h), ndomain 16: x [B,11,7,7,64] and the layer's
@@ -2819,25 +2627,16 @@ extern "C" int rdgan_op_upconv_wgrad_slab16(const float* x, const float* dy, flo
 extern "C" int rdgan_op_d2_fwd_slab16(const float* x, const float* w, const float* bias, float* y, int B, uint64_t seed, void* stream) {
   if (!x || !w || !bias || !y || B < 1) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const long nx = (long)B * 539 * 64, ny = (long)B * 96 * 128;
-  void *xb = nullptr, *yb = nullptr, *wi = nullptr;
-  int rc = (int)hipMalloc(&xb, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&yb, ny * 2);
-  if (rc == 0) rc = (int)hipMalloc(&wi, (long)RD_D2F_KSTEPS * 4 * 64 * 16);
-  if (rc == 0) rc = launch_to_bf16(nullptr, x, xb, nx, st);
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_d2f_wimg, dim3(RD_D2F_KSTEPS), dim3(256), 0, st, w, (unsigned short*)wi);
-    rc = ensure_lds(nullptr, (const void*)k_d2_fwd_slab16, RD_D2F_LDS);
-  }
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_d2_fwd_slab16, dim3((unsigned)std::min(B, 512)), dim3(256), RD_D2F_LDS, st, (const rd_bf16_t*)xb,
-                       (const rd_bf16_t*)wi, bias, (rd_bf16_t*)yb, B, seed != 0, rd_make_key(seed, RD_STREAM_D1 + 1), 0u);
-    hipLaunchKernelGGL(k_bf16_to_f32, dim3(ew_blocks(ny)), dim3(256), 0, st, (const rd_bf16_t*)yb, y, ny);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  for (void* p : {xb, yb, wi}) if (p) (void)hipFree(p);
-  return rc;
+  const long ny = (long)B * 96 * 128;
+  TmpBufs t;
+  void* xb = t.to_bf16(x, (long)B * 539 * 64, st);
+  void* yb = t.bf16(ny);
+  void* wi = t.bytes((size_t)RD_D2F_KSTEPS * 4 * 64 * 16);
+  RD_TRY(t.rc);
+  launch_d2f_wimg(w, wi, st);
+  RD_TRY(launch_d2_fwd_slab(nullptr, kOpRec, xb, wi, bias, yb, B, seed != 0, rd_make_key(seed, RD_STREAM_D1 + 1), st));
+  RD_TRY(launch_widen_bf16(yb, y, ny, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 // Weight gradient of the critic's third layer through the slab kernel alone (rdgan_d3wgrad16.hip.h), ndomain 16: x [B,6,4,4,128]
@@ -2845,23 +2644,14 @@ extern "C" int rdgan_op_d2_fwd_slab16(const float* x, const float* w, const floa
 extern "C" int rdgan_op_d3_wgrad_slab16(const float* x, const float* dy, float* dW, int B, void* stream) {
   if (!x || !dy || !dW || B < 1) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const long nx = (long)B * 96 * 128, ny = (long)B * 12 * 256;
-  const int G = B >= 256 ? 16 : 8;
-  void *xb = nullptr, *yb = nullptr; float* part = nullptr;
-  int rc = (int)hipMalloc(&xb, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&yb, ny * 2);
-  if (rc == 0) rc = (int)hipMalloc((void**)&part, (size_t)G * 27 * RD_D3W_TILE * sizeof(float));
-  if (rc == 0) rc = launch_to_bf16(nullptr, x, xb, nx, st);
-  if (rc == 0) rc = launch_to_bf16(nullptr, dy, yb, ny, st);
-  if (rc == 0) rc = ensure_lds(nullptr, (const void*)k_d3_wgrad_slab16, RD_D3W_LDS);
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_d3_wgrad_slab16, dim3(16 * G), dim3(512), RD_D3W_LDS, st, (const rd_bf16_t*)xb, (const rd_bf16_t*)yb, part, B, G);
-    hipLaunchKernelGGL(k_d3_wgrad_fold, dim3((27 * RD_D3W_TILE / 4 + 255) / 256), dim3(256), 0, st, part, G, dW);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  for (void* p : {xb, yb, (void*)part}) if (p) (void)hipFree(p);
-  return rc;
+  const size_t need = d3w_partial_floats(d3w_groups(B));
+  TmpBufs t;
+  void* xb = t.to_bf16(x, (long)B * 96 * 128, st);
+  void* yb = t.to_bf16(dy, (long)B * 12 * 256, st);
+  float* part = t.floats(need);
+  RD_TRY(t.rc);
+  RD_TRY(launch_d3_wgrad_slab(nullptr, kOpRec, xb, yb, part, need, dW, B, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 // Weight gradient of the critic's second layer through the slab kernel alone (rdgan_d2wgrad16.hip.h), ndomain 16: x [B,11,7,7,64]
@@ -2869,23 +2659,14 @@ extern "C" int rdgan_op_d3_wgrad_slab16(const float* x, const float* dy, float* 
 extern "C" int rdgan_op_d2_wgrad_slab16(const float* x, const float* dy, float* dW, int B, void* stream) {
   if (!x || !dy || !dW || B < 1) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const long nx = (long)B * 539 * 64, ny = (long)B * 96 * 128;
-  const int G = B >= 64 ? 64 : 8;
-  void *xb = nullptr, *yb = nullptr; float* part = nullptr;
-  int rc = (int)hipMalloc(&xb, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&yb, ny * 2);
-  if (rc == 0) rc = (int)hipMalloc((void**)&part, (size_t)G * 27 * RD_D2W_TILE * sizeof(float));
-  if (rc == 0) rc = launch_to_bf16(nullptr, x, xb, nx, st);
-  if (rc == 0) rc = launch_to_bf16(nullptr, dy, yb, ny, st);
-  if (rc == 0) rc = ensure_lds(nullptr, (const void*)k_d2_wgrad_slab16, RD_D2W_LDS);
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_d2_wgrad_slab16, dim3(4 * G), dim3(512), RD_D2W_LDS, st, (const rd_bf16_t*)xb, (const rd_bf16_t*)yb, part, B, G);
-    hipLaunchKernelGGL(k_d2_wgrad_fold, dim3((27 * RD_D2W_TILE / 4 + 255) / 256), dim3(256), 0, st, part, G, dW);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  for (void* p : {xb, yb, (void*)part}) if (p) (void)hipFree(p);
-  return rc;
+  const size_t need = d2w_partial_floats(d2w_groups(B));
+  TmpBufs t;
+  void* xb = t.to_bf16(x, (long)B * 539 * 64, st);
+  void* yb = t.to_bf16(dy, (long)B * 96 * 128, st);
+  float* part = t.floats(need);
+  RD_TRY(t.rc);
+  RD_TRY(launch_d2_wgrad_slab(nullptr, kOpRec, xb, yb, part, need, dW, B, nullptr, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 // The same through the tiled kernel (k_d2_wgrad_slab_t16): x [B,11,2 OH - 1,2 OW - 1,64], dy [B,6,OH,OW,128], OH and OW multiples of 4.
@@ -2893,23 +2674,14 @@ extern "C" int rdgan_op_d2_wgrad_slab_t16(const float* x, const float* dy, float
   if (!x || !dy || !dW || B < 1 || OH < 4 || OW < 4 || OH % 4 || OW % 4) return -2;
   hipStream_t st = (hipStream_t)stream;
   const RdD2wGeom geo = {2 * OH - 1, 2 * OW - 1, OH, OW, OH / 4, OW / 4};
-  const long nx = (long)B * 11 * geo.IH * geo.IW * 64, ny = (long)B * 6 * OH * OW * 128;
-  const int G = (long)B * geo.TH * geo.TW >= 64 ? 64 : 8;
-  void *xb = nullptr, *yb = nullptr; float* part = nullptr;
-  int rc = (int)hipMalloc(&xb, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&yb, ny * 2);
-  if (rc == 0) rc = (int)hipMalloc((void**)&part, (size_t)G * 27 * RD_D2W_TILE * sizeof(float));
-  if (rc == 0) rc = launch_to_bf16(nullptr, x, xb, nx, st);
-  if (rc == 0) rc = launch_to_bf16(nullptr, dy, yb, ny, st);
-  if (rc == 0) rc = ensure_lds(nullptr, (const void*)k_d2_wgrad_slab_t16, RD_D2WT_LDS);
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_d2_wgrad_slab_t16, dim3(4 * G), dim3(512), RD_D2WT_LDS, st, (const rd_bf16_t*)xb, (const rd_bf16_t*)yb, part, B, G, geo);
-    hipLaunchKernelGGL(k_d2_wgrad_fold, dim3((27 * RD_D2W_TILE / 4 + 255) / 256), dim3(256), 0, st, part, G, dW);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  for (void* p : {xb, yb, (void*)part}) if (p) (void)hipFree(p);
-  return rc;
+  const size_t need = d2w_partial_floats(d2w_groups((long)B * geo.TH * geo.TW));
+  TmpBufs t;
+  void* xb = t.to_bf16(x, (long)B * 11 * geo.IH * geo.IW * 64, st);
+  void* yb = t.to_bf16(dy, (long)B * 6 * OH * OW * 128, st);
+  float* part = t.floats(need);
+  RD_TRY(t.rc);
+  RD_TRY(launch_d2_wgrad_slab(nullptr, kOpRec, xb, yb, part, need, dW, B, &geo, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 // Input gradient of the critic's second layer through the slab kernel alone (rdgan_d2slab16.hip.h), ndomain 16: gy [B,6,4,4,128],
@@ -2920,27 +2692,17 @@ extern "C" int rdgan_op_d2_wgrad_slab_t16(const float* x, const float* dy, float
 extern "C" int rdgan_op_d2_dgrad_slab16(const float* gy, const float* w, const float* aux, float* gx, int B, int use_drop, void* stream) {
   if (!gy || !w || !aux || !gx || B < 1) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const long ny = (long)B * RD_D2S_SROWS * 128, nx = (long)B * RD_D2S_OPOS * 64;
-  void *yb = nullptr, *ab = nullptr, *xb = nullptr, *wi = nullptr;
-  int rc = (int)hipMalloc(&yb, ny * 2);
-  if (rc == 0) rc = (int)hipMalloc(&ab, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&xb, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&wi, (long)RD_D2S_KSTEPS * 2 * 64 * 16);
-  if (rc == 0) rc = launch_to_bf16(nullptr, gy, yb, ny, st);
-  if (rc == 0) rc = launch_to_bf16(nullptr, aux, ab, nx, st);
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_d2s_wimg, dim3((RD_D2S_KSTEPS * 2 * 64 + 255) / 256), dim3(256), 0, st, w, (unsigned short*)wi);
-    rc = ensure_lds(nullptr, (const void*)k_d2_dgrad_slab16, RD_D2S_LDS);
-  }
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_d2_dgrad_slab16, dim3((unsigned)std::min((B + 1) / 2, 512)), dim3(256), RD_D2S_LDS, st, (const rd_bf16_t*)yb,
-                       (const rd_bf16_t*)wi, (const rd_bf16_t*)ab, (rd_bf16_t*)xb, B, use_drop != 0);
-    hipLaunchKernelGGL(k_bf16_to_f32, dim3(ew_blocks(nx)), dim3(256), 0, st, (const rd_bf16_t*)xb, gx, nx);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  for (void* p : {yb, ab, xb, wi}) if (p) (void)hipFree(p);
-  return rc;
+  const long nx = (long)B * RD_D2S_OPOS * 64;
+  TmpBufs t;
+  void* yb = t.to_bf16(gy, (long)B * RD_D2S_SROWS * 128, st);
+  void* ab = t.to_bf16(aux, nx, st);
+  void* xb = t.bf16(nx);
+  void* wi = t.bytes((size_t)RD_D2S_KSTEPS * 2 * 64 * 16);
+  RD_TRY(t.rc);
+  launch_d2s_wimg(w, wi, st);
+  RD_TRY(launch_d2_dgrad_slab(nullptr, kOpRec, yb, wi, ab, xb, B, use_drop != 0, nullptr, st));
+  RD_TRY(launch_widen_bf16(xb, gx, nx, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 // The same through the TILED kernel (k_d2_dgrad_slab_t16): gy [B,6,OH,OW,128], aux / gx [B,11,2 OH - 1,2 OW - 1,64]; OH, OW multiples of 4.
@@ -2948,30 +2710,19 @@ extern "C" int rdgan_op_d2_dgrad_slab_t16(const float* gy, const float* w, const
                                           void* stream) {
   if (!gy || !w || !aux || !gx || B < 1 || OH < 4 || OW < 4 || (OH & 3) || (OW & 3)) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const long ny = (long)B * 6 * OH * OW * 128, nx = (long)B * 11 * (2 * OH - 1) * (2 * OW - 1) * 64;
+  const long nx = (long)B * 11 * (2 * OH - 1) * (2 * OW - 1) * 64;
   if (nx * 2 >= 0x7FFFFFF0L) return -2;
-  void *yb = nullptr, *ab = nullptr, *xb = nullptr, *wi = nullptr;
-  int rc = (int)hipMalloc(&yb, ny * 2);
-  if (rc == 0) rc = (int)hipMalloc(&ab, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&xb, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&wi, (long)RD_D2S_KSTEPS * 2 * 64 * 16);
-  if (rc == 0) rc = launch_to_bf16(nullptr, gy, yb, ny, st);
-  if (rc == 0) rc = launch_to_bf16(nullptr, aux, ab, nx, st);
-  if (rc == 0) rc = (int)hipMemsetAsync(xb, 0xFF, nx * 2, st);          // (NaN pattern: every destination must be written)
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_d2s_wimg, dim3((RD_D2S_KSTEPS * 2 * 64 + 255) / 256), dim3(256), 0, st, w, (unsigned short*)wi);
-    rc = ensure_lds(nullptr, (const void*)k_d2_dgrad_slab_t16, RD_D2T_LDS);
-  }
-  if (rc == 0) {
-    const long items = (long)((B + 1) / 2) * (OH / 4) * (OW / 4);
-    hipLaunchKernelGGL(k_d2_dgrad_slab_t16, dim3((unsigned)std::min<long>(items, 512)), dim3(256), RD_D2T_LDS, st, (const rd_bf16_t*)yb,
-                       (const rd_bf16_t*)wi, (const rd_bf16_t*)ab, (rd_bf16_t*)xb, B, OH, OW, use_drop != 0, (const unsigned char*)nullptr);
-    hipLaunchKernelGGL(k_bf16_to_f32, dim3(ew_blocks(nx)), dim3(256), 0, st, (const rd_bf16_t*)xb, gx, nx);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  for (void* p : {yb, ab, xb, wi}) if (p) (void)hipFree(p);
-  return rc;
+  TmpBufs t;
+  void* yb = t.to_bf16(gy, (long)B * 6 * OH * OW * 128, st);
+  void* ab = t.to_bf16(aux, nx, st);
+  void* xb = t.bf16(nx);
+  void* wi = t.bytes((size_t)RD_D2S_KSTEPS * 2 * 64 * 16);
+  RD_TRY(t.rc);
+  RD_TRY((int)hipMemsetAsync(xb, 0xFF, nx * 2, st));          // (NaN pattern: every destination must be written)
+  launch_d2s_wimg(w, wi, st);
+  RD_TRY(launch_d2_dgrad_slab_t(nullptr, kOpRec, yb, wi, ab, xb, B, OH, OW, use_drop != 0, nullptr, st));
+  RD_TRY(launch_widen_bf16(xb, gx, nx, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 // Generator block 2 forward of the bf16 storage mode through the slab kernel alone (rdgan_upconv16b.hip.h): x [B,6,4,4,256] and the
@@ -2980,27 +2731,18 @@ extern "C" int rdgan_op_d2_dgrad_slab_t16(const float* gy, const float* w, const
 extern "C" int rdgan_op_upconv2_slab16(const float* x, const float* w, const float* bias, float* y, float* rinv, int B, void* stream) {
   if (!x || !w || !bias || !y || !rinv || B < 1) return -2;
   hipStream_t st = (hipStream_t)stream;
-  const long nx = (long)B * 96 * 256, ny = (long)B * 768 * 128;
-  void *xb = nullptr, *yb = nullptr, *wi = nullptr; float* wc = nullptr;
-  int rc = (int)hipMalloc(&xb, nx * 2);
-  if (rc == 0) rc = (int)hipMalloc(&yb, ny * 2);
-  if (rc == 0) rc = (int)hipMalloc(&wi, (long)RD_UP2_KSTEPS * 4 * 64 * 16);
-  if (rc == 0) rc = (int)hipMalloc((void**)&wc, 64L * 256 * 128 * sizeof(float));
-  if (rc == 0) rc = launch_to_bf16(nullptr, x, xb, nx, st);
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * 256 * 128)), dim3(256), 0, st, w, wc, 256 * 128);
-    hipLaunchKernelGGL(k_upconv2_wimg, dim3(RD_UP2_KSTEPS), dim3(256), 0, st, wc, (unsigned short*)wi);
-    rc = ensure_lds(nullptr, (const void*)k_upconv2_slab16, RD_UP2_LDS);
-  }
-  if (rc == 0) {
-    hipLaunchKernelGGL(k_upconv2_slab16, dim3((unsigned)std::min(B, 256 * RD_UP2_WGS)), dim3(256), RD_UP2_LDS, st, (const rd_bf16_t*)xb,
-                       (const rd_bf16_t*)wi, bias, (rd_bf16_t*)yb, rinv, B);
-    hipLaunchKernelGGL(k_bf16_to_f32, dim3(ew_blocks(ny)), dim3(256), 0, st, (const rd_bf16_t*)yb, y, ny);
-    rc = (int)hipGetLastError();
-  }
-  if (rc == 0) rc = (int)hipStreamSynchronize(st);
-  for (void* p : {xb, yb, wi, (void*)wc}) if (p) (void)hipFree(p);
-  return rc;
+  const long ny = (long)B * 768 * 128;
+  TmpBufs t;
+  void* xb = t.to_bf16(x, (long)B * 96 * 256, st);
+  void* yb = t.bf16(ny);
+  void* wi = t.bytes((size_t)RD_UP2_KSTEPS * 4 * 64 * 16);
+  float* wc = t.floats(64L * 256 * 128);
+  RD_TRY(t.rc);
+  hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * 256 * 128)), dim3(256), 0, st, w, wc, 256 * 128);
+  launch_upconv2_wimg(wc, wi, st);
+  RD_TRY(launch_upconv2_slab(nullptr, kOpRec, xb, wi, bias, yb, rinv, B, st));
+  RD_TRY(launch_widen_bf16(yb, y, ny, st));
+  return (int)hipStreamSynchronize(st);
 }
 
 extern "C" int rdgan_op_pixelnorm_lrelu(const float* y, float* hout, float* rinv, long npix, int C, void* stream) {

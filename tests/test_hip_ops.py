@@ -604,8 +604,8 @@ def test_d3_wgrad_slab_kernel_vs_definition(B):
 # ---- The bf16 slab kernels alone at the sizes the engine launches them with: BASELINE configs[2] (the critic's 3B = 6144 rows, the
 # generator's B = 2048) and configs[4]'s ndomain-64 shard (3B = 192).  References in fp64 ON THE DEVICE,
 # on the bf16-rounded operands, with the tolerances of the small-batch rows above.  Every rdgan_op_* wrapper used here allocates its own
-# bf16 copies and partial-slab workspace, sized for its B, and picks the group count G the engine picks for the same B (rdgan_api.hip);
-# none caps B.  The engine's own workspace at these sizes is covered by the oracle comparisons of tests/test_hip_fullsize.py.
+# bf16 copies and partial-slab workspace, sized for its B, and launches through the step's own launcher (csrc/rdgan_slab_launch.h: grid, LDS,
+# group count G and fold are the ones the engine runs for the same B); none caps B.  The engine's own workspace at these sizes is covered by the oracle comparisons of tests/test_hip_fullsize.py.
 
 def _randn_dev(shape, seed, scale=1.0):
     g = torch.Generator(device="cuda")
