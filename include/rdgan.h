@@ -389,6 +389,35 @@ long rdgan_ecdf_workspace_bytes(int n_grid);
 int rdgan_ecdf_grid(const float* x, long n_values, const float* grid, int n_grid, long long* counts_out, void* workspace,
                     long workspace_bytes, void* stream);
 
+/* Whole daily fields through the generator: the tiling and stitching around rdgan_gen_forward.
+ * daily [n_days][ny][nx] fp32 on the device, mm/day.  Tile plan, the same in all three entries: nd = the generator's ndomain (one
+ * rdgan_create accepts), 0 <= overlap <= nd / 2, ny >= nd, nx >= nd; step = nd - overlap; along an axis of length L the tiles start
+ * at min(i * step, L - nd), i = 0 .. ceil((L - nd) / step); tile = iy * n_tx + ix, T = n_ty * n_tx tiles per day, n_days * T < 2^31.
+ * All three: asynchronous on the stream (a host table is copied before the call returns), 0 = success, -2 = bad argument -- a null
+ * pointer, an nd rdgan_create refuses, an overlap outside 0 .. nd / 2, ny or nx < nd, a count < 1, an entry or slot out of range --
+ * and nothing is launched on a bad argument.
+ *
+ * rdgan_field_scan: counts_out [n_days][T][3] int32 (device) = per (day, tile) the number of wet pixels (finite and > 0), of NaN
+ * pixels and of bad ones (negative or infinite).
+ * rdgan_field_cond: the condition batch of m tiles.  entries [m] int32 on the HOST, entries[i] = day * T + tile, each in
+ * 0 .. n_days * T - 1; cond_out [m][nd][nd][1] (device) = (float)((double)daily / norm_scale) -- the quotient
+ * raindisagg_gan_pretrained.generate_scenarios forms -- and 0 where daily is NaN.  norm_scale > 0.
+ * rdgan_field_blend: a group of `units` whole (scenario, day) units.  frac [m][24][nd][nd] (device), the output of rdgan_gen_forward
+ * as it stands, m < 2^31; slots [units][T] int32 on the HOST: the row of frac that holds (unit, tile), -1 for a tile that was
+ * skipped, every other value in 0 .. m - 1; unit u of the group is day (first_unit + u) % n_days, first_unit >= 0; ytab_idx [ny][3]
+ * int32 and ytab_w [ny][3] fp32 (device): the (up to 3) tiles along y that cover a row, ascending, -1 when there are fewer, and
+ * their weights, which sum to 1; xtab_idx [nx][3], xtab_w likewise; out [units][24][ny][nx] (device), any 4-byte alignment:
+ *   out[u][h][y][x] = daily[day][y][x] * sum_a sum_b (ytab_w[y][a] * xtab_w[x][b]) * frac[slot][h][y - oy][x - ox]
+ * in fp32, a outer and b inner, the products rounded before they are added; a skipped tile adds nothing; where daily is 0 the 24
+ * values are 0 and where it is NaN they are NaN, whatever frac holds.  A table entry that does not cover its coordinate is ignored.
+ * All offsets are 64-bit.  No atomics: repeated calls agree bit for bit. */
+int rdgan_field_scan(const float* daily, long n_days, int ny, int nx, int nd, int overlap, int* counts_out, void* stream);
+int rdgan_field_cond(const float* daily, long n_days, int ny, int nx, int nd, int overlap, const int* entries, long m,
+                     double norm_scale, float* cond_out, void* stream);
+int rdgan_field_blend(const float* frac, long m, const int* slots, long units, long first_unit, const int* ytab_idx,
+                      const float* ytab_w, const int* xtab_idx, const float* xtab_w, const float* daily, long n_days, int ny, int nx,
+                      int nd, int overlap, float* out, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

@@ -6,6 +6,7 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
   * ``engine.Engine`` -- thin object over the C ABI of include/rdgan.h
   * evaluation, imported as submodules like the rest: ``ensemble``, ``spectral``, ``rainfarm``, ``crps_experiment``,
     ``distribution``
+  * ``field`` -- disaggregate: whole daily fields through the generator, overlapping tiles blended on the device
 """
 from .engine import Engine, require_gpu  # noqa: F401
 from . import weights  # noqa: F401

@@ -37,6 +37,7 @@
 #include "rdgan_crps.hip.h"
 #include "rdgan_dist.hip.h"
 #include "rdgan_radar.hip.h"
+#include "rdgan_field.hip.h"
 static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
 // k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
 static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
@@ -3002,6 +3003,75 @@ extern "C" int rdgan_ecdf_grid(const float* x, long n_values, const float* grid,
                      n_values, grid, n_grid, hist);
   hipLaunchKernelGGL(k_ecdf_scan, dim3(1), dim3(RD_DIST_THREADS), 0, st, hist, n_grid, counts_out);
   return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// whole daily fields (rdgan_field.hip.h): tile scan, condition batch, blend
+// ------------------------------------------------------------------------------------
+static bool rd_field_geometry_ok(long n_days, int ny, int nx, int nd, int overlap) {
+  return rd_geometry_ok(nd, 1, 1) && overlap >= 0 && overlap <= nd / 2 && ny >= nd && nx >= nd && n_days >= 1;
+}
+
+// a small host table for the next launch: a stream-ordered device copy, freed behind the launch by the caller
+static int rd_field_upload(const int* host, size_t n, int** dev, hipStream_t st) {
+  hipError_t e = hipMallocAsync((void**)dev, n * sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  e = hipMemcpyAsync(*dev, host, n * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) {
+    (void)hipFreeAsync(*dev, st);
+    return (int)e;
+  }
+  return 0;
+}
+
+extern "C" int rdgan_field_scan(const float* daily, long n_days, int ny, int nx, int nd, int overlap, int* counts_out, void* stream) {
+  if (!daily || !counts_out || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
+  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
+  if ((long)n_ty * n_tx > 0x7FFFFFFFL / n_days) return -2;                 // an entry number day * T + tile is an int32
+  const long entries = n_days * n_ty * n_tx;
+  const long blocks = std::min<long>((entries + 3) / 4, 0xFFFFFFL);        // the kernel loops over the rest
+  hipLaunchKernelGGL(k_field_scan, dim3((unsigned)blocks), dim3(RD_FIELD_THREADS), 0, (hipStream_t)stream, daily, entries, ny, nx, nd,
+                     step, n_ty, n_tx, counts_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_field_cond(const float* daily, long n_days, int ny, int nx, int nd, int overlap, const int* entries, long m,
+                                double norm_scale, float* cond_out, void* stream) {
+  if (!daily || !entries || !cond_out || m < 1 || !(norm_scale > 0.0) || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
+  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
+  if ((long)n_ty * n_tx > 0x7FFFFFFFL / n_days) return -2;
+  const long n_entries = n_days * n_ty * n_tx;
+  for (long i = 0; i < m; ++i)
+    if (entries[i] < 0 || entries[i] >= n_entries) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  int* dev = nullptr;
+  RD_TRY(rd_field_upload(entries, (size_t)m, &dev, st));
+  hipLaunchKernelGGL(k_field_cond, dim3(ew_blocks(m * nd * nd, RD_FIELD_THREADS)), dim3(RD_FIELD_THREADS), 0, st, daily, dev, m, ny, nx,
+                     nd, step, n_ty, n_tx, norm_scale, cond_out);
+  hipError_t e = hipGetLastError();
+  hipError_t f = hipFreeAsync(dev, st);
+  return (int)(e != hipSuccess ? e : f);
+}
+
+extern "C" int rdgan_field_blend(const float* frac, long m, const int* slots, long units, long first_unit, const int* ytab_idx,
+                                 const float* ytab_w, const int* xtab_idx, const float* xtab_w, const float* daily, long n_days,
+                                 int ny, int nx, int nd, int overlap, float* out, void* stream) {
+  if (!frac || !slots || !ytab_idx || !ytab_w || !xtab_idx || !xtab_w || !daily || !out) return -2;
+  if (m < 1 || m > 0x7FFFFFFFL || units < 1 || first_unit < 0 || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
+  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
+  const long T = (long)n_ty * n_tx;
+  if (T > 0x7FFFFFFFL || units > 0x7FFFFFFFL / T) return -2;
+  for (long i = 0; i < units * T; ++i)
+    if (slots[i] < -1 || slots[i] >= m) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  int* dev = nullptr;
+  RD_TRY(rd_field_upload(slots, (size_t)(units * T), &dev, st));
+  const long nb = units * ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * ((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
+  hipLaunchKernelGGL(k_field_blend, dim3((unsigned)std::min<long>(nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0, st, frac, dev, ytab_idx,
+                     ytab_w, xtab_idx, xtab_w, daily, out, units, first_unit, n_days, ny, nx, nd, step, n_ty, n_tx);
+  hipError_t e = hipGetLastError();
+  hipError_t f = hipFreeAsync(dev, st);
+  return (int)(e != hipSuccess ? e : f);
 }
 
 // ------------------------------------------------------------------------------------

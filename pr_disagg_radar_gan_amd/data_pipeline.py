@@ -209,6 +209,10 @@ class DeviceDataset:
             self.daily = daily
         return self.daily
 
+    def daily_plane(self):
+        """The (n_days, ny, nx) daily sums on the device (built on first use): what field.disaggregate takes without a host copy."""
+        return self.ensure_daily()
+
     def save_npy(self, path):
         """write self.data as the reference's `{start}-{end}_tres1.npy` (write_npy)"""
         return write_npy(path, self.data)

@@ -61,6 +61,22 @@ def generate_scenarios(cond, n_scenarios):
     return generated * cond.squeeze() * norm_scale
 
 
+def generate_scenarios_field(daily, n_scenarios, overlap=4, latent_mode="shared"):
+    """generate_scenarios for a whole daily map instead of one tile (field.disaggregate on the module's ``gen`` and
+    ``norm_scale``).  daily: ndarray (ny, nx) or (n_days, ny, nx), daily sums in mm/day, ny, nx >= ndomain; a trailing axis of 1, as
+    ``cond`` has it, is accepted.  Returns float64 ndarray (n_scenarios, [n_days,] 24, ny, nx) in mm/h, squeezed as
+    generate_scenarios squeezes; every pixel's 24 values sum to its daily value, NaN pixels give NaN.  Tiles overlap by ``overlap``
+    pixels and are blended; the latent noise comes from the global numpy RNG, one vector per (scenario, day) shared by all tiles
+    (``latent_mode="shared"``) or one per tile (``"independent"``).  On an (ndomain, ndomain) field with overlap 0 this is
+    generate_scenarios."""
+    from . import field
+    daily = np.asarray(daily)
+    if daily.ndim >= 3 and daily.shape[-1] == 1:
+        daily = daily[..., 0]
+    out, _ = field.disaggregate(gen, daily, n_scenarios, overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
+    return out.cpu().numpy().astype(np.float64).squeeze()
+
+
 def plot_scenarios(scenarios):
     """reference :68-90: one row per scenario, 24 hourly panels, LogNorm(0.01, 50), gist_earth_r.
     Keeps the reference's indexing ``scenarios[iplot, jplot - 1]`` (the column labelled 00:00 shows
