@@ -305,11 +305,16 @@ int rdgan_launch_table(rdgan_handle* h, rdgan_launch_stat* out, int cap, int* n_
  * rdgan_data_gather: the tile gather + normalisation of generate_real_samples / generate_latent_points
  * (T:149-166, T:181-190): indices[n][3] = (tidx, yidx, xidx) int32 on the device; batch_out [n,24,nd,nd,1] =
  * hourly fractions of the daily sum (NULL: condition only), cond_out [n,nd,nd,1] = daily sum / norm_scale;
- * *flags |= 1 for a non-finite value (the reference asserts none, T:169-170), |= 2 for a fraction outside [0,1].
+ * *flags |= 1 for a non-finite value (the reference asserts none, T:169-170), |= 2 for a finite fraction outside [0,1]
+ * (T:171-172; with batch_out NULL only bit 1, for the condition).  The word ACCUMULATES: rdgan_data_gather never clears it, so one
+ * read after several gathers sees all of them.  The caller owns it: it zeroes the word before the first gather and again after it
+ * has read it (DeviceDataset.check_flags does both).  -2 = bad argument (NULL data / indices / cond_out / flags, non-positive
+ * n_days / n / ndomain, ndomain > ny or > nx); the indices themselves are not checked on the device (DeviceDataset.set_indices does).
  * rdgan_data_valid_tiles: compute_valid_indices.py:74-92 -- valid_out[day][ii/stride][jj/stride] (int32 0/1) for the
  * boxes ii in range(0, ny-ndomain, stride), jj in range(0, nx-ndomain, stride): no NaN in the daily sum and at
  * least n_thresh points above tp_thresh_daily.  Bit-identical to the numpy forms.  rdgan_data_valid_tiles takes at most 2^24 - 1
- * boxes per call (-2 beyond: one workgroup per box; rdgan_data_valid_tiles_daily has no such limit). */
+ * boxes per call (-2 beyond: one workgroup per box; rdgan_data_valid_tiles_daily has no such limit); -2 also for a NULL pointer,
+ * non-positive extents, stride < 1 and ndomain > ny or > nx.  No boxes (ny == ndomain, say) is success and writes nothing. */
 int rdgan_data_gather(const float* data, int n_days, int ny, int nx, const int* indices, int n, int ndomain,
                       float norm_scale, float* batch_out, float* cond_out, int* flags, void* stream);
 int rdgan_data_valid_tiles(const float* data, int n_days, int ny, int nx, int ndomain, int stride,

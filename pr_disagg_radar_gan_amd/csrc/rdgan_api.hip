@@ -2818,18 +2818,16 @@ extern "C" int rdgan_op_rng(uint64_t seed, uint32_t stream_id, float* mask_out, 
 // ------------------------------------------------------------------------------------
 extern "C" int rdgan_data_gather(const float* data, int n_days, int ny, int nx, const int* indices, int n, int ndomain,
                                  float norm_scale, float* batch_out, float* cond_out, int* flags, void* stream) {
-  if (!data || !indices || !cond_out || !flags || n < 1 || ndomain < 1 || ndomain > ny || ndomain > nx) return -2;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(flags, 0, sizeof(int), st);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(k_gather_tiles, dim3(ew_blocks((long)n * ndomain * ndomain)), dim3(256), 0, st, data, n_days, RDGAN_NHOURS,
-                     ny, nx, indices, n, ndomain, norm_scale, batch_out, cond_out, flags);
+  if (!data || !indices || !cond_out || !flags || n_days < 1 || n < 1 || ndomain < 1 || ndomain > ny || ndomain > nx) return -2;
+  // *flags accumulates over calls (include/rdgan.h): the caller zeroes it before the first gather and after reading it
+  hipLaunchKernelGGL(k_gather_tiles, dim3(ew_blocks((long)n * ndomain * ndomain)), dim3(256), 0, (hipStream_t)stream, data, n_days,
+                     RDGAN_NHOURS, ny, nx, indices, n, ndomain, norm_scale, batch_out, cond_out, flags);
   return (int)hipGetLastError();
 }
 
 extern "C" int rdgan_data_valid_tiles(const float* data, int n_days, int ny, int nx, int ndomain, int stride,
                                       float tp_thresh_daily, int n_thresh, int* valid_out, void* stream) {
-  if (!data || !valid_out || n_days < 1 || stride < 1 || ndomain < 1) return -2;
+  if (!data || !valid_out || n_days < 1 || ny < 1 || nx < 1 || stride < 1 || ndomain < 1 || ndomain > ny || ndomain > nx) return -2;
   const int nbi = (ny - ndomain + stride - 1) / stride, nbj = (nx - ndomain + stride - 1) / stride;   // len(range(0, ny-nd, stride))
   if (nbi < 1 || nbj < 1) return 0;
   const long blocks = (long)n_days * nbi * nbj;

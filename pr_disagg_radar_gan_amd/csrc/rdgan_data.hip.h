@@ -9,7 +9,8 @@
 #include <hip/hip_runtime.h>
 
 // one thread per (sample, y, x) pixel of the tile; coalesced along x.  flags[0] |= 1 if any output is non-finite
-// (the reference asserts ~isnan, T:169-170), flags[0] |= 2 if a fraction is outside [0,1] (T:171-172).
+// (the reference asserts ~isnan, T:169-170), flags[0] |= 2 if a fraction is outside [0,1] (T:171-172).  The word is only ever
+// OR-ed into: whoever reads it clears it (include/rdgan.h).
 __global__ void k_gather_tiles(const float* __restrict__ data, int n_days, int nh, int ny, int nx,
                                const int* __restrict__ idx, int n, int nd, float norm_scale, float* __restrict__ batch,
                                float* __restrict__ cond, int* __restrict__ flags) {

@@ -251,11 +251,19 @@ class DeviceDataset:
         return torch.cat([cond] + planes, dim=-1).contiguous()
 
     def set_indices(self, indices):
-        idx = np.ascontiguousarray(np.asarray(indices), dtype=np.int32)
-        if idx.ndim != 2 or idx.shape[1] != 3:
+        """(n_samples, 3) rows (tidx, yidx, xidx) of tile origins, checked here because the gather kernel does not: every tile must lie
+        inside the array (yidx <= ny - ndomain, xidx <= nx - ndomain), no component negative, at least one row.  ValueError otherwise,
+        before anything is uploaded."""
+        raw = np.asarray(indices)
+        if raw.ndim != 2 or raw.shape[1] != 3:
             raise ValueError("indices must have shape (n_samples, 3)")
-        if idx[:, 0].max() >= self.n_days or idx[:, 1].max() + self.ndomain > self.ny or idx[:, 2].max() + self.ndomain > self.nx:
+        if raw.shape[0] == 0:
+            raise ValueError("indices are empty: no tile to sample from")
+        if raw.min() < 0:                  # (checked before the cast to int32: the gather would read in front of the array)
+            raise ValueError("negative index: tidx, yidx and xidx count from 0")
+        if raw[:, 0].max() >= self.n_days or raw[:, 1].max() + self.ndomain > self.ny or raw[:, 2].max() + self.ndomain > self.nx:
             raise ValueError("index outside the data array")
+        idx = np.ascontiguousarray(raw, dtype=np.int32)
         self.indices = torch.from_numpy(idx).to(self.device)
         self.n_samples = idx.shape[0]
 
@@ -277,8 +285,13 @@ class DeviceDataset:
         return batch, cond
 
     def check_flags(self):
-        """the reference's asserts (T:169-172), checked once per call site instead of per batch element"""
+        """The reference's asserts (T:169-172), checked once per call site instead of per batch element.  The flag word on the device
+        accumulates over every gather since the last check (rdgan_data_gather only ORs into it; it starts at zero): this reads it,
+        clears it on the device, then raises AssertionError if a bit was set -- so one check after several sample_real / sample_latent
+        calls covers all of them, and the check after a raise starts from a clean word."""
         f = int(self.flags.item())
+        if f:
+            self.flags.zero_()
         if f & 1:
             raise AssertionError("NaN/Inf in gathered batch or condition (daily sum of zero or missing data)")
         if f & 2:

@@ -336,7 +336,7 @@ def train(n_epochs, _batch_size, start_epoch=0, make_plots=False, max_batches_pe
                     latent = torch.from_numpy(np.random.normal(size=(per, latent_dim)).astype(np.float32)).to(dev)
                     crit.append((X_real, cond_real, latent))
                 gen_batch = device_dataset.sample_latent(per, latent_dim)
-                device_dataset.check_flags()
+                device_dataset.check_flags()             # the flag word accumulated over all the gathers above
             else:
                 for _ in range(n_disc):
                     X_real, cond_real = next(sample_gen)
