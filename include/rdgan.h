@@ -232,7 +232,14 @@ int rdgan_critic_param_layout(const rdgan_handle* h, long* offsets, long* sizes)
  * "d1_dgrad_fused" (default 1; bf16 storage mode, ndomain 16, one condition channel): the first critic layer's input gradient
  * with respect to the sample channel (the penalty's dD/dx_hat and the generator step's dL/dfake) in one pass per sample
  * (k_d1_dgrad_sample16: the 539 x 27 tap products of a sample stay in LDS, the outputs gather from there); same sums in the same
- * order as 0 = column GEMM [rows][64] in HBM + k_d1_col2im.
+ * order as 0 = column GEMM [rows][64] in HBM + k_d1_col2im.  fp32 storage, ndomain 16: the same by k_d1_dgrad_sample32 on the fp32
+ * matrix pipe (the k order of the streaming GEMM: the same products); in the critic step's gradient-penalty sweep that pass also
+ * takes the per-sample norm, the penalty term and the second sweep's input (k_gp_norm_r0's work, same reduction order): 0 = the
+ * column GEMM + k_d1_col2im + k_gp_norm_r0.  Other ndomains with fp32 storage keep the column GEMM.
+ * "combine_dx_fused" (default 1; fp32 storage, shared-centre backward "fast_bwd"): the gradient of a block's difference part is
+ * folded into the block's input gradient by the PixelNorm/LeakyReLU backward of the block before it (k_pn_lrelu_bwd_pairs /
+ * k_pn_lrelu_bwd form dx + (dE[d] - dE[d+1]) per element, k_combine_dx's expression; the combined dx is not stored: nothing else
+ * reads it).  0 = k_combine_dx in a pass of its own.  Bit-identical either way.
  * "d1_wgrad16" (default 1; bf16 storage mode, one condition channel): the first critic layer's weight gradient runs on the bf16
  * matrix pipe (k_d1_wgrad16: im2col rows rounded to bf16 as in the layer's forward GEMM, both operands read transposed from
  * position-major LDS images) and delivers the layer's bias gradient from a ones column of the same product; 0 = the fp32-pipe
@@ -571,6 +578,12 @@ int rdgan_op_pixelnorm_lrelu_bwd(const float* gh, const float* h, const float* r
  * gate bytes of critic layer 1 as floats, 16 per row: byte q of a row = channels 4 q .. 4 q + 3, two bits each (bit 0: output > 0,
  * bit 1: dropped). */
 int rdgan_debug_activation(rdgan_handle* h, int which, float* out, long n, void* stream);
+/* Test hook (fp32 storage): the first critic layer's input gradient with respect to the sample channel, g0_out [B][24][nd][nd],
+ * from a given output gradient u1 [B][L1][64] (device, fp32) by the route the steps take (option "d1_dgrad_fused").  with_norm != 0:
+ * as the critic step's gradient-penalty sweep, also gp_out [B] = ||g0|| - 1 and cin_hat_out [B][24 nd nd][CP] = the second sweep's
+ * input (r0, 0).  Asynchronous on `stream`; overwrites the critic workspace. */
+int rdgan_debug_d1_input_grad(rdgan_handle* h, const float* critic_params, const float* u1, int B, int with_norm,
+                              float* g0_out, float* cin_hat_out, float* gp_out, void* stream);
 /* dropout keep-scale mask (0 or 1/0.75) and uniforms of the counter RNG, for pinning it to oracle/rng.py */
 int rdgan_op_rng(uint64_t seed, uint32_t stream_id, float* mask_out, float* uniform_out, long n,
                  void* stream);

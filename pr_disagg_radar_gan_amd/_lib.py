@@ -116,6 +116,8 @@ SIGNATURES = {
     "rdgan_op_pixelnorm_lrelu": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, c_stream]),
     "rdgan_op_pixelnorm_lrelu_bwd": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, c_stream]),
     "rdgan_debug_activation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_f32p, ctypes.c_long, c_stream]),
+    "rdgan_debug_d1_input_grad": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, c_f32p,
+                                                 c_stream]),
     "rdgan_op_rng": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_f32p, c_f32p, ctypes.c_long, c_stream]),
 }
 

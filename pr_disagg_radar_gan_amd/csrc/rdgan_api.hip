@@ -92,7 +92,9 @@ struct rdgan_handle : RdGeom {     // geometry + parameter layout: rdgan_hostpla
   int d3_wgrad_slab = 1;          // 1: bf16 storage mode, ndomain 16: weight gradient of critic layer 3 by k_d3_wgrad_slab16
   int d2_wgrad_slab = 1;          // 1: bf16 storage mode, ndomain 16: weight gradient of critic layer 2 by k_d2_wgrad_slab16
   int upwgrad_slab = 1;           // 1: bf16 storage mode, ndomain 16, collapsed form: weight gradient of generator block 3 by k_upconv_wgrad_slab16
-  int d1_dgrad_fused = 1;         // 1: bf16 storage mode, ndomain 16: dD/d(sample) of layer 1 in one pass per sample (k_d1_dgrad_sample16)
+  int d1_dgrad_fused = 1;         // 1: ndomain 16: dD/d(sample) of layer 1 in one pass per sample (k_d1_dgrad_sample16; fp32 storage: k_d1_dgrad_sample32,
+                                  // which in the critic step also takes the penalty's norm pass k_gp_norm_r0)
+  int combine_dx_fused = 1;       // 1: fp32 storage, shared-centre backward: the next PixelNorm backward folds the difference part's gradient into dx itself (no k_combine_dx)
   int d1_wgrad16 = 1;             // 1: bf16 storage mode: layer-1 weight gradient + bias gradient on the bf16 matrix pipe (k_d1_wgrad16)
   void* bW2F = nullptr;           // weight image of the slab kernel of critic layer 2's forward (rdgan_d2fwd16.hip.h): 448 KB
   int d2_fwd_slab = 0;            // 1: bf16 storage mode, ndomain 16: forward of critic layer 2 by k_d2_fwd_slab16 (measured: no faster than the streaming GEMM, default off)
@@ -821,13 +823,15 @@ static int launch_pn_fwd(rdgan_handle* h, const float* y, float* hout, float* ri
   RD_CHECK(h, hipGetLastError());
   return 0;
 }
+// dE (fp32 storage, pool = 0): the difference part's gradient [B][D + 1][H][W][C] that the kernel folds into g (k_combine_dx fused in)
 static int launch_pn_bwd(rdgan_handle* h, const float* g, const float* hh, const float* rinv, float* dy, long npix, int C,
-                         int pool, int D, int H, int W, hipStream_t st, bool a16 = false) {
+                         int pool, int D, int H, int W, hipStream_t st, bool a16 = false, const float* dE = nullptr) {
   long threads = npix * (C / 4);
   dim3 grid((unsigned)((threads + 255) / 256));
-#define RD_PNB(LP, PO) hipLaunchKernelGGL((k_pn_lrelu_bwd<LP, PO>), grid, dim3(256), 0, st, g, hh, rinv, dy, npix, D, H, W)
+  if (dE && (a16 || pool || D < 1 || H < 1 || W < 1)) return bad_arg(h, "pixelnorm bwd: dE needs fp32 storage and the collapsed form");
+#define RD_PNB(LP, PO) hipLaunchKernelGGL((k_pn_lrelu_bwd<LP, PO>), grid, dim3(256), 0, st, g, hh, rinv, dy, npix, D, H, W, dE)
 #define RD_PNB16(LP) hipLaunchKernelGGL((k_pn_lrelu_bwd<LP, 0, rd_bf16_t>), grid, dim3(256), 0, st, (const rd_bf16_t*)g, \
-                                        (const rd_bf16_t*)hh, rinv, (rd_bf16_t*)dy, npix, D, H, W)
+                                        (const rd_bf16_t*)hh, rinv, (rd_bf16_t*)dy, npix, D, H, W, (const rd_bf16_t*)nullptr)
   if (a16) {
     if (pool) return bad_arg(h, "pixelnorm bwd: the bf16 storage mode needs the collapsed form");
     if (C == 256) RD_PNB16(64); else if (C == 128) RD_PNB16(32); else if (C == 64) RD_PNB16(16);
@@ -844,19 +848,21 @@ static int launch_pn_bwd(rdgan_handle* h, const float* g, const float* hh, const
 }
 
 // PixelNorm+LeakyReLU backward over hour-plane pairs, also writing the pair sums gS (shared-centre backward)
+// dE (fp32 storage): the difference part's gradient [B][2 Ds + 1][HW][C], folded into g as in launch_pn_bwd
 static int launch_pn_bwd_pairs(rdgan_handle* h, const float* g, const float* hh, const float* rinv, float* dy, float* gS,
-                               long npair, long HW, int C, hipStream_t st, bool a16 = false) {
+                               long npair, long HW, int C, hipStream_t st, bool a16 = false, const float* dE = nullptr, int Ds = 1) {
   long threads = npair * (C / 4);
   dim3 grid((unsigned)((threads + 255) / 256));
+  if (dE && (a16 || Ds < 1)) return bad_arg(h, "pixelnorm bwd: dE needs fp32 storage");
 #define RD_PNP16(LP) hipLaunchKernelGGL((k_pn_lrelu_bwd_pairs<LP, rd_bf16_t>), grid, dim3(256), 0, st, (const rd_bf16_t*)g, \
-                                        (const rd_bf16_t*)hh, rinv, (rd_bf16_t*)dy, (rd_bf16_t*)gS, npair, HW)
+                                        (const rd_bf16_t*)hh, rinv, (rd_bf16_t*)dy, (rd_bf16_t*)gS, npair, HW, (const rd_bf16_t*)nullptr, 1)
   if (a16) {
     if (C == 256) RD_PNP16(64); else if (C == 128) RD_PNP16(32); else if (C == 64) RD_PNP16(16);
     else return bad_arg(h, "pixelnorm bwd: C must be 64/128/256");
   }
-  else if (C == 256) hipLaunchKernelGGL(k_pn_lrelu_bwd_pairs<64>, grid, dim3(256), 0, st, g, hh, rinv, dy, gS, npair, HW);
-  else if (C == 128) hipLaunchKernelGGL(k_pn_lrelu_bwd_pairs<32>, grid, dim3(256), 0, st, g, hh, rinv, dy, gS, npair, HW);
-  else if (C == 64) hipLaunchKernelGGL(k_pn_lrelu_bwd_pairs<16>, grid, dim3(256), 0, st, g, hh, rinv, dy, gS, npair, HW);
+  else if (C == 256) hipLaunchKernelGGL(k_pn_lrelu_bwd_pairs<64>, grid, dim3(256), 0, st, g, hh, rinv, dy, gS, npair, HW, dE, Ds);
+  else if (C == 128) hipLaunchKernelGGL(k_pn_lrelu_bwd_pairs<32>, grid, dim3(256), 0, st, g, hh, rinv, dy, gS, npair, HW, dE, Ds);
+  else if (C == 64) hipLaunchKernelGGL(k_pn_lrelu_bwd_pairs<16>, grid, dim3(256), 0, st, g, hh, rinv, dy, gS, npair, HW, dE, Ds);
   else return bad_arg(h, "pixelnorm bwd: C must be 64/128/256");
 #undef RD_PNP16
   RD_CHECK(h, hipGetLastError());
@@ -1091,6 +1097,7 @@ extern "C" int rdgan_set_option(rdgan_handle* h, const char* name, int value) {
   if (!strcmp(name, "d2_wgrad_slab")) { h->d2_wgrad_slab = value ? 1 : 0; return 0; }
   if (!strcmp(name, "upwgrad_slab")) { h->upwgrad_slab = value ? 1 : 0; return 0; }
   if (!strcmp(name, "d1_dgrad_fused")) { h->d1_dgrad_fused = value ? 1 : 0; return 0; }
+  if (!strcmp(name, "combine_dx_fused")) { h->combine_dx_fused = value ? 1 : 0; return 0; }
   if (!strcmp(name, "d1_wgrad16")) { h->d1_wgrad16 = value ? 1 : 0; return 0; }
   if (!strcmp(name, "wgrad_wide")) { h->wgrad_wide = value ? 1 : 0; return 0; }
   if (!strcmp(name, "conv_f16")) {      // (the forms are rebuilt: their fragment-order twins exist only while the option is on)
@@ -1852,7 +1859,31 @@ static int critic_dgrad_chain(rdgan_handle* h, const float* dp, int NBt, int B, 
 }
 
 // dD/d(sample channel) for `B` samples whose u1 starts at u1: column GEMM + col2im -> h->g0
-static int critic_input_grad(rdgan_handle* h, const float* dp, const float* u1, int B, hipStream_t st) {
+// cin_hat (the gradient-penalty sweep): where the one-pass fp32 kernel runs it also leaves the penalty's norm, coefficient and
+// second-sweep input (k_gp_norm_r0's outputs: h->gpv, cin_hat) and sets *norm_done; otherwise the caller launches that pass
+static int critic_input_grad(rdgan_handle* h, const float* dp, const float* u1, int B, hipStream_t st, float* cin_hat = nullptr,
+                             bool* norm_done = nullptr) {
+  if (norm_done) *norm_done = false;
+  if (!h->a16 && h->d1_dgrad_fused && h->nd == 16 && d1_gemm_ok(h)) {     // one pass, no column matrix (k_d1_dgrad_sample32)
+    ProfScope ps(h, RDGAN_TAG_CRITIC_GEMM, st);
+    LaunchScope ls(h, PL_D1B, RD_KIND_CONV, B, 2.0 * B * h->dL[1] * 27 * 64, st);
+    h->flops_acc += 2.0 * B * h->dL[1] * 27 * 64;
+    const dim3 grid((unsigned)std::min(B, 512));
+    if (cin_hat && norm_done) {
+      RD_KNAME(h, "k_d1_dgrad_sample32<gp>");
+      RD_TRY(ensure_lds(h, (const void*)k_d1_dgrad_sample32<true>, RD_D1DG_LDS_GP));
+      hipLaunchKernelGGL(k_d1_dgrad_sample32<true>, grid, dim3(256), RD_D1DG_LDS_GP, st, u1, dp + h->doff[0], h->g0, B, cin_hat, h->gpv,
+                         RD_GP_WEIGHT);
+      *norm_done = true;
+    } else {
+      RD_KNAME(h, "k_d1_dgrad_sample32");
+      RD_TRY(ensure_lds(h, (const void*)k_d1_dgrad_sample32<false>, RD_D1DG_LDS));
+      hipLaunchKernelGGL(k_d1_dgrad_sample32<false>, grid, dim3(256), RD_D1DG_LDS, st, u1, dp + h->doff[0], h->g0, B, (float*)nullptr,
+                         (float*)nullptr, 0.f);
+    }
+    RD_CHECK(h, hipGetLastError());
+    return 0;
+  }
   if (h->a16 && h->d1_dgrad_fused && h->nd == 16 && d1_gemm_ok(h)) {      // one pass, no column matrix (k_d1_dgrad_sample16)
     ProfScope ps(h, RDGAN_TAG_CRITIC_GEMM, st);
     LaunchScope ls(h, PL_D1B, RD_KIND_CONV, B, 2.0 * B * h->dL[1] * 27 * 64, st);
@@ -1885,6 +1916,22 @@ static int critic_input_grad(rdgan_handle* h, const float* dp, const float* u1, 
   ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
   hipLaunchKernelGGL(k_d1_col2im, dim3(ew_blocks((long)B * h->dL[0])), dim3(256), 0, st, h->P1, h->g0, B, h->ddim[0][0],
                      h->ddim[0][1], h->ddim[0][2], h->ddim[1][0], h->ddim[1][1], h->ddim[1][2], h->Cin, h->ldp1);
+  RD_CHECK(h, hipGetLastError());
+  return 0;
+}
+
+// gradient penalty (T:238-241, T:382) from the x_hat third's u1: h->g0 = dD/dx_hat, h->gpv = ||g0|| - 1 per sample, cin_hat = the
+// second sweep's input (r0, 0) -- in one pass where critic_input_grad has one, else the norm in a pass of its own
+static int critic_penalty_input(rdgan_handle* h, const float* dp, const float* u1, int B, float* cin_hat, hipStream_t st) {
+  bool norm_done = false;
+  RD_TRY(critic_input_grad(h, dp, u1, B, st, cin_hat, &norm_done));
+  if (norm_done) return 0;
+  ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+  // S blocks per sample when there are few samples of many elements (ndomain 64)
+  const int per = (int)h->dL[0];
+  const int S = std::max(1, std::min({(1024 + B - 1) / B, per / 4096, 64}));
+  if (S > 1) hipLaunchKernelGGL(k_gp_norm_part, dim3(B * S), dim3(256), 0, st, h->g0, h->gp_part, per, S);
+  hipLaunchKernelGGL(k_gp_norm_r0, dim3(B * S), dim3(256), 0, st, h->g0, cin_hat, h->gpv, per, B, RD_GP_WEIGHT, h->CP, S, h->gp_part);
   RD_CHECK(h, hipGetLastError());
   return 0;
 }
@@ -1963,16 +2010,8 @@ extern "C" int rdgan_critic_grad_ahead(rdgan_handle* h, const float* dp, const f
     }
   }
   // gradient penalty (T:238-241, T:382): g0 = dD/dx_hat, n = ||g0||, r0 = d(10 mean((n-1)^2))/dg0
-  RD_TRY(critic_input_grad(h, dp, act_off(h, h->du[1], (long)2 * B * h->dL[1] * 64), B, st));
   float* cin_hat = h->cin + (long)2 * B * h->dL[0] * h->CP;
-  {
-    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    // S blocks per sample when there are few samples of many elements (ndomain 64)
-    const int per = (int)h->dL[0];
-    const int S = std::max(1, std::min({(1024 + B - 1) / B, per / 4096, 64}));
-    if (S > 1) hipLaunchKernelGGL(k_gp_norm_part, dim3(B * S), dim3(256), 0, st, h->g0, h->gp_part, per, S);
-    hipLaunchKernelGGL(k_gp_norm_r0, dim3(B * S), dim3(256), 0, st, h->g0, cin_hat, h->gpv, per, B, RD_GP_WEIGHT, h->CP, S, h->gp_part);
-  }
+  RD_TRY(critic_penalty_input(h, dp, act_off(h, h->du[1], (long)2 * B * h->dL[1] * 64), B, cin_hat, st));
   // second forward sweep of the double backward: r_l = gate_l * conv_l(r_{l-1}), in place over the x_hat third
   h->gate_keep_B = 0;
   if (h->keep_gates) {       // test hook: keep the x_hat third of every h_l (see rdgan_debug_activation)
@@ -2139,6 +2178,7 @@ extern "C" int rdgan_gen_grad_after(rdgan_handle* h, const float* dp, const floa
   float* dys[4] = {nullptr, h->dy1, h->dy2, h->gh3};
   float* gups[4] = {nullptr, h->gup1, h->gup2, h->gup3};   // direct: gradient on the upsampled grid; collapsed: on the source grid
   const int col = h->collapse;
+  const float* dE_in = nullptr;     // "combine_dx_fused": block l + 1 has left gups[l + 1] without its difference part, which block l's PixelNorm backward folds in
   if (col) {
     RdSliceMap map;
     collapsed_dgrad_slice_map(map.src);
@@ -2177,13 +2217,14 @@ extern "C" int rdgan_gen_grad_after(rdgan_handle* h, const float* dp, const floa
       ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
       const long HW = (long)h->gdim[l][1] * h->gdim[l][2];
       RD_TRY(launch_pn_bwd_pairs(h, l == 3 ? h->gh3 : gups[l + 1], hs[l], rs[l], dys[l], h->fgS, (long)B * h->gdim[l - 1][0] * HW,
-                                 HW, h->gch[l], st, a16));
+                                 HW, h->gch[l], st, a16, l == 3 ? nullptr : dE_in, h->gdim[l - 1][0]));
     } else {
       ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
       if (l == 3) RD_TRY(launch_pn_bwd(h, h->gh3, hs[3], rs[3], dys[3], npix3, 64, 0, 0, 0, 0, st, a16));
       else RD_TRY(launch_pn_bwd(h, gups[l + 1], hs[l], rs[l], dys[l], (long)B * h->gpix[l], h->gch[l], col ? 0 : 1,
-                                h->gdim[l][0], h->gdim[l][1], h->gdim[l][2], st, a16));
+                                h->gdim[l][0], h->gdim[l][1], h->gdim[l][2], st, a16, dE_in));
     }
+    dE_in = nullptr;
     const long cc = (long)h->gch[l - 1] * h->gch[l];
     if (fast) {
       // shared-centre form along d: E = d-differences of the block input, gS = sums of the output-gradient plane pairs
@@ -2252,7 +2293,10 @@ extern "C" int rdgan_gen_grad_after(rdgan_handle* h, const float* dp, const floa
         RD_TRY(launch_conv(h, h->plans[pbe], h->d_plans + pbe, B, dys[l], h->fUT, h->gch[l - 1], h->fdE, eb, st,
                            RDGAN_TAG_GCONV_DGRAD));
       }
-      {
+      // dx += adjoint of the differencing of dE: by the PixelNorm backward of block l - 1 (fp32 storage: both of its kernels take
+      // dE; nothing else reads the combined dx), else in a pass of its own
+      if (!a16 && h->combine_dx_fused && l >= 2) dE_in = h->fdE;
+      else {
         ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
         const dim3 cg(ew_blocks((long)B * D * P / 4));
         if (a16) hipLaunchKernelGGL(k_combine_dx<rd_bf16_t>, cg, dim3(256), 0, st, (rd_bf16_t*)gups[l], (const rd_bf16_t*)h->fdE, B, D, P);
@@ -2756,6 +2800,28 @@ extern "C" int rdgan_op_pixelnorm_lrelu_bwd(const float* gh, const float* hh, co
   if (!gh || !hh || !rinv || !dy) return -2;
   RD_TRY(launch_pn_bwd(nullptr, gh, hh, rinv, dy, npix, C, 0, 0, 0, 0, (hipStream_t)stream));
   return (int)hipStreamSynchronize((hipStream_t)stream);
+}
+
+// test hook: the first critic layer's input gradient w.r.t. the sample channel from a given u1 [B][L1][64] (fp32), by the route
+// the steps take (critic_input_grad).  with_norm: as the critic step's gradient-penalty sweep does, also leaving gp_out [B] =
+// ||g0|| - 1 and cin_hat_out [B][L0][CP] = the second sweep's input.  fp32 storage only.
+extern "C" int rdgan_debug_d1_input_grad(rdgan_handle* h, const float* critic_params, const float* u1, int B, int with_norm,
+                                         float* g0_out, float* cin_hat_out, float* gp_out, void* stream) {
+  if (!h || !critic_params || !u1 || !g0_out) return bad_arg(h, "debug_d1_input_grad: null pointer");
+  if (with_norm && (!cin_hat_out || !gp_out)) return bad_arg(h, "debug_d1_input_grad: with_norm needs cin_hat_out and gp_out");
+  if (B < 1 || B > h->MB) return bad_arg(h, "debug_d1_input_grad: B outside [1, max_batch]");
+  if (h->a16) return bad_arg(h, "debug_d1_input_grad: fp32 storage only");
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ahead_drain(h, st));
+  RD_TRY(prep_critic_weights(h, critic_params, st));
+  if (with_norm) {
+    RD_TRY(critic_penalty_input(h, critic_params, u1, B, h->cin, st));
+    RD_CHECK(h, hipMemcpyAsync(cin_hat_out, h->cin, sizeof(float) * B * h->dL[0] * h->CP, hipMemcpyDeviceToDevice, st));
+    RD_CHECK(h, hipMemcpyAsync(gp_out, h->gpv, sizeof(float) * B, hipMemcpyDeviceToDevice, st));
+  } else
+    RD_TRY(critic_input_grad(h, critic_params, u1, B, st));
+  RD_CHECK(h, hipMemcpyAsync(g0_out, h->g0, sizeof(float) * B * h->dL[0], hipMemcpyDeviceToDevice, st));
+  return 0;
 }
 
 // test hook: the activations the last forward left in the workspace (generator h0..h3: which = 0..3, critic layers 1..4

@@ -782,6 +782,87 @@ k_d1_dgrad_sample16(const rd_bf16_t* __restrict__ u1, const float* __restrict__ 
     __syncthreads();                                  // the products are read: the next sample may overwrite them
   }
 }
+// The same with fp32 storage: u1 [B][539][64] fp32 against the 27 sample-channel taps on the fp32 matrix pipe.  A block of 32 rows
+// takes 32 v_mfma_f32_32x32x2f32 steps whose k pairs (8 j + s, 8 j + 4 + s) run in the order of the streaming GEMM k_conv_gemm_ws
+// (a lane holds the row's quad 2 j + lhalf), so the products equal the column matrix that GEMM writes and the gather (the same
+// rd_d1dg_class) adds them in k_d1_col2im's order.  The column GEMM + k_d1_col2im move the [539][64] column matrix out and back
+// (35 MB each way at 256 samples, half of it the condition channel's columns); this reads u1 once and writes the 24 KB result.
+// GP (the critic step's gradient-penalty sweep): the workgroup holds the whole g0 of its sample, so it also does k_gp_norm_r0's
+// work (S = 1: per = 6144) -- g0 goes to LDS behind the products, thread t squares and adds elements t, t + 256, ... in that
+// kernel's order, rd_block_sum folds them, thread 0 takes n = sqrt(sum), gp_out[b] = n - 1 and the coefficient, and the
+// (coef * g0, 0) pairs go to cin_hat (CP = 2).  A sample of norm 0 gives 0 * inf = NaN there, as in k_gp_norm_r0.
+#define RD_D1DG_LDS_GP (RD_D1DG_LDS + 6144 * 4)
+template <bool GP>
+__global__ void __launch_bounds__(256, GP ? 1 : 2)      // (GP: 94 KB of LDS, one workgroup per CU anyway -- the whole register file, no scratch)
+k_d1_dgrad_sample32(const float* __restrict__ u1, const float* __restrict__ w1, float* __restrict__ g0, int B,
+                    float* __restrict__ cin_hat, float* __restrict__ gp_out, float gp_weight) {
+  extern __shared__ __attribute__((aligned(16))) float Dl[];
+  __shared__ float red[4];
+  __shared__ float coef_s;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, lhalf = lane >> 5;
+  // B operand, once: tap n = l31 (27 used), channels 8 j + 4 lhalf + s of the sample channel's kernel w1[tap][0][c]
+  f32x4 wf[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    wf[j] = l31 < 27 ? *(const f32x4*)(w1 + (l31 * 2) * 64 + (j * 2 + lhalf) * 4) : z;
+  }
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const float* ub = u1 + (long)b * (539 * 64);
+    // ---- products: 17 blocks of 32 rows dealt to the four waves (5, 4, 4, 4), all of a wave's rows requested before the first
+    // product as in k_d1_dgrad_sample16; rows past 538 are zeros
+    f32x4 a[5][8];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      const int row = (wave + 4 * i) * 32 + l31;
+      const float* rp = ub + (long)(row < 539 ? row : 0) * 64 + lhalf * 4;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a[i][j] = *(const f32x4*)(rp + j * 8);
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      const int blk = wave + 4 * i;
+      if (blk < 17) {
+        const bool ok = blk * 32 + l31 < 539;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ok ? a[i][j][s] : 0.f, wf[j][s], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Dl[(blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf) * 33 + l31] = acc[r];
+      }
+    }
+    __syncthreads();
+    // ---- outputs: voxel (d, h, w), <= 8 terms, in the order of k_d1_col2im; one parity class at a time (GP: into LDS first)
+    float* gg = g0 + (long)b * 6144;
+    float* gb = GP ? Dl + 544 * 33 : gg;
+    rd_d1dg_class<0, 0, 0>(Dl, gb, tid); rd_d1dg_class<0, 0, 1>(Dl, gb, tid); rd_d1dg_class<0, 1, 0>(Dl, gb, tid);
+    rd_d1dg_class<0, 1, 1>(Dl, gb, tid); rd_d1dg_class<1, 0, 0>(Dl, gb, tid); rd_d1dg_class<1, 0, 1>(Dl, gb, tid);
+    rd_d1dg_class<1, 1, 0>(Dl, gb, tid); rd_d1dg_class<1, 1, 1>(Dl, gb, tid);
+    __syncthreads();                                  // the products are read: the next sample may overwrite them
+    if (GP) {
+      float s = 0.f;
+      for (int i = tid; i < 6144; i += 256) { const float v = gb[i]; gg[i] = v; s += v * v; }
+      s = rd_block_sum(s, red);
+      if (tid == 0) {
+        const float n = sqrtf(s);
+        gp_out[b] = n - 1.0f;
+        coef_s = (gp_weight / B) * 2.0f * (n - 1.0f) / n;
+      }
+      __syncthreads();
+      const float coef = coef_s;
+      float2* o = (float2*)cin_hat + (long)b * 6144;
+      for (int i = tid; i < 6144; i += 256) { const float2 v = {coef * gb[i], 0.f}; o[i] = v; }
+      __syncthreads();                                // g0 and the coefficient are read
+    }
+  }
+}
 
 // The same for domains larger than 16 x 16 (round 4; the large-domain variant L:286: ndomain 64 -> layer-1 grid 11 x 31 x 31): a work
 // item is a TILE of 24 x 16 x 8 input voxels of one sample.  Its outputs need the layer-1 rows o = (i - tap) / 2, i.e. the 11 x 9 x 5

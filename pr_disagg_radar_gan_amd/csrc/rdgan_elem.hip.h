@@ -92,9 +92,12 @@ __device__ __forceinline__ f32x4 rd_pn_lrelu_bwd_row(f32x4 gh, f32x4 hv, float r
   o.z = ri * (gn.z - n.z * dot); o.w = ri * (gn.w - n.w * dot);
   return o;
 }
+// dE (optional, POOL = 0, grid [B][D][H][W]): the gradient of the next block's difference part on its (D + 1)-plane grid.  The
+// row then forms g + (dE[b][d] - dE[b][d+1]) itself -- k_combine_dx's expression, in its order -- instead of reading a g that a
+// pass of its own has combined (option "combine_dx_fused"); the combined g is not stored: nothing else reads it.
 template <int LP, int POOL, typename T = float>
 __global__ void k_pn_lrelu_bwd(const T* __restrict__ g, const T* __restrict__ h, const float* __restrict__ rinv,
-                               T* __restrict__ dy, long npix, int D, int H, int W) {
+                               T* __restrict__ dy, long npix, int D, int H, int W, const T* __restrict__ dE = nullptr) {
   constexpr int C = LP * 4;
   const long gid = blockIdx.x * (long)blockDim.x + threadIdx.x;
   const long pix = gid / LP;
@@ -118,6 +121,11 @@ __global__ void k_pn_lrelu_bwd(const T* __restrict__ g, const T* __restrict__ h,
       }
     } else {
       gh = rd_ld4(g + pix * C + sub * 4);
+      if (dE) {
+        const long HW = (long)H * W, bd = pix / HW, b = bd / D;
+        const T* e = dE + ((bd + b) * HW + (pix - bd * HW)) * C + sub * 4;      // plane b * (D + 1) + d
+        gh += rd_ld4(e) - rd_ld4(e + HW * C);
+      }
     }
   }
   const f32x4 o = rd_pn_lrelu_bwd_row<LP>(gh, hv, ri);
@@ -125,10 +133,12 @@ __global__ void k_pn_lrelu_bwd(const T* __restrict__ g, const T* __restrict__ h,
 }
 // same (POOL = 0) over PAIRS of hour planes (2s, 2s+1) of a block output, additionally writing their sum
 // gS[b][s][h][w][:] = dy[b][2s][h][w][:] + dy[b][2s+1][h][w][:] for the shared-centre backward (k_presum_d fused in).
-// npair = B * Ds * HW pixel pairs, HW = pixels per hour plane.
+// npair = B * Ds * HW pixel pairs, HW = pixels per hour plane.  dE (optional; Ds = plane pairs per sample): as in k_pn_lrelu_bwd,
+// on the (2 Ds + 1)-plane grid -- the pair's rows take dE[2s] - dE[2s+1] and dE[2s+1] - dE[2s+2], the middle plane read once.
 template <int LP, typename T = float>
 __global__ void k_pn_lrelu_bwd_pairs(const T* __restrict__ g, const T* __restrict__ h, const float* __restrict__ rinv,
-                                     T* __restrict__ dy, T* __restrict__ gS, long npair, long HW) {
+                                     T* __restrict__ dy, T* __restrict__ gS, long npair, long HW,
+                                     const T* __restrict__ dE = nullptr, int Ds = 1) {
   constexpr int C = LP * 4;
   const long gid = blockIdx.x * (long)blockDim.x + threadIdx.x;
   const long pr = gid / LP;
@@ -141,6 +151,12 @@ __global__ void k_pn_lrelu_bwd_pairs(const T* __restrict__ g, const T* __restric
   if (ok) {
     ga = rd_ld4(g + pixA * C + sub * 4); ha = rd_ld4(h + pixA * C + sub * 4); ra = rinv[pixA];
     gb = rd_ld4(g + pixB * C + sub * 4); hb = rd_ld4(h + pixB * C + sub * 4); rb = rinv[pixB];
+    if (dE) {
+      const T* e = dE + ((2 * bs + bs / Ds) * HW + hw) * C + sub * 4;           // plane b * (2 Ds + 1) + 2 s
+      const f32x4 e0 = rd_ld4(e), e1 = rd_ld4(e + HW * C), e2 = rd_ld4(e + 2 * HW * C);
+      ga += e0 - e1;
+      gb += e1 - e2;
+    }
   }
   const f32x4 oa = rd_pn_lrelu_bwd_row<LP>(ga, ha, ra);
   const f32x4 ob = rd_pn_lrelu_bwd_row<LP>(gb, hb, rb);

@@ -223,6 +223,23 @@ class Engine:
                    "rdgan_debug_activation")
         return out
 
+    def debug_d1_input_grad(self, critic_params, u1, with_norm=False):
+        """test hook (rdgan_debug_d1_input_grad, fp32 storage): dD/d(sample channel) of the first critic layer from a given
+        u1 [B, L1, 64]; returns g0 [B, 24, nd, nd], and with with_norm also (cin_hat [B, 24 nd nd, CP], gp [B]) as the critic
+        step's gradient-penalty sweep leaves them"""
+        B, nd = u1.shape[0], self.ndomain
+        self._check_batch(B, self.max_batch)
+        _chk_tensor(critic_params, (self.n_critic,), "critic_params")
+        _chk_tensor(u1, (B, u1.shape[1], 64), "u1")
+        g0 = torch.empty((B, W.NHOURS, nd, nd), dtype=torch.float32, device=self.device)
+        cin_hat = torch.empty((B, W.NHOURS * nd * nd, 1 + self.n_cond_channels), dtype=torch.float32, device=self.device) if with_norm else None
+        gp = torch.empty((B,), dtype=torch.float32, device=self.device) if with_norm else None
+        _lib.check(self.lib.rdgan_debug_d1_input_grad(self._h, _ptr(critic_params), _ptr(u1), B, int(bool(with_norm)), _ptr(g0),
+                                                      ctypes.c_void_p(cin_hat.data_ptr() if with_norm else 0),
+                                                      ctypes.c_void_p(gp.data_ptr() if with_norm else 0), self._stream()),
+                   self._h, "rdgan_debug_d1_input_grad")
+        return (g0, cin_hat, gp) if with_norm else g0
+
     def flop_count(self, reset=False):
         """algorithmic FLOPs of every GEMM launched since the last reset (rdgan_flop_count)"""
         f = ctypes.c_double()
