@@ -430,6 +430,41 @@ int rdgan_field_blend(const float* frac, long m, const int* slots, long units, l
                       const float* ytab_w, const int* xtab_idx, const float* xtab_w, const float* daily, long n_days, int ny, int nx,
                       int nd, int overlap, float* out, void* stream);
 
+/* Ensemble products of whole fields.  All three: asynchronous on the stream, 0 = success, -2 = bad argument
+ * (a null pointer, a bad shape, window list, probability, threshold, member count, stride or slot) with nothing launched and no
+ * output touched; no floating-point atomics, repeated calls agree bit for bit; all offsets are 64-bit.
+ *
+ * rdgan_hourly_peaks: hourly [units][24][ny][nx] fp32 (device): scenarios of rdgan_field_blend, observed days, RainFARM members.
+ * windows [n_windows] int32 on the HOST, strictly increasing, each in 1 .. 24, 1 <= n_windows <= 8.  With v the 24 hours of a pixel:
+ *   peaks_out[u][i][y][x] = max over h0 = 0 .. 24 - windows[i] of v[h0] + v[h0 + 1] + .. + v[h0 + windows[i] - 1]
+ * the sum taken in fp32 from left to right, every add rounded (no FMA), the maximum taken with `>` from h0 = 0 on;
+ * peak_hour_out[u][y][x] (uint8) = the first h0 that reaches the maximum of windows[0].  A pixel with a NaN in any of its 24 hours
+ * gives NaN for every window and hour 255.  peaks_out [units][n_windows][ny][nx] fp32, peak_hour_out [units][ny][nx] (device).
+ * rdgan_field_blend_peaks: the arguments of rdgan_field_blend with the window list and the two outputs of rdgan_hourly_peaks in
+ * place of `out`.  The hourly values are the ones rdgan_field_blend forms (same cover resolution, same order of products and adds)
+ * and are reduced in registers: the result equals rdgan_hourly_peaks of rdgan_field_blend's output bit for bit, and the 24 hourly
+ * planes are never written.  Where daily is 0 the peaks are 0 and the hour 0, where it is NaN they are NaN and 255, whatever frac
+ * holds.
+ * rdgan_member_stats: statistics across the members of an ensemble at every position.  x[s * member_stride + p] fp32 (device),
+ * s < n_members (1 .. 4096), p < n_positions (1 .. 2^40), member_stride >= n_positions.  probs [n_probs] doubles on the HOST,
+ * 1 <= n_probs <= 16, each in [0, 1]; thresholds [n_thresholds] doubles on the HOST, 0 <= n_thresholds <= 16, each finite
+ * (thresholds and exceed_out may be NULL for 0).  Per position, over its n_members values:
+ *   quantiles_out[q][p] = (float) np.quantile(x, probs[q], method="linear") -- virtual index (n - 1) q, numpy's lerp, fp64;
+ *   mean_out[p]         = (float) (fp64 sum in a fixed order / n_members);
+ *   exceed_out[t][p]    = (float) ((double) #{x > thresholds[t]} / n_members).
+ * A position where any member is NaN gives NaN in every output; n_nan_positions_out (device, one 64-bit integer, cleared by the
+ * call) counts those positions.  A workgroup sorts a run of adjacent positions side by side in LDS -- 64 positions up to 512
+ * members, 32 up to 1024, 16 up to 2048, 8 up to 4096 -- so member rows are read in contiguous segments of that many floats. */
+int rdgan_hourly_peaks(const float* hourly, long units, int ny, int nx, const int* windows, int n_windows, float* peaks_out,
+                       unsigned char* peak_hour_out, void* stream);
+int rdgan_field_blend_peaks(const float* frac, long m, const int* slots, long units, long first_unit, const int* ytab_idx,
+                            const float* ytab_w, const int* xtab_idx, const float* xtab_w, const float* daily, long n_days, int ny,
+                            int nx, int nd, int overlap, const int* windows, int n_windows, float* peaks_out,
+                            unsigned char* peak_hour_out, void* stream);
+int rdgan_member_stats(const float* x, int n_members, long member_stride, long n_positions, const double* probs, int n_probs,
+                       const double* thresholds, int n_thresholds, float* quantiles_out, float* mean_out, float* exceed_out,
+                       long long* n_nan_positions_out, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

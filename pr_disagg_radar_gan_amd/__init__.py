@@ -7,6 +7,8 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
   * evaluation, imported as submodules like the rest: ``ensemble``, ``spectral``, ``rainfarm``, ``crps_experiment``,
     ``distribution``
   * ``field`` -- disaggregate: whole daily fields through the generator, overlapping tiles blended on the device
+  * ``field_products`` -- k-hour peaks of hourly maps and statistics across an ensemble's members, the hourly ensemble never held
 """
 from .engine import Engine, require_gpu  # noqa: F401
 from . import weights  # noqa: F401
+from . import field_products  # noqa: F401

@@ -81,6 +81,14 @@ SIGNATURES = {
     "rdgan_field_blend": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, c_f32p,
                                          ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, c_f32p, c_stream]),
+    "rdgan_hourly_peaks": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, c_f32p,
+                                          ctypes.c_void_p, c_stream]),
+    "rdgan_field_blend_peaks": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,
+                                               c_f32p, ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, c_f32p, ctypes.c_void_p,
+                                               c_stream]),
+    "rdgan_member_stats": (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_int,
+                                          ctypes.c_void_p, ctypes.c_int, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_stream]),
     "rdgan_spectra_bins": (ctypes.c_int, [ctypes.c_int]),
     "rdgan_radial_spectra": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_stream]),
     "rdgan_lsd_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long]),

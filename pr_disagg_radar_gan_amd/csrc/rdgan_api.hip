@@ -38,6 +38,7 @@
 #include "rdgan_dist.hip.h"
 #include "rdgan_radar.hip.h"
 #include "rdgan_field.hip.h"
+#include "rdgan_products.hip.h"
 static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
 // k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
 static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
@@ -3136,6 +3137,89 @@ extern "C" int rdgan_field_blend(const float* frac, long m, const int* slots, lo
   hipError_t e = hipGetLastError();
   hipError_t f = hipFreeAsync(dev, st);
   return (int)(e != hipSuccess ? e : f);
+}
+
+// ------------------------------------------------------------------------------------
+// ensemble products (rdgan_products.hip.h): k-hour peaks of hourly maps, the blend fused with them, member statistics
+// ------------------------------------------------------------------------------------
+// the window list as the kernels take it: bit w - 1 set for every window w; false for a list that is not strictly increasing in 1 .. 24
+static bool rd_peaks_mask(const int* windows, int n_windows, unsigned* mask) {
+  if (!windows || n_windows < 1 || n_windows > RD_PEAKS_MAXK) return false;
+  unsigned m = 0;
+  for (int i = 0; i < n_windows; ++i) {
+    if (windows[i] < 1 || windows[i] > RD_FIELD_HOURS || (i > 0 && windows[i] <= windows[i - 1])) return false;
+    m |= 1u << (windows[i] - 1);
+  }
+  *mask = m;
+  return true;
+}
+
+extern "C" int rdgan_hourly_peaks(const float* hourly, long units, int ny, int nx, const int* windows, int n_windows, float* peaks_out,
+                                  unsigned char* peak_hour_out, void* stream) {
+  unsigned mask = 0;
+  if (!hourly || !peaks_out || !peak_hour_out || units < 1 || ny < 1 || nx < 1 || !rd_peaks_mask(windows, n_windows, &mask)) return -2;
+  const long nb = ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * (long)((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
+  if (units > (1L << 40) / nb) return -2;
+  hipLaunchKernelGGL(k_hourly_peaks, dim3((unsigned)std::min<long>(units * nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0,
+                     (hipStream_t)stream, hourly, units, ny, nx, mask, windows[0], peaks_out, peak_hour_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_field_blend_peaks(const float* frac, long m, const int* slots, long units, long first_unit, const int* ytab_idx,
+                                       const float* ytab_w, const int* xtab_idx, const float* xtab_w, const float* daily, long n_days,
+                                       int ny, int nx, int nd, int overlap, const int* windows, int n_windows, float* peaks_out,
+                                       unsigned char* peak_hour_out, void* stream) {
+  unsigned mask = 0;
+  if (!frac || !slots || !ytab_idx || !ytab_w || !xtab_idx || !xtab_w || !daily || !peaks_out || !peak_hour_out) return -2;
+  if (m < 1 || m > 0x7FFFFFFFL || units < 1 || first_unit < 0 || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
+  if (!rd_peaks_mask(windows, n_windows, &mask)) return -2;
+  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
+  const long T = (long)n_ty * n_tx;
+  if (T > 0x7FFFFFFFL || units > 0x7FFFFFFFL / T) return -2;
+  for (long i = 0; i < units * T; ++i)
+    if (slots[i] < -1 || slots[i] >= m) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  int* dev = nullptr;
+  RD_TRY(rd_field_upload(slots, (size_t)(units * T), &dev, st));
+  const long nb = units * ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * ((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
+  hipLaunchKernelGGL(k_field_blend_peaks, dim3((unsigned)std::min<long>(nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0, st, frac, dev,
+                     ytab_idx, ytab_w, xtab_idx, xtab_w, daily, peaks_out, peak_hour_out, units, first_unit, n_days, ny, nx, nd, step,
+                     n_ty, n_tx, mask, windows[0]);
+  hipError_t e = hipGetLastError();
+  hipError_t f = hipFreeAsync(dev, st);
+  return (int)(e != hipSuccess ? e : f);
+}
+
+extern "C" int rdgan_member_stats(const float* x, int n_members, long member_stride, long n_positions, const double* probs, int n_probs,
+                                  const double* thresholds, int n_thresholds, float* quantiles_out, float* mean_out, float* exceed_out,
+                                  long long* n_nan_positions_out, void* stream) {
+  if (!x || !probs || !quantiles_out || !mean_out || !n_nan_positions_out) return -2;
+  if (n_members < 1 || n_members > RD_MS_MAXS || n_positions < 1 || n_positions > (1L << 40) || member_stride < n_positions) return -2;
+  if (n_probs < 1 || n_probs > RD_MS_MAXQ || n_thresholds < 0 || n_thresholds > RD_MS_MAXT) return -2;
+  if (n_thresholds > 0 && (!thresholds || !exceed_out)) return -2;
+  rd_ms_args a;
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < n_probs; ++i) {
+    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return -2;
+    a.probs[i] = probs[i];
+  }
+  for (int i = 0; i < n_thresholds; ++i) {
+    if (!std::isfinite(thresholds[i])) return -2;
+    a.thr[i] = thresholds[i];
+  }
+  const int np2 = rd_pow2_at_least(n_members);
+  const int px = rd_ms_run_width(np2);
+  int lpx = 0;
+  while ((1 << lpx) < px) ++lpx;
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ensure_lds(nullptr, (const void*)k_member_stats, RD_MS_LDS_MAX));
+  hipError_t e = hipMemsetAsync(n_nan_positions_out, 0, sizeof(long long), st);
+  if (e != hipSuccess) return (int)e;
+  const long runs = (n_positions + px - 1) / px;
+  hipLaunchKernelGGL(k_member_stats, dim3((unsigned)std::min<long>(runs, 1L << 16)), dim3(RD_MS_THREADS),
+                     RD_MS_LDS_HEAD + (size_t)np2 * px * sizeof(float), st, x, member_stride, n_members, np2, lpx, n_positions, n_probs,
+                     n_thresholds, a, quantiles_out, mean_out, exceed_out, (unsigned long long*)n_nan_positions_out);
+  return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------

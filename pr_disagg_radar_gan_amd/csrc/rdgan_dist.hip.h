@@ -55,20 +55,21 @@ __device__ __forceinline__ void rd_dist_load_sort(const float* __restrict__ col,
     }
 }
 
-// #{ xs[i] <= v } and #{ xs[i] < v } over the ascending xs[0 .. n)
-__device__ __forceinline__ int rd_count_le(const float* xs, int n, double v) {
+// #{ xs[i] <= v } and #{ xs[i] < v } over the ascending xs[0 .. n), element i at xs[i * stride] (columns sorted side by side in LDS,
+// rdgan_products.hip.h, pass their run width)
+__device__ __forceinline__ int rd_count_le(const float* xs, int n, double v, int stride = 1) {
   int lo = 0, hi = n;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
-    if ((double)xs[mid] <= v) lo = mid + 1; else hi = mid;
+    if ((double)xs[mid * stride] <= v) lo = mid + 1; else hi = mid;
   }
   return lo;
 }
-__device__ __forceinline__ int rd_count_lt(const float* xs, int n, double v) {
+__device__ __forceinline__ int rd_count_lt(const float* xs, int n, double v, int stride = 1) {
   int lo = 0, hi = n;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
-    if ((double)xs[mid] < v) lo = mid + 1; else hi = mid;
+    if ((double)xs[mid * stride] < v) lo = mid + 1; else hi = mid;
   }
   return lo;
 }
@@ -139,14 +140,14 @@ k_ks_2samp(const float* __restrict__ a, const float* __restrict__ b, int n, int 
 }
 
 // np.percentile(x, 100 q) of the ascending xs[0 .. n), method "linear": virtual index (n - 1) q, numpy's lerp a + (b - a) g, and
-// b - (b - a)(1 - g) for g >= 0.5; fp64, no contraction into FMA
-__device__ __forceinline__ double rd_np_quantile(const float* xs, int n, double q) {
+// b - (b - a)(1 - g) for g >= 0.5; fp64, no contraction into FMA.  Element i lies at xs[i * stride].
+__device__ __forceinline__ double rd_np_quantile(const float* xs, int n, double q, int stride = 1) {
 #pragma clang fp contract(off)
   const double vi = (double)(n - 1) * q;
   const int lo = (int)floor(vi);
   const int hi = min(lo + 1, n - 1);
   const double g = vi - (double)lo;
-  const double a = (double)xs[lo], b = (double)xs[hi];
+  const double a = (double)xs[lo * stride], b = (double)xs[hi * stride];
   const double diff = b - a;
   double r = a + diff * g;
   if (g >= 0.5) r = b - diff * (1.0 - g);

@@ -79,6 +79,46 @@ k_field_cond(const float* __restrict__ daily, const int* __restrict__ entries, l
   }
 }
 
+// The per-pixel resolve k_field_blend and k_field_blend_peaks (rdgan_products.hip.h) share: the (at most 9) covering tiles of
+// pixel (y, x) of a unit whose slot row is srow, as off[k] = the offset of the pixel's hour 0 in frac (-1: the tile contributes
+// nothing) and w[k] = wy * wx, y entries outer and x entries inner.  A table entry that does not cover its coordinate is ignored.
+__device__ __forceinline__ void rd_field_resolve(const int* __restrict__ srow, const int* __restrict__ ytab_i,
+                                                 const float* __restrict__ ytab_w, const int* __restrict__ xtab_i,
+                                                 const float* __restrict__ xtab_w, int y, int x, int ny, int nx, int nd, int step,
+                                                 int n_ty, int n_tx, long (&off)[RD_FIELD_COVER * RD_FIELD_COVER],
+                                                 float (&w)[RD_FIELD_COVER * RD_FIELD_COVER]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int a = 0; a < RD_FIELD_COVER; ++a) {
+    const int iy = ytab_i[y * RD_FIELD_COVER + a];
+    const float wy = ytab_w[y * RD_FIELD_COVER + a];
+    const bool oky = iy >= 0 && iy < n_ty;
+    const int ty = y - rd_field_origin(oky ? iy : 0, step, ny, nd);
+#pragma unroll
+    for (int c = 0; c < RD_FIELD_COVER; ++c) {
+      const int ix = xtab_i[x * RD_FIELD_COVER + c];
+      const float wx = xtab_w[x * RD_FIELD_COVER + c];
+      const bool okx = ix >= 0 && ix < n_tx;
+      const int tx = x - rd_field_origin(okx ? ix : 0, step, nx, nd);
+      const bool ok = oky && okx && ty >= 0 && ty < nd && tx >= 0 && tx < nd;
+      const int slot = ok ? srow[iy * n_tx + ix] : -1;
+      off[a * RD_FIELD_COVER + c] = slot >= 0 ? ((long)slot * RD_FIELD_HOURS * nd + ty) * nd + tx : -1;
+      w[a * RD_FIELD_COVER + c] = wy * wx;
+    }
+  }
+}
+
+// hour h of a resolved pixel: d * sum_k w[k] * frac[off[k] + h * tile], the products rounded before they are added, k ascending
+__device__ __forceinline__ float rd_field_hour(const float* __restrict__ frac, const long (&off)[RD_FIELD_COVER * RD_FIELD_COVER],
+                                               const float (&w)[RD_FIELD_COVER * RD_FIELD_COVER], int h, long tile, float d) {
+#pragma clang fp contract(off)
+  float acc = 0.f;
+#pragma unroll
+  for (int k = 0; k < RD_FIELD_COVER * RD_FIELD_COVER; ++k)
+    if (off[k] >= 0) acc = acc + w[k] * frac[off[k] + h * tile];
+  return d * acc;
+}
+
 // A workgroup takes a 4 x 64 patch of one unit's field and walks the 24 hours; lane = x, so a wave reads nd contiguous floats per
 // tile row it crosses and writes 64 contiguous floats of an output row.  The (at most 9) covering tiles of a pixel are resolved once,
 // into registers; per hour a pixel then costs its loads, as many multiply-adds, one multiply and one store.
@@ -112,32 +152,8 @@ k_field_blend(const float* __restrict__ frac, const int* __restrict__ slots, con
     }
     long off[RD_FIELD_COVER * RD_FIELD_COVER];
     float w[RD_FIELD_COVER * RD_FIELD_COVER];
-    const int* srow = slots + u * T;
-#pragma unroll
-    for (int a = 0; a < RD_FIELD_COVER; ++a) {
-      const int iy = ytab_i[y * RD_FIELD_COVER + a];
-      const float wy = ytab_w[y * RD_FIELD_COVER + a];
-      const bool oky = iy >= 0 && iy < n_ty;
-      const int ty = y - rd_field_origin(oky ? iy : 0, step, ny, nd);
-#pragma unroll
-      for (int c = 0; c < RD_FIELD_COVER; ++c) {
-        const int ix = xtab_i[x * RD_FIELD_COVER + c];
-        const float wx = xtab_w[x * RD_FIELD_COVER + c];
-        const bool okx = ix >= 0 && ix < n_tx;
-        const int tx = x - rd_field_origin(okx ? ix : 0, step, nx, nd);
-        const bool ok = oky && okx && ty >= 0 && ty < nd && tx >= 0 && tx < nd;
-        const int slot = ok ? srow[iy * n_tx + ix] : -1;
-        off[a * RD_FIELD_COVER + c] = slot >= 0 ? ((long)slot * RD_FIELD_HOURS * nd + ty) * nd + tx : -1;
-        w[a * RD_FIELD_COVER + c] = wy * wx;
-      }
-    }
+    rd_field_resolve(slots + u * T, ytab_i, ytab_w, xtab_i, xtab_w, y, x, ny, nx, nd, step, n_ty, n_tx, off, w);
 #pragma unroll 4
-    for (int h = 0; h < RD_FIELD_HOURS; ++h) {
-      float acc = 0.f;
-#pragma unroll
-      for (int k = 0; k < RD_FIELD_COVER * RD_FIELD_COVER; ++k)
-        if (off[k] >= 0) acc = acc + w[k] * frac[off[k] + h * tile];
-      dst[h * plane] = d * acc;
-    }
+    for (int h = 0; h < RD_FIELD_HOURS; ++h) dst[h * plane] = rd_field_hour(frac, off, w, h, tile, d);
   }
 }

@@ -204,21 +204,9 @@ def _group_units(rows_per_unit, chunk):
     return groups
 
 
-def disaggregate(gen, daily, n_scenarios, overlap=4, latent_mode="shared", seed=None, latent=None, chunk=1024,
-                 norm_scale=W.NORM_SCALE, out=None):
-    """Hourly scenarios for whole daily fields.  daily: (ny, nx) or (n_days, ny, nx) daily sums in mm/day, a numpy array, a CUDA
-    tensor or a DeviceDataset (its daily plane is used where it lies); ny, nx >= gen.ndomain.  Returns (fields, info): fields
-    (n_scenarios, [n_days,] 24, ny, nx) float32 CUDA in mm/h, whose 24 values sum to the daily value at every pixel, and a FieldInfo.
-
-    The field is tiled by tile_plan(ny, nx, gen.ndomain, overlap).  A tile without a finite pixel > 0 never reaches the generator (a
-    dry pixel's output is 0 whatever the fractions are).  A NaN pixel enters the condition as 0 and its 24 output values are NaN.
-    A negative or infinite daily value raises ValueError.
-    latent_mode "shared": one latent vector per (scenario, day) serves every tile of that day (the reference's same-noise device,
-    generate_and_evaluate.py:519-528), so neighbouring tiles do not time their rain independently; "independent": one per
-    (scenario, day, tile).  The noise comes from the global numpy RNG, as generate_scenarios draws it, from a device generator
-    when `seed` is given, or from `latent`: (n_scenarios, n_days, 100), or (n_scenarios, n_days, n_tiles, 100) for "independent".
-    The generator runs in batches of at most `chunk` tiles; whole (scenario, day) units are blended as soon as their tiles are
-    there, so the fraction buffer holds a few units, never the ensemble.  out: the tensor to write, of the returned shape."""
+def _check_request(gen, daily, n_scenarios, overlap, latent_mode, latent, chunk, norm_scale):
+    """The argument checks of disaggregate (and of field_products.disaggregate_peaks), host code only.
+    -> (daily, squeeze_day, D, ny, nx, plan, z_shape)"""
     nd = int(gen.ndomain)
     n_scenarios, chunk = int(n_scenarios), int(chunk)
     if int(getattr(gen, "n_cond_channels", 1)) != 1:
@@ -245,19 +233,19 @@ def disaggregate(gen, daily, n_scenarios, overlap=4, latent_mode="shared", seed=
     z_shape = (S, D, W.LATENT_DIM) if latent_mode == "shared" else (S, D, T, W.LATENT_DIM)
     if latent is not None and tuple(np.shape(latent)) != z_shape:
         raise ValueError(f"latent must have shape {z_shape} for latent_mode {latent_mode!r}, got {tuple(np.shape(latent))}")
-    out_shape = (S, W.NHOURS, ny, nx) if squeeze_day else (S, D, W.NHOURS, ny, nx)
-    if out is not None:
-        _check_f32_cuda(out, out_shape, "out")
+    return daily, squeeze_day, D, ny, nx, plan, z_shape
 
+
+def _scan_request(daily, D, ny, nx, plan):
+    """The daily plane on the device and what the tile scan found.  -> (dd (D, ny, nx) float32 CUDA, info, active_tiles per day)"""
     require_gpu()
     if isinstance(daily, torch.Tensor):
         dd = daily.detach().to(torch.float32).contiguous().view(D, ny, nx)
     else:
         dd = torch.from_numpy(np.ascontiguousarray(daily, dtype=np.float32).reshape(D, ny, nx)).cuda()
-    dev = dd.device
-
+    T = plan.n_tiles
     # which tiles hold rain: D * T * 3 counts and the number of NaN pixels, in one copy
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dd.device):
         counts = scan_device(dd, plan)
         n_nan = torch.isnan(dd).sum().to(torch.int32).view(1)
         host = torch.cat([counts.view(-1), n_nan]).cpu().numpy()
@@ -266,15 +254,15 @@ def disaggregate(gen, daily, n_scenarios, overlap=4, latent_mode="shared", seed=
         raise ValueError("daily holds negative or infinite values")
     active = counts_h[..., 0] > 0                                   # (D, T)
     info = FieldInfo(n_tiles=T, n_active=int(active.sum()), n_nan_pixels=n_nan_pixels)
-    if out is None:
-        out = torch.empty(out_shape, dtype=torch.float32, device=dev)
-    out_units = out.view(S * D, W.NHOURS, ny, nx)
-    active_tiles = [np.flatnonzero(active[d]).astype(np.int32) for d in range(D)]
-    rows_per_unit = [len(active_tiles[u % D]) for u in range(S * D)]            # unit u = scenario * D + day
-    if info.n_active == 0:                                          # nothing to generate: zeros and NaNs straight from the plane
-        out_units.copy_((dd * 0.0)[None, :, None].expand(S, D, W.NHOURS, ny, nx).reshape(S * D, W.NHOURS, ny, nx))
-        return out, info
+    return dd, info, [np.flatnonzero(active[d]).astype(np.int32) for d in range(D)]
 
+
+def _run_groups(gen, dd, plan, S, active_tiles, latent_mode, seed, latent, z_shape, chunk, norm_scale, blend, dry):
+    """The group loop disaggregate and field_products.disaggregate_peaks share: units u = scenario * D + day in order, grouped by
+    _group_units; per group the condition batch, the latent rows and the generator in batches of at most `chunk` tiles, then
+    blend(frac (m, 24, nd, nd, 1), slots (u1 - u0, T), u0, u1) -- or dry(u0, u1) for a group without a wet tile."""
+    nd, T, D, dev = plan.ndomain, plan.n_tiles, int(dd.shape[0]), dd.device
+    rows_per_unit = [len(active_tiles[u % D]) for u in range(S * D)]            # unit u = scenario * D + day
     with torch.cuda.device(dev):
         if latent is not None:
             z_all = torch.as_tensor(latent, dtype=torch.float32).to(dev)
@@ -302,7 +290,7 @@ def disaggregate(gen, daily, n_scenarios, overlap=4, latent_mode="shared", seed=
                 zrows.append(np.full(len(tiles), u, dtype=np.int64) if latent_mode == "shared" else u * T + tiles.astype(np.int64))
                 m += len(tiles)
             if m == 0:                                              # a run of dry days
-                out_units[u0:u1].copy_(torch.stack([dd[u % D] * 0.0 for u in range(u0, u1)])[:, None].expand(-1, W.NHOURS, -1, -1))
+                dry(u0, u1)
                 continue
             cond_device(dd, plan, np.concatenate(entries), norm_scale, out=cond[:m])
             z = z_all.index_select(0, torch.from_numpy(np.concatenate(zrows)).to(dev))
@@ -310,5 +298,44 @@ def disaggregate(gen, daily, n_scenarios, overlap=4, latent_mode="shared", seed=
                 k = min(eng.max_batch, m - i)
                 eng.gen_forward(slab, z[i:i + k].contiguous(), cond[i:i + k], out=frac[i:i + k], gen_version=version)
                 eng.check_numerics()             # reference T:349-350
-            blend_device(frac[:m], slots, plan, dd, first_unit=u0, out=out_units[u0:u1])
+            blend(frac[:m], slots, u0, u1)
+
+
+def disaggregate(gen, daily, n_scenarios, overlap=4, latent_mode="shared", seed=None, latent=None, chunk=1024,
+                 norm_scale=W.NORM_SCALE, out=None):
+    """Hourly scenarios for whole daily fields.  daily: (ny, nx) or (n_days, ny, nx) daily sums in mm/day, a numpy array, a CUDA
+    tensor or a DeviceDataset (its daily plane is used where it lies); ny, nx >= gen.ndomain.  Returns (fields, info): fields
+    (n_scenarios, [n_days,] 24, ny, nx) float32 CUDA in mm/h, whose 24 values sum to the daily value at every pixel, and a FieldInfo.
+
+    The field is tiled by tile_plan(ny, nx, gen.ndomain, overlap).  A tile without a finite pixel > 0 never reaches the generator (a
+    dry pixel's output is 0 whatever the fractions are).  A NaN pixel enters the condition as 0 and its 24 output values are NaN.
+    A negative or infinite daily value raises ValueError.
+    latent_mode "shared": one latent vector per (scenario, day) serves every tile of that day (the reference's same-noise device,
+    generate_and_evaluate.py:519-528), so neighbouring tiles do not time their rain independently; "independent": one per
+    (scenario, day, tile).  The noise comes from the global numpy RNG, as generate_scenarios draws it, from a device generator
+    when `seed` is given, or from `latent`: (n_scenarios, n_days, 100), or (n_scenarios, n_days, n_tiles, 100) for "independent".
+    The generator runs in batches of at most `chunk` tiles; whole (scenario, day) units are blended as soon as their tiles are
+    there, so the fraction buffer holds a few units, never the ensemble.  out: the tensor to write, of the returned shape."""
+    n_scenarios, chunk = int(n_scenarios), int(chunk)
+    daily, squeeze_day, D, ny, nx, plan, z_shape = _check_request(gen, daily, n_scenarios, overlap, latent_mode, latent, chunk, norm_scale)
+    S = n_scenarios
+    out_shape = (S, W.NHOURS, ny, nx) if squeeze_day else (S, D, W.NHOURS, ny, nx)
+    if out is not None:
+        _check_f32_cuda(out, out_shape, "out")
+
+    dd, info, active_tiles = _scan_request(daily, D, ny, nx, plan)
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.float32, device=dd.device)
+    out_units = out.view(S * D, W.NHOURS, ny, nx)
+    if info.n_active == 0:                                          # nothing to generate: zeros and NaNs straight from the plane
+        out_units.copy_((dd * 0.0)[None, :, None].expand(S, D, W.NHOURS, ny, nx).reshape(S * D, W.NHOURS, ny, nx))
+        return out, info
+
+    def blend(frac, slots, u0, u1):
+        blend_device(frac, slots, plan, dd, first_unit=u0, out=out_units[u0:u1])
+
+    def dry(u0, u1):
+        out_units[u0:u1].copy_(torch.stack([dd[u % D] * 0.0 for u in range(u0, u1)])[:, None].expand(-1, W.NHOURS, -1, -1))
+
+    _run_groups(gen, dd, plan, S, active_tiles, latent_mode, seed, latent, z_shape, chunk, norm_scale, blend, dry)
     return out, info

@@ -77,6 +77,24 @@ def generate_scenarios_field(daily, n_scenarios, overlap=4, latent_mode="shared"
     return out.cpu().numpy().astype(np.float64).squeeze()
 
 
+def scenario_products_field(daily, n_scenarios, windows=(1, 3, 6, 12, 24), probs=(0.1, 0.5, 0.9, 0.99), thresholds=None, overlap=4,
+                            latent_mode="shared"):
+    """Per-pixel statistics of the k-hour peaks across n_scenarios scenarios of a whole daily map (field_products.ensemble_products
+    on the module's ``gen`` and ``norm_scale``), numpy in, numpy out.  daily as generate_scenarios_field takes it.  Returns a
+    field_products.FieldProducts of ndarrays: quantiles ([n_days,] K, Q, ny, nx), mean ([n_days,] K, ny, nx) and exceedance
+    ([n_days,] K, T, ny, nx), or None without thresholds, float32 in mm per window; peak_hour (n_scenarios, [n_days,] ny, nx) uint8,
+    the hour at which each scenario's windows[0]-hour peak begins (255 at a NaN pixel).  thresholds: None, a sequence in mm (the
+    same for every window) or a (K, T) array.  The hourly scenarios themselves are never held."""
+    from . import field_products
+    daily = np.asarray(daily)
+    if daily.ndim >= 3 and daily.shape[-1] == 1:
+        daily = daily[..., 0]
+    r = field_products.ensemble_products(gen, daily, n_scenarios, windows=windows, probs=probs, thresholds=thresholds, overlap=overlap,
+                                         latent_mode=latent_mode, norm_scale=norm_scale)
+    host = lambda t: None if t is None else t.cpu().numpy()
+    return r._replace(quantiles=host(r.quantiles), mean=host(r.mean), exceedance=host(r.exceedance), peak_hour=host(r.peak_hour))
+
+
 def plot_scenarios(scenarios):
     """reference :68-90: one row per scenario, 24 hourly panels, LogNorm(0.01, 50), gist_earth_r.
     Keeps the reference's indexing ``scenarios[iplot, jplot - 1]`` (the column labelled 00:00 shows
