@@ -465,6 +465,48 @@ int rdgan_member_stats(const float* x, int n_members, long member_stride, long n
                        const double* thresholds, int n_thresholds, float* quantiles_out, float* mean_out, float* exceed_out,
                        long long* n_nan_positions_out, void* stream);
 
+/* Verification of field ensembles against the observed hours: rank histogram, Brier sums with the
+ * reliability table, fractions skill score.  Positions p < n_positions are laid out ([D,] 24, ny, nx): the hour of p is
+ * (p / (ny nx)) % 24.  thresholds [n_thresholds] doubles on the HOST, 1 <= n_thresholds <= 8, each rounded once to fp32 and compared
+ * in fp32; finite, >= 0 and strictly increasing after the rounding.  n_members S in 1 .. 4096.  All four: asynchronous on the
+ * stream, 0 = success, -2 = bad argument (a null pointer, a count, n_bins or threshold list out of range, an even or unsorted
+ * width, S w^2 >= 2^26, a stride below n_positions, a workspace too small) with nothing launched and no output touched; every
+ * accumulated value is an integer (the FSS sums: fp64 sums of integers in a fixed order, no floating-point atomics), so the results
+ * do not depend on how the members are split into calls and repeated calls agree bit for bit; all offsets are 64-bit.
+ *
+ * rdgan_verify_accumulate: members[s * member_stride + p] fp32 (device), s < n_members of THIS call, member_stride >= n_positions
+ * (1 .. 2^40); obs [n_positions] fp32.  Adds to the state (device, zeroed by the caller before the first call):
+ *   exceed[t][p] += #{s : x_s[p] > thresholds[t]},  below[p] += #{s : x_s[p] < obs[p]},  equal[p] += #{s : x_s[p] == obs[p]}  (int32)
+ *   bad[p] |= obs[p] is NaN or a member is NaN at p                                                                        (uint8)
+ * IEEE comparisons: a NaN counts nowhere.  16-byte loads when the pointers are 16-byte aligned and member_stride and n_positions
+ * are multiples of 4, a scalar path otherwise (4-byte alignment is required).  The caller keeps the total number of members <= 4096.
+ * rdgan_verify_reduce: one pass over the state of S = n_members members in all; plane = ny nx, n_positions a multiple of plane (the last day may stop short of 24 hours).
+ * Over the valid positions (bad == 0 and obs not NaN), per hour:
+ *   rank = below + ((b24 (equal + 1)) >> 24) in 64 bits, b24 = rd_bits(rd_member_key(rd_make_key(seed, 8), p), 0) >> 8 (rdgan_rng.h):
+ *   a tie among `equal` members and the observation is broken uniformly by a hash of (seed, p);
+ *   rank_hist_out [24][S + 1] counts the ranks;
+ *   with c = exceed[t][p], e = [obs[p] > thresholds[t]], bin = (c n_bins) / (S + 1), 2 <= n_bins <= min(S + 1, 64):
+ *   reliability_out [T][24][n_bins][3] = (count, sum e, sum c) and brier_out [T][24][4] = (N, sum e, sum c e, sum c^2).
+ * 64-bit integers (device), cleared by the call.
+ * rdgan_verify_fss: per day, hour and threshold the planes C = exceed[t] and E = e, both 0 at a bad position; BC, BE their sums over
+ * the w x w box centred at each pixel, clipped at the field's edge; at every pixel num += (BC - S BE)^2, den += BC^2 + (S BE)^2.
+ * widths [n_widths] int32 on the HOST, 1 <= n_widths <= 8, odd, strictly increasing, S w^2 < 2^26.  fss_sums_out [T][W][24][2]
+ * doubles (device) = (num, den) summed over days and pixels, cleared by the call; FSS = 1 - num / den.  Summed-area tables (a row
+ * scan, a column scan, four reads per box): the cost per pixel does not grow with w^2.  workspace: at least
+ * rdgan_verify_fss_workspace_bytes(ny, nx, n_thresholds, n_widths) bytes of device memory, 8-byte aligned (-2 from the sizing entry
+ * for a count out of range); it holds one day's tables, whatever n_days is.  A state that holds more members than n_members (the
+ * caller's error) is clamped to n_members by reduce and FSS alike, so every bound above holds whatever the state is. */
+int rdgan_verify_accumulate(const float* members, int n_members, long member_stride, long n_positions, const float* obs,
+                            const double* thresholds, int n_thresholds, int* exceed, int* below, int* equal, unsigned char* bad,
+                            void* stream);
+int rdgan_verify_reduce(const float* obs, const int* exceed, const int* below, const int* equal, const unsigned char* bad,
+                        long n_positions, long plane, int n_members, const double* thresholds, int n_thresholds, int n_bins,
+                        uint64_t seed, long long* rank_hist_out, long long* reliability_out, long long* brier_out, void* stream);
+long rdgan_verify_fss_workspace_bytes(int ny, int nx, int n_thresholds, int n_widths);
+int rdgan_verify_fss(const float* obs, const int* exceed, const unsigned char* bad, long n_days, int ny, int nx, int n_members,
+                     const double* thresholds, int n_thresholds, const int* widths, int n_widths, double* fss_sums_out, void* workspace,
+                     long workspace_bytes, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

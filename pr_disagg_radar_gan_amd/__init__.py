@@ -8,7 +8,10 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
     ``distribution``
   * ``field`` -- disaggregate: whole daily fields through the generator, overlapping tiles blended on the device
   * ``field_products`` -- k-hour peaks of hourly maps and statistics across an ensemble's members, the hourly ensemble never held
+  * ``verification`` -- rank histogram, Brier score with reliability table and fractions skill score of field ensembles against the
+    observed hours, accumulated over groups of scenarios
 """
 from .engine import Engine, require_gpu  # noqa: F401
 from . import weights  # noqa: F401
 from . import field_products  # noqa: F401
+from . import verification  # noqa: F401

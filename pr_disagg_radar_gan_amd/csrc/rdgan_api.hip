@@ -39,6 +39,7 @@
 #include "rdgan_radar.hip.h"
 #include "rdgan_field.hip.h"
 #include "rdgan_products.hip.h"
+#include "rdgan_verify.hip.h"
 static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
 // k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
 static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
@@ -3220,6 +3221,142 @@ extern "C" int rdgan_member_stats(const float* x, int n_members, long member_str
                      RD_MS_LDS_HEAD + (size_t)np2 * px * sizeof(float), st, x, member_stride, n_members, np2, lpx, n_positions, n_probs,
                      n_thresholds, a, quantiles_out, mean_out, exceed_out, (unsigned long long*)n_nan_positions_out);
   return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// verification of field ensembles (rdgan_verify.hip.h): state accumulation, rank / reliability / Brier reduction, FSS
+// ------------------------------------------------------------------------------------
+// the thresholds as the kernels compare them: each rounded once to fp32; false unless finite, >= 0 and strictly increasing there
+static bool rd_vf_thresholds(const double* thresholds, int n, rd_vf_thr* out) {
+  if (!thresholds || n < 1 || n > RD_VF_MAXT) return false;
+  memset(out, 0, sizeof(*out));
+  for (int i = 0; i < n; ++i) {
+    if (!(thresholds[i] >= 0.0 && thresholds[i] <= 3.4028234663852886e38)) return false;        // (a NaN fails both)
+    const float f = (float)thresholds[i];
+    if (i > 0 && !(f > out->v[i - 1])) return false;
+    out->v[i] = f;
+  }
+  return true;
+}
+
+static bool rd_vf_widths_ok(const int* widths, int n, int S, rd_vf_widths* out) {
+  if (!widths || n < 1 || n > RD_VF_MAXW) return false;
+  memset(out, 0, sizeof(*out));
+  for (int i = 0; i < n; ++i) {
+    if (widths[i] < 1 || widths[i] % 2 == 0 || (i > 0 && widths[i] <= widths[i - 1])) return false;
+    if (widths[i] > 8192 || (long)S * widths[i] * widths[i] >= (1L << 26)) return false;
+    out->v[i] = widths[i];
+  }
+  return true;
+}
+
+template <int V>
+static void rd_vf_launch_accumulate(int T, unsigned blocks, hipStream_t st, const float* x, long stride, int n, long P, const float* obs,
+                                    const rd_vf_thr& thr, int* exceed, int* below, int* equal, unsigned char* bad) {
+#define RD_VF_CASE(TT)                                                                                                              \
+  case TT:                                                                                                                          \
+    hipLaunchKernelGGL((k_verify_accumulate<TT, V>), dim3(blocks), dim3(RD_VF_THREADS), 0, st, x, stride, n, P, obs, thr, exceed,    \
+                       below, equal, bad);                                                                                          \
+    break;
+  switch (T) {
+    RD_VF_CASE(1) RD_VF_CASE(2) RD_VF_CASE(3) RD_VF_CASE(4) RD_VF_CASE(5) RD_VF_CASE(6) RD_VF_CASE(7) RD_VF_CASE(8)
+  }
+#undef RD_VF_CASE
+}
+
+extern "C" int rdgan_verify_accumulate(const float* members, int n_members, long member_stride, long n_positions, const float* obs,
+                                       const double* thresholds, int n_thresholds, int* exceed, int* below, int* equal,
+                                       unsigned char* bad, void* stream) {
+  rd_vf_thr thr;
+  if (!members || !obs || !exceed || !below || !equal || !bad) return -2;
+  if (n_members < 1 || n_members > RD_VF_MAXS || n_positions < 1 || n_positions > (1L << 40) || member_stride < n_positions) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  const unsigned long long align = (unsigned long long)members | (unsigned long long)obs | (unsigned long long)exceed |
+                                   (unsigned long long)below | (unsigned long long)equal;
+  if (align & 3) return -2;
+  // 16-byte loads where every row of every array starts on 16 bytes: the member rows (base and stride), the T planes of exceed (P)
+  const bool vec = !(align & 15) && !((unsigned long long)bad & 3) && member_stride % 4 == 0 && n_positions % 4 == 0;
+  const long groups = vec ? n_positions / 4 : n_positions;
+  const unsigned blocks = (unsigned)std::min<long>((groups + RD_VF_THREADS - 1) / RD_VF_THREADS, 1L << 16);
+  if (vec)
+    rd_vf_launch_accumulate<4>(n_thresholds, blocks, (hipStream_t)stream, members, member_stride, n_members, n_positions, obs, thr,
+                               exceed, below, equal, bad);
+  else
+    rd_vf_launch_accumulate<1>(n_thresholds, blocks, (hipStream_t)stream, members, member_stride, n_members, n_positions, obs, thr,
+                               exceed, below, equal, bad);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_verify_reduce(const float* obs, const int* exceed, const int* below, const int* equal, const unsigned char* bad,
+                                   long n_positions, long plane, int n_members, const double* thresholds, int n_thresholds, int n_bins,
+                                   uint64_t seed, long long* rank_hist_out, long long* reliability_out, long long* brier_out,
+                                   void* stream) {
+  rd_vf_thr thr;
+  if (!obs || !exceed || !below || !equal || !bad || !rank_hist_out || !reliability_out || !brier_out) return -2;
+  if (n_members < 1 || n_members > RD_VF_MAXS || n_bins < 2 || n_bins > std::min(n_members + 1, RD_VF_MAXBINS)) return -2;
+  if (plane < 1 || n_positions < 1 || n_positions > (1L << 40) || n_positions % plane) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  const int S = n_members, T = n_thresholds;
+  const long n_planes = n_positions / plane;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(rank_hist_out, 0, (size_t)RD_VF_HOURS * (S + 1) * sizeof(long long), st);
+  if (e == hipSuccess) e = hipMemsetAsync(reliability_out, 0, (size_t)T * RD_VF_HOURS * n_bins * 3 * sizeof(long long), st);
+  if (e == hipSuccess) e = hipMemsetAsync(brier_out, 0, (size_t)T * RD_VF_HOURS * 4 * sizeof(long long), st);
+  if (e != hipSuccess) return (int)e;
+  const long units = ((n_planes + RD_VF_HOURS - 1) / RD_VF_HOURS) * ((plane + RD_VF_CHUNK - 1) / RD_VF_CHUNK);       // per hour
+  // at most RD_VF_MAXUNITS chunks per workgroup (the 32-bit LDS counters), at least 64 workgroups per hour where there is work
+  const long nbx = std::max<long>((units + RD_VF_MAXUNITS - 1) / RD_VF_MAXUNITS, std::min<long>(units, 64));
+  const size_t lds = RD_VF_MAXT * 4 * sizeof(unsigned long long) + (size_t)(T * n_bins * 3 + S + 1) * sizeof(unsigned);
+  hipLaunchKernelGGL(k_verify_reduce, dim3((unsigned)nbx, RD_VF_HOURS), dim3(RD_VF_THREADS), lds, st, obs, exceed, below, equal, bad,
+                     n_positions, plane, n_planes, S, T, thr, n_bins, rd_make_key(seed, RD_STREAM_VERIFY),
+                     (unsigned long long*)rank_hist_out, (unsigned long long*)reliability_out, (unsigned long long*)brier_out);
+  return (int)hipGetLastError();
+}
+
+static long rd_vf_box_blocks(long plane) { return std::min<long>((plane + RD_VF_THREADS - 1) / RD_VF_THREADS, RD_VF_BOX_MAXBLOCKS); }
+
+extern "C" long rdgan_verify_fss_workspace_bytes(int ny, int nx, int n_thresholds, int n_widths) {
+  if (ny < 1 || nx < 1 || n_thresholds < 1 || n_thresholds > RD_VF_MAXT || n_widths < 1 || n_widths > RD_VF_MAXW) return -2;
+  const long plane = (long)ny * nx, planes = (long)RD_VF_HOURS * n_thresholds;
+  if (plane > (1L << 36)) return -2;
+  return planes * rd_vf_box_blocks(plane) * n_widths * 2 * (long)sizeof(double) + 2 * planes * plane * (long)sizeof(unsigned);
+}
+
+extern "C" int rdgan_verify_fss(const float* obs, const int* exceed, const unsigned char* bad, long n_days, int ny, int nx,
+                                int n_members, const double* thresholds, int n_thresholds, const int* widths, int n_widths,
+                                double* fss_sums_out, void* workspace, long workspace_bytes, void* stream) {
+  rd_vf_thr thr;
+  rd_vf_widths wd;
+  if (!obs || !exceed || !bad || !fss_sums_out || !workspace || ((unsigned long long)workspace & 7)) return -2;
+  if (n_days < 1 || ny < 1 || nx < 1 || n_members < 1 || n_members > RD_VF_MAXS) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr) || !rd_vf_widths_ok(widths, n_widths, n_members, &wd)) return -2;
+  const long need = rdgan_verify_fss_workspace_bytes(ny, nx, n_thresholds, n_widths);
+  if (need < 0 || workspace_bytes < need) return -2;
+  const int T = n_thresholds, W = n_widths;
+  const long plane = (long)ny * nx, planes = (long)RD_VF_HOURS * T;
+  if (n_days > (1L << 40) / (plane * RD_VF_HOURS)) return -2;
+  const long P = n_days * RD_VF_HOURS * plane, rows = planes * ny, cols = planes * nx;
+  if ((rows + 3) / 4 > 0x7FFFFFFFL || (cols + RD_VF_THREADS - 1) / RD_VF_THREADS > 0x7FFFFFFFL) return -2;
+  const int nblk = (int)rd_vf_box_blocks(plane);
+  double* partial = (double*)workspace;
+  unsigned* satC = (unsigned*)(partial + planes * nblk * W * 2);
+  unsigned* satE = satC + planes * plane;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(fss_sums_out, 0, (size_t)T * W * RD_VF_HOURS * 2 * sizeof(double), st);
+  if (e != hipSuccess) return (int)e;
+  for (long day = 0; day < n_days; ++day) {                 // the days one after another: the workspace holds one day's tables
+    hipLaunchKernelGGL(k_verify_fss_rows, dim3((unsigned)((rows + 3) / 4)), dim3(RD_VF_THREADS), 0, st, obs, exceed, bad, P, day, ny, nx,
+                       n_members, T, thr, satC, satE);
+    hipLaunchKernelGGL(k_verify_fss_cols, dim3((unsigned)((cols + RD_VF_THREADS - 1) / RD_VF_THREADS)), dim3(RD_VF_THREADS), 0, st, satC,
+                       satE, planes, ny, nx);
+    hipLaunchKernelGGL(k_verify_fss_box, dim3((unsigned)nblk, (unsigned)planes), dim3(RD_VF_THREADS), 0, st, satC, satE, ny, nx,
+                       n_members, wd, W, partial);
+    hipLaunchKernelGGL(k_verify_fss_final, dim3((unsigned)((planes * W + RD_VF_THREADS - 1) / RD_VF_THREADS)), dim3(RD_VF_THREADS), 0,
+                       st, partial, nblk, T, W, fss_sums_out);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------

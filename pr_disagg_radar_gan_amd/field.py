@@ -257,6 +257,17 @@ def _scan_request(daily, D, ny, nx, plan):
     return dd, info, [np.flatnonzero(active[d]).astype(np.int32) for d in range(D)]
 
 
+def _draw_latent(latent, seed, z_shape, dev):
+    """The latent array of a request, on the device: `latent` as given, else z_shape draws from the global numpy RNG (as
+    generate_scenarios draws them), or from a device generator when `seed` is given.  Called with the device current."""
+    if latent is not None:
+        return torch.as_tensor(latent, dtype=torch.float32).to(dev)
+    if seed is None:
+        return torch.from_numpy(np.random.normal(size=z_shape).astype(np.float32)).to(dev)
+    g = torch.Generator(device=dev); g.manual_seed(int(seed))
+    return torch.randn(z_shape, generator=g, device=dev)
+
+
 def _run_groups(gen, dd, plan, S, active_tiles, latent_mode, seed, latent, z_shape, chunk, norm_scale, blend, dry):
     """The group loop disaggregate and field_products.disaggregate_peaks share: units u = scenario * D + day in order, grouped by
     _group_units; per group the condition batch, the latent rows and the generator in batches of at most `chunk` tiles, then
@@ -264,14 +275,7 @@ def _run_groups(gen, dd, plan, S, active_tiles, latent_mode, seed, latent, z_sha
     nd, T, D, dev = plan.ndomain, plan.n_tiles, int(dd.shape[0]), dd.device
     rows_per_unit = [len(active_tiles[u % D]) for u in range(S * D)]            # unit u = scenario * D + day
     with torch.cuda.device(dev):
-        if latent is not None:
-            z_all = torch.as_tensor(latent, dtype=torch.float32).to(dev)
-        elif seed is None:
-            z_all = torch.from_numpy(np.random.normal(size=z_shape).astype(np.float32)).to(dev)
-        else:
-            g = torch.Generator(device=dev); g.manual_seed(int(seed))
-            z_all = torch.randn(z_shape, generator=g, device=dev)
-        z_all = z_all.reshape(-1, W.LATENT_DIM).contiguous()                   # row u (shared) or u * T + tile (independent)
+        z_all = _draw_latent(latent, seed, z_shape, dev).reshape(-1, W.LATENT_DIM).contiguous()      # row u (shared) or u * T + tile (independent)
 
         groups = _group_units(rows_per_unit, chunk)
         max_rows = max(sum(rows_per_unit[u0:u1]) for u0, u1 in groups)

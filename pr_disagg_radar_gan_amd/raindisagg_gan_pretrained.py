@@ -95,6 +95,19 @@ def scenario_products_field(daily, n_scenarios, windows=(1, 3, 6, 12, 24), probs
     return r._replace(quantiles=host(r.quantiles), mean=host(r.mean), exceedance=host(r.exceedance), peak_hour=host(r.peak_hour))
 
 
+def verify_scenarios_field(observed, n_scenarios, thresholds, scales=(1, 3, 5, 9, 17), n_bins=11, rank_seed=0, overlap=4,
+                           latent_mode="shared", scenario_chunk=16):
+    """Verify n_scenarios scenarios of a whole observed day against its hours (verification.verify_field on the module's ``gen`` and
+    ``norm_scale``).  observed: ndarray ([n_days,] 24, ny, nx) in mm/h; its daily sums are the condition.  thresholds: the events in
+    mm/h; scales: the FSS neighbourhood widths in pixels.  Returns a verification.Verification (numpy): rank_histogram(), brier(),
+    reliability_curve(t), fss().  The latent noise comes from the global numpy RNG as in generate_scenarios_field; the hourly
+    scenarios are produced scenario_chunk at a time and never held together."""
+    from . import verification
+    return verification.verify_field(gen, np.asarray(observed), n_scenarios, thresholds, scales=scales, n_bins=n_bins,
+                                     rank_seed=rank_seed, scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode,
+                                     norm_scale=norm_scale)
+
+
 def plot_scenarios(scenarios):
     """reference :68-90: one row per scenario, 24 hourly panels, LogNorm(0.01, 50), gist_earth_r.
     Keeps the reference's indexing ``scenarios[iplot, jplot - 1]`` (the column labelled 00:00 shows
