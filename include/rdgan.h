@@ -507,6 +507,45 @@ int rdgan_verify_fss(const float* obs, const int* exceed, const unsigned char* b
                      const double* thresholds, int n_thresholds, const int* widths, int n_widths, double* fss_sums_out, void* workspace,
                      long workspace_bytes, void* stream);
 
+/* Temporal structure of hourly fields: wet spells, transitions, wet hours per day, lagged products.
+ * x [n][24][plane] fp32 (device), plane = ny nx, the leading axis with stride day_stride >= 24 plane (a view of a wider buffer is
+ * accepted); leading axes -- days, or scenarios x days -- are flattened to n.  A series is one (i, q), i < n, q < plane: the 24
+ * values x[h] = X[i day_stride + h plane + q].  Series are cut at the day boundary on purpose: generated days are independent of
+ * each other, and observed days must be cut the same way to be comparable.  A series with a NaN or +-inf among its 24 hours is
+ * bad: it adds 1 to n_bad and nothing else; n_valid counts the others.
+ * thresholds [n_thresholds] doubles on the HOST, 1 <= n_thresholds = T <= 8, each rounded once to fp32 and compared in fp32;
+ * finite, >= 0 and strictly increasing after the rounding.  Hour h is wet when x[h] > thr[t] (a value equal to the threshold is
+ * dry); m is the 24-bit mask of wet hours.  A run is a maximal block of equal bits of m and never wraps round the day; its edge
+ * class c is 1 if it contains hour 0 or hour 23 (it is cut off by the day boundary) and 0 otherwise.
+ * counts_inout [T * 286 + 2] 64-bit integers (device), over the valid series; per threshold t, at t * 286 +
+ *     0  wet_hours[k], k = 0 .. 24: series with popcount(m) = k
+ *    25  longest_wet[k], k = 0 .. 24: series whose longest wet run has length k
+ *    50  wet_spell[c][L - 1], c = 0, 1, L = 1 .. 24: wet runs of length L and edge class c
+ *    98  dry_spell[c][L - 1]: the same for dry runs (a wholly dry day is one run with c = 1, L = 24)
+ *   146  first_wet[h], h = 0 .. 23: series with a wet hour whose first wet hour is h
+ *   170  last_wet[h]: the same for the last wet hour
+ *   194  trans[h][a][b], h = 0 .. 22: series with wet(h) = a and wet(h + 1) = b
+ * then n_valid at T * 286 and n_bad at T * 286 + 1.
+ * sums_inout [48 + K + 24 T] doubles (device), over the valid series, K = max_lag in 1 .. 12:
+ *     0  moments[h] = (sum x[h], sum x[h]^2), h = 0 .. 23
+ *    48  lag[k - 1] = sum over series of sum_{h = 0}^{23 - k} x[h] x[h + k], k = 1 .. K
+ *  48+K  wet_amount[t][h] = sum of x[h] over the valid series with hour h wet
+ * every product formed exactly in fp64.  Both arrays ACCUMULATE over any number of calls; the caller zeroes them before the first.
+ * The counts do not depend on how the series are split into calls or on the launch geometry (LDS counters merged with 64-bit
+ * integer atomics).  The sums use no floating-point atomics: a fixed order in a thread, a fixed reduction in a workgroup, the
+ * workgroups' partials added in order by a final kernel -- two identical sequences of calls agree bit for bit, and for
+ * non-negative input a sum of N terms is within (N - 1) 2^-53 relative of the exact one in any grouping.
+ * 16-byte loads when x is 16-byte aligned and plane and day_stride are multiples of 4, a scalar path otherwise (4-byte alignment
+ * is required).  n * 24 * plane <= 2^40.  workspace: at least rdgan_temporal_workspace_bytes(n, plane, n_thresholds, max_lag)
+ * bytes of device memory, 8-byte aligned (-2 from the sizing entry for an argument out of range).  Asynchronous on the stream;
+ * 0 = success, -2 = bad argument (a null pointer, a misaligned pointer, n or plane < 1, a size above the limit, a threshold list
+ * or max_lag out of range, day_stride < 24 plane, a workspace too small) with nothing launched and no output touched.  All
+ * offsets are 64-bit. */
+long rdgan_temporal_workspace_bytes(long n, long plane, int n_thresholds, int max_lag);
+int rdgan_temporal_accumulate(const float* x, long n, long day_stride, long plane, const double* thresholds, int n_thresholds,
+                              int max_lag, long long* counts_inout, double* sums_inout, void* workspace, long workspace_bytes,
+                              void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

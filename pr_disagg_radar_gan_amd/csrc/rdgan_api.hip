@@ -40,6 +40,7 @@
 #include "rdgan_field.hip.h"
 #include "rdgan_products.hip.h"
 #include "rdgan_verify.hip.h"
+#include "rdgan_temporal.hip.h"
 static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
 // k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
 static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
@@ -3357,6 +3358,54 @@ extern "C" int rdgan_verify_fss(const float* obs, const int* exceed, const unsig
     if (e != hipSuccess) return (int)e;
   }
   return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// temporal structure of hourly fields (rdgan_temporal.hip.h): spells, transitions, wet hours, lagged products
+// ------------------------------------------------------------------------------------
+// workgroups of k_temporal_accumulate for `groups` threads' worth of work
+static long rd_ts_blocks(long groups) { return std::min<long>((groups + RD_TS_THREADS - 1) / RD_TS_THREADS, RD_TS_MAXBLOCKS); }
+
+static bool rd_ts_shape_ok(long n, long plane, int n_thresholds, int max_lag) {
+  if (n < 1 || plane < 1 || n_thresholds < 1 || n_thresholds > RD_TS_MAXT || max_lag < 1 || max_lag > RD_TS_MAXK) return false;
+  return plane <= RD_TS_MAXELEMS / RD_TS_HOURS && n <= RD_TS_MAXELEMS / (RD_TS_HOURS * plane);
+}
+
+extern "C" long rdgan_temporal_workspace_bytes(long n, long plane, int n_thresholds, int max_lag) {
+  if (!rd_ts_shape_ok(n, plane, n_thresholds, max_lag)) return -2;
+  return rd_ts_blocks(n * plane) * rd_ts_nsums(n_thresholds, max_lag) * (long)sizeof(double);       // (the scalar path has the most)
+}
+
+extern "C" int rdgan_temporal_accumulate(const float* x, long n, long day_stride, long plane, const double* thresholds,
+                                         int n_thresholds, int max_lag, long long* counts_inout, double* sums_inout, void* workspace,
+                                         long workspace_bytes, void* stream) {
+  rd_vf_thr thr;
+  if (!x || !counts_inout || !sums_inout || !workspace) return -2;
+  if (((unsigned long long)x & 3) || (((unsigned long long)counts_inout | (unsigned long long)sums_inout | (unsigned long long)workspace) & 7))
+    return -2;
+  if (!rd_ts_shape_ok(n, plane, n_thresholds, max_lag) || day_stride < RD_TS_HOURS * plane || day_stride > (1L << 50) / n) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  if (workspace_bytes < rdgan_temporal_workspace_bytes(n, plane, n_thresholds, max_lag)) return -2;
+  const bool vec = !((unsigned long long)x & 15) && plane % 4 == 0 && day_stride % 4 == 0;
+  const int nblk = (int)rd_ts_blocks(vec ? n * (plane / 4) : n * plane), nsums = rd_ts_nsums(n_thresholds, max_lag);
+  const size_t lds = rd_ts_lds_bytes(n_thresholds);
+  hipStream_t st = (hipStream_t)stream;
+#define RD_TS_LAUNCH(VV, KK)                                                                                                        \
+  do {                                                                                                                              \
+    RD_TRY(ensure_lds(nullptr, (const void*)k_temporal_accumulate<VV, KK>, rd_ts_lds_bytes(RD_TS_MAXT)));                           \
+    hipLaunchKernelGGL((k_temporal_accumulate<VV, KK>), dim3((unsigned)nblk), dim3(RD_TS_THREADS), lds, st, x, n, day_stride, plane, \
+                       thr, n_thresholds, max_lag, (unsigned long long*)counts_inout, (double*)workspace);                          \
+  } while (0)
+  if (vec && max_lag <= 6) RD_TS_LAUNCH(4, 6);
+  else if (vec) RD_TS_LAUNCH(4, 12);
+  else if (max_lag <= 6) RD_TS_LAUNCH(1, 6);
+  else RD_TS_LAUNCH(1, 12);
+#undef RD_TS_LAUNCH
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(k_temporal_final, dim3((unsigned)nsums), dim3(RD_TS_THREADS), 0, st, (const double*)workspace, nblk, nsums,
+                     sums_inout);
+  return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------
