@@ -546,6 +546,47 @@ int rdgan_temporal_accumulate(const float* x, long n, long day_stride, long plan
                               int max_lag, long long* counts_inout, double* sums_inout, void* workspace, long workspace_bytes,
                               void* stream);
 
+/* Rain cells of hourly fields: the connected wet areas of every hour, labelled and counted.
+ * x [n][24][ny][nx] fp32 (device), the leading axis with stride day_stride >= 24 ny nx (a view of a wider buffer is accepted);
+ * leading axes -- days, or scenarios x days -- are flattened to n.  A plane is one (i, h), i < n, h < 24: ny nx values at
+ * X[i day_stride + h ny nx + y nx + x].  ny nx <= 2^24 and n 24 ny nx <= 2^40.
+ * thresholds [n_thresholds] doubles on the HOST, 1 <= n_thresholds = T <= 8, each rounded once to fp32 and compared in fp32;
+ * finite, >= 0 and strictly increasing after the rounding.  A pixel is wet at threshold t when x > thr[t] (a value equal to the
+ * threshold is dry).  A pixel that is NaN or +-inf is bad: never wet, and counted in n_bad_pixels.
+ * A cell is a maximal set of wet pixels of ONE plane connected under `connectivity`, 4 (edges) or 8 (edges and corners); cells
+ * never link across hours, days or scenarios.  The canonical label of a cell is the smallest flat index y nx + x among its
+ * pixels; a pixel in no cell has label -1.  A cell has edge class c = 1 if it has a pixel in the first or last row or column of
+ * the plane, or a bad pixel in the 8-neighbourhood of any of its pixels (the domain or the coverage cuts it off), else c = 0.
+ * Per cell: area, its pixel count, and volume = sum of q(x), q(x) = rint(min(x, 2^20) 2^16) as a 64-bit integer -- the product is
+ * exact in fp64, the rounding is half to even and happens once per pixel, so a volume does not depend on the order of the sum.
+ * counts_inout [T * 317 + 2] 64-bit integers (device); per threshold t, at t * 317 +
+ *     0  wet_pixels[h], h = 0 .. 23: wet pixels of the planes of hour h
+ *    24  cells[c][h]: cells of edge class c in the planes of hour h
+ *    72  area_hist[c][b], b = floor(log2(area)) = 0 .. 24: cells by area (bin 0 is exactly the single-pixel cells)
+ *   122  area_sum[c]: the sum of the areas
+ *   124  area_sq_sum[c]: the sum of the squared areas
+ *   126  volume_by_area[c][b]: the sum of the volumes of the cells of bin b
+ *   176  cells_per_plane[k], k = 0 .. 64: planes with k cells, the last bin open (64 or more)
+ *   241  largest_area[b]: planes whose largest cell falls in bin b
+ *   266  dry_planes: planes without a cell
+ *   267  area_by_area[c][b]: the sum of the areas of the cells of bin b (volume_by_area over it is the bin's mean intensity)
+ * then n_planes at T * 317 and n_bad_pixels at T * 317 + 1, once per state.  The array ACCUMULATES over any number of calls; the
+ * caller zeroes it before the first.  Everything is an integer merged with integer atomics, so the state does not depend on how
+ * the planes are split into calls, on the workspace size or on the launch geometry.  (The sums wrap modulo 2^64; area_sq_sum
+ * reaches 2^63 only beyond 2^15 all-wet planes of 2^24 pixels.)
+ * labels_out: null, or [n][24][ny][nx] int32 (device, dense): the canonical labels at threshold index label_threshold in 0 .. T-1.
+ * workspace: device memory, 8-byte aligned.  rdgan_cells_workspace_bytes(ny, nx, planes_per_pass) is the size that lets a pass take
+ * planes_per_pass planes (1 .. 65535; 16 bytes per pixel and 8 per plane; -2 for an argument out of range); the entry takes
+ * floor(workspace_bytes / rdgan_cells_workspace_bytes(ny, nx, 1)) planes per pass, loops over the passes and the thresholds, and
+ * the result does not depend on it.  Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, n,
+ * ny or nx < 1, a size above the limits, a threshold list out of range, connectivity not 4 or 8, label_threshold out of range
+ * with labels_out given, day_stride < 24 ny nx, a workspace too small for one plane) with nothing launched and no output touched.
+ * All offsets are 64-bit. */
+long rdgan_cells_workspace_bytes(long ny, long nx, long planes_per_pass);
+int rdgan_cells_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds, int n_thresholds,
+                           int connectivity, long long* counts_inout, int* labels_out, int label_threshold, void* workspace,
+                           long workspace_bytes, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

@@ -102,6 +102,10 @@ SIGNATURES = {
     "rdgan_temporal_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
                                                  c_stream]),
+    "rdgan_cells_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_long]),
+    "rdgan_cells_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_long, c_stream]),
     "rdgan_spectra_bins": (ctypes.c_int, [ctypes.c_int]),
     "rdgan_radial_spectra": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_stream]),
     "rdgan_lsd_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long]),

@@ -41,6 +41,7 @@
 #include "rdgan_products.hip.h"
 #include "rdgan_verify.hip.h"
 #include "rdgan_temporal.hip.h"
+#include "rdgan_cells.hip.h"
 static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
 // k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
 static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
@@ -3406,6 +3407,68 @@ extern "C" int rdgan_temporal_accumulate(const float* x, long n, long day_stride
   hipLaunchKernelGGL(k_temporal_final, dim3((unsigned)nsums), dim3(RD_TS_THREADS), 0, st, (const double*)workspace, nblk, nsums,
                      sums_inout);
   return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// rain cells of hourly fields (rdgan_cells.hip.h): connected wet areas, labelled and counted
+// ------------------------------------------------------------------------------------
+static bool rd_cl_shape_ok(long ny, long nx) {
+  return ny >= 1 && nx >= 1 && ny <= RD_CL_MAXPLANE && nx <= RD_CL_MAXPLANE && ny * nx <= RD_CL_MAXPLANE;
+}
+
+extern "C" long rdgan_cells_workspace_bytes(long ny, long nx, long planes_per_pass) {
+  if (!rd_cl_shape_ok(ny, nx) || planes_per_pass < 1 || planes_per_pass > RD_CL_MAXPASS) return -2;
+  return rd_cl_ws_bytes(ny * nx, planes_per_pass);
+}
+
+extern "C" int rdgan_cells_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds,
+                                      int n_thresholds, int connectivity, long long* counts_inout, int* labels_out,
+                                      int label_threshold, void* workspace, long workspace_bytes, void* stream) {
+  rd_vf_thr thr;
+  if (!x || !counts_inout || !workspace) return -2;
+  if (((unsigned long long)x & 3) || ((unsigned long long)labels_out & 3) ||
+      (((unsigned long long)counts_inout | (unsigned long long)workspace) & 7))
+    return -2;
+  if (n < 1 || !rd_cl_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8)) return -2;
+  const long plane = ny * nx;
+  if (n > RD_CL_MAXELEMS / (RD_CL_HOURS * plane) || day_stride < RD_CL_HOURS * plane || day_stride > (1L << 50) / n) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  if (labels_out && (label_threshold < 0 || label_threshold >= n_thresholds)) return -2;
+  // the planes of a pass: as many as the workspace holds
+  const long n_planes = n * RD_CL_HOURS;
+  const long per_pass = std::min<long>(std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / rd_cl_ws_bytes(plane, 1), n_planes), RD_CL_MAXPASS);
+  if (per_pass < 1) return -2;
+  unsigned long long* vol = (unsigned long long*)workspace;
+  int* parent = (int*)(vol + per_pass * plane);
+  unsigned* area = (unsigned*)(parent + per_pass * plane);
+  unsigned* words = area + per_pass * plane;
+  unsigned long long* counts = (unsigned long long*)counts_inout;
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ensure_lds(nullptr, (const void*)k_cells_label_tile, RD_CL_LDS_BYTES));
+  const int tiles_x = (int)((nx + RD_CL_TILE - 1) / RD_CL_TILE), tiles_y = (int)((ny + RD_CL_TILE - 1) / RD_CL_TILE);
+  const long border = (long)(tiles_x - 1) * ny + (long)(tiles_y - 1) * nx;
+  const int conn8 = connectivity == 8;
+  for (long p0 = 0; p0 < n_planes; p0 += per_pass) {
+    const unsigned P = (unsigned)std::min<long>(per_pass, n_planes - p0);
+    for (int t = 0; t < n_thresholds; ++t) {
+      unsigned long long* ct = counts + (long)t * RD_CL_NC;
+      hipLaunchKernelGGL(k_cells_label_tile, dim3((unsigned)(tiles_x * tiles_y), P), dim3(RD_CL_THREADS), RD_CL_LDS_BYTES, st, x, day_stride,
+                         (int)ny, (int)nx, p0, thr.v[t], conn8, (int)(t == 0), ct + RD_CL_WET,
+                         counts + (long)n_thresholds * RD_CL_NC + 1, vol, parent, area, words);
+      if (border > 0)
+        hipLaunchKernelGGL(k_cells_merge, dim3((unsigned)((border + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st,
+                           (int)ny, (int)nx, conn8, parent);
+      hipLaunchKernelGGL(k_cells_resolve, dim3((unsigned)((plane + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st, plane,
+                         p0, vol, parent, area, labels_out && t == label_threshold ? labels_out : (int*)nullptr);
+      hipLaunchKernelGGL(k_cells_reduce, dim3((unsigned)((plane + RD_CL_RCHUNK - 1) / RD_CL_RCHUNK), P), dim3(RD_CL_THREADS), 0, st, plane, p0,
+                         (const unsigned long long*)vol, (const int*)parent, (const unsigned*)area, words, ct);
+      hipLaunchKernelGGL(k_cells_planes, dim3((P + RD_CL_THREADS - 1) / RD_CL_THREADS), dim3(RD_CL_THREADS), 0, st, (int)P,
+                         (const unsigned*)words, ct, t == 0 ? counts + (long)n_thresholds * RD_CL_NC : (unsigned long long*)nullptr);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return (int)e;
+    }
+  }
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------

@@ -122,6 +122,20 @@ def temporal_structure_field(daily, n_scenarios, thresholds, max_lag=6, overlap=
                                              overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
 
+def cell_structure_field(daily, n_scenarios, thresholds, connectivity=8, overlap=4, latent_mode="shared", scenario_chunk=16):
+    """The rain cells of n_scenarios scenarios of a whole daily map (cells.cell_structure_field on the module's ``gen`` and
+    ``norm_scale``): how many connected wet areas an hour has, how large they are, how much water they carry, by hour of day.
+    daily as generate_scenarios_field takes it; thresholds: the wet-pixel events in mm/h.  Returns a cells.CellStats (numpy);
+    cells.compare sets it against the same statistics of observed days.  The latent noise comes from the global numpy RNG as in
+    generate_scenarios_field; the hourly scenarios are produced scenario_chunk at a time and never held together."""
+    from . import cells
+    daily = np.asarray(daily)
+    if daily.ndim >= 3 and daily.shape[-1] == 1:
+        daily = daily[..., 0]
+    return cells.cell_structure_field(gen, daily, n_scenarios, thresholds, connectivity=connectivity, scenario_chunk=scenario_chunk,
+                                      overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
+
+
 def plot_scenarios(scenarios):
     """reference :68-90: one row per scenario, 24 hourly panels, LogNorm(0.01, 50), gist_earth_r.
     Keeps the reference's indexing ``scenarios[iplot, jplot - 1]`` (the column labelled 00:00 shows
