@@ -18,8 +18,9 @@ import torch
 from . import _lib
 from . import field as F
 from . import weights as W
+from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
+from ._hourly import NHOURS, admit, div as _div, to_state_device, tv as _tv
 from .engine import require_gpu
-from .temporal import NHOURS, _check_hourly_shape, _div, _tv, tensor_layout
 from .verification import check_event_thresholds
 
 N_COUNTS = 317                                                               # RD_CL_NC: counters per threshold
@@ -34,17 +35,13 @@ _DEFAULT_PASS_PIXELS = 1 << 24                                               # 2
 
 
 def check_connectivity(connectivity):
-    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (4, 8):
+    if whole_number(connectivity, 4, 8, "connectivity") not in (4, 8):
         raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
     return int(connectivity)
 
 
 def check_planes_per_pass(planes_per_pass):
-    if planes_per_pass is None:
-        return None
-    if isinstance(planes_per_pass, bool) or not isinstance(planes_per_pass, (int, np.integer)) or not 1 <= int(planes_per_pass) <= MAX_PASS:
-        raise ValueError(f"planes_per_pass must be None or a whole number in 1 .. {MAX_PASS}, got {planes_per_pass!r}")
-    return int(planes_per_pass)
+    return None if planes_per_pass is None else whole_number(planes_per_pass, 1, MAX_PASS, "planes_per_pass, unless None,")
 
 
 def split_state(counts, n_thresholds):
@@ -184,52 +181,32 @@ class CellStructure:
         entries (temporal.tensor_layout has the rule, and refuses a crop, a step or a transpose at any rank), or a numpy array.
         The plane shape is fixed by the first call.  labels_out: None, or a contiguous int32 CUDA tensor of hourly's shape that
         receives the canonical labels at thresholds[label_threshold].  Returns self."""
-        if isinstance(hourly, torch.Tensor):
-            if not hourly.is_cuda:                     # (a host view's strides would not survive the copy to the device)
-                raise ValueError("hourly: expected a CUDA tensor or a numpy array, got a torch tensor on the host")
-            host = None
-        else:
-            hourly = np.asarray(hourly)
-            if not (np.issubdtype(hourly.dtype, np.floating) or np.issubdtype(hourly.dtype, np.integer)):
-                raise ValueError("hourly: expected an array of numbers")
-            host = hourly
-        shape = _check_hourly_shape(hourly.shape)
-        if self.plane_shape is not None and shape[-2:] != self.plane_shape:
-            raise ValueError(f"hourly: the plane shape is {self.plane_shape} since the first call, got {shape[-2:]}")
-        if host is None and hourly.dtype != torch.float32:
-            raise ValueError("hourly: expected float32")
+        hourly, from_host, shape, n, stride = admit(hourly, self.plane_shape)
         ny, nx = shape[-2:]
         plane = ny * nx
         if plane > MAX_PLANE:
             raise ValueError(f"hourly: a plane has {plane} pixels, the limit is {MAX_PLANE}")
-        n, stride = (int(np.prod(shape[:-3], dtype=np.int64)), NHOURS * plane) if host is not None else tensor_layout(shape, hourly.stride())
-        if isinstance(label_threshold, bool) or not isinstance(label_threshold, (int, np.integer)) or not 0 <= int(label_threshold) < len(self.thr):
-            raise ValueError(f"label_threshold must be an index in 0 .. {len(self.thr) - 1}, got {label_threshold!r}")
+        label_threshold = whole_number(label_threshold, 0, len(self.thr) - 1, "label_threshold")
         if labels_out is not None and not (isinstance(labels_out, torch.Tensor) and labels_out.is_cuda and labels_out.dtype == torch.int32
                                            and labels_out.is_contiguous() and tuple(labels_out.shape) == shape):
             raise ValueError(f"labels_out: expected a contiguous int32 CUDA tensor of shape {shape}")
         if self.counts is None:
-            self._start(hourly.device if host is None else "cuda")
-        if host is not None:
-            hourly = torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)).to(self.counts.device)
-        elif hourly.device != self.counts.device:
-            raise ValueError(f"hourly lies on {hourly.device}, the state on {self.counts.device}")
+            self._start("cuda" if from_host else hourly.device)
+        hourly = to_state_device(hourly, from_host, self.counts.device)
         if labels_out is not None and labels_out.device != self.counts.device:
             raise ValueError(f"labels_out lies on {labels_out.device}, the state on {self.counts.device}")
         self.plane_shape = shape[-2:]
         per_pass = self.planes_per_pass or max(1, _DEFAULT_PASS_PIXELS // plane)
         per_pass = min(per_pass, n * NHOURS, MAX_PASS)
         with torch.cuda.device(self.counts.device):
-            nbytes = self.lib.rdgan_cells_workspace_bytes(ny, nx, per_pass)
-            if nbytes < 0:
-                raise _lib.RdganError(f"rdgan_cells_workspace_bytes failed with code {nbytes}")
+            nbytes = workspace_bytes(self.lib, "rdgan_cells_workspace_bytes", ny, nx, per_pass)
             # (exactly this size: the entry takes as many planes per pass as the workspace holds)
             if self._ws is None or self._ws.numel() * 8 != nbytes:
                 self._ws = None
                 self._ws = torch.empty(nbytes // 8, dtype=torch.int64, device=self.counts.device)
-            rc = self.lib.rdgan_cells_accumulate(F._p(hourly), n, stride, ny, nx, F._hp(self.thr), len(self.thr), self.connectivity,
-                                                 F._p(self.counts), F._p(labels_out) if labels_out is not None else None,
-                                                 int(label_threshold), F._p(self._ws), nbytes, F._stream(self.counts))
+            rc = self.lib.rdgan_cells_accumulate(_p(hourly), n, stride, ny, nx, _hp(self.thr), len(self.thr), self.connectivity,
+                                                 _p(self.counts), _p(labels_out), label_threshold, _p(self._ws), nbytes,
+                                                 _stream(self.counts))
         _lib.check(rc, None, "rdgan_cells_accumulate")
         return self
 
@@ -253,14 +230,9 @@ def label_cells(hourly, threshold, connectivity=8):
     """The canonical labels of the cells of hourly (..., 24, ny, nx; a float32 CUDA tensor or numpy) at one threshold: an int32
     CUDA tensor of the same shape, every pixel of a cell holding the smallest flat index y nx + x of the cell, -1 elsewhere"""
     cs = CellStructure((threshold,), connectivity)
-    if isinstance(hourly, torch.Tensor) and hourly.is_cuda:
-        shape, device = _check_hourly_shape(hourly.shape), hourly.device
-    else:
-        if isinstance(hourly, torch.Tensor):
-            raise ValueError("hourly: expected a CUDA tensor or a numpy array, got a torch tensor on the host")
-        shape, device = _check_hourly_shape(np.shape(hourly)), "cuda"
+    hourly, from_host, shape, _, _ = admit(hourly)
     require_gpu()
-    labels = torch.empty(shape, dtype=torch.int32, device=device)
+    labels = torch.empty(shape, dtype=torch.int32, device="cuda" if from_host else hourly.device)
     cs.add(hourly, labels_out=labels)
     return labels
 
@@ -274,26 +246,10 @@ def cell_structure_field(gen, daily, n_scenarios, thresholds, connectivity=8, pl
     equal the ones of a single disaggregate call only when the generator's batches are the same (`chunk` at most one unit's wet
     tiles, or one scenario chunk).  -> CellStats"""
     cs = CellStructure(thresholds, connectivity, planes_per_pass)
-    S, step = int(n_scenarios), int(scenario_chunk)
-    if S < 1:
-        raise ValueError(f"the number of scenarios must be at least 1, got {S}")
-    if step < 1:
-        raise ValueError("scenario_chunk must be at least 1")
-    _req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
-    daily, squeeze_day, D, ny, nx, plan, z_shape = _req
+    S, step = F._check_scenarios(n_scenarios, scenario_chunk)
+    req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
+    ny, nx = req[3:5]
     if ny * nx > MAX_PLANE:
         raise ValueError(f"daily: a plane has {ny * nx} pixels, the limit is {MAX_PLANE}")
-    dd, info, _ = F._scan_request(daily, D, ny, nx, plan)
-    dev = dd.device
-    with torch.cuda.device(dev):
-        # (without a wet tile disaggregate draws nothing)
-        z_all = F._draw_latent(latent, seed, z_shape, dev) if info.n_active else None
-        shape = ((NHOURS, ny, nx) if squeeze_day else (D, NHOURS, ny, nx))
-        buf = torch.empty((min(step, S),) + shape, dtype=torch.float32, device=dev)
-        cond = dd[0] if squeeze_day else dd
-        for s0 in range(0, S, step):
-            n = min(step, S - s0)
-            F.disaggregate(gen, cond, n, overlap=overlap, latent_mode=latent_mode, latent=None if z_all is None else z_all[s0:s0 + n],
-                           chunk=chunk, norm_scale=norm_scale, out=buf[:n])
-            cs.add(buf[:n])
+    F._stream_scenarios(gen, req, req[0], S, step, cs.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
     return cs.result()

@@ -7,7 +7,6 @@ The fixed ensemble is sorted once per call and every day costs one binary search
 from the project's counter RNG on the device; the t statistic comes from device moments and its p-value from the regularised
 incomplete beta function on the host (own continued fraction: the package does not depend on scipy).  No CPU fallback: without a
 visible MI355X every device entry point raises RdganError; argument errors are ValueErrors raised before any device call."""
-import ctypes
 import math
 from dataclasses import dataclass
 from typing import Optional
@@ -17,18 +16,11 @@ import torch
 
 from . import _lib, ensemble, rainfarm
 from . import weights as W
+from ._dev import device_f32, ptr as _p, stream as _stream
 from .engine import require_gpu
 
 NHOURS = 24
 MAX_MEMBERS = 8192              # RD_CRPS_MAXN of csrc/rdgan_crps.hip.h
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _check_days(a, name):
@@ -77,8 +69,8 @@ def crps_fixed_ensemble_device(ens, obs, per_position=False):
         raise ValueError(f"obs: fewer than 2^31 values per call, got {D * NHOURS * nd * nd}")
     require_gpu()
     lib = _lib.load()
-    ens = rainfarm._device_f32(ens, "ens")
-    obs = rainfarm._device_f32(obs, "obs").to(ens.device)
+    ens = device_f32(ens, "ens")
+    obs = device_f32(obs, "obs").to(ens.device)
     hourly = torch.empty((D, NHOURS), dtype=torch.float32, device=ens.device)
     crps = torch.empty((D, NHOURS, nd, nd), dtype=torch.float32, device=ens.device) if per_position else None
     _lib.check(lib.rdgan_crps_fixed_ensemble(_p(ens), _p(obs), _p(crps), _p(hourly), n, D, nd, _stream(ens)), None,
@@ -131,7 +123,7 @@ def rainfarm_crps_for_days(reals_precip, alpha, beta, n_members=1000, seed=None)
     if int(n_members) < 1 or int(n_members) > MAX_MEMBERS:
         raise ValueError(f"1 .. {MAX_MEMBERS} members per day, got {n_members}")
     require_gpu()
-    reals = rainfarm._device_f32(reals_precip, "reals_precip")
+    reals = device_f32(reals_precip, "reals_precip")
     rows = []
     for d in range(shape[0]):
         real = reals[d]

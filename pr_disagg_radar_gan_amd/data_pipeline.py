@@ -15,11 +15,8 @@ import torch
 
 from . import _lib
 from . import weights as W
+from ._dev import ptr as _p
 from .engine import require_gpu
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 FRAMES_PER_HOUR = (1, 2, 3, 4, 6, 12)          # what rdgan_data_radar_hourly accepts; SMHI: 12 (5-minute frames)
@@ -278,7 +275,7 @@ class DeviceDataset:
         batch = torch.empty((n, W.NHOURS, nd, nd, 1), dtype=torch.float32, device=self.device) if with_batch else None
         cond = torch.empty((n, nd, nd, 1), dtype=torch.float32, device=self.device)
         rc = self.lib.rdgan_data_gather(_p(self.data), self.n_days, self.ny, self.nx, _p(sel), n, nd, self.norm_scale,
-                                        _p(batch) if with_batch else ctypes.c_void_p(0), _p(cond), _p(self.flags), self._stream())
+                                        _p(batch if with_batch else None), _p(cond), _p(self.flags), self._stream())
         _lib.check(rc, None, "rdgan_data_gather")
         if self.extra is not None:
             cond = self._extra_channels(sel, cond)

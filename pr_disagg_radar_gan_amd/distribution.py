@@ -7,7 +7,6 @@ most, the box-plot statistics as matplotlib.cbook.boxplot_stats defines them, EC
 KS p-value is taken on the host in fp64 by the package's own code (no scipy): exact for equal sample sizes, asymptotic otherwise.
 The figures themselves are not drawn here.  No CPU fallback: without a visible MI355X every device entry point raises RdganError;
 argument errors are ValueErrors raised before any device call."""
-import ctypes
 import math
 from dataclasses import dataclass
 from typing import Optional
@@ -17,20 +16,13 @@ import torch
 
 from . import _lib, ensemble
 from . import weights as W
+from ._dev import device_f32, ptr as _p, stream as _stream
 from .engine import require_gpu
 
 NHOURS = 24
 MAX_N = 16384                   # RD_DIST_MAXN of csrc/rdgan_dist.hip.h: a column is sorted in LDS
 MAX_GRID = 4096                 # RD_ECDF_MAXT
 STAT_FIELDS = ("n", "mean", "q1", "med", "q3", "iqr", "whislo", "whishi", "cilo", "cihi", "n_fliers_lo", "n_fliers_hi")
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _columns_shape(x, name):
@@ -47,14 +39,6 @@ def _columns_shape(x, name):
     if shape[0] < 1 or shape[2] < 1 or shape[0] * shape[2] >= 2 ** 31:
         raise ValueError(f"{name}: 1 .. 2^31 - 1 columns, got shape {tuple(x.shape)}")
     return shape
-
-
-def _device_f32(a, name, device=None):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError(f"{name}: expected a CUDA tensor or a numpy array")
-        return a.detach().to(torch.float32).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device or "cuda")
 
 
 def _check_kind(a, name):
@@ -128,8 +112,8 @@ def ks_statistic_device(a, b):
         raise ValueError(f"a and b differ in batch or columns: {tuple(a.shape)} and {tuple(b.shape)}")
     require_gpu()
     lib = _lib.load()
-    a = _device_f32(a, "a")
-    b = _device_f32(b, "b", a.device).to(a.device)
+    a = device_f32(a, "a")
+    b = device_f32(b, "b", a.device).to(a.device)
     counts = torch.empty((sa[0], sa[2], 2), dtype=torch.int32, device=a.device)
     d = torch.empty((sa[0], sa[2]), dtype=torch.float64, device=a.device)
     _lib.check(lib.rdgan_ks_2samp(_p(a), _p(b), sa[1], sb[1], sa[2], sa[0], _p(counts), _p(d), _stream(a)), None, "rdgan_ks_2samp")
@@ -214,7 +198,7 @@ def boxplot_stats(x, keep_sorted=True):
     shape = _columns_shape(x, "x")
     require_gpu()
     lib = _lib.load()
-    x = _device_f32(x, "x")
+    x = device_f32(x, "x")
     stats = torch.empty((shape[0], shape[2], len(STAT_FIELDS)), dtype=torch.float64, device=x.device)
     srt = torch.empty(shape, dtype=torch.float32, device=x.device) if keep_sorted else None
     _lib.check(lib.rdgan_box_stats(_p(x), shape[1], shape[2], shape[0], _p(stats), _p(srt), _stream(x)), None, "rdgan_box_stats")
@@ -280,7 +264,7 @@ def ecdf_counts_device(data, grid):
         raise ValueError(f"1 .. 2^40 values, got {n}")
     require_gpu()
     lib = _lib.load()
-    x = _device_f32(data, "data").reshape(-1)
+    x = device_f32(data, "data").reshape(-1)
     gd = torch.from_numpy(g).to(x.device)
     T = g.shape[0]
     nbytes = lib.rdgan_ecdf_workspace_bytes(T)
@@ -316,7 +300,7 @@ def daily_cycle(ameans):
     launch."""
     arrs, shape = _check_ameans(ameans)
     require_gpu()
-    dev = [_device_f32(a, k) for a, k in zip(arrs, AMEAN_KEYS)]
+    dev = [device_f32(a, k) for a, k in zip(arrs, AMEAN_KEYS)]
     stats = boxplot_stats(torch.stack([d.to(dev[0].device) for d in dev]))
     out = {}
     for b, key in enumerate(AMEAN_KEYS):

@@ -1,17 +1,13 @@
 """Batched ensemble inference and on-device CRPS: the body of the reference's
 generate_and_evaluate_crps.py loop (:177-195) -- n_fake_per_real scenarios for one real day, CRPS of the
 ensemble against the observed hourly field per grid point, area mean per hour -- without leaving the GPU."""
-import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib, models
 from . import weights as W
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+from ._dev import ptr as _p, stream as _stream
 
 
 def crps_ensemble_device(ens, obs, scale=None):
@@ -23,7 +19,7 @@ def crps_ensemble_device(ens, obs, scale=None):
     if ens.numel() != n * npix:
         raise ValueError("ens must have shape (n,) + obs.shape")
     out = torch.empty_like(obs)
-    st = ctypes.c_void_p(torch.cuda.current_stream(ens.device).cuda_stream)
+    st = _stream(ens)
     _lib.check(lib.rdgan_crps_ensemble(_p(ens), _p(obs), _p(scale.contiguous() if scale is not None else None), _p(out),
                                        n, npix, st), None, "rdgan_crps_ensemble")
     return out

@@ -5,7 +5,6 @@ blending weights sum to 1 at every pixel, so every pixel's 24 values sum to its 
 
 No CPU fallback: without a visible MI355X disaggregate and blend_device raise RdganError; argument errors are ValueErrors raised
 before any device call."""
-import ctypes
 from dataclasses import dataclass, field as _dc_field
 
 import numpy as np
@@ -13,22 +12,11 @@ import torch
 
 from . import _lib, models
 from . import weights as W
+from ._dev import host_ptr as _hp, ptr as _p, stream as _stream
 from .engine import require_gpu
 
 MAX_COVER = 3                   # RD_FIELD_COVER of csrc/rdgan_field.hip.h: tiles covering a coordinate per axis
 LATENT_MODES = ("shared", "independent")
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _hp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def axis_origins(L, ndomain, overlap):
@@ -303,6 +291,36 @@ def _run_groups(gen, dd, plan, S, active_tiles, latent_mode, seed, latent, z_sha
                 eng.gen_forward(slab, z[i:i + k].contiguous(), cond[i:i + k], out=frac[i:i + k], gen_version=version)
                 eng.check_numerics()             # reference T:349-350
             blend(frac[:m], slots, u0, u1)
+
+
+def _check_scenarios(n_scenarios, scenario_chunk, max_scenarios=None):
+    """The counts of a scenario stream, host code.  -> (S, scenario_chunk) as ints"""
+    S, step = int(n_scenarios), int(scenario_chunk)
+    if S < 1 or (max_scenarios is not None and S > max_scenarios):
+        raise ValueError(f"the number of scenarios must be at least 1{f' and at most {max_scenarios}' if max_scenarios else ''}, got {S}")
+    if step < 1:
+        raise ValueError("scenario_chunk must be at least 1")
+    return S, step
+
+
+def _stream_scenarios(gen, request, daily, S, scenario_chunk, sink, overlap, latent_mode, seed, latent, chunk, norm_scale):
+    """The scenario stream the *_field evaluations share.  request: what _check_request returned for S scenarios; daily: the plane
+    to scan (request[0], unless the request was checked on a stand-in).  The latent array is drawn once for all S scenarios, exactly
+    as disaggregate draws it -- and, as there, not at all without a wet tile; disaggregate then runs for scenario_chunk scenarios at
+    a time into one reused buffer, and sink(buf[:n]) takes each chunk ([D,] 24, ny, nx per scenario) before the next overwrites it."""
+    _, squeeze_day, D, ny, nx, plan, z_shape = request
+    dd, info, _ = _scan_request(daily, D, ny, nx, plan)
+    dev = dd.device
+    with torch.cuda.device(dev):
+        z_all = _draw_latent(latent, seed, z_shape, dev) if info.n_active else None
+        shape = (W.NHOURS, ny, nx) if squeeze_day else (D, W.NHOURS, ny, nx)
+        buf = torch.empty((min(scenario_chunk, S),) + shape, dtype=torch.float32, device=dev)
+        cond = dd[0] if squeeze_day else dd
+        for s0 in range(0, S, scenario_chunk):
+            n = min(scenario_chunk, S - s0)
+            disaggregate(gen, cond, n, overlap=overlap, latent_mode=latent_mode, latent=None if z_all is None else z_all[s0:s0 + n],
+                         chunk=chunk, norm_scale=norm_scale, out=buf[:n])
+            sink(buf[:n])
 
 
 def disaggregate(gen, daily, n_scenarios, overlap=4, latent_mode="shared", seed=None, latent=None, chunk=1024,

@@ -7,7 +7,6 @@ members of an ensemble -- quantiles, mean, exceedance frequencies.
 
 No CPU fallback: without a visible MI355X the device functions raise RdganError; argument errors are ValueErrors raised before any
 device call."""
-import ctypes
 from collections import namedtuple
 
 import numpy as np
@@ -16,9 +15,11 @@ import torch
 from . import _lib
 from . import field as F
 from . import weights as W
+from ._dev import host_ptr as _hp, ptr as _p, stream as _stream
+from ._hourly import MAX_MEMBERS, member_layout
 from .engine import require_gpu
 
-MAX_WINDOWS, MAX_PROBS, MAX_THRESHOLDS, MAX_MEMBERS = 8, 16, 16, 4096   # RD_PEAKS_MAXK, RD_MS_MAXQ, RD_MS_MAXT, RD_MS_MAXS
+MAX_WINDOWS, MAX_PROBS, MAX_THRESHOLDS = 8, 16, 16                       # RD_PEAKS_MAXK, RD_MS_MAXQ, RD_MS_MAXT (MAX_MEMBERS: RD_MS_MAXS)
 DEFAULT_WINDOWS = (1, 3, 6, 12, 24)
 DEFAULT_PROBS = (0.1, 0.5, 0.9, 0.99)
 
@@ -75,7 +76,7 @@ def peaks_device(hourly, windows=DEFAULT_WINDOWS):
     F._check_f32_cuda(hourly, hourly.shape, "hourly")
     peaks = torch.empty((units, len(win), ny, nx), dtype=torch.float32, device=hourly.device)
     hour = torch.empty((units, ny, nx), dtype=torch.uint8, device=hourly.device)
-    rc = lib.rdgan_hourly_peaks(F._p(hourly), units, ny, nx, F._hp(win), len(win), F._p(peaks), F._p(hour), F._stream(hourly))
+    rc = lib.rdgan_hourly_peaks(_p(hourly), units, ny, nx, _hp(win), len(win), _p(peaks), _p(hour), _stream(hourly))
     _lib.check(rc, None, "rdgan_hourly_peaks")
     return peaks, hour
 
@@ -109,33 +110,11 @@ def blend_peaks_device(frac, slots, plan, daily, windows=DEFAULT_WINDOWS, first_
             and tuple(hour.shape) == (units, plan.ny, plan.nx)):
         raise ValueError(f"peak_hour out: expected a contiguous uint8 CUDA tensor of shape {(units, plan.ny, plan.nx)}")
     yi, yw, xi, xw = plan.device_tables(frac.device)
-    rc = lib.rdgan_field_blend_peaks(F._p(frac), m, F._hp(slots), units, int(first_unit), F._p(yi), F._p(yw), F._p(xi), F._p(xw),
-                                     F._p(daily), int(daily.shape[0]), plan.ny, plan.nx, nd, plan.overlap, F._hp(win), len(win),
-                                     F._p(peaks), F._p(hour), F._stream(frac))
+    rc = lib.rdgan_field_blend_peaks(_p(frac), m, _hp(slots), units, int(first_unit), _p(yi), _p(yw), _p(xi), _p(xw),
+                                     _p(daily), int(daily.shape[0]), plan.ny, plan.nx, nd, plan.overlap, _hp(win), len(win),
+                                     _p(peaks), _p(hour), _stream(frac))
     _lib.check(rc, None, "rdgan_field_blend_peaks")
     return peaks, hour
-
-
-def _member_layout(x):
-    """(S, P, member_stride, shape) of x (S, *shape): every axis behind the first must be contiguous, the first may have any stride
-    >= P (a view of a wider buffer)"""
-    if not isinstance(x, torch.Tensor) or x.dim() < 1:
-        raise ValueError("x: expected a tensor of shape (S, *shape)")
-    S, shape = int(x.shape[0]), tuple(int(n) for n in x.shape[1:])
-    P = int(np.prod(shape, dtype=np.int64))
-    if not 1 <= S <= MAX_MEMBERS:
-        raise ValueError(f"the number of members must lie in 1 .. {MAX_MEMBERS}, got {S}")
-    if P < 1:
-        raise ValueError(f"x holds no position: shape {tuple(x.shape)}")
-    expect = 1
-    for n, st in zip(reversed(shape), reversed(x.stride()[1:])):
-        if n != 1 and st != expect:
-            raise ValueError("x: the axes behind the member axis must be contiguous")
-        expect *= n
-    stride = int(x.stride(0)) if S > 1 else P
-    if stride < P:
-        raise ValueError(f"x: the member stride {stride} is below the number of positions {P}")
-    return S, P, stride, shape
 
 
 def member_stats_device(x, probs, thresholds=()):
@@ -144,7 +123,7 @@ def member_stats_device(x, probs, thresholds=()):
     n_nan_positions): np.quantile(x, probs, axis=0) (method "linear", fp64, rounded once to fp32), the mean (fp64 sum), the share
     of members above each threshold; NaN at every position where a member is NaN, n_nan_positions (an int) counting those."""
     p, t = check_probs(probs), check_thresholds(thresholds)
-    S, P, stride, shape = _member_layout(x)
+    S, P, stride, shape = member_layout(x)
     require_gpu()
     lib = _lib.load()
     if not (x.is_cuda and x.dtype == torch.float32):
@@ -154,8 +133,8 @@ def member_stats_device(x, probs, thresholds=()):
     mean = torch.empty(shape, dtype=torch.float32, device=dev)
     exceed = torch.empty((len(t),) + shape, dtype=torch.float32, device=dev)
     n_nan = torch.empty(1, dtype=torch.int64, device=dev)
-    rc = lib.rdgan_member_stats(F._p(x), S, stride, P, F._hp(p), len(p), F._hp(t) if len(t) else ctypes.c_void_p(0), len(t), F._p(quant),
-                                F._p(mean), F._p(exceed) if len(t) else ctypes.c_void_p(0), F._p(n_nan), F._stream(x))
+    rc = lib.rdgan_member_stats(_p(x), S, stride, P, _hp(p), len(p), _hp(t) if len(t) else _p(None), len(t), _p(quant),
+                                _p(mean), _p(exceed if len(t) else None), _p(n_nan), _stream(x))
     _lib.check(rc, None, "rdgan_member_stats")
     return MemberStats(quant, mean, exceed, int(n_nan.item()))
 

@@ -5,13 +5,13 @@ The log-power statistics of the calibration run in fp64 on the device, reduced p
 (R:6-19) runs on the host over the classes with the reference's own abscissae, so the points it keeps are R's.  Generation is
 fp32 on the device; its phases come from a caller's uniforms (np.random.rand, as R:103 draws them) or from the project's counter
 RNG.  No CPU fallback: without a visible MI355X every device entry point raises RdganError."""
-import ctypes
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._dev import device_f32, ptr as _p, stream as _stream
 from .engine import require_gpu
 from .ensemble import crps_ensemble_device
 
@@ -21,26 +21,10 @@ N_TCLASS = 13                   # |m| = 0 .. 12 of the 24-point DFT
 MAX_N = 1 << 24                 # samples / members per kernel call
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _check_nd(nd):
     if int(nd) not in ND_SUPPORTED:
         raise ValueError(f"ndomain {nd} is not covered by the RainFARM kernels {ND_SUPPORTED}")
     return int(nd)
-
-
-def _device_f32(a, name):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError(f"{name}: expected a CUDA tensor or a numpy array")
-        return a.to(torch.float32).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -132,7 +116,7 @@ def slope_statistics(p_samples):
         raise ValueError(f"p_samples: 1 .. {MAX_N} samples per call, got {n}")
     require_gpu()
     lib = _lib.load()
-    x = _device_f32(x, "p_samples")
+    x = device_f32(x, "p_samples")
     if x.data_ptr() % 16:
         x = x.clone()
     nc = int(lib.rdgan_rainfarm_classes(nd))
@@ -226,7 +210,7 @@ def downscale_device(precip, alpha, beta, n_members=None, seed=None, uniforms=No
         raise ValueError("first_member must be >= 0")
     require_gpu()
     lib = _lib.load()
-    pr = _device_f32(pr, "precip")
+    pr = device_f32(pr, "precip")
     dev = pr.device
     amp = torch.from_numpy(spectral_amplitudes(alpha, beta, nd).astype(np.complex64).view(np.float32)).to(dev)
     u = None
@@ -270,7 +254,7 @@ def generate_one_per_day(real_precip, alpha, beta, seed=None):
     or from the counter RNG (member i = day i) when a seed is given."""
     real = _check_days(real_precip)
     require_gpu()
-    real = _device_f32(real, "real_precip")
+    real = device_f32(real, "real_precip")
     return downscale_device(real.sum(1), alpha, beta, seed=seed)
 
 
@@ -282,7 +266,7 @@ def crps_for_day(real_precip, alpha, beta, n_members=1000, seed=None):
         raise ValueError(f"real_precip must have shape ({NHOURS}, nd, nd), got {shape}")
     _check_nd(shape[1])
     require_gpu()
-    real = _device_f32(real_precip, "real_precip")
+    real = device_f32(real_precip, "real_precip")
     ens = downscale_device(real.sum(0), alpha, beta, n_members=n_members, seed=seed)
     crps = crps_ensemble_device(ens, real)
     return crps.mean(dim=(1, 2)).cpu().numpy()

@@ -1,7 +1,6 @@
 """Log-spectral distance on the device (reference log_spectral_distance.py): radial power spectra of the hourly fields and the
 distance of every ordered pair of them, reduced to a histogram and moments so that the N x M distances never need to exist.
 No CPU fallback: without a visible MI355X every entry point raises RdganError."""
-import ctypes
 from dataclasses import dataclass
 from typing import Optional
 
@@ -9,27 +8,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._dev import device_f32, ptr as _p, stream as _stream
 from .engine import require_gpu
 
 DEFAULT_BINS = 512
 DEFAULT_RANGE = (0.0, 20.0)          # dB; the evaluation's distances lie well inside (the reference plots a KDE of them)
 MATRIX_LIMIT_BYTES = 1 << 31         # matrix=True refuses an N x M fp32 output above 2 GiB: use the histogram instead
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _device_f32(a, name):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError(f"{name}: expected a CUDA tensor")
-        return a.to(torch.float32).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
 
 def spectra_bins(nd):
@@ -88,8 +72,8 @@ def log_spectral_distance_device(spec_a, spec_b=None, *, bins=DEFAULT_BINS, rang
     matrix=True also returns the (N, M) distances (0 on an excluded diagonal) and raises ValueError above MATRIX_LIMIT_BYTES."""
     require_gpu()
     lib = _lib.load()
-    a = _device_f32(spec_a, "spec_a")
-    b = a if spec_b is None else _device_f32(spec_b, "spec_b")
+    a = device_f32(spec_a, "spec_a")
+    b = a if spec_b is None else device_f32(spec_b, "spec_b")
     if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
         raise ValueError(f"spec_a (N, K) and spec_b (M, K) expected, got {tuple(a.shape)} and {tuple(b.shape)}")
     if b.device != a.device:
@@ -129,8 +113,8 @@ def lsd_evaluation(real_precip, generated_precip, **hist_kw):
     mm/h, host or device, flattened to (24 n, nd, nd) with the hour fastest; returns {"real": real vs real, "gen": generated vs
     generated, "gen_real": generated (rows) vs real (columns)} as LSDResult, the diagonal excluded in all three."""
     require_gpu()
-    real = _device_f32(real_precip, "real_precip")
-    gen = _device_f32(generated_precip, "generated_precip")
+    real = device_f32(real_precip, "real_precip")
+    gen = device_f32(generated_precip, "generated_precip")
     if real.dim() != 4 or tuple(real.shape) != tuple(gen.shape) or real.shape[2] != real.shape[3]:
         raise ValueError(f"real and generated precipitation of one shape (n, 24, nd, nd) expected, got {tuple(real.shape)} "
                          f"and {tuple(gen.shape)}")

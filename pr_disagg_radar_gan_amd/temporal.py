@@ -17,10 +17,11 @@ import torch
 from . import _lib
 from . import field as F
 from . import weights as W
+from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
+from ._hourly import NHOURS, admit, div as _div, tensor_layout, to_state_device, tv as _tv    # noqa: F401 (tensor_layout is public here)
 from .engine import require_gpu
 from .verification import check_event_thresholds
 
-NHOURS = 24
 MAX_LAG = 12                                                                 # RD_TS_MAXK
 N_COUNTS = 286                                                               # RD_TS_NC: counters per threshold
 THREADS, MAX_BLOCKS = 256, 1024                                              # RD_TS_THREADS, RD_TS_MAXBLOCKS
@@ -29,43 +30,7 @@ _WH, _LW, _WS, _DS, _FW, _LAST, _TR = 0, 25, 50, 98, 146, 170, 194
 
 
 def check_max_lag(max_lag):
-    if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 1 <= int(max_lag) <= MAX_LAG:
-        raise ValueError(f"max_lag must be a whole number in 1 .. {MAX_LAG}, got {max_lag!r}")
-    return int(max_lag)
-
-
-def _check_hourly_shape(shape, what="hourly"):
-    shape = tuple(int(n) for n in shape)
-    if len(shape) < 3 or shape[-3] != NHOURS or min(shape) < 1:
-        raise ValueError(f"{what}: expected shape (..., 24, ny, nx) with no empty axis, got {shape}")
-    return shape
-
-
-def tensor_layout(shape, strides):
-    """(n, day_stride) of a tensor of shape (..., 24, ny, nx) with these strides (in elements), as rdgan_temporal_accumulate reads
-    it: the last three axes must be dense, whatever the rank; the leading axes must flatten to one axis of stride day_stride >= 24
-    ny nx, which a single leading axis does with any stride (a view of a wider buffer) and several do only when they are dense
-    among themselves.  Anything a stride argument cannot express -- a crop, a step, a transposed plane -- is a ValueError."""
-    shape, strides = tuple(int(m) for m in shape), tuple(int(st) for st in strides)
-    expect = 1
-    for m, st in zip(reversed(shape[-3:]), reversed(strides[-3:])):
-        if m != 1 and st != expect:
-            raise ValueError("hourly: the hour, row and column axes must be contiguous (a crop, a step or a transpose is not)")
-        expect *= m
-    day = expect
-    lead = [(m, st) for m, st in zip(shape[:-3], strides[:-3]) if m != 1]
-    n = int(np.prod(shape[:-3], dtype=np.int64))
-    if not lead:
-        return n, day
-    stride = lead[-1][1]
-    if stride < day:
-        raise ValueError(f"hourly: the leading stride {stride} is below the size of a day {day}")
-    expect = stride
-    for m, st in reversed(lead):
-        if st != expect:
-            raise ValueError("hourly: several leading axes must be contiguous among themselves")
-        expect *= m
-    return n, stride
+    return whole_number(max_lag, 1, MAX_LAG, "max_lag")
 
 
 def n_sums(n_thresholds, max_lag):
@@ -86,11 +51,6 @@ def split_state(counts, sums, n_thresholds, max_lag):
                 trans=per[:, _TR:].reshape(T, NHOURS - 1, 2, 2).copy(), n_valid=int(c[-2]), n_bad=int(c[-1]),
                 moments=s[:2 * NHOURS].reshape(NHOURS, 2).copy(), lag=s[2 * NHOURS:2 * NHOURS + K].copy(),
                 wet_amount=s[2 * NHOURS + K:].reshape(T, NHOURS).copy())
-
-
-def _div(a, b):
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.where(np.asarray(b) != 0, np.asarray(a, dtype=np.float64) / np.asarray(b, dtype=np.float64), np.nan)
 
 
 @dataclass
@@ -173,11 +133,6 @@ class TemporalStats:
         return _div(self.wet_amount, self._wet_by_hour())
 
 
-def _tv(a, b):
-    with np.errstate(invalid="ignore"):
-        return 0.5 * np.abs(a - b).sum(axis=-1)
-
-
 def compare(a, b):
     """Two TemporalStats with the same thresholds (real days against generated days) -> dict, per threshold: the total-variation
     distance of the wet-hours, wet-spell and dry-spell distributions (tv_wet_hours, tv_wet_spell, tv_dry_spell, each (T,)); the
@@ -225,38 +180,19 @@ class TemporalStructure:
         """hourly (..., 24, ny, nx) float32: a CUDA tensor, whose leading axis may have any stride >= the size of one of its
         entries (a view of a wider buffer; tensor_layout has the rule, and refuses a crop, a step or a transpose at any rank), or
         a numpy array.  The plane shape is fixed by the first call.  Returns self."""
-        if isinstance(hourly, torch.Tensor):
-            if not hourly.is_cuda:                     # (a host view's strides would not survive the copy to the device)
-                raise ValueError("hourly: expected a CUDA tensor or a numpy array, got a torch tensor on the host")
-            host = None
-        else:
-            hourly = np.asarray(hourly)
-            if not (np.issubdtype(hourly.dtype, np.floating) or np.issubdtype(hourly.dtype, np.integer)):
-                raise ValueError("hourly: expected an array of numbers")
-            host = hourly
-        shape = _check_hourly_shape(hourly.shape)
-        if self.plane_shape is not None and shape[-2:] != self.plane_shape:
-            raise ValueError(f"hourly: the plane shape is {self.plane_shape} since the first call, got {shape[-2:]}")
-        if host is None and hourly.dtype != torch.float32:
-            raise ValueError("hourly: expected float32")
+        hourly, from_host, shape, n, stride = admit(hourly, self.plane_shape)
         plane = shape[-2] * shape[-1]
-        n, stride = (int(np.prod(shape[:-3], dtype=np.int64)), NHOURS * plane) if host is not None else tensor_layout(shape, hourly.stride())
         if self.counts is None:
-            self._start(hourly.device if host is None else "cuda")
-        if host is not None:
-            hourly = torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)).to(self.counts.device)
-        elif hourly.device != self.counts.device:
-            raise ValueError(f"hourly lies on {hourly.device}, the state on {self.counts.device}")
+            self._start("cuda" if from_host else hourly.device)
+        hourly = to_state_device(hourly, from_host, self.counts.device)
         self.plane_shape = shape[-2:]
         T = len(self.thr)
         with torch.cuda.device(self.counts.device):
-            nbytes = self.lib.rdgan_temporal_workspace_bytes(n, plane, T, self.max_lag)
-            if nbytes < 0:
-                raise _lib.RdganError(f"rdgan_temporal_workspace_bytes failed with code {nbytes}")
+            nbytes = workspace_bytes(self.lib, "rdgan_temporal_workspace_bytes", n, plane, T, self.max_lag)
             if self._ws is None or self._ws.numel() * 8 < nbytes:
                 self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.counts.device)
-            rc = self.lib.rdgan_temporal_accumulate(F._p(hourly), n, stride, plane, F._hp(self.thr), T, self.max_lag, F._p(self.counts),
-                                                    F._p(self.sums), F._p(self._ws), self._ws.numel() * 8, F._stream(self.counts))
+            rc = self.lib.rdgan_temporal_accumulate(_p(hourly), n, stride, plane, _hp(self.thr), T, self.max_lag, _p(self.counts),
+                                                    _p(self.sums), _p(self._ws), self._ws.numel() * 8, _stream(self.counts))
         _lib.check(rc, None, "rdgan_temporal_accumulate")
         return self
 
@@ -288,24 +224,7 @@ def temporal_structure_field(gen, daily, n_scenarios, thresholds, max_lag=6, sce
     are equal and the sums within the reordering bound when the batches are the same (`chunk` at most one unit's wet tiles, or one
     scenario chunk); otherwise the two differ as disaggregate's own outputs differ between values of `chunk`.  -> TemporalStats"""
     ts = TemporalStructure(thresholds, max_lag)
-    S, step = int(n_scenarios), int(scenario_chunk)
-    if S < 1:
-        raise ValueError(f"the number of scenarios must be at least 1, got {S}")
-    if step < 1:
-        raise ValueError("scenario_chunk must be at least 1")
-    _req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
-    daily, squeeze_day, D, ny, nx, plan, z_shape = _req
-    dd, info, _ = F._scan_request(daily, D, ny, nx, plan)
-    dev = dd.device
-    with torch.cuda.device(dev):
-        # (without a wet tile disaggregate draws nothing)
-        z_all = F._draw_latent(latent, seed, z_shape, dev) if info.n_active else None
-        shape = ((NHOURS, ny, nx) if squeeze_day else (D, NHOURS, ny, nx))
-        buf = torch.empty((min(step, S),) + shape, dtype=torch.float32, device=dev)
-        cond = dd[0] if squeeze_day else dd
-        for s0 in range(0, S, step):
-            n = min(step, S - s0)
-            F.disaggregate(gen, cond, n, overlap=overlap, latent_mode=latent_mode, latent=None if z_all is None else z_all[s0:s0 + n],
-                           chunk=chunk, norm_scale=norm_scale, out=buf[:n])
-            ts.add(buf[:n])
+    S, step = F._check_scenarios(n_scenarios, scenario_chunk)
+    req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
+    F._stream_scenarios(gen, req, req[0], S, step, ts.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
     return ts.result()

@@ -22,10 +22,11 @@ import torch
 from . import _lib
 from . import field as F
 from . import weights as W
+from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
+from ._hourly import MAX_MEMBERS, admit_array, member_layout, to_state_device
 from .engine import require_gpu
-from .field_products import _member_layout
 
-MAX_THRESHOLDS, MAX_SCALES, MAX_MEMBERS, MAX_BINS = 8, 8, 4096, 64          # RD_VF_MAXT, RD_VF_MAXW, RD_VF_MAXS, RD_VF_MAXBINS
+MAX_THRESHOLDS, MAX_SCALES, MAX_BINS = 8, 8, 64                             # RD_VF_MAXT, RD_VF_MAXW, RD_VF_MAXBINS (MAX_MEMBERS: RD_VF_MAXS)
 MAX_BOX_MEMBERS = 1 << 26                                                   # S * w_max^2 stays below this
 DEFAULT_SCALES = (1, 3, 5, 9, 17)
 
@@ -71,22 +72,12 @@ def check_scales(scales, n_members=1):
 
 
 def _check_bins(n_bins, n_members):
-    if isinstance(n_bins, bool) or int(n_bins) != n_bins or not 2 <= int(n_bins) <= min(int(n_members) + 1, MAX_BINS):
-        raise ValueError(f"n_bins must lie in 2 .. min(n_members + 1, {MAX_BINS}) = {min(int(n_members) + 1, MAX_BINS)}, got {n_bins!r}")
-    return int(n_bins)
+    """(a whole-valued float such as 11.0 counts as its integer)"""
+    return whole_number(n_bins, 2, min(int(n_members) + 1, MAX_BINS), f"n_bins (at most n_members + 1 and {MAX_BINS})", whole_floats=True)
 
 
 def _check_seed(seed):
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
-        raise ValueError(f"the rank seed must be an integer in 0 .. 2^64 - 1, got {seed!r}")
-    return int(seed)
-
-
-def _check_obs_shape(shape, what="obs"):
-    shape = tuple(int(n) for n in shape)
-    if len(shape) < 3 or shape[-3] != W.NHOURS or min(shape) < 1:
-        raise ValueError(f"{what}: expected shape (..., 24, ny, nx) with no empty axis, got {shape}")
-    return shape
+    return whole_number(seed, 0, (1 << 64) - 1, "the rank seed")
 
 
 @dataclass
@@ -144,21 +135,10 @@ class EnsembleVerifier:
 
     def __init__(self, obs, thresholds):
         self.thr = check_event_thresholds(thresholds)
-        if isinstance(obs, torch.Tensor):
-            if not (obs.is_cuda and obs.dtype == torch.float32):
-                raise ValueError("obs: expected a numpy array or a float32 CUDA tensor")
-            self.shape = _check_obs_shape(obs.shape)
-        else:
-            obs = np.asarray(obs)
-            if not (np.issubdtype(obs.dtype, np.floating) or np.issubdtype(obs.dtype, np.integer)):
-                raise ValueError("obs: expected an array of numbers")
-            self.shape = _check_obs_shape(obs.shape)
+        obs, from_host, self.shape = admit_array(obs, "obs")
         require_gpu()
         self.lib = _lib.load()
-        if isinstance(obs, torch.Tensor):
-            self.obs = obs.detach().contiguous()
-        else:
-            self.obs = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).cuda()
+        self.obs = to_state_device(obs, True, "cuda", "obs") if from_host else obs.detach().contiguous()
         dev = self.obs.device
         self.P = int(np.prod(self.shape, dtype=np.int64))
         self.ny, self.nx = self.shape[-2], self.shape[-1]
@@ -171,27 +151,19 @@ class EnsembleVerifier:
     def add(self, members):
         """members (s, *obs.shape) float32: a CUDA tensor, whose member axis may have any stride >= prod(obs.shape) (a view of a
         wider buffer, as member_stats_device accepts it), or a numpy array.  Returns self."""
-        if isinstance(members, torch.Tensor):
-            if not members.is_cuda:                    # (a host view's strides would not survive the copy to the device)
-                raise ValueError("members: expected a CUDA tensor or a numpy array, got a torch tensor on the host")
-            host = None
-        else:
-            host = members = torch.from_numpy(np.ascontiguousarray(members, dtype=np.float32))       # dense: member stride P
-        s, P, stride, shape = _member_layout(members)
+        members, from_host, _ = admit_array(members, "members")
+        if from_host:
+            members = np.ascontiguousarray(members, dtype=np.float32)                                 # dense: member stride P
+        s, P, stride, shape = member_layout(torch.from_numpy(members) if from_host else members)
         if shape != self.shape:
             raise ValueError(f"members: expected shape (s,) + {self.shape}, got {tuple(members.shape)}")
         if self.n_members + s > MAX_MEMBERS:
             raise ValueError(f"a verification holds at most {MAX_MEMBERS} members: {self.n_members} held, {s} more offered")
-        if members.dtype != torch.float32:
-            raise ValueError("members: expected float32")
-        if host is not None:
-            members, stride = host.to(self.obs.device), P
-        elif members.device != self.obs.device:
-            raise ValueError(f"members lie on {members.device}, the observation on {self.obs.device}")
+        members = to_state_device(members, from_host, self.obs.device, "members")
         with torch.cuda.device(self.obs.device):
-            rc = self.lib.rdgan_verify_accumulate(F._p(members), s, stride, P, F._p(self.obs), F._hp(self.thr), len(self.thr),
-                                                  F._p(self.exceed), F._p(self.below), F._p(self.equal), F._p(self.bad),
-                                                  F._stream(self.obs))
+            rc = self.lib.rdgan_verify_accumulate(_p(members), s, stride, P, _p(self.obs), _hp(self.thr), len(self.thr),
+                                                  _p(self.exceed), _p(self.below), _p(self.equal), _p(self.bad),
+                                                  _stream(self.obs))
         _lib.check(rc, None, "rdgan_verify_accumulate")
         self.n_members += s
         return self
@@ -214,17 +186,15 @@ class EnsembleVerifier:
             rel = torch.empty((T, W.NHOURS, n_bins, 3), dtype=torch.int64, device=dev)
             brier = torch.empty((T, W.NHOURS, 4), dtype=torch.int64, device=dev)
             fss = torch.empty((T, Wn, W.NHOURS, 2), dtype=torch.float64, device=dev)
-            st = F._stream(self.obs)
-            rc = self.lib.rdgan_verify_reduce(F._p(self.obs), F._p(self.exceed), F._p(self.below), F._p(self.equal), F._p(self.bad),
-                                              self.P, self.ny * self.nx, S, F._hp(self.thr), T, n_bins, ctypes.c_uint64(seed),
-                                              F._p(rank), F._p(rel), F._p(brier), st)
+            st = _stream(self.obs)
+            rc = self.lib.rdgan_verify_reduce(_p(self.obs), _p(self.exceed), _p(self.below), _p(self.equal), _p(self.bad),
+                                              self.P, self.ny * self.nx, S, _hp(self.thr), T, n_bins, ctypes.c_uint64(seed),
+                                              _p(rank), _p(rel), _p(brier), st)
             _lib.check(rc, None, "rdgan_verify_reduce")
-            nbytes = self.lib.rdgan_verify_fss_workspace_bytes(self.ny, self.nx, T, Wn)
-            if nbytes < 0:
-                raise _lib.RdganError(f"rdgan_verify_fss_workspace_bytes failed with code {nbytes}")
+            nbytes = workspace_bytes(self.lib, "rdgan_verify_fss_workspace_bytes", self.ny, self.nx, T, Wn)
             ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-            rc = self.lib.rdgan_verify_fss(F._p(self.obs), F._p(self.exceed), F._p(self.bad), n_days, self.ny, self.nx, S,
-                                           F._hp(self.thr), T, F._hp(wd), Wn, F._p(fss), F._p(ws), nbytes, st)
+            rc = self.lib.rdgan_verify_fss(_p(self.obs), _p(self.exceed), _p(self.bad), n_days, self.ny, self.nx, S,
+                                           _hp(self.thr), T, _hp(wd), Wn, _p(fss), _p(ws), nbytes, st)
             _lib.check(rc, None, "rdgan_verify_fss")
             rank, rel, brier, fss = rank.cpu().numpy(), rel.cpu().numpy(), brier.cpu().numpy(), fss.cpu().numpy()
         return Verification(tuple(float(t) for t in self.thr), tuple(int(w) for w in wd), S, int(brier[0, :, 0].sum()), rank, rel,
@@ -235,12 +205,7 @@ def verify_hourly(ens, obs, thresholds, **result_kw):
     """One call for an ensemble that is held: ens (S, *obs.shape), obs (..., 24, ny, nx); result_kw: scales, n_bins, seed of
     EnsembleVerifier.result.  -> Verification"""
     thr = check_event_thresholds(thresholds)
-    if not isinstance(obs, torch.Tensor):
-        obs = np.asarray(obs)
-    if not isinstance(ens, torch.Tensor):
-        ens = np.asarray(ens)
-    elif not ens.is_cuda:
-        raise ValueError("ens: expected a CUDA tensor or a numpy array, got a torch tensor on the host")
+    obs, ens = admit_array(obs, "obs")[0], admit_array(ens, "ens")[0]
     if len(ens.shape) < 4:
         raise ValueError("ens: expected an array or tensor of shape (S, ..., 24, ny, nx)")
     S = int(ens.shape[0])
@@ -267,20 +232,11 @@ def verify_field(gen, observed, n_scenarios, thresholds, scales=DEFAULT_SCALES, 
     verify_hourly(disaggregate(...all scenarios...)[0], observed, ...) exactly, for any scenario_chunk and chunk.
     -> Verification"""
     thr = check_event_thresholds(thresholds)
-    S, step = int(n_scenarios), int(scenario_chunk)
-    if not 1 <= S <= MAX_MEMBERS:
-        raise ValueError(f"the number of scenarios must lie in 1 .. {MAX_MEMBERS}, got {S}")
-    if step < 1:
-        raise ValueError("scenario_chunk must be at least 1")
+    S, step = F._check_scenarios(n_scenarios, scenario_chunk, MAX_MEMBERS)
     wd, n_bins, rank_seed = check_scales(scales, S), _check_bins(n_bins, S), _check_seed(rank_seed)
     dataset = hasattr(observed, "daily_plane")
     obs = observed.data if dataset else observed
-    if isinstance(obs, torch.Tensor):
-        if not (obs.is_cuda and obs.dtype == torch.float32):
-            raise ValueError("observed: expected a numpy array, a float32 CUDA tensor or a DeviceDataset")
-    else:
-        obs = np.asarray(obs)
-    shape = _check_obs_shape(obs.shape, "observed")
+    obs, _, shape = admit_array(obs, "observed")
     if len(shape) not in (3, 4):
         raise ValueError(f"observed must have shape (24, ny, nx) or (n_days, 24, ny, nx), got {shape}")
     day_shape = shape[:-3] + shape[-2:]
@@ -289,21 +245,10 @@ def verify_field(gen, observed, n_scenarios, thresholds, scales=DEFAULT_SCALES, 
     if daily is not None and tuple(daily.shape) != day_shape:
         raise ValueError(f"daily: expected shape {day_shape}, got {tuple(daily.shape)}")
     # the checks of disaggregate on a stand-in of the daily map's shape: nothing has touched the device so far
-    _, squeeze_day, D, ny, nx, plan, z_shape = F._check_request(gen, np.broadcast_to(np.float32(0), day_shape), S, overlap, latent_mode,
-                                                                latent, chunk, norm_scale)
+    req = F._check_request(gen, np.broadcast_to(np.float32(0), day_shape), S, overlap, latent_mode, latent, chunk, norm_scale)
     ver = EnsembleVerifier(obs, thr)
-    dev = ver.obs.device
-    with torch.cuda.device(dev):
+    with torch.cuda.device(ver.obs.device):
         if daily is None:
             daily = observed.daily_plane() if dataset else ver.obs.sum(dim=-3)
-        dd, info, _ = F._scan_request(daily, D, ny, nx, plan)
-        # (without a wet tile disaggregate draws nothing)
-        z_all = F._draw_latent(latent, seed, z_shape, dev) if info.n_active else None
-        buf = torch.empty((min(step, S),) + shape, dtype=torch.float32, device=dev)
-        cond = dd[0] if squeeze_day else dd
-        for s0 in range(0, S, step):
-            n = min(step, S - s0)
-            F.disaggregate(gen, cond, n, overlap=overlap, latent_mode=latent_mode, latent=None if z_all is None else z_all[s0:s0 + n],
-                           chunk=chunk, norm_scale=norm_scale, out=buf[:n])
-            ver.add(buf[:n])
+        F._stream_scenarios(gen, req, daily, S, step, ver.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
     return ver.result(scales=wd, n_bins=n_bins, seed=rank_seed)

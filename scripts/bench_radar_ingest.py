@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from pr_disagg_radar_gan_amd import data_pipeline as dp
+from pr_disagg_radar_gan_amd._dev import ptr
 
 HBM_ACHIEVABLE_GBS = 6290.0            # float4 copy on an MI355X (8 000 spec)
 FPH = 12
@@ -107,8 +108,8 @@ def main():
 
     def kernel(shift):
         view = buf[shift:shift + n_codes]
-        return lambda: dp._lib.check(lib.rdgan_data_radar_hourly(dp._p(view), dp._p(lut), n_days, FPH, ny, nx, dp._p(hourly), dp._p(daily),
-                                                                 dp._p(missing), st), None, "rdgan_data_radar_hourly")
+        return lambda: dp._lib.check(lib.rdgan_data_radar_hourly(ptr(view), ptr(lut), n_days, FPH, ny, nx, ptr(hourly), ptr(daily),
+                                                                 ptr(missing), st), None, "rdgan_data_radar_hourly")
 
     copy = lambda: dst.copy_(src)
     res["kernel"] = {}
@@ -135,9 +136,9 @@ def main():
             nbi, nbj = len(range(0, ny - nd, stride)), len(range(0, nx - nd, stride))
             v_new = torch.empty((n_days, nbi, nbj), dtype=torch.int32, device="cuda")
             v_old = torch.empty_like(v_new)
-            new = lambda: lib.rdgan_data_valid_tiles_daily(dp._p(daily), n_days, ny, nx, nd, stride, 5.0, 20, dp._p(v_new), st)
+            new = lambda: lib.rdgan_data_valid_tiles_daily(ptr(daily), n_days, ny, nx, nd, stride, 5.0, 20, ptr(v_new), st)
             days_old = min(n_days, 0xFFFFFF // (nbi * nbj))            # k_valid_tiles: one workgroup per box, < 2^24 boxes per call
-            old = lambda: dp._lib.check(lib.rdgan_data_valid_tiles(dp._p(hourly), days_old, ny, nx, nd, stride, 5.0, 20, dp._p(v_old), st))
+            old = lambda: dp._lib.check(lib.rdgan_data_valid_tiles(ptr(hourly), days_old, ny, nx, nd, stride, 5.0, 20, ptr(v_old), st))
             ms_new, ms_old = alternate([new, old], max(2, a.reps // 2), 1)
             res["scan"][f"nd{nd}_stride{stride}"] = dict(
                 boxes=n_days * nbi * nbj, valid=int(v_new.sum().item()), daily_ms=ms_new, daily_ns_per_box=ms_new * 1e6 / (n_days * nbi * nbj),

@@ -126,6 +126,7 @@ def test_grouping_strides_passes_and_thresholds():
             assert np.array_equal(single[:CL.N_COUNTS], ref[t * CL.N_COUNTS:(t + 1) * CL.N_COUNTS]) and np.array_equal(single[-2:], ref[-2:])
     # numpy in: the same
     assert torch.equal(CL.CellStructure(THR3, 8).add(x).state(), whole.state())
+    assert torch.equal(CL.CellStructure(THR3, 8).add(xd[:1]).add(x[1:]).state(), whole.state())       # numpy onto a state that exists
     with pytest.raises(ValueError):
         whole.add(xd[..., ::2])
     assert torch.equal(CL.label_cells(x[0], 1.0, 4).cpu(), torch.from_numpy(cn.labels_np(x[0], 1.0, 4)))

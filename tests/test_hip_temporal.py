@@ -151,6 +151,7 @@ def test_grouping(exact):
     want = tn.temporal_np(x, thr, K)
     agree(whole.result(), want, T, K, exact=exact)
     n = tn.terms(want, T, K)
+    assert torch.equal(TS.TemporalStructure(thr, K).add(xd[:9]).add(x[9:]).state()[0], whole.state()[0])       # numpy onto a state that exists
     for g in (1, 7, 15):
         runs = []
         for _ in range(2):
