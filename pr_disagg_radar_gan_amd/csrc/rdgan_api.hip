@@ -1280,8 +1280,6 @@ static bool upconv2_slab_on(const rdgan_handle* h, int l) {
   return h->upconv2_slab && h->a16 && h->collapse && l == 2 && h->nd == 16 && !gen_block_fast(h, 2, fast_fwd_on(h));
 }
 
-// `ws`: stream of the weight-only kernels (the handle's side stream, forked by the caller, or `st` itself): the weight forms of
-// block l are complete behind event ev_g[l], which `st` waits for in front of the block's GEMM
 // plan of the forward / second-sweep GEMM of critic layer l >= 2 over n samples: the border-class boxes where they pay -- with
 // few rows the boxes' short tap lists lose the K splits that fill the chip (layer 3 at 256 samples: 60 -> 68 us), so a small
 // launch keeps the one-phase plan unless the boxes drop more than half of the work (layer 4: 70 %)
@@ -1331,20 +1329,66 @@ static bool dense_skinny_on(const rdgan_handle* h) {
 static bool g9_fused_on(const rdgan_handle* h) { return h->g9_fused && h->tapgather && upconv_slab_on(h, 3); }
 // the same inside the TILED block-3 kernel (ndomain 32, 64: k_upconv_slab_t16<G9>, k_tapsum_softmax12t)
 static bool g9_fused_t_on(const rdgan_handle* h) { return h->g9_fused && h->tapgather && upconv_slab_t_on(h, 3); }
+// the Dense layer on the bf16 matrix pipe, a third of the columns per launch (the skinny kernel goes first where it is on): at
+// ndomain 64 its 825 MB fp32 kernel is the launch (HBM-bound); the bf16 image halves it
+static bool dense16_on(const rdgan_handle* h) { return h->a16 && h->dense16 && h->dense16_ok && h->bW0 && h->xcat16; }
 
-// keep_h3: block 3's output and 1/l2 are needed afterwards (generator step: its backward; rdgan_gen_forward: the test hook) --
-// a critic step passes false, and with the fused last conv the 1.6 GB tensor (2048 samples) is then never written
-static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, const float* cond, float* out, int B,
-                            hipStream_t st, hipStream_t ws, bool keep_h3 = true) {
-  const int nd = h->nd;
+// ---- routes of the generator step's backward
+// weight gradient of a generator block (collapsed form, or one tap group of the shared-centre form) through the streaming kernels
+// on the (h, w) border boxes `box` of plan `one` (12 % of a block's row-tap products are products with a zero row) -- where they
+// drop at least a fifth of the work (block 2: 23 %, 0.237 -> 0.219 ms per launch; block 3's 12 % do not pay for the extra partial
+// slabs and short row tiles of its 256 x 64 tiling: 0.43 -> 0.51 ms, measured)
+static bool gen_wgrad_boxes_on(const rdgan_handle* h, int one, int box) {
+  return h->wgrad_boxes && h->border_boxes && h->wave_spec && wgrad_box_ok(h->plans[box]) &&
+         (h->border_boxes >= 2 || plan_flops(h->plans[box], 1) < 0.8 * plan_flops(h->plans[one], 1));
+}
+// weight gradient (and bias gradient) of collapsed block 3 / block 2 by k_upconv_wgrad_slab16 / k_upconv2_wgrad_slab16: bf16
+// storage mode, ndomain 16
+static bool upwgrad_slab_on(const rdgan_handle* h, int l) { return h->a16 && (l == 3 || l == 2) && h->upwgrad_slab && h->nd == 16; }
+// Backward of the 64 -> 1 conv in its direct form: straight from the 1-channel dlogits with the four neighbouring hour planes in
+// LDS -- no im2col matrix, and the input gradient goes through block 3's PixelNorm+LeakyReLU backward in the same kernel; needs
+// the planes to fit in LDS and the weight gradient's partial rows in the workspace
+static size_t g9_pairs_lds(const rdgan_handle* h) { return 4 * (size_t)(h->nd + 2) * (h->nd + 2) * sizeof(float); }
+static bool g9_direct_on(const rdgan_handle* h, int B) {
+  return h->g9_direct && g9_pairs_lds(h) <= 96 * 1024 && g9w_partial_floats(B * (RDGAN_NHOURS / 2)) <= h->wpartial_cap;
+}
+// ... with exact fp32 products on the matrix pipe and the row's backward in registers (k_g9_bwd_mfma16, rdgan_g9bwd16.hip.h): bf16
+// storage mode, block 3 in the collapsed form (the shared-centre form also wants the plane-pair sums, which k_g9_bwd_pairs leaves)
+static bool g9_bwd_mfma_on(const rdgan_handle* h) {
+  return h->a16 && !gen_block_fast(h, 3, fast_bwd_on(h)) && h->g9_bwd_mfma && (h->nd * h->nd) % 32 == 0;
+}
+
+// What the stages of one pass over the generator share, built once per call: bf16 storage mode, collapsed form, the last conv's
+// backward in its direct form (g9_direct_on); per block l its output hs[l] and PixelNorm's 1/l2 rs[l]; backward: the gradient wrt
+// its conv output dys[l] and wrt its input gups[l] (direct form: on the upsampled grid; collapsed: on the source grid)
+struct GenPass { bool a16; int col; bool g9_direct; float *hs[4], *rs[4], *dys[4], *gups[4]; };
+static GenPass gen_pass(const rdgan_handle* h, int B) {
+  return {h->a16 != 0, h->collapse, g9_direct_on(h, B), {h->h0, h->h1, h->h2, h->h3}, {nullptr, h->r1, h->r2, h->r3},
+          {nullptr, h->dy1, h->dy2, h->gh3}, {nullptr, h->gup1, h->gup2, h->gup3}};
+}
+
+// hour differences E of a block input (shared-centre form): forward, and the backward of a block whose forward ran another form
+static void launch_diff_d(const GenPass& s, const float* x, float* E, int B, int D, long P, hipStream_t st) {
+  const dim3 dg(ew_blocks((long)B * (D + 1) * P / 4));
+  if (s.a16) hipLaunchKernelGGL(k_diff_d<rd_bf16_t>, dg, dim3(256), 0, st, (const rd_bf16_t*)x, (rd_bf16_t*)E, B, D, P);
+  else hipLaunchKernelGGL(k_diff_d<float>, dg, dim3(256), 0, st, x, E, B, D, P);
+}
+// epilogue of the last conv where the GEMM / streaming kernel has left gq = 3 (9) in-tile tap sums per grid point in P9: the
+// remaining sums, bias, Softmax(axis=1), check_numerics
+static void launch_tapsum_softmax(rdgan_handle* h, int gq, float* out, const float* gp, int B, hipStream_t st) {
+  const dim3 grid((unsigned)(((long)B * h->nd * h->nd + 63) / 64));
+  if (gq == 3) hipLaunchKernelGGL((k_tapsum_softmax<RDGAN_NHOURS, 3>), grid, dim3(256), 0, st, h->P9, gp + h->goff[9], out, B, h->nd, h->nd, h->d_flag);
+  else hipLaunchKernelGGL((k_tapsum_softmax<RDGAN_NHOURS, 9>), grid, dim3(256), 0, st, h->P9, gp + h->goff[9], out, B, h->nd, h->nd, h->d_flag);
+}
+
+// Weight forms (read only the weights), on `ws`: skipped when the caller vouches that the forms in the workspace were built from
+// these very weights (same slab, same content version, same form options).  *built: the form kernels were issued.
+static int gen_build_forms(rdgan_handle* h, const float* gp, hipStream_t st, hipStream_t ws, bool* built) {
   const bool a16 = h->a16 != 0;
-  RD_TRY(a16_check(h));
-  // ---- weight forms (read only the weights): skipped when the caller vouches that the forms in the workspace were built from
-  // these very weights (same slab, same content version, same form options)
   const int gcfg = (h->collapse ? 1 : 0) | (fast_fwd_on(h) ? 2 : 0) | (a16 ? 4 : 0) | (h->upconv_slab ? 8 : 0) | (h->upconv2_slab ? 16 : 0) |
                    (h->g9_fused && h->tapgather ? 32 : 0) | (h->dense16 ? 64 : 0) | (h->upconv_slab_t ? 128 : 0) | (h->dense_skinny ? 256 : 0);
-  const bool forms_cached = h->gver_in != 0 && gp == h->gcache_ptr && h->gver_in == h->gcache_ver && gcfg == h->gcache_cfg;
-  if (!forms_cached) {
+  *built = !(h->gver_in != 0 && gp == h->gcache_ptr && h->gver_in == h->gcache_ver && gcfg == h->gcache_cfg);
+  if (!*built) return 0;
   h->form_builds[0]++;
   h->gcache_ptr = nullptr; h->gcache_ver = 0; h->gcache_cfg = -1;     // (valid again only once every form kernel has been issued)
   // W9T [64][32] = W9[tap][ci]^T (zero padded taps 27..31)
@@ -1353,9 +1397,7 @@ static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, co
     const long nimg = (long)(h->n_nodes / 32) * dense_skinny_ks(h) * 16;      // (threads: four lanes' fragments each)
     hipLaunchKernelGGL(k_dense_wimg, dim3((unsigned)((nimg + 255) / 256)), dim3(256), 0, ws, gp + h->goff[0], (unsigned short*)h->bW0,
                        h->n_in, h->n_nodes, dense_skinny_ks(h));
-  } else
-  if (a16 && h->dense16 && h->dense16_ok && h->bW0)
-    hipLaunchKernelGGL(k_dense_w16, dim3((h->n_nodes + 31) / 32, (h->KP0 + 31) / 32), dim3(256), 0, ws, gp + h->goff[0],
+  } else if (dense16_on(h)) hipLaunchKernelGGL(k_dense_w16, dim3((h->n_nodes + 31) / 32, (h->KP0 + 31) / 32), dim3(256), 0, ws, gp + h->goff[0],
                        (unsigned short*)h->bW0, h->n_in, h->n_nodes, h->KP0);
   if (g9_fused_on(h) || g9_fused_t_on(h)) hipLaunchKernelGGL(k_g9_wimg, dim3(1), dim3(256), 0, ws, gp + h->goff[8], (unsigned short*)h->bW9I);
   for (int l = 1; l <= 3; ++l) {
@@ -1372,27 +1414,29 @@ static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, co
       if (upconv_slab_on(h, l)) launch_upconv_wimg(h->GWC[l], h->bW3I, ws);
       else if (upconv_slab_t_on(h, l)) launch_upconv_wimg_t(h->GWC[l], h->bW3T, ws);
       else if (upconv2_slab_on(h, l)) launch_upconv2_wimg(h->GWC[l], h->bW2I, ws);
-      else if (a16) {
-        RD_TRY(launch_weights_to_bf16_t(h, h->GWC[l], h->bG1F[l], 64, h->gch[l - 1], h->gch[l], ws, h->conv_f16 ? h->fG1F[l] : nullptr));
-      }
+      else if (a16) RD_TRY(launch_weights_to_bf16_t(h, h->GWC[l], h->bG1F[l], 64, h->gch[l - 1], h->gch[l], ws, h->conv_f16 ? h->fG1F[l] : nullptr));
     }
     if (ws != st) RD_CHECK(h, hipEventRecord(h->ev_g[l], ws));
   }
   RD_CHECK(h, hipGetLastError());
   h->gcache_ptr = gp; h->gcache_ver = h->gver_in; h->gcache_cfg = gcfg;
-  }
-  // ---- activations
+  return 0;
+}
+
+// concat, then Dense + LeakyReLU (T:326-327); the Reshape (T:328) is a view.  wait_forms: the weight forms were built on another
+// stream by this call (the Dense images are built in front of block 1's forms: behind ev_g[1])
+static int gen_dense_fwd(rdgan_handle* h, const GenPass& s, const float* gp, const float* z, const float* cond, int B, bool wait_forms, hipStream_t st) {
+  const int nd = h->nd;
   {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    const bool d16 = a16 && h->dense16 && h->dense16_ok && h->xcat16 && !dense_skinny_on(h);
+    const bool d16 = dense16_on(h) && !dense_skinny_on(h);
     hipLaunchKernelGGL(k_concat, dim3(ew_blocks((long)B * h->n_in)), dim3(256), 0, st, z, cond, h->xcat, B,
                        RDGAN_LATENT_DIM, nd * nd * h->nc, h->d_flag,       // (first kernel of every entry: clears the non-finite flag)
                        d16 ? (unsigned short*)h->xcat16 : (unsigned short*)nullptr, h->KP0);
   }
-  // Dense + LeakyReLU (T:326-327); the Reshape (T:328) is a view
   if (dense_skinny_on(h)) {
     // small batch: the kernel is the launch (415 MB of bf16 weights at ndomain 64) -- weights and input rows streamed in fragment order
-    if (ws != st && !forms_cached) RD_CHECK(h, hipStreamWaitEvent(st, h->ev_g[1], 0));      // (the image is built in front of block 1's forms)
+    if (wait_forms) RD_CHECK(h, hipStreamWaitEvent(st, h->ev_g[1], 0));
     const int RB = (B + 31) / 32, KS = dense_skinny_ks(h);
     ProfScope ps(h, -1, st);
     LaunchScope ls(h, PL_GDENSE16, RD_KIND_CONV, B, 3.0 * plan_flops(h->plans[PL_GDENSE16], B), st);
@@ -1408,10 +1452,8 @@ static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, co
     else if (RB == 3) hipLaunchKernelGGL(k_dense16_skinny<3>, dg, dim3(128), 0, st, xi, wi, bs, (rd_bf16_t*)h->h0, B, KS, h->n_nodes);
     else hipLaunchKernelGGL(k_dense16_skinny<4>, dg, dim3(128), 0, st, xi, wi, bs, (rd_bf16_t*)h->h0, B, KS, h->n_nodes);
     RD_CHECK(h, hipGetLastError());
-  } else
-  if (a16 && h->dense16 && h->dense16_ok && h->xcat16) {
-    // the Dense layer on the bf16 matrix pipe: at ndomain 64 its 825 MB fp32 kernel is the launch (HBM-bound); the bf16 image halves it
-    if (ws != st && !forms_cached) RD_CHECK(h, hipStreamWaitEvent(st, h->ev_g[1], 0));      // (the image is built in front of block 1's forms)
+  } else if (dense16_on(h)) {
+    if (wait_forms) RD_CHECK(h, hipStreamWaitEvent(st, h->ev_g[1], 0));
     const int n3 = h->n_nodes / 3;
     for (int j = 0; j < 3; ++j) {
       RdEpi ed = epi_make(RD_EPI_BIAS_LRELU, gp + h->goff[1] + (long)j * n3);
@@ -1424,122 +1466,115 @@ static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, co
         h->flops_acc += plan_flops(h->plans[PL_GDENSE16], B);
         RD_TRY((launch_conv_ws_cfg<128, 64, 2, 2, true>(h, h->plans[PL_GDENSE16], h->d_plans + PL_GDENSE16, B, (const float*)h->xcat16,
                                                         (const float*)wj, 0, dj, ed, st)));
-      } else
-      RD_TRY(launch_conv16(h, h->plans[PL_GDENSE16], h->d_plans + PL_GDENSE16, B, h->xcat16, wj, dj, ed, st, -1));
+      } else RD_TRY(launch_conv16(h, h->plans[PL_GDENSE16], h->d_plans + PL_GDENSE16, B, h->xcat16, wj, dj, ed, st, -1));
     }
-  } else
-  if (a16) RD_TRY(launch_conv_a16(h, h->plans[PL_GDENSE], h->d_plans + PL_GDENSE, B, h->xcat, gp + h->goff[0], h->n_nodes, h->h0,
-                                  epi_make(RD_EPI_BIAS_LRELU, gp + h->goff[1]), st, -1, false, true));
-  else
-  RD_TRY(launch_conv(h, h->plans[PL_GDENSE], h->d_plans + PL_GDENSE, B, h->xcat, gp + h->goff[0], h->n_nodes, h->h0,
-                     epi_make(RD_EPI_BIAS_LRELU, gp + h->goff[1]), st, -1));
-  float* hs[4] = {h->h0, h->h1, h->h2, h->h3};
-  float* rs[4] = {nullptr, h->r1, h->r2, h->r3};
-  for (int l = 1; l <= 3; ++l) {
-    // UpSampling3D + Conv3D + bias (T:330-331), then PixelNorm + LeakyReLU (T:332-333)
-    const float* Wl = gp + h->goff[2 * l];
-    int pl = PL_G1F + l - 1;
-    if (ws != st && !forms_cached) RD_CHECK(h, hipStreamWaitEvent(st, h->ev_g[l], 0));       // this block's weight forms
-    if (gen_block_fast(h, l, fast_fwd_on(h))) {
-      // shared-centre form along the hour axis: T = S x[s] once per output plane pair, then the difference part
-      const int* sd = h->gdim[l - 1];
-      const long P = (long)sd[1] * sd[2] * h->gch[l - 1];
-      {
-        ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-        const dim3 dg(ew_blocks((long)B * (sd[0] + 1) * P / 4));
-        if (a16) hipLaunchKernelGGL(k_diff_d<rd_bf16_t>, dg, dim3(256), 0, st, (const rd_bf16_t*)hs[l - 1], (rd_bf16_t*)h->fE[l], B, sd[0], P);
-        else hipLaunchKernelGGL(k_diff_d<float>, dg, dim3(256), 0, st, (const float*)hs[l - 1], h->fE[l], B, sd[0], P);
-      }
-      const int pls = PL_F1WS + l - 1, ple = PL_F1FE + l - 1;
-      RdEpi et = epi_make(RD_EPI_PLAIN);
-      et.out16 = a16;
-      if (a16) RD_TRY(launch_conv16(h, h->plans[pls], h->d_plans + pls, B, hs[l - 1], h->bU[l], h->fgS, et, st, RDGAN_TAG_GCONV_FWD));
-      else
-      RD_TRY(launch_conv(h, h->plans[pls], h->d_plans + pls, B, hs[l - 1], h->fU[l], h->gch[l], h->fgS, et, st,
-                         RDGAN_TAG_GCONV_FWD));
-      const bool fuse = a16 ? conv16_rows_owned(h->plans[ple]) : conv_rows_owned(h->plans[ple], B);
-      RdEpi ep = epi_make(fuse ? RD_EPI_BIAS_PN_LRELU : RD_EPI_BIAS, gp + h->goff[2 * l + 1]);
-      ep.rinv = rs[l];
-      ep.addt = h->fgS; ep.addt_plane = 4 * sd[1] * sd[2] * h->gch[l];
-      ep.nametag = l == 3;
-      ep.out16 = a16;
-      if (a16) RD_TRY(launch_conv16(h, h->plans[ple], h->d_plans + ple, B, h->fE[l], h->bU[l], hs[l], ep, st,
-                                    l == 3 ? RDGAN_TAG_GCONV3_FWD : RDGAN_TAG_GCONV_FWD));
-      else
-      RD_TRY(launch_conv(h, h->plans[ple], h->d_plans + ple, B, h->fE[l], h->fU[l], h->gch[l], hs[l], ep, st,
-                         l == 3 ? RDGAN_TAG_GCONV3_FWD : RDGAN_TAG_GCONV_FWD));
-      if (!fuse) {
-        ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-        RD_TRY(launch_pn_fwd(h, hs[l], hs[l], rs[l], (long)B * h->gpix[l], h->gch[l], st, a16));
-      }
-      continue;
-    }
-    if (h->collapse) {
-      Wl = h->GWC[l];
-      pl = PL_G1FC + l - 1;
-      if (!upconv_slab_on(h, l) && !upconv2_slab_on(h, l) && !upconv_slab_t_on(h, l)) pl = gen_box_plan(h, pl, PL_G1FCX + l - 1, B);
-    }
-    const bool fuse = a16 ? conv16_rows_owned(h->plans[pl]) : conv_rows_owned(h->plans[pl], B);       // PixelNorm+LeakyReLU in the GEMM epilogue
-    RdEpi ep = epi_make(fuse ? RD_EPI_BIAS_PN_LRELU : RD_EPI_BIAS, gp + h->goff[2 * l + 1]);
-    ep.rinv = rs[l];
-    ep.out16 = a16;
-    ep.nametag = a16 && l == 3;
-    if (upconv_slab_on(h, l)) {     // block 3, bf16 storage: source slab resident in LDS, weights streamed in fragment order
-      // (with the fused last conv the launch also carries that layer's 2 * rows * 64 * 27 FLOPs, and its tap products (Q12 in P9)
-      // leave the kernel from the rows while they are in registers)
-      const bool g9 = g9_fused_on(h);
-      const double fl3 = plan_flops(h->plans[pl], B) + (g9 ? 2.0 * B * h->gpix[3] * 64 * 27 : 0.0);
-      RD_TRY(launch_upconv_slab<1>(h, {pl, fl3, RDGAN_TAG_GCONV3_FWD}, hs[l - 1], h->bW3I, gp + h->goff[2 * l + 1], hs[l], rs[l], B, nullptr,
-                                   g9 ? h->bW9I : nullptr, g9 ? h->P9 : nullptr, keep_h3, st));
-      continue;
-    }
-    if (upconv_slab_t_on(h, l)) {   // block 3, bf16 storage, planes larger than 8 x 8: (h, w) tiles with their halo resident, K in two halves
-      const bool g9t = g9_fused_t_on(h);
-      const double fl3 = plan_flops(h->plans[pl], B) + (g9t ? 2.0 * B * h->gpix[3] * 64 * 27 : 0.0);
-      RD_TRY(launch_upconv_slab_t(h, {pl, fl3, RDGAN_TAG_GCONV3_FWD}, hs[l - 1], h->bW3T, gp + h->goff[2 * l + 1], hs[l], rs[l], B,
-                                  h->gdim[2][1], h->gdim[2][2], nullptr, g9t ? h->bW9I : nullptr, g9t ? h->P9 : nullptr, keep_h3, st));
-      continue;
-    }
-    if (upconv2_slab_on(h, l)) {    // block 2, bf16 storage: a sample resident in LDS, the four waves split the 128 channels
-      RD_TRY(launch_upconv2_slab(h, {pl, plan_flops(h->plans[pl], B), RDGAN_TAG_GCONV_FWD}, hs[l - 1], h->bW2I, gp + h->goff[2 * l + 1], hs[l],
-                                 rs[l], B, st));
-      continue;
-    }
-    if (a16) {     // collapsed form (64 taps) on the bf16 matrix pipe
-      RD_TRY(launch_conv16(h, h->plans[pl], h->d_plans + pl, B, hs[l - 1], h->bG1F[l], hs[l], ep, st,
-                           l == 3 ? RDGAN_TAG_GCONV3_FWD : RDGAN_TAG_GCONV_FWD, h->conv_f16 ? h->fG1F[l] : nullptr));
-    } else
-    RD_TRY(launch_conv(h, h->plans[pl], h->d_plans + pl, B, hs[l - 1], Wl, h->gch[l], hs[l], ep, st,
-                       l == 3 ? RDGAN_TAG_GCONV3_FWD : RDGAN_TAG_GCONV_FWD));
-    if (!fuse) {
-      ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-      RD_TRY(launch_pn_fwd(h, hs[l], hs[l], rs[l], (long)B * h->gpix[l], h->gch[l], st, a16));
-    }
+  } else if (s.a16) RD_TRY(launch_conv_a16(h, h->plans[PL_GDENSE], h->d_plans + PL_GDENSE, B, h->xcat, gp + h->goff[0], h->n_nodes, h->h0,
+                           epi_make(RD_EPI_BIAS_LRELU, gp + h->goff[1]), st, -1, false, true));
+  else RD_TRY(launch_conv(h, h->plans[PL_GDENSE], h->d_plans + PL_GDENSE, B, h->xcat, gp + h->goff[0], h->n_nodes, h->h0,
+                       epi_make(RD_EPI_BIAS_LRELU, gp + h->goff[1]), st, -1));
+  return 0;
+}
+
+// block l in the shared-centre form along the hour axis: T = S x[s] once per output plane pair, then the difference part
+static int gen_block_fwd_shared_centre(rdgan_handle* h, const GenPass& s, const float* gp, int l, int B, hipStream_t st) {
+  const bool a16 = s.a16;
+  const int* sd = h->gdim[l - 1];
+  const int tag = l == 3 ? RDGAN_TAG_GCONV3_FWD : RDGAN_TAG_GCONV_FWD;
+  {
+    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+    launch_diff_d(s, s.hs[l - 1], h->fE[l], B, sd[0], (long)sd[1] * sd[2] * h->gch[l - 1], st);
   }
-  // Conv3D 64->1 (T:345) as column GEMM + gather, bias, Softmax(axis=1) (T:347), check_numerics (T:349-350).
-  // When a 256-row tile holds whole (h,w) planes (nd = 8, 16) or whole w rows (nd = 32, 64, 128) the GEMM's epilogue
-  // sums the in-tile taps itself and writes 3 (9) floats per grid point instead of 32.
+  const int pls = PL_F1WS + l - 1, ple = PL_F1FE + l - 1;
+  RdEpi et = epi_make(RD_EPI_PLAIN);
+  et.out16 = a16;
+  if (a16) RD_TRY(launch_conv16(h, h->plans[pls], h->d_plans + pls, B, s.hs[l - 1], h->bU[l], h->fgS, et, st, RDGAN_TAG_GCONV_FWD));
+  else RD_TRY(launch_conv(h, h->plans[pls], h->d_plans + pls, B, s.hs[l - 1], h->fU[l], h->gch[l], h->fgS, et, st, RDGAN_TAG_GCONV_FWD));
+  const bool fuse = a16 ? conv16_rows_owned(h->plans[ple]) : conv_rows_owned(h->plans[ple], B);
+  RdEpi ep = epi_make(fuse ? RD_EPI_BIAS_PN_LRELU : RD_EPI_BIAS, gp + h->goff[2 * l + 1]);
+  ep.rinv = s.rs[l];
+  ep.addt = h->fgS; ep.addt_plane = 4 * sd[1] * sd[2] * h->gch[l];
+  ep.nametag = l == 3;
+  ep.out16 = a16;
+  if (a16) RD_TRY(launch_conv16(h, h->plans[ple], h->d_plans + ple, B, h->fE[l], h->bU[l], s.hs[l], ep, st, tag));
+  else RD_TRY(launch_conv(h, h->plans[ple], h->d_plans + ple, B, h->fE[l], h->fU[l], h->gch[l], s.hs[l], ep, st, tag));
+  if (!fuse) {
+    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+    RD_TRY(launch_pn_fwd(h, s.hs[l], s.hs[l], s.rs[l], (long)B * h->gpix[l], h->gch[l], st, a16));
+  }
+  return 0;
+}
+
+// block l: UpSampling3D + Conv3D + bias (T:330-331), then PixelNorm + LeakyReLU (T:332-333).  keep_h3: see gen_forward_impl
+static int gen_block_fwd(rdgan_handle* h, const GenPass& s, const float* gp, int l, int B, bool keep_h3, bool wait_forms, hipStream_t st) {
+  const bool a16 = s.a16;
+  float* const* hs = s.hs;
+  float* const* rs = s.rs;
+  const float* bias = gp + h->goff[2 * l + 1];
+  const int tag = l == 3 ? RDGAN_TAG_GCONV3_FWD : RDGAN_TAG_GCONV_FWD;
+  if (wait_forms) RD_CHECK(h, hipStreamWaitEvent(st, h->ev_g[l], 0));       // this block's weight forms
+  if (gen_block_fast(h, l, fast_fwd_on(h))) return gen_block_fwd_shared_centre(h, s, gp, l, B, st);
+  const float* Wl = gp + h->goff[2 * l];
+  int pl = PL_G1F + l - 1;
+  if (h->collapse) {
+    Wl = h->GWC[l];
+    pl = PL_G1FC + l - 1;
+    if (!upconv_slab_on(h, l) && !upconv2_slab_on(h, l) && !upconv_slab_t_on(h, l)) pl = gen_box_plan(h, pl, PL_G1FCX + l - 1, B);
+  }
+  if (upconv_slab_on(h, l)) {     // block 3, bf16 storage: source slab resident in LDS, weights streamed in fragment order
+    // (with the fused last conv the launch also carries that layer's 2 * rows * 64 * 27 FLOPs, and its tap products (Q12 in P9)
+    // leave the kernel from the rows while they are in registers)
+    const bool g9 = g9_fused_on(h);
+    const double fl3 = plan_flops(h->plans[pl], B) + (g9 ? 2.0 * B * h->gpix[3] * 64 * 27 : 0.0);
+    return launch_upconv_slab<1>(h, {pl, fl3, RDGAN_TAG_GCONV3_FWD}, hs[l - 1], h->bW3I, bias, hs[l], rs[l], B, nullptr,
+                                 g9 ? h->bW9I : nullptr, g9 ? h->P9 : nullptr, keep_h3, st);
+  }
+  if (upconv_slab_t_on(h, l)) {   // block 3, bf16 storage, planes larger than 8 x 8: (h, w) tiles with their halo resident, K in two halves
+    const bool g9t = g9_fused_t_on(h);
+    const double fl3 = plan_flops(h->plans[pl], B) + (g9t ? 2.0 * B * h->gpix[3] * 64 * 27 : 0.0);
+    return launch_upconv_slab_t(h, {pl, fl3, RDGAN_TAG_GCONV3_FWD}, hs[l - 1], h->bW3T, bias, hs[l], rs[l], B, h->gdim[2][1], h->gdim[2][2],
+                                nullptr, g9t ? h->bW9I : nullptr, g9t ? h->P9 : nullptr, keep_h3, st);
+  }
+  if (upconv2_slab_on(h, l))      // block 2, bf16 storage: a sample resident in LDS, the four waves split the 128 channels
+    return launch_upconv2_slab(h, {pl, plan_flops(h->plans[pl], B), RDGAN_TAG_GCONV_FWD}, hs[l - 1], h->bW2I, bias, hs[l], rs[l], B, st);
+  const bool fuse = a16 ? conv16_rows_owned(h->plans[pl]) : conv_rows_owned(h->plans[pl], B);       // PixelNorm+LeakyReLU in the GEMM epilogue
+  RdEpi ep = epi_make(fuse ? RD_EPI_BIAS_PN_LRELU : RD_EPI_BIAS, bias);
+  ep.rinv = rs[l];
+  ep.out16 = a16;
+  ep.nametag = a16 && l == 3;
+  if (a16)       // collapsed form (64 taps) on the bf16 matrix pipe
+    RD_TRY(launch_conv16(h, h->plans[pl], h->d_plans + pl, B, hs[l - 1], h->bG1F[l], hs[l], ep, st, tag, h->conv_f16 ? h->fG1F[l] : nullptr));
+  else RD_TRY(launch_conv(h, h->plans[pl], h->d_plans + pl, B, hs[l - 1], Wl, h->gch[l], hs[l], ep, st, tag));
+  if (!fuse) {
+    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+    RD_TRY(launch_pn_fwd(h, hs[l], hs[l], rs[l], (long)B * h->gpix[l], h->gch[l], st, a16));
+  }
+  return 0;
+}
+
+// Conv3D 64->1 (T:345) as column GEMM + gather, bias, Softmax(axis=1) (T:347), check_numerics (T:349-350).
+// When a 256-row tile holds whole (h,w) planes (nd = 8, 16) or whole w rows (nd = 32, 64, 128) the GEMM's epilogue
+// sums the in-tile taps itself and writes 3 (9) floats per grid point instead of 32.
+static int gen_last_conv_fwd(rdgan_handle* h, const GenPass& s, const float* gp, float* out, int B, hipStream_t st) {
+  const int nd = h->nd;
+  const bool a16 = s.a16;
   const int gq = 256 % (nd * nd) == 0 ? 3 : (256 % nd == 0 ? 9 : 0);
   const long ncol = (long)B * nd * nd;
+  const long rows9 = (long)B * h->gpix[3];
   if (g9_fused_on(h)) {
     // the tap products left the block-3 slab kernel as Q12: the sums over kd and the source classes, bias, softmax
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    hipLaunchKernelGGL((k_tapsum_softmax12<RDGAN_NHOURS>), dim3((unsigned)((ncol / 4 + 63) / 64)), dim3(256), 0, st, h->P9,
-                       gp + h->goff[9], out, B, h->d_flag);
+    hipLaunchKernelGGL((k_tapsum_softmax12<RDGAN_NHOURS>), dim3((unsigned)((ncol / 4 + 63) / 64)), dim3(256), 0, st, h->P9, gp + h->goff[9], out, B, h->d_flag);
   } else if (g9_fused_t_on(h)) {
     // the same behind the tiled kernel: main sums per tile + the halo terms of the neighbouring tiles
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    {
-      const int TH = h->gdim[2][1] / 8, TW = h->gdim[2][2] / 8;
-      const long nthr = (long)B * 6 * TH * TW * 24 * 32;
-      hipLaunchKernelGGL(k_g9_halo_fold, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, h->P9, B, TH, TW);
-    }
+    const int TH = h->gdim[2][1] / 8, TW = h->gdim[2][2] / 8;
+    const long nthr = (long)B * 6 * TH * TW * 24 * 32;
+    hipLaunchKernelGGL(k_g9_halo_fold, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, h->P9, B, TH, TW);
     hipLaunchKernelGGL((k_tapsum_softmax12t<RDGAN_NHOURS>), dim3((unsigned)((ncol / 4 + 63) / 64)), dim3(256), 0, st, h->P9,
                        gp + h->goff[9], out, B, h->gdim[2][1], h->gdim[2][2], h->d_flag);
-  } else if (!a16 && h->tapgather && h->edge_kernels == 1 && g9w_mfma_ok(nd, (long)B * h->gpix[3])) {
+  } else if (!a16 && h->tapgather && h->edge_kernels == 1 && g9w_mfma_ok(nd, rows9)) {
     // fp32 storage: pipelined streaming kernel on 128-pixel tiles (rdgan_edge.hip.h), nine kw-sums per grid point
     ProfScope ps(h, RDGAN_TAG_GCONV_FWD, st);
-    const long rows9 = (long)B * h->gpix[3];
     LaunchScope ls(h, PL_G9F, RD_KIND_EDGE, B, 2.0 * rows9 * 64 * 27, st);
     RD_KNAME(h, "k_g9_fwd_mfma + k_tapsum_softmax");
     h->flops_acc += 2.0 * rows9 * 64 * 27;
@@ -1548,15 +1583,13 @@ static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, co
       RD_TRY(ensure_lds(h, (const void*)k_g9_fwd_mfma<256>, lds9));
       hipLaunchKernelGGL(k_g9_fwd_mfma<256>, dim3((unsigned)std::min<long>((rows9 + 255) / 256, 256)), dim3(512), lds9, st,
                          (const float*)h->h3, gp + h->goff[8], h->P9, rows9, nd, 2 * ilog2(nd));
-      hipLaunchKernelGGL((k_tapsum_softmax<RDGAN_NHOURS, 3>), dim3((unsigned)((ncol + 63) / 64)), dim3(256), 0, st, h->P9,
-                         gp + h->goff[9], out, B, nd, nd, h->d_flag);
+      launch_tapsum_softmax(h, 3, out, gp, B, st);
     } else {
       const size_t lds9 = (size_t)(128 * 64 + 128 * 33) * sizeof(float);
       RD_TRY(ensure_lds(h, (const void*)k_g9_fwd_mfma<128>, lds9));
       hipLaunchKernelGGL(k_g9_fwd_mfma<128>, dim3((unsigned)std::min<long>((rows9 + 127) / 128, 768)), dim3(256), lds9, st,
                          (const float*)h->h3, gp + h->goff[8], h->P9, rows9, nd, 2 * ilog2(nd));
-      hipLaunchKernelGGL((k_tapsum_softmax<RDGAN_NHOURS, 9>), dim3((unsigned)((ncol + 63) / 64)), dim3(256), 0, st, h->P9,
-                         gp + h->goff[9], out, B, nd, nd, h->d_flag);
+      launch_tapsum_softmax(h, 9, out, gp, B, st);
     }
   } else if (gq && h->tapgather && (h->edge_kernels >= 2 || (h->edge_kernels && a16))) {
     // dedicated streaming kernel (rdgan_edge.hip.h): same tiles, same arithmetic and output as the tap-gathering GEMM below.
@@ -1564,42 +1597,46 @@ static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, co
     // one-tile-per-workgroup form (64 KB tiles, two workgroups per CU in lockstep) only matches the GEMM (159 vs 147 us),
     // so fp32 keeps the GEMM unless "edge_kernels" is 2 (tests).
     ProfScope ps(h, RDGAN_TAG_GCONV_FWD, st);
-    const long rows9 = (long)B * h->gpix[3];
     LaunchScope ls(h, PL_G9F, RD_KIND_EDGE, B, 2.0 * rows9 * 64 * 27, st);
     RD_KNAME(h, "k_g9_fwd + k_tapsum_softmax");
     h->flops_acc += 2.0 * rows9 * 64 * 27;
     RD_TRY(ensure_lds(h, a16 ? (const void*)k_g9_fwd<rd_bf16_t> : (const void*)k_g9_fwd<float>, a16 ? 36 * 1024 : 72 * 1024));
     const dim3 g9((unsigned)((rows9 + 255) / 256));
-    if (a16) hipLaunchKernelGGL(k_g9_fwd<rd_bf16_t>, g9, dim3(256), 36 * 1024, st, (const rd_bf16_t*)h->h3, gp + h->goff[8], h->P9, rows9, nd,
-                                nd * nd, gq);
-    else hipLaunchKernelGGL(k_g9_fwd<float>, g9, dim3(256), 72 * 1024, st, (const float*)h->h3, gp + h->goff[8], h->P9, rows9, nd,
-                            nd * nd, gq);
-    if (gq == 3) hipLaunchKernelGGL((k_tapsum_softmax<RDGAN_NHOURS, 3>), dim3((unsigned)((ncol + 63) / 64)), dim3(256), 0, st, h->P9,
-                                    gp + h->goff[9], out, B, nd, nd, h->d_flag);
-    else hipLaunchKernelGGL((k_tapsum_softmax<RDGAN_NHOURS, 9>), dim3((unsigned)((ncol + 63) / 64)), dim3(256), 0, st, h->P9,
-                            gp + h->goff[9], out, B, nd, nd, h->d_flag);
+    if (a16) hipLaunchKernelGGL(k_g9_fwd<rd_bf16_t>, g9, dim3(256), 36 * 1024, st, (const rd_bf16_t*)h->h3, gp + h->goff[8], h->P9, rows9, nd, nd * nd, gq);
+    else hipLaunchKernelGGL(k_g9_fwd<float>, g9, dim3(256), 72 * 1024, st, (const float*)h->h3, gp + h->goff[8], h->P9, rows9, nd, nd * nd, gq);
+    launch_tapsum_softmax(h, gq, out, gp, B, st);
   } else if (gq && h->tapgather) {
     RdEpi e = epi_make(RD_EPI_TAPGATHER);
     e.gw = nd; e.ghw = nd * nd; e.gq = gq;
     if (a16) RD_TRY(launch_conv_a16(h, h->plans[PL_G9F], h->d_plans + PL_G9F, B, h->h3, h->W9T, 32, h->P9, e, st, -1, true, false));
-    else
-    RD_TRY(launch_conv(h, h->plans[PL_G9F], h->d_plans + PL_G9F, B, h->h3, h->W9T, 32, h->P9, e, st, -1));
+    else RD_TRY(launch_conv(h, h->plans[PL_G9F], h->d_plans + PL_G9F, B, h->h3, h->W9T, 32, h->P9, e, st, -1));
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    if (gq == 3) hipLaunchKernelGGL((k_tapsum_softmax<RDGAN_NHOURS, 3>), dim3((unsigned)((ncol + 63) / 64)), dim3(256), 0, st, h->P9,
-                                    gp + h->goff[9], out, B, nd, nd, h->d_flag);
-    else hipLaunchKernelGGL((k_tapsum_softmax<RDGAN_NHOURS, 9>), dim3((unsigned)((ncol + 63) / 64)), dim3(256), 0, st, h->P9,
-                            gp + h->goff[9], out, B, nd, nd, h->d_flag);
+    launch_tapsum_softmax(h, gq, out, gp, B, st);
   } else {
-    if (a16) RD_TRY(launch_conv_a16(h, h->plans[PL_G9F], h->d_plans + PL_G9F, B, h->h3, h->W9T, 32, h->P9, epi_make(RD_EPI_PLAIN), st, -1,
-                                    true, false));
-    else
-    RD_TRY(launch_conv(h, h->plans[PL_G9F], h->d_plans + PL_G9F, B, h->h3, h->W9T, 32, h->P9, epi_make(RD_EPI_PLAIN), st, -1));
+    const RdEpi e = epi_make(RD_EPI_PLAIN);
+    if (a16) RD_TRY(launch_conv_a16(h, h->plans[PL_G9F], h->d_plans + PL_G9F, B, h->h3, h->W9T, 32, h->P9, e, st, -1, true, false));
+    else RD_TRY(launch_conv(h, h->plans[PL_G9F], h->d_plans + PL_G9F, B, h->h3, h->W9T, 32, h->P9, e, st, -1));
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    hipLaunchKernelGGL(k_colgather_softmax, dim3((unsigned)((ncol + 63) / 64)), dim3(64), 0, st, h->P9, gp + h->goff[9],
-                       out, B, RDGAN_NHOURS, nd, nd, h->d_flag);
+    hipLaunchKernelGGL(k_colgather_softmax, dim3((unsigned)((ncol + 63) / 64)), dim3(64), 0, st, h->P9, gp + h->goff[9], out, B, RDGAN_NHOURS, nd, nd, h->d_flag);
   }
   RD_CHECK(h, hipGetLastError());
   return 0;
+}
+
+// keep_h3: block 3's output and 1/l2 are needed afterwards (generator step: its backward; rdgan_gen_forward: the test hook) --
+// a critic step passes false, and with the fused last conv the 1.6 GB tensor (2048 samples) is then never written
+// `ws`: stream of the weight-only kernels (the handle's side stream, forked by the caller, or `st` itself): the weight forms of
+// block l are complete behind event ev_g[l], which `st` waits for in front of the block's GEMM
+static int gen_forward_impl(rdgan_handle* h, const float* gp, const float* z, const float* cond, float* out, int B,
+                            hipStream_t st, hipStream_t ws, bool keep_h3 = true) {
+  RD_TRY(a16_check(h));
+  const GenPass s = gen_pass(h, B);
+  bool built = false;
+  RD_TRY(gen_build_forms(h, gp, st, ws, &built));
+  const bool wait_forms = built && ws != st;
+  RD_TRY(gen_dense_fwd(h, s, gp, z, cond, B, wait_forms, st));
+  for (int l = 1; l <= 3; ++l) RD_TRY(gen_block_fwd(h, s, gp, l, B, keep_h3, wait_forms, st));
+  return gen_last_conv_fwd(h, s, gp, out, B, st);
 }
 
 static bool fwd_ahead_on(const rdgan_handle* h) { return h->ahead && h->ev_ahead_done && (h->fwd_ahead < 0 ? !h->a16 : h->fwd_ahead); }
@@ -1702,7 +1739,12 @@ static inline const float* d1_weights(const rdgan_handle* h, const float* dp) {
 
 // First critic layer as one K = 64 GEMM per tile (rdgan_edge.hip.h): one condition channel (2 floats per voxel), any ndomain
 static bool d1_gemm_ok(const rdgan_handle* h) { return h->edge_kernels && h->CP == 2 && h->Cin == 2; }
-// critic layer 2's weight gradient on tiles of 4 x 4 output positions (k_d2_wgrad_slab_t16): the geometry of 'valid' layer 1 +
+// critic layer 2's weight gradient by k_d2_wgrad_slab16 (bf16 storage mode, ndomain 16): a wave owns one tap, its [64 x 128]
+// product stays in registers over the workgroup's share of the batch
+static bool d2_wgrad_slab_on(const rdgan_handle* h) { return h->a16 && h->d2_wgrad_slab && h->nd == 16; }
+// layer 3's by k_d3_wgrad_slab16: a wave owns (tap, quarter of the output channels); items of four samples (12 output positions each)
+static bool d3_wgrad_slab_on(const rdgan_handle* h) { return h->a16 && h->d3_wgrad_slab && h->nd == 16; }
+// layer 2's on tiles of 4 x 4 output positions (k_d2_wgrad_slab_t16; ndomain 32 / 48 / 64): the geometry of 'valid' layer 1 +
 // stride-2 'same' layer 2 on an ndomain that is a multiple of 16 (11 x (2 OH - 1)^2 -> 6 x OH^2, OH % 4 == 0)
 static bool d2_wgrad_slab_t_on(const rdgan_handle* h) {
   return h->d2_wgrad_slab && h->a16 && h->nd > 16 && h->nd % 16 == 0 && h->ddim[1][0] == 11 && h->ddim[2][0] == 6 &&
@@ -1961,6 +2003,101 @@ extern "C" int rdgan_critic_forward(rdgan_handle* h, const float* critic_params,
   return 0;
 }
 
+// ---- stages of the critic step behind its forward and input-gradient chain (rdgan_critic_grad_ahead)
+// bias gradients: only the real|fake passes reach the loss through the bias (the penalty term does not).  Column sums of
+// the output gradients the chain has just left: on the side stream, beside the penalty's second sweep and the weight-gradient
+// GEMMs (nothing behind the chain writes du[l]; the column-sum scratch is used by these launches only)
+static int critic_bias_grads(rdgan_handle* h, float* grad, int B, hipStream_t st) {
+  hipStream_t cs = side_fork(h, st);
+  for (int l = 1; l <= 4; ++l) {
+    if (l == 1 && d1_gemm_ok(h) && d1_wgrad16_on(h)) continue;      // comes out of the weight-gradient GEMM (k_d1_wgrad16)
+    RD_TRY(launch_colsum(h, h->du[l], (long)2 * B * h->dL[l], h->dch[l], grad + h->doff[2 * (l - 1) + 1], cs, h->a16 != 0));
+  }
+  return 0;
+}
+
+// second forward sweep of the double backward: r_l = gate_l * conv_l(r_{l-1}), in place over the x_hat third
+static int critic_second_sweep(rdgan_handle* h, const float* dp, const float* cin_hat, int B, uint64_t seed, hipStream_t st) {
+  const bool a16 = h->a16 != 0;
+  const int use_drop = seed != 0;
+  h->gate_keep_B = 0;
+  if (h->keep_gates) {       // test hook: keep the x_hat third of every h_l (see rdgan_debug_activation)
+    for (int l = 1; l <= 4; ++l) {
+      const long third = (long)2 * B * h->dL[l] * h->dch[l];
+      RD_CHECK(h, hipMemcpyAsync(h->gate_keep[l], act_off(h, h->dh[l], third), (size_t)(third / 2) * (a16 ? 2 : 4), hipMemcpyDeviceToDevice, st));
+    }
+    h->gate_keep_B = B;
+  }
+  const float* in = cin_hat;
+  for (int l = 1; l <= 4; ++l) {
+    int pl = l == 1 ? PL_D1F : critic_fwd_plan(h, l, B);
+    long third = (long)2 * B * h->dL[l] * h->dch[l];
+    float* dst = act_off(h, h->dh[l], third);
+    RdEpi ep = epi_make(RD_EPI_GATE_AUX, nullptr, dst, use_drop, rd_make_key(seed, RD_STREAM_D1 + l - 1), (uint32_t)third);
+    ep.out16 = a16;
+    if (l == 1 && d1_gemm_ok(h)) RD_TRY(launch_d1_fwd(h, in, dp + h->doff[0], nullptr, dst, dst, B, 1, use_drop, ep.key, (uint32_t)third, st));
+    else if (a16 && l == 1) RD_TRY(launch_conv_a16(h, h->plans[pl], h->d_plans + pl, B, in, d1_weights(h, dp), h->dch[l], dst, ep, st,
+                             RDGAN_TAG_CRITIC_GEMM, false, true));
+    else if (a16) RD_TRY(launch_conv16(h, h->plans[pl], h->d_plans + pl, B, in, h->bWF[l], dst, ep, st, RDGAN_TAG_CRITIC_GEMM, h->conv_f16 ? h->fWF[l] : nullptr));
+    else RD_TRY(launch_conv(h, h->plans[pl], h->d_plans + pl, B, in, l == 1 ? d1_weights(h, dp) : dp + h->doff[2 * (l - 1)],
+                         h->dch[l], dst, ep, st, RDGAN_TAG_CRITIC_GEMM));
+    in = dst;
+  }
+  return 0;
+}
+
+// weight gradients over the 3B batch: inputs [h_real; h_fake; r_hat], output grads [u_real; u_fake; u_hat]
+static int critic_weight_grads(rdgan_handle* h, float* grad, int B, hipStream_t st) {
+  const bool a16 = h->a16 != 0;
+  const int NBt = 3 * B;
+  for (int l = 1; l <= 4; ++l) {
+    int pl = l == 1 ? PL_D1F : PL_D2F + l - 2;
+    const float* in = l == 1 ? h->cin : h->dh[l - 1];
+    const bool padded = l == 1 && h->CP != h->Cin;   // D1 with padding channels: gradient of the padded kernel, then drop the pad rows
+    const SlabRec rec = {pl, plan_flops(h->plans[pl], NBt), RDGAN_TAG_CRITIC_GEMM};
+    if (l == 1 && d1_gemm_ok(h)) {
+      RD_TRY(launch_d1_wgrad(h, in, h->du[1], grad + h->doff[0], NBt, st, grad + h->doff[1], (long)2 * B * h->dL[1]));
+    } else if (l == 2 && d2_wgrad_slab_on(h)) {
+      RD_TRY(launch_d2_wgrad_slab(h, rec, in, h->du[2], h->wpartial, h->wpartial_cap, grad + h->doff[2], NBt, nullptr, st));
+    } else if (l == 2 && d2_wgrad_slab_t_on(h)) {
+      const RdD2wGeom geo = {h->ddim[1][1], h->ddim[1][2], h->ddim[2][1], h->ddim[2][2], h->ddim[2][1] / 4, h->ddim[2][2] / 4};
+      RD_TRY(launch_d2_wgrad_slab(h, rec, in, h->du[2], h->wpartial, h->wpartial_cap, grad + h->doff[2], NBt, &geo, st));
+    } else if (l == 3 && d3_wgrad_slab_on(h)) {
+      RD_TRY(launch_d3_wgrad_slab(h, rec, in, h->du[3], h->wpartial, h->wpartial_cap, grad + h->doff[4], NBt, st));
+    } else if (a16 && l >= 2) {      // layers 2-4: bf16 activations against bf16 output gradients (on the border-class boxes)
+      pl = critic_wgrad_plan(h, l, NBt);
+      if (!wgrad16_ok(h->plans[pl], NBt)) return bad_arg(h, "bf16 storage mode: no bf16 weight-gradient tile for this critic layer");
+      RD_TRY(launch_wgrad16(h, h->plans[pl], h->d_plans + pl, NBt, in, h->du[l], grad + h->doff[2 * (l - 1)], h->wpartial,
+                            h->wpartial_cap, st, RDGAN_TAG_CRITIC_GEMM));
+    } else {
+      // fp32 storage, layers 2-4: the border-class boxes of the layer's forward plan (k_wgrad_gemm_ws<128,128> + k_wgrad_reduce_box)
+      if (l >= 2 && !a16 && h->wave_spec) pl = critic_wgrad_plan(h, l, NBt);
+      RD_TRY(launch_wgrad(h, h->plans[pl], h->d_plans + pl, NBt, in, h->du[l], padded ? h->dW1P : grad + h->doff[2 * (l - 1)],
+                          h->wpartial, h->wpartial_cap, st, RDGAN_TAG_CRITIC_GEMM, a16));
+    }
+    if (padded) hipLaunchKernelGGL(k_unpad_w1, dim3(27), dim3(256), 0, st, h->dW1P, grad + h->doff[0], h->Cin, h->CP);
+  }
+  return 0;
+}
+
+// Dense weight gradient (row slices where the batch is large), then the losses
+static int critic_dense_grad_and_losses(rdgan_handle* h, float* grad, int B, hipStream_t st) {
+  const int NBt = 3 * B;
+  {
+    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+    const int RS = h->dense_slices > 0 ? std::min(16, h->dense_slices) : std::max(1, std::min(16, NBt / 384));   // row slices of the Dense weight gradient
+    float* dwo = RS > 1 ? h->dw6_part : grad + h->doff[8];
+    const dim3 dg((h->F + 15) / 16, RS);
+    if (h->a16) hipLaunchKernelGGL(k_critic_dense_wgrad<rd_bf16_t>, dg, dim3(256), 0, st, (const rd_bf16_t*)h->dh[4], dwo, NBt, h->F, B);
+    else hipLaunchKernelGGL(k_critic_dense_wgrad<float>, dg, dim3(256), 0, st, (const float*)h->dh[4], dwo, NBt, h->F, B);
+    if (RS > 1) hipLaunchKernelGGL(k_reduce_partials, dim3((h->F + 15) / 16), dim3(256), 0, st, h->dw6_part, RS, h->F, grad + h->doff[8]);
+    // (grad[doff[9]] = sum of dv over real|fake = 0, cleared by the loss kernel together with the unused loss slots)
+    hipLaunchKernelGGL(k_critic_losses, dim3(1), dim3(256), 0, st, h->v, h->gpv, grad + h->n_critic, B, RD_GP_WEIGHT, h->d_flag, grad + h->doff[9]);
+  }
+  RD_CHECK(h, hipGetLastError());
+  return 0;
+}
+
 extern "C" int rdgan_critic_grad(rdgan_handle* h, const float* dp, const float* gp, const float* x_real,
                                  const float* cond, const float* z, uint64_t seed, float* grad, int B, void* stream) {
   return rdgan_critic_grad_after(h, dp, gp, x_real, cond, z, seed, grad, B, nullptr, stream);
@@ -1983,7 +2120,6 @@ extern "C" int rdgan_critic_grad_ahead(rdgan_handle* h, const float* dp, const f
   hipStream_t st = (hipStream_t)stream;
   RD_TRY(ahead_drain(h, st));
   const int NBt = 3 * B;
-  const int use_drop = seed != 0;
   // fake = G(z, cond), generator frozen (T:363,370): reads no critic weight, so it is issued in front of the wait for
   // them -- the previous critic update's all-reduce + Adam (on the caller's other stream) hide behind it
   // The weight-only kernels (generator weight forms, then the critic's transposes / bf16 images behind the "critic ready"
@@ -1994,7 +2130,6 @@ extern "C" int rdgan_critic_grad_ahead(rdgan_handle* h, const float* dp, const f
   RD_TRY(prep_critic_weights(h, dp, ws));
   RD_TRY(side_join(h, st, h->ev_cw));
   // [real; fake; alpha*real + (1-alpha)*fake] with the condition as 2nd channel (T:275-282, T:376)
-  const bool a16 = h->a16 != 0;
   {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
     launch_build_critic_input(h, x_real, h->fake, cond, B, 0, rd_make_key(seed, RD_STREAM_ALPHA), (uint32_t)h->sample_offset, st);
@@ -2003,104 +2138,228 @@ extern "C" int rdgan_critic_grad_ahead(rdgan_handle* h, const float* dp, const f
   if (gen_z && fwd_ahead_on(h)) RD_TRY(ahead_issue(h, gp, gen_z, gen_cond, gen_B, st));
   RD_TRY(critic_forward_impl(h, dp, NBt, seed, st));           // T:372,373,379 as one batch
   RD_TRY(critic_dgrad_chain(h, dp, NBt, B, 0, seed, st));       // dL/dh for real|fake, dD/dh for x_hat
-  // bias gradients: only the real|fake passes reach the loss through the bias (the penalty term does not).  Column sums of
-  // the output gradients the chain has just left: on the side stream, beside the penalty's second sweep and the weight-gradient
-  // GEMMs below (nothing below writes du[l]; the column-sum scratch is used by these launches only)
-  {
-    hipStream_t cs = side_fork(h, st);
-    for (int l = 1; l <= 4; ++l) {
-      if (l == 1 && d1_gemm_ok(h) && d1_wgrad16_on(h)) continue;      // comes out of the weight-gradient GEMM (k_d1_wgrad16)
-      RD_TRY(launch_colsum(h, h->du[l], (long)2 * B * h->dL[l], h->dch[l], grad + h->doff[2 * (l - 1) + 1], cs, h->a16 != 0));
-    }
-  }
+  RD_TRY(critic_bias_grads(h, grad, B, st));                    // (side stream, joined below)
   // gradient penalty (T:238-241, T:382): g0 = dD/dx_hat, n = ||g0||, r0 = d(10 mean((n-1)^2))/dg0
   float* cin_hat = h->cin + (long)2 * B * h->dL[0] * h->CP;
   RD_TRY(critic_penalty_input(h, dp, act_off(h, h->du[1], (long)2 * B * h->dL[1] * 64), B, cin_hat, st));
-  // second forward sweep of the double backward: r_l = gate_l * conv_l(r_{l-1}), in place over the x_hat third
-  h->gate_keep_B = 0;
-  if (h->keep_gates) {       // test hook: keep the x_hat third of every h_l (see rdgan_debug_activation)
-    for (int l = 1; l <= 4; ++l) {
-      const long third = (long)2 * B * h->dL[l] * h->dch[l];
-      RD_CHECK(h, hipMemcpyAsync(h->gate_keep[l], act_off(h, h->dh[l], third), (size_t)(third / 2) * (a16 ? 2 : 4),
-                                 hipMemcpyDeviceToDevice, st));
-    }
-    h->gate_keep_B = B;
-  }
-  {
-    const float* in = cin_hat;
-    for (int l = 1; l <= 4; ++l) {
-      int pl = l == 1 ? PL_D1F : critic_fwd_plan(h, l, B);
-      long third = (long)2 * B * h->dL[l] * h->dch[l];
-      float* dst = act_off(h, h->dh[l], third);
-      RdEpi ep = epi_make(RD_EPI_GATE_AUX, nullptr, dst, use_drop, rd_make_key(seed, RD_STREAM_D1 + l - 1), (uint32_t)third);
-      ep.out16 = a16;
-      if (l == 1 && d1_gemm_ok(h))
-        RD_TRY(launch_d1_fwd(h, in, dp + h->doff[0], nullptr, dst, dst, B, 1, use_drop, ep.key, (uint32_t)third, st));
-      else if (a16 && l == 1)
-        RD_TRY(launch_conv_a16(h, h->plans[pl], h->d_plans + pl, B, in, d1_weights(h, dp), h->dch[l], dst, ep, st,
-                               RDGAN_TAG_CRITIC_GEMM, false, true));
-      else if (a16)
-        RD_TRY(launch_conv16(h, h->plans[pl], h->d_plans + pl, B, in, h->bWF[l], dst, ep, st, RDGAN_TAG_CRITIC_GEMM,
-                             h->conv_f16 ? h->fWF[l] : nullptr));
-      else
-      RD_TRY(launch_conv(h, h->plans[pl], h->d_plans + pl, B, in, l == 1 ? d1_weights(h, dp) : dp + h->doff[2 * (l - 1)],
-                         h->dch[l], dst, ep, st, RDGAN_TAG_CRITIC_GEMM));
-      in = dst;
-    }
-  }
-  // weight gradients over the 3B batch: inputs [h_real; h_fake; r_hat], output grads [u_real; u_fake; u_hat]
-  for (int l = 1; l <= 4; ++l) {
-    int pl = l == 1 ? PL_D1F : PL_D2F + l - 2;
-    const float* in = l == 1 ? h->cin : h->dh[l - 1];
-    const bool padded = l == 1 && h->CP != h->Cin;   // D1 with padding channels: gradient of the padded kernel, then drop the pad rows
-    if (l == 1 && d1_gemm_ok(h)) {
-      RD_TRY(launch_d1_wgrad(h, in, h->du[1], grad + h->doff[0], NBt, st, grad + h->doff[1], (long)2 * B * h->dL[1]));
-    } else if (a16 && l == 2 && h->d2_wgrad_slab && h->nd == 16) {
-      // a wave owns one tap: its [64 x 128] product stays in registers over the workgroup's share of the batch
-      RD_TRY(launch_d2_wgrad_slab(h, {pl, plan_flops(h->plans[pl], NBt), RDGAN_TAG_CRITIC_GEMM}, in, h->du[2], h->wpartial, h->wpartial_cap,
-                                  grad + h->doff[2], NBt, nullptr, st));
-    } else if (a16 && l == 2 && d2_wgrad_slab_t_on(h)) {
-      // the same on (h, w) tiles of 4 x 4 output positions (ndomain 32 / 48 / 64)
-      const RdD2wGeom geo = {h->ddim[1][1], h->ddim[1][2], h->ddim[2][1], h->ddim[2][2], h->ddim[2][1] / 4, h->ddim[2][2] / 4};
-      RD_TRY(launch_d2_wgrad_slab(h, {pl, plan_flops(h->plans[pl], NBt), RDGAN_TAG_CRITIC_GEMM}, in, h->du[2], h->wpartial, h->wpartial_cap,
-                                  grad + h->doff[2], NBt, &geo, st));
-    } else if (a16 && l == 3 && h->d3_wgrad_slab && h->nd == 16) {
-      // a wave owns (tap, quarter of the output channels); items of four samples (12 output positions each)
-      RD_TRY(launch_d3_wgrad_slab(h, {pl, plan_flops(h->plans[pl], NBt), RDGAN_TAG_CRITIC_GEMM}, in, h->du[3], h->wpartial, h->wpartial_cap,
-                                  grad + h->doff[4], NBt, st));
-    } else if (a16 && l >= 2) {      // layers 2-4: bf16 activations against bf16 output gradients (on the border-class boxes)
-      pl = critic_wgrad_plan(h, l, NBt);
-      if (!wgrad16_ok(h->plans[pl], NBt)) return bad_arg(h, "bf16 storage mode: no bf16 weight-gradient tile for this critic layer");
-      RD_TRY(launch_wgrad16(h, h->plans[pl], h->d_plans + pl, NBt, in, h->du[l], grad + h->doff[2 * (l - 1)], h->wpartial,
-                            h->wpartial_cap, st, RDGAN_TAG_CRITIC_GEMM));
-    } else {
-    // fp32 storage, layers 2-4: the border-class boxes of the layer's forward plan (k_wgrad_gemm_ws<128,128> + k_wgrad_reduce_box)
-    if (l >= 2 && !a16 && h->wave_spec) pl = critic_wgrad_plan(h, l, NBt);
-    RD_TRY(launch_wgrad(h, h->plans[pl], h->d_plans + pl, NBt, in, h->du[l], padded ? h->dW1P : grad + h->doff[2 * (l - 1)],
-                        h->wpartial, h->wpartial_cap, st, RDGAN_TAG_CRITIC_GEMM, a16));
-    }
-    if (padded) hipLaunchKernelGGL(k_unpad_w1, dim3(27), dim3(256), 0, st, h->dW1P, grad + h->doff[0], h->Cin, h->CP);
-  }
+  RD_TRY(critic_second_sweep(h, dp, cin_hat, B, seed, st));
+  RD_TRY(critic_weight_grads(h, grad, B, st));
   RD_TRY(side_join(h, st, h->ev_join));                 // the bias-gradient sums issued on the side stream above
-  {
-    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    const int RS = h->dense_slices > 0 ? std::min(16, h->dense_slices) : std::max(1, std::min(16, NBt / 384));   // row slices of the Dense weight gradient
-    float* dwo = RS > 1 ? h->dw6_part : grad + h->doff[8];
-    const dim3 dg((h->F + 15) / 16, RS);
-    if (a16) hipLaunchKernelGGL(k_critic_dense_wgrad<rd_bf16_t>, dg, dim3(256), 0, st, (const rd_bf16_t*)h->dh[4], dwo, NBt, h->F, B);
-    else hipLaunchKernelGGL(k_critic_dense_wgrad<float>, dg, dim3(256), 0, st, (const float*)h->dh[4], dwo, NBt, h->F, B);
-    if (RS > 1) hipLaunchKernelGGL(k_reduce_partials, dim3((h->F + 15) / 16), dim3(256), 0, st, h->dw6_part, RS, h->F, grad + h->doff[8]);
-    // (grad[doff[9]] = sum of dv over real|fake = 0, cleared by the loss kernel together with the unused loss slots)
-    hipLaunchKernelGGL(k_critic_losses, dim3(1), dim3(256), 0, st, h->v, h->gpv, grad + h->n_critic, B, RD_GP_WEIGHT, h->d_flag,
-                       grad + h->doff[9]);
-  }
-  RD_CHECK(h, hipGetLastError());
-  return 0;
+  return critic_dense_grad_and_losses(h, grad, B, st);
 }
 
 // ------------------------------------------------------------------------------------
 // generator step gradients (T:395-408)
 // ------------------------------------------------------------------------------------
+// ---- stages of the backward through the generator (rdgan_gen_grad_after), from g0 = dL/d fake
+// softmax backward, then the last conv (64 -> 1, T:345): weight grad [27][64], input grad (im2col route; the direct route's is
+// part of block 3's PixelNorm backward, gen_block_pn_bwd), bias grad
+static int gen_last_conv_bwd(rdgan_handle* h, const GenPass& s, const float* gp, float* grad, int B, hipStream_t st) {
+  const int nd = h->nd;
+  const long npix3 = (long)B * h->gpix[3];
+  {
+    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+    long ncol = (long)B * nd * nd;
+    hipLaunchKernelGGL(k_softmax_bwd, dim3((unsigned)((ncol + 63) / 64)), dim3(64), 0, st, h->fake, h->g0, h->dl, B, RDGAN_NHOURS, nd, nd);
+  }
+  if (s.a16 && !s.g9_direct) return bad_arg(h, "bf16 storage mode needs the direct backward of the last conv (g9_direct)");
+  if (s.g9_direct) {
+    RD_TRY(ensure_lds(h, s.a16 ? (const void*)k_g9_bwd_pairs<rd_bf16_t> : (const void*)k_g9_bwd_pairs<float>, 96 * 1024));
+    // weight gradient on the matrix pipe, the h3 tensor streamed once (rdgan_edge.hip.h), where its partial rows fit
+    const bool mfma = h->edge_kernels && g9w_mfma_ok(nd, npix3) && g9w_partial_floats(g9w_groups(true, B, nd)) <= h->wpartial_cap;
+    RD_TRY(launch_g9_wgrad(h, {PL_G9B, 2.0 * npix3 * 64 * 27, RDGAN_TAG_GCONV_WGRAD}, mfma, s.a16, h->dl, h->h3, h->wpartial, h->wpartial_cap,
+                           grad + h->goff[8], B, nd, st));
+  } else {
+    {
+      ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+      hipLaunchKernelGGL(k_dl_im2col, dim3(ew_blocks(npix3 * 8)), dim3(256), 0, st, h->dl, h->P9, B, RDGAN_NHOURS, nd, nd);
+    }
+    RD_TRY(launch_wgrad(h, h->plans[PL_G9B], h->d_plans + PL_G9B, B, h->P9, h->h3, grad + h->goff[8], h->wpartial, h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
+    RD_TRY(launch_conv(h, h->plans[PL_G9B], h->d_plans + PL_G9B, B, h->P9, gp + h->goff[8], 64, h->gh3, epi_make(RD_EPI_PLAIN), st, RDGAN_TAG_GCONV_DGRAD));
+  }
+  // bias gradient of the last conv = sum of dl: on the side stream (dl is not written again in this call)
+  hipStream_t cs = side_fork(h, st);
+  RD_TRY(launch_colsum(h, h->dl, npix3 / 64, 64, h->g9b_tmp, cs));   // 64 partial sums of dl (npix3 % 64 == 0)
+  RD_TRY(launch_colsum(h, h->g9b_tmp, 64, 1, grad + h->goff[9], cs));
+  return 0;
+}
+
+// collapsed form: the input-gradient forms Wd[q][Cout][Cin] <- Wc (written by the forward unless that block ran in the shared-centre form)
+static int gen_build_dgrad_forms(rdgan_handle* h, const GenPass& s, const float* gp, hipStream_t st) {
+  if (!s.col) return 0;
+  RdSliceMap map;
+  collapsed_dgrad_slice_map(map.src);
+  for (int l = 1; l <= 3; ++l) {
+    if (gen_block_fast(h, l, fast_bwd_on(h))) continue;
+    if (gen_block_fast(h, l, fast_fwd_on(h))) hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * h->gch[l - 1] * h->gch[l])), dim3(256), 0, st,
+                         gp + h->goff[2 * l], h->GWC[l], h->gch[l - 1] * h->gch[l]);
+    if (s.a16) continue;              // (bf16 storage: the input gradient reads the bf16 image of Wc re-ordered by tap: gen_block_bwd_collapsed)
+    hipLaunchKernelGGL(k_transpose_map, dim3((h->gch[l] + 31) / 32, (h->gch[l - 1] + 31) / 32, 64), dim3(256), 0, st,
+                       h->GWC[l], h->GWD[l], h->gch[l - 1], h->gch[l], map);
+  }
+  return 0;
+}
+
+// PixelNorm + LeakyReLU backward of block l: dys[l] from the gradient wrt the block output.  dE_in ("combine_dx_fused"): block
+// l + 1 has left gups[l + 1] without its difference part, which this pass folds in
+static int gen_block_pn_bwd(rdgan_handle* h, const GenPass& s, const float* gp, int l, int B, const float* dE_in, hipStream_t st) {
+  const int nd = h->nd;
+  const bool a16 = s.a16, fast = gen_block_fast(h, l, fast_bwd_on(h));
+  ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+  if (l == 3 && s.g9_direct) {
+    // input gradient of the 64 -> 1 conv + block 3's PixelNorm+LeakyReLU backward (+ plane-pair sums)
+    if (g9_bwd_mfma_on(h)) {
+      const int PP = nd <= 16 ? 4 : 1;        // plane pairs per unit (ten staged planes = 13 KB at ndomain 16; 3 B units deal evenly to 768 workgroups)
+      const size_t lds9 = (size_t)(2 * PP + 2) * (nd + 2) * (nd + 2) * sizeof(float);
+      const int nunits = B * (RDGAN_NHOURS / 2 / PP);
+      RD_TRY(ensure_lds(h, (const void*)k_g9_bwd_mfma16, lds9));
+      hipLaunchKernelGGL(k_g9_bwd_mfma16, dim3((unsigned)std::min(nunits, PP > 1 ? 768 : 1536)), dim3(256), lds9, st, h->dl, gp + h->goff[8],
+                         (const rd_bf16_t*)s.hs[3], s.rs[3], (rd_bf16_t*)s.dys[3], nunits, RDGAN_NHOURS, nd, nd, PP);
+    } else if (a16) hipLaunchKernelGGL(k_g9_bwd_pairs<rd_bf16_t>, dim3(B * (RDGAN_NHOURS / 2)), dim3(256), g9_pairs_lds(h), st, h->dl, gp + h->goff[8],
+                         (const rd_bf16_t*)s.hs[3], s.rs[3], (rd_bf16_t*)s.dys[3], fast ? (rd_bf16_t*)h->fgS : (rd_bf16_t*)nullptr, RDGAN_NHOURS, nd, nd);
+    else hipLaunchKernelGGL(k_g9_bwd_pairs<float>, dim3(B * (RDGAN_NHOURS / 2)), dim3(256), g9_pairs_lds(h), st, h->dl, gp + h->goff[8],
+                         (const float*)s.hs[3], s.rs[3], s.dys[3], fast ? h->fgS : (float*)nullptr, RDGAN_NHOURS, nd, nd);
+    RD_CHECK(h, hipGetLastError());
+  } else if (fast) {     // ... and the sums of the output-gradient plane pairs the shared-centre form reads
+    const long HW = (long)h->gdim[l][1] * h->gdim[l][2];
+    RD_TRY(launch_pn_bwd_pairs(h, l == 3 ? h->gh3 : s.gups[l + 1], s.hs[l], s.rs[l], s.dys[l], h->fgS, (long)B * h->gdim[l - 1][0] * HW,
+                               HW, h->gch[l], st, a16, l == 3 ? nullptr : dE_in, h->gdim[l - 1][0]));
+  } else if (l == 3) RD_TRY(launch_pn_bwd(h, h->gh3, s.hs[3], s.rs[3], s.dys[3], (long)B * h->gpix[3], 64, 0, 0, 0, 0, st, a16));
+  else RD_TRY(launch_pn_bwd(h, s.gups[l + 1], s.hs[l], s.rs[l], s.dys[l], (long)B * h->gpix[l], h->gch[l], s.col ? 0 : 1,
+                         h->gdim[l][0], h->gdim[l][1], h->gdim[l][2], st, a16, dE_in));
+  return 0;
+}
+
+// block l in the shared-centre form along d: E = d-differences of the block input, gS = sums of the output-gradient plane pairs.
+// *dE_out: the gradient wrt E where the next PixelNorm backward is to fold it into dx (else it has been folded here)
+static int gen_block_bwd_shared_centre(rdgan_handle* h, const GenPass& s, const float* gp, float* grad, int l, int B, const float** dE_out, hipStream_t st) {
+  const bool a16 = s.a16;
+  float* const* hs = s.hs;
+  float* const* dys = s.dys;
+  float* const* gups = s.gups;
+  const long cc = (long)h->gch[l - 1] * h->gch[l];
+  const int* sd = h->gdim[l - 1];
+  const int D = sd[0];
+  const long P = (long)sd[1] * sd[2] * h->gch[l - 1];
+  RdWeightMap wm;
+  fastd_weight_map(wm);
+  {
+    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+    if (!gen_block_fast(h, l, fast_fwd_on(h))) {      // (otherwise the forward pass has left both)
+      launch_diff_d(s, hs[l - 1], h->fE[l], B, D, P, st);
+      hipLaunchKernelGGL(k_weight_transform, dim3(ew_blocks(48L * cc / 4)), dim3(256), 0, st, gp + h->goff[2 * l], h->fU[l], (int)cc, 48, wm);
+    }
+  }
+  // weight gradients of the three tap groups: E[s] x even planes, x x plane sums, E[s+1] x odd planes
+  const float* wsrc[3] = {h->fE[l], hs[l - 1], h->fE[l]};
+  const float* wdy[3] = {dys[l], h->fgS, dys[l]};
+  for (int g = 0; g < 3; ++g) {
+    int pl = PL_F1WA + 3 * g + l - 1;
+    if (!a16 && gen_wgrad_boxes_on(h, pl, PL_F1WAX + 3 * g + l - 1)) pl = PL_F1WAX + 3 * g + l - 1;      // fp32 storage: the border boxes
+    if (a16) {
+      if (!wgrad16_ok(h->plans[pl], B)) return bad_arg(h, "bf16 storage mode: no bf16 weight-gradient tile for this block");
+      RD_TRY(launch_wgrad16(h, h->plans[pl], h->d_plans + pl, B, wsrc[g], wdy[g], h->fdU, h->wpartial, h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
+    } else RD_TRY(launch_wgrad(h, h->plans[pl], h->d_plans + pl, B, wsrc[g], wdy[g], h->fdU, h->wpartial, h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
+  }
+  hipLaunchKernelGGL(k_weight_transform_adj, dim3(ew_blocks(27L * cc / 4)), dim3(256), 0, st, h->fdU, grad + h->goff[2 * l], (int)cc, 48, wm);
+  RD_TRY(launch_colsum(h, dys[l], (long)B * h->gpix[l], h->gch[l], grad + h->goff[2 * l + 1], side_fork(h, st), a16));   // bias gradient, beside the GEMMs (dys[l] is read-only from here on)
+  // input gradients: the shared part from gS, the difference part dE from dy
+  const int pbs = PL_F1BS + l - 1, pbe = PL_F1BE + l - 1;
+  RdEpi eb = epi_make(RD_EPI_PLAIN);
+  eb.out16 = a16;
+  RdSliceMap map;
+  fastd_dgrad_slice_map(map.src);
+  if (a16) {
+    // the forward forms U re-ordered by tap ([Cin][Cout] is already the [N][K] layout of these GEMMs)
+    {
+      ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+      hipLaunchKernelGGL(k_blocks_to_bf16, dim3((unsigned)std::min<long>((cc / 8 + 255) / 256, 64), 48), dim3(256), 0, st,
+                         h->fU[l], (unsigned short*)h->bUT, cc, map);
+    }
+    RD_TRY(launch_conv16(h, h->plans[pbs], h->d_plans + pbs, B, h->fgS, h->bUT, gups[l], eb, st, RDGAN_TAG_GCONV_DGRAD));
+    RD_TRY(launch_conv16(h, h->plans[pbe], h->d_plans + pbe, B, dys[l], h->bUT, h->fdE, eb, st, RDGAN_TAG_GCONV_DGRAD));
+  } else {
+    hipLaunchKernelGGL(k_transpose_map, dim3((h->gch[l] + 31) / 32, (h->gch[l - 1] + 31) / 32, 48), dim3(256), 0, st, h->fU[l],
+                       h->fUT, h->gch[l - 1], h->gch[l], map);
+    RD_TRY(launch_conv(h, h->plans[pbs], h->d_plans + pbs, B, h->fgS, h->fUT, h->gch[l - 1], gups[l], eb, st, RDGAN_TAG_GCONV_DGRAD));
+    RD_TRY(launch_conv(h, h->plans[pbe], h->d_plans + pbe, B, dys[l], h->fUT, h->gch[l - 1], h->fdE, eb, st, RDGAN_TAG_GCONV_DGRAD));
+  }
+  // dx += adjoint of the differencing of dE: by the PixelNorm backward of block l - 1 (fp32 storage: both of its kernels take
+  // dE; nothing else reads the combined dx), else in a pass of its own
+  if (!a16 && h->combine_dx_fused && l >= 2) *dE_out = h->fdE;
+  else {
+    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+    const dim3 cg(ew_blocks((long)B * D * P / 4));
+    if (a16) hipLaunchKernelGGL(k_combine_dx<rd_bf16_t>, cg, dim3(256), 0, st, (rd_bf16_t*)gups[l], (const rd_bf16_t*)h->fdE, B, D, P);
+    else hipLaunchKernelGGL(k_combine_dx<float>, cg, dim3(256), 0, st, gups[l], (const float*)h->fdE, B, D, P);
+  }
+  return 0;
+}
+
+// block l in the collapsed form (8 taps per phase on the source grid): weight gradient folded back to 27 taps, bias, input gradient
+static int gen_block_bwd_collapsed(rdgan_handle* h, const GenPass& s, float* grad, int l, int B, hipStream_t st) {
+  const bool a16 = s.a16;
+  const float* x = s.hs[l - 1];
+  const float* dy = s.dys[l];
+  const long cc = (long)h->gch[l - 1] * h->gch[l];
+  int plf = PL_G1FC + l - 1, plb = gen_box_plan(h, PL_G1BC + l - 1, PL_G1BCX + l - 1, B);
+  const int plfx = PL_G1FCX + l - 1;
+  const bool wbox = gen_wgrad_boxes_on(h, plf, plfx);      // weight gradient through the streaming kernels: as the shared-centre ones
+  bool bias_done = false;         // (the slab kernels deliver the bias gradient too)
+  if (upwgrad_slab_on(h, l)) {
+    const SlabRec rec = {plf, plan_flops(h->plans[plf], B), RDGAN_TAG_GCONV_WGRAD};
+    if (l == 3)     // each workgroup owns one phase and keeps its eight tap products in registers over its share of the batch
+      RD_TRY(launch_upconv_wgrad_slab(h, rec, x, dy, h->wpartial, h->wpartial_cap, h->dWc, h->ubias_part, grad + h->goff[2 * l + 1], B, st));
+    else            // the same on block 2's geometry: a workgroup owns (phase, quarter of the 256 input channels)
+      RD_TRY(launch_upconv2_wgrad_slab(h, rec, x, dy, h->wpartial, h->wpartial_cap, h->dWc, h->ubias_part, grad + h->goff[2 * l + 1], B, st));
+    bias_done = true;
+  } else if (a16) {
+    if (wbox && wgrad16_ok(h->plans[plfx], B)) plf = plfx;
+    if (!wgrad16_ok(h->plans[plf], B)) return bad_arg(h, "bf16 storage mode: no bf16 weight-gradient tile for this block");
+    RD_TRY(launch_wgrad16(h, h->plans[plf], h->d_plans + plf, B, x, dy, h->dWc, h->wpartial, h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
+  } else {
+    if (wbox) plf = plfx;
+    RD_TRY(launch_wgrad(h, h->plans[plf], h->d_plans + plf, B, x, dy, h->dWc, h->wpartial, h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
+  }
+  hipLaunchKernelGGL(k_fold_collapsed_wgrad, dim3(ew_blocks(27L * cc / 4)), dim3(256), 0, st, h->dWc, grad + h->goff[2 * l], (int)cc);
+  if (!bias_done)
+    RD_TRY(launch_colsum(h, dy, (long)B * h->gpix[l], h->gch[l], grad + h->goff[2 * l + 1], side_fork(h, st), a16));   // bias gradient, beside the GEMMs (dys[l] is read-only from here on)
+  if (a16) {      // the collapsed forms re-ordered by tap are already [N = Cin][K = Cout]
+    RdSliceMap map;
+    collapsed_dgrad_slice_map(map.src);
+    hipLaunchKernelGGL(k_blocks_to_bf16, dim3((unsigned)std::min<long>((cc / 8 + 255) / 256, 64), 64), dim3(256), 0, st,
+                       h->GWC[l], (unsigned short*)h->bG1B, cc, map, h->conv_f16 ? (unsigned short*)h->fG1B : nullptr, h->gch[l]);
+    RdEpi eb = epi_make(RD_EPI_PLAIN);
+    eb.out16 = 1;
+    RD_TRY(launch_conv16(h, h->plans[plb], h->d_plans + plb, B, dy, h->bG1B, s.gups[l], eb, st, RDGAN_TAG_GCONV_DGRAD, h->conv_f16 ? h->fG1B : nullptr));
+  } else RD_TRY(launch_conv(h, h->plans[plb], h->d_plans + plb, B, dy, h->GWD[l], h->gch[l - 1], s.gups[l], epi_make(RD_EPI_PLAIN), st, RDGAN_TAG_GCONV_DGRAD));
+  return 0;
+}
+
+// block l in the direct 27-tap form ("collapse" off): the gradient wrt the block input stays on the upsampled grid
+static int gen_block_bwd_direct(rdgan_handle* h, const GenPass& s, float* grad, int l, int B, hipStream_t st) {
+  const int plf = PL_G1F + l - 1, plb = PL_G1B + l - 1;
+  RD_TRY(launch_wgrad(h, h->plans[plf], h->d_plans + plf, B, s.hs[l - 1], s.dys[l], grad + h->goff[2 * l], h->wpartial, h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
+  RD_TRY(launch_colsum(h, s.dys[l], (long)B * h->gpix[l], h->gch[l], grad + h->goff[2 * l + 1], side_fork(h, st)));
+  RD_TRY(launch_conv(h, h->plans[plb], h->d_plans + plb, B, s.dys[l], h->GWT[l], h->gch[l - 1], s.gups[l], epi_make(RD_EPI_PLAIN), st, RDGAN_TAG_GCONV_DGRAD));
+  return 0;
+}
+
+// Dense (T:326): (pool the upsample adjoint,) LeakyReLU', then dW = xcat^T ga0, db = colsum(ga0)
+static int gen_dense_bwd(rdgan_handle* h, const GenPass& s, float* grad, int B, hipStream_t st) {
+  {
+    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
+    const dim3 lg(ew_blocks((long)B * h->gpix[0] * 64));
+    if (s.col && s.a16) hipLaunchKernelGGL(k_lrelu_bwd<rd_bf16_t>, lg, dim3(256), 0, st, (const rd_bf16_t*)h->gup1, (const rd_bf16_t*)h->h0, h->ga0,
+                         (long)B * h->gpix[0] * 64);
+    else if (s.col) hipLaunchKernelGGL(k_lrelu_bwd<float>, lg, dim3(256), 0, st, (const float*)h->gup1, (const float*)h->h0, h->ga0, (long)B * h->gpix[0] * 64);
+    else hipLaunchKernelGGL(k_pool_lrelu_bwd, lg, dim3(256), 0, st, h->gup1, h->h0, h->ga0, (long)B * h->gpix[0], h->gdim[0][0], h->gdim[0][1], h->gdim[0][2], 256);
+  }
+  RD_TRY(launch_wgrad(h, h->plans[PL_GDENSE], h->d_plans + PL_GDENSE, B, h->xcat, h->ga0, grad + h->goff[0], h->wpartial,
+                      h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
+  return launch_colsum(h, h->ga0, B, h->n_nodes, grad + h->goff[1], side_fork(h, st));   // (same stream as the other column sums: they share their scratch)
+}
+
 extern "C" int rdgan_gen_grad(rdgan_handle* h, const float* dp, const float* gp, const float* z, const float* cond,
                               uint64_t seed, float* grad, int B, void* stream) {
   return rdgan_gen_grad_after(h, dp, gp, z, cond, seed, grad, B, nullptr, stream);
@@ -2111,7 +2370,6 @@ extern "C" int rdgan_gen_grad_after(rdgan_handle* h, const float* dp, const floa
   if (!h || !dp || !gp || !z || !cond || !grad) return bad_arg(h, "gen_grad: null pointer");
   if (B < 1 || B > h->MB) return bad_arg(h, "gen_grad: B outside [1, max_batch]");
   hipStream_t st = (hipStream_t)stream;
-  const int nd = h->nd;
   // the forward issued by the last critic step (rdgan_critic_grad_ahead) is this step's when it was made from the same
   // generator slab (pointer and content version), latent and condition buffers and batch size; otherwise it is dropped
   const bool ahead = h->ahead_pending && gp == h->ahead_gp && z == h->ahead_z && cond == h->ahead_cond && B == h->ahead_B &&
@@ -2140,242 +2398,21 @@ extern "C" int rdgan_gen_grad_after(rdgan_handle* h, const float* dp, const floa
   RD_TRY(critic_forward_impl(h, dp, B, seed, st));              // critic frozen, dropout active (T:395,405)
   RD_TRY(critic_dgrad_chain(h, dp, B, B, 1, seed, st));
   RD_TRY(critic_input_grad(h, dp, h->du[1], B, st));                 // g0 = dL/d fake
-  const bool a16 = h->a16 != 0;
-  const long npix3 = (long)B * h->gpix[3];
-  {
-    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    long ncol = (long)B * nd * nd;
-    hipLaunchKernelGGL(k_softmax_bwd, dim3((unsigned)((ncol + 63) / 64)), dim3(64), 0, st, h->fake, h->g0, h->dl, B,
-                       RDGAN_NHOURS, nd, nd);
-  }
-  // last conv (64 -> 1, T:345): weight grad [27][64], bias grad, input grad.  Direct form (h->g9_direct): straight from the
-  // 1-channel dlogits with the four neighbouring hour planes in LDS -- no im2col matrix, and the input gradient goes
-  // through block 3's PixelNorm+LeakyReLU backward in the same kernel (below); needs the planes to fit in LDS.
-  const size_t g9_lds = 4 * (size_t)(nd + 2) * (nd + 2) * sizeof(float);
-  const bool g9_direct = h->g9_direct && g9_lds <= 96 * 1024 &&
-                         g9w_partial_floats(B * (RDGAN_NHOURS / 2)) <= h->wpartial_cap;
-  if (a16 && !g9_direct) return bad_arg(h, "bf16 storage mode needs the direct backward of the last conv (g9_direct)");
-  if (g9_direct) {
-    RD_TRY(ensure_lds(h, a16 ? (const void*)k_g9_bwd_pairs<rd_bf16_t> : (const void*)k_g9_bwd_pairs<float>, 96 * 1024));
-    // weight gradient on the matrix pipe, the h3 tensor streamed once (rdgan_edge.hip.h), where its partial rows fit
-    const bool mfma = h->edge_kernels && g9w_mfma_ok(nd, npix3) && g9w_partial_floats(g9w_groups(true, B, nd)) <= h->wpartial_cap;
-    RD_TRY(launch_g9_wgrad(h, {PL_G9B, 2.0 * npix3 * 64 * 27, RDGAN_TAG_GCONV_WGRAD}, mfma, a16, h->dl, h->h3, h->wpartial, h->wpartial_cap,
-                           grad + h->goff[8], B, nd, st));
-  } else {
-    {
-      ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-      hipLaunchKernelGGL(k_dl_im2col, dim3(ew_blocks(npix3 * 8)), dim3(256), 0, st, h->dl, h->P9, B, RDGAN_NHOURS, nd, nd);
-    }
-    RD_TRY(launch_wgrad(h, h->plans[PL_G9B], h->d_plans + PL_G9B, B, h->P9, h->h3, grad + h->goff[8], h->wpartial,
-                        h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
-    RD_TRY(launch_conv(h, h->plans[PL_G9B], h->d_plans + PL_G9B, B, h->P9, gp + h->goff[8], 64, h->gh3,
-                       epi_make(RD_EPI_PLAIN), st, RDGAN_TAG_GCONV_DGRAD));
-  }
-  {   // bias gradient of the last conv = sum of dl: on the side stream (dl is not written again in this call)
-    hipStream_t cs = side_fork(h, st);
-    RD_TRY(launch_colsum(h, h->dl, npix3 / 64, 64, h->g9b_tmp, cs));   // 64 partial sums of dl (npix3 % 64 == 0)
-    RD_TRY(launch_colsum(h, h->g9b_tmp, 64, 1, grad + h->goff[9], cs));
-  }
-  // three [upsample, conv, pixelnorm, lrelu] blocks, last to first
-  float* hs[4] = {h->h0, h->h1, h->h2, h->h3};
-  float* rs[4] = {nullptr, h->r1, h->r2, h->r3};
-  float* dys[4] = {nullptr, h->dy1, h->dy2, h->gh3};
-  float* gups[4] = {nullptr, h->gup1, h->gup2, h->gup3};   // direct: gradient on the upsampled grid; collapsed: on the source grid
-  const int col = h->collapse;
-  const float* dE_in = nullptr;     // "combine_dx_fused": block l + 1 has left gups[l + 1] without its difference part, which block l's PixelNorm backward folds in
-  if (col) {
-    RdSliceMap map;
-    collapsed_dgrad_slice_map(map.src);
-    for (int l = 1; l <= 3; ++l) {   // Wd[q][Cout][Cin] <- Wc (written by gen_forward_impl above unless that block ran in the shared-centre form)
-      if (gen_block_fast(h, l, fast_bwd_on(h))) continue;
-      if (gen_block_fast(h, l, fast_fwd_on(h)))
-        hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * h->gch[l - 1] * h->gch[l])), dim3(256), 0, st,
-                           gp + h->goff[2 * l], h->GWC[l], h->gch[l - 1] * h->gch[l]);
-      if (a16) continue;              // (bf16 storage: the input gradient reads the bf16 image of Wc re-ordered by tap, below)
-      hipLaunchKernelGGL(k_transpose_map, dim3((h->gch[l] + 31) / 32, (h->gch[l - 1] + 31) / 32, 64), dim3(256), 0, st,
-                         h->GWC[l], h->GWD[l], h->gch[l - 1], h->gch[l], map);
-    }
-  }
+  // back through the generator: the last conv, then three [upsample, conv, pixelnorm, lrelu] blocks, last to first, then Dense
+  const GenPass s = gen_pass(h, B);
+  RD_TRY(gen_last_conv_bwd(h, s, gp, grad, B, st));
+  RD_TRY(gen_build_dgrad_forms(h, s, gp, st));
+  const float* dE = nullptr;      // block l + 1's gradient wrt its hour differences, handed to block l's PixelNorm backward
   for (int l = 3; l >= 1; --l) {
+    RD_TRY(gen_block_pn_bwd(h, s, gp, l, B, dE, st));
+    dE = nullptr;
     // shared-centre backward only where the hour axis is long enough to pay for its (D+1)/D boundary plane
-    const bool fast = gen_block_fast(h, l, fast_bwd_on(h));
-    if (l == 3 && g9_direct) {
-      // input gradient of the 64 -> 1 conv + block 3's PixelNorm+LeakyReLU backward (+ plane-pair sums)
-      ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-      if (a16 && !fast && h->g9_bwd_mfma && (nd * nd) % 32 == 0) {
-        // exact fp32 products on the matrix pipe, the row's backward in registers (rdgan_g9bwd16.hip.h)
-        const int PP = nd <= 16 ? 4 : 1;        // plane pairs per unit (ten staged planes = 13 KB at ndomain 16; 3 B units deal evenly to 768 workgroups)
-        const size_t lds9 = (size_t)(2 * PP + 2) * (nd + 2) * (nd + 2) * sizeof(float);
-        const int nunits = B * (RDGAN_NHOURS / 2 / PP);
-        RD_TRY(ensure_lds(h, (const void*)k_g9_bwd_mfma16, lds9));
-        hipLaunchKernelGGL(k_g9_bwd_mfma16, dim3((unsigned)std::min(nunits, PP > 1 ? 768 : 1536)), dim3(256), lds9, st, h->dl, gp + h->goff[8],
-                           (const rd_bf16_t*)hs[3], rs[3], (rd_bf16_t*)dys[3], nunits, RDGAN_NHOURS, nd, nd, PP);
-      } else
-      if (a16) hipLaunchKernelGGL(k_g9_bwd_pairs<rd_bf16_t>, dim3(B * (RDGAN_NHOURS / 2)), dim3(256), g9_lds, st, h->dl, gp + h->goff[8],
-                                  (const rd_bf16_t*)hs[3], rs[3], (rd_bf16_t*)dys[3], fast ? (rd_bf16_t*)h->fgS : (rd_bf16_t*)nullptr,
-                                  RDGAN_NHOURS, nd, nd);
-      else hipLaunchKernelGGL(k_g9_bwd_pairs<float>, dim3(B * (RDGAN_NHOURS / 2)), dim3(256), g9_lds, st, h->dl, gp + h->goff[8],
-                              (const float*)hs[3], rs[3], dys[3], fast ? h->fgS : (float*)nullptr, RDGAN_NHOURS, nd, nd);
-      RD_CHECK(h, hipGetLastError());
-    } else if (fast) {
-      ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-      const long HW = (long)h->gdim[l][1] * h->gdim[l][2];
-      RD_TRY(launch_pn_bwd_pairs(h, l == 3 ? h->gh3 : gups[l + 1], hs[l], rs[l], dys[l], h->fgS, (long)B * h->gdim[l - 1][0] * HW,
-                                 HW, h->gch[l], st, a16, l == 3 ? nullptr : dE_in, h->gdim[l - 1][0]));
-    } else {
-      ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-      if (l == 3) RD_TRY(launch_pn_bwd(h, h->gh3, hs[3], rs[3], dys[3], npix3, 64, 0, 0, 0, 0, st, a16));
-      else RD_TRY(launch_pn_bwd(h, gups[l + 1], hs[l], rs[l], dys[l], (long)B * h->gpix[l], h->gch[l], col ? 0 : 1,
-                                h->gdim[l][0], h->gdim[l][1], h->gdim[l][2], st, a16, dE_in));
-    }
-    dE_in = nullptr;
-    const long cc = (long)h->gch[l - 1] * h->gch[l];
-    if (fast) {
-      // shared-centre form along d: E = d-differences of the block input, gS = sums of the output-gradient plane pairs
-      const int* sd = h->gdim[l - 1];
-      const int D = sd[0];
-      const long P = (long)sd[1] * sd[2] * h->gch[l - 1];
-      RdWeightMap wm;
-      fastd_weight_map(wm);
-      {
-        ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-        if (!gen_block_fast(h, l, fast_fwd_on(h))) {      // (otherwise the forward pass above has left both)
-          const dim3 dg(ew_blocks((long)B * (D + 1) * P / 4));
-          if (a16) hipLaunchKernelGGL(k_diff_d<rd_bf16_t>, dg, dim3(256), 0, st, (const rd_bf16_t*)hs[l - 1], (rd_bf16_t*)h->fE[l], B, D, P);
-          else
-          hipLaunchKernelGGL(k_diff_d<float>, dg, dim3(256), 0, st, (const float*)hs[l - 1],
-                             h->fE[l], B, D, P);
-          hipLaunchKernelGGL(k_weight_transform, dim3(ew_blocks(48L * cc / 4)), dim3(256), 0, st, gp + h->goff[2 * l], h->fU[l],
-                             (int)cc, 48, wm);
-        }
-      }
-      // weight gradients of the three tap groups: E[s] x even planes, x x plane sums, E[s+1] x odd planes
-      const float* wsrc[3] = {h->fE[l], hs[l - 1], h->fE[l]};
-      const float* wdy[3] = {dys[l], h->fgS, dys[l]};
-      for (int g = 0; g < 3; ++g) {
-        int pl = PL_F1WA + 3 * g + l - 1;
-        // fp32 storage: the (h, w) border boxes of the block (12 % of its row-tap products are products with a zero row)
-        // -- where they drop at least a fifth of the work (block 2: 23 %, 0.237 -> 0.219 ms per launch; block 3's 12 % do not pay
-        // for the extra partial slabs and short row tiles of its 256 x 64 tiling: 0.43 -> 0.51 ms, measured)
-        if (!a16 && h->wgrad_boxes && h->border_boxes && h->wave_spec && wgrad_box_ok(h->plans[PL_F1WAX + 3 * g + l - 1]) &&
-            (h->border_boxes >= 2 || plan_flops(h->plans[PL_F1WAX + 3 * g + l - 1], 1) < 0.8 * plan_flops(h->plans[pl], 1)))
-          pl = PL_F1WAX + 3 * g + l - 1;
-        if (a16) {
-          if (!wgrad16_ok(h->plans[pl], B)) return bad_arg(h, "bf16 storage mode: no bf16 weight-gradient tile for this block");
-          RD_TRY(launch_wgrad16(h, h->plans[pl], h->d_plans + pl, B, wsrc[g], wdy[g], h->fdU, h->wpartial, h->wpartial_cap, st,
-                                RDGAN_TAG_GCONV_WGRAD));
-        } else
-        RD_TRY(launch_wgrad(h, h->plans[pl], h->d_plans + pl, B, wsrc[g], wdy[g], h->fdU, h->wpartial, h->wpartial_cap, st,
-                            RDGAN_TAG_GCONV_WGRAD));
-      }
-      hipLaunchKernelGGL(k_weight_transform_adj, dim3(ew_blocks(27L * cc / 4)), dim3(256), 0, st, h->fdU, grad + h->goff[2 * l],
-                         (int)cc, 48, wm);
-      RD_TRY(launch_colsum(h, dys[l], (long)B * h->gpix[l], h->gch[l], grad + h->goff[2 * l + 1], side_fork(h, st), a16));   // bias gradient, beside the GEMMs (dys[l] is read-only from here on)
-      const int pbs = PL_F1BS + l - 1, pbe = PL_F1BE + l - 1;
-      RdEpi eb = epi_make(RD_EPI_PLAIN);
-      eb.out16 = a16;
-      if (a16) {
-        // the forward forms U re-ordered by tap ([Cin][Cout] is already the [N][K] layout of these GEMMs)
-        RdSliceMap map;
-        fastd_dgrad_slice_map(map.src);
-        {
-          ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-          hipLaunchKernelGGL(k_blocks_to_bf16, dim3((unsigned)std::min<long>((cc / 8 + 255) / 256, 64), 48), dim3(256), 0, st,
-                             h->fU[l], (unsigned short*)h->bUT, cc, map);
-        }
-        RD_TRY(launch_conv16(h, h->plans[pbs], h->d_plans + pbs, B, h->fgS, h->bUT, gups[l], eb, st, RDGAN_TAG_GCONV_DGRAD));
-        RD_TRY(launch_conv16(h, h->plans[pbe], h->d_plans + pbe, B, dys[l], h->bUT, h->fdE, eb, st, RDGAN_TAG_GCONV_DGRAD));
-      } else {
-        {
-          RdSliceMap map;
-          fastd_dgrad_slice_map(map.src);
-          hipLaunchKernelGGL(k_transpose_map, dim3((h->gch[l] + 31) / 32, (h->gch[l - 1] + 31) / 32, 48), dim3(256), 0, st, h->fU[l],
-                             h->fUT, h->gch[l - 1], h->gch[l], map);
-        }
-        RD_TRY(launch_conv(h, h->plans[pbs], h->d_plans + pbs, B, h->fgS, h->fUT, h->gch[l - 1], gups[l], eb, st,
-                           RDGAN_TAG_GCONV_DGRAD));
-        RD_TRY(launch_conv(h, h->plans[pbe], h->d_plans + pbe, B, dys[l], h->fUT, h->gch[l - 1], h->fdE, eb, st,
-                           RDGAN_TAG_GCONV_DGRAD));
-      }
-      // dx += adjoint of the differencing of dE: by the PixelNorm backward of block l - 1 (fp32 storage: both of its kernels take
-      // dE; nothing else reads the combined dx), else in a pass of its own
-      if (!a16 && h->combine_dx_fused && l >= 2) dE_in = h->fdE;
-      else {
-        ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-        const dim3 cg(ew_blocks((long)B * D * P / 4));
-        if (a16) hipLaunchKernelGGL(k_combine_dx<rd_bf16_t>, cg, dim3(256), 0, st, (rd_bf16_t*)gups[l], (const rd_bf16_t*)h->fdE, B, D, P);
-        else hipLaunchKernelGGL(k_combine_dx<float>, cg, dim3(256), 0, st, gups[l], (const float*)h->fdE, B, D, P);
-      }
-    } else if (col) {
-      int plf = PL_G1FC + l - 1, plb = gen_box_plan(h, PL_G1BC + l - 1, PL_G1BCX + l - 1, B);
-      // weight gradient through the streaming kernels: on the boxes where they drop a fifth of the work (as the shared-centre ones)
-      const int plfx = PL_G1FCX + l - 1;
-      const bool wbox = h->wgrad_boxes && h->border_boxes && h->wave_spec && wgrad_box_ok(h->plans[plfx]) &&
-                        (h->border_boxes >= 2 || plan_flops(h->plans[plfx], 1) < 0.8 * plan_flops(h->plans[plf], 1));
-      bool bias_done = false;         // (the slab kernel delivers the bias gradient too)
-      if (a16 && l == 3 && h->upwgrad_slab && h->nd == 16) {
-        // each workgroup owns one phase and keeps its eight tap products in registers over its share of the batch
-        RD_TRY(launch_upconv_wgrad_slab(h, {plf, plan_flops(h->plans[plf], B), RDGAN_TAG_GCONV_WGRAD}, hs[l - 1], dys[l], h->wpartial,
-                                        h->wpartial_cap, h->dWc, h->ubias_part, grad + h->goff[2 * l + 1], B, st));
-        bias_done = true;
-      } else if (a16 && l == 2 && h->upwgrad_slab && h->nd == 16) {
-        // the same on block 2's geometry: a workgroup owns (phase, quarter of the 256 input channels)
-        RD_TRY(launch_upconv2_wgrad_slab(h, {plf, plan_flops(h->plans[plf], B), RDGAN_TAG_GCONV_WGRAD}, hs[l - 1], dys[l], h->wpartial,
-                                         h->wpartial_cap, h->dWc, h->ubias_part, grad + h->goff[2 * l + 1], B, st));
-        bias_done = true;
-      } else if (a16) {
-        if (wbox && wgrad16_ok(h->plans[plfx], B)) plf = plfx;
-        if (!wgrad16_ok(h->plans[plf], B)) return bad_arg(h, "bf16 storage mode: no bf16 weight-gradient tile for this block");
-        RD_TRY(launch_wgrad16(h, h->plans[plf], h->d_plans + plf, B, hs[l - 1], dys[l], h->dWc, h->wpartial, h->wpartial_cap, st,
-                              RDGAN_TAG_GCONV_WGRAD));
-      } else {
-      if (wbox) plf = plfx;
-      RD_TRY(launch_wgrad(h, h->plans[plf], h->d_plans + plf, B, hs[l - 1], dys[l], h->dWc, h->wpartial, h->wpartial_cap,
-                          st, RDGAN_TAG_GCONV_WGRAD));
-      }
-      hipLaunchKernelGGL(k_fold_collapsed_wgrad, dim3(ew_blocks(27L * cc / 4)), dim3(256), 0, st, h->dWc,
-                         grad + h->goff[2 * l], (int)cc);
-      if (!bias_done)
-      RD_TRY(launch_colsum(h, dys[l], (long)B * h->gpix[l], h->gch[l], grad + h->goff[2 * l + 1], side_fork(h, st), a16));   // bias gradient, beside the GEMMs (dys[l] is read-only from here on)
-      if (a16) {      // the collapsed forms re-ordered by tap are already [N = Cin][K = Cout]
-        RdSliceMap map;
-        collapsed_dgrad_slice_map(map.src);
-        hipLaunchKernelGGL(k_blocks_to_bf16, dim3((unsigned)std::min<long>((cc / 8 + 255) / 256, 64), 64), dim3(256), 0, st,
-                           h->GWC[l], (unsigned short*)h->bG1B, cc, map, h->conv_f16 ? (unsigned short*)h->fG1B : nullptr, h->gch[l]);
-        RdEpi eb = epi_make(RD_EPI_PLAIN);
-        eb.out16 = 1;
-        RD_TRY(launch_conv16(h, h->plans[plb], h->d_plans + plb, B, dys[l], h->bG1B, gups[l], eb, st, RDGAN_TAG_GCONV_DGRAD,
-                             h->conv_f16 ? h->fG1B : nullptr));
-      } else
-      RD_TRY(launch_conv(h, h->plans[plb], h->d_plans + plb, B, dys[l], h->GWD[l], h->gch[l - 1], gups[l],
-                         epi_make(RD_EPI_PLAIN), st, RDGAN_TAG_GCONV_DGRAD));
-    } else {
-      int plf = PL_G1F + l - 1, plb = PL_G1B + l - 1;
-      RD_TRY(launch_wgrad(h, h->plans[plf], h->d_plans + plf, B, hs[l - 1], dys[l], grad + h->goff[2 * l], h->wpartial,
-                          h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
-      RD_TRY(launch_colsum(h, dys[l], (long)B * h->gpix[l], h->gch[l], grad + h->goff[2 * l + 1], side_fork(h, st)));
-      RD_TRY(launch_conv(h, h->plans[plb], h->d_plans + plb, B, dys[l], h->GWT[l], h->gch[l - 1], gups[l],
-                         epi_make(RD_EPI_PLAIN), st, RDGAN_TAG_GCONV_DGRAD));
-    }
+    if (gen_block_fast(h, l, fast_bwd_on(h))) RD_TRY(gen_block_bwd_shared_centre(h, s, gp, grad, l, B, &dE, st));
+    else if (s.col) RD_TRY(gen_block_bwd_collapsed(h, s, grad, l, B, st));
+    else RD_TRY(gen_block_bwd_direct(h, s, grad, l, B, st));
   }
-  // Dense (T:326): (pool the upsample adjoint,) LeakyReLU', then dW = xcat^T ga0, db = colsum(ga0)
-  {
-    ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    const dim3 lg(ew_blocks((long)B * h->gpix[0] * 64));
-    if (col && a16)
-      hipLaunchKernelGGL(k_lrelu_bwd<rd_bf16_t>, lg, dim3(256), 0, st, (const rd_bf16_t*)h->gup1, (const rd_bf16_t*)h->h0, h->ga0,
-                         (long)B * h->gpix[0] * 64);
-    else if (col)
-      hipLaunchKernelGGL(k_lrelu_bwd<float>, lg, dim3(256), 0, st, (const float*)h->gup1, (const float*)h->h0, h->ga0,
-                         (long)B * h->gpix[0] * 64);
-    else
-      hipLaunchKernelGGL(k_pool_lrelu_bwd, lg, dim3(256), 0, st, h->gup1, h->h0,
-                         h->ga0, (long)B * h->gpix[0], h->gdim[0][0], h->gdim[0][1], h->gdim[0][2], 256);
-  }
-  RD_TRY(launch_wgrad(h, h->plans[PL_GDENSE], h->d_plans + PL_GDENSE, B, h->xcat, h->ga0, grad + h->goff[0], h->wpartial,
-                      h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
-  RD_TRY(launch_colsum(h, h->ga0, B, h->n_nodes, grad + h->goff[1], side_fork(h, st)));   // (same stream as the other column sums: they share their scratch)
-  RD_TRY(side_join(h, st, h->ev_join));                 // the bias-gradient sums issued on the side stream above
+  RD_TRY(gen_dense_bwd(h, s, grad, B, st));
+  RD_TRY(side_join(h, st, h->ev_join));                // the bias-gradient sums issued on the side stream above
   {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
     hipLaunchKernelGGL(k_gen_loss, dim3(1), dim3(256), 0, st, h->v, grad + h->n_gen, B, h->d_flag);
