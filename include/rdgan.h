@@ -144,6 +144,9 @@ int rdgan_critic_param_layout(const rdgan_handle* h, long* offsets, long* sizes)
  * instead of 64 tap products per position, algebraically identical.  Forward: T = S x once per output plane pair,
  * then the difference part adds T in its epilogue; backward: plane-pair sums of the output gradient feed the S part,
  * the gradient wrt E is folded back by the adjoint of the differencing.  0 = the 64-tap collapsed form.
+ * "bf16" (default 0; needs "collapse" and "g9_direct" at 1; ndomain <= 72, refused above): the bf16 storage mode -- today's name
+ * of the option introduced as "mfma_bf16" (next entry; the old name is still accepted and sets the same option).  Since then the
+ * activations and activation gradients also live in the workspace as bf16 and the slab kernels listed below exist only in this mode.
  * "mfma_bf16" (default 0; needs the shared-centre form): mixed mode for BASELINE configs 3-5.  The forward,
  * input-gradient, second-sweep and weight-gradient GEMMs of generator blocks 1-3 and critic layers 2-4 read bf16
  * copies of their operands (weight forms stored [N][K]) and run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation;

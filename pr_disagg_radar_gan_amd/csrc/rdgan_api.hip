@@ -42,235 +42,7 @@
 #include "rdgan_verify.hip.h"
 #include "rdgan_temporal.hip.h"
 #include "rdgan_cells.hip.h"
-static_assert(RDGAN_LOSS_SLOTS == 8, "k_critic_losses / k_gen_loss write slots 0..7");
-// k_g9_wgrad_mfma: W a power of two in [8, 128]; dynamic LDS = tile + staged dlogits rows + row descriptors (>= the 32 KB fold)
-static bool g9w_mfma_ok(int nd, long npix) { return nd >= 8 && nd <= 128 && (nd & (nd - 1)) == 0 && npix < 0x7FFFFFFFL; }
-static size_t g9w_mfma_lds(bool bf16) { return std::max<size_t>((size_t)128 * (bf16 ? 128 : 256) + (1440 + 144) * sizeof(float), 32768); }
-
-#define RD_GP_WEIGHT 10.0f   // the literal at T:392
-
-
-
-// one GEMM launch under rdgan_profile_launches: which plan, through which kernel, how many samples and algorithmic FLOPs
-struct RdLaunchRec { int plan, kind, batch; double flops; char kernel[48]; hipEvent_t e0, e1; };
-
-struct rdgan_handle : RdGeom {     // geometry + parameter layout: rdgan_hostplan.h
-  std::string err;
-  // plans
-  std::vector<RdPlan> plans;
-  RdPlan* d_plans = nullptr;
-  RdRow* d_tab = nullptr;
-  // workspace
-  char* ws = nullptr;
-  size_t ws_bytes = 0;
-  float *xcat, *h0, *h1, *r1, *h2, *r2, *h3, *r3, *P9, *fake, *dl, *gh3, *gup3, *dy2, *gup2, *dy1, *gup1, *ga0;
-  float *cin, *dh[5], *du[5], *v, *P1, *g0, *gpv;
-  float* ubias_part = nullptr;    // k_upconv_wgrad_slab16's bias-gradient partials [32 groups][8 phases][64]
-  float *wpartial, *cpartial, *kpartial;
-  size_t wpartial_cap = 0, cpartial_cap = 0, kpartial_cap = 0;
-  float *DWT[5], *W1T, *GWT[4], *W9T, *W1P, *dW1P;
-  // shared-centre form: per block the hour differences E of its input and the 48 weight forms U (written by the forward,
-  // reused by the backward); T / plane sums gS, the gradient wrt E, weight-form gradients and transposes (scratch)
-  float *fE[4], *fU[4], *fgS, *fdE, *fdU, *fUT;
-  // "bf16" storage mode: activations and activation gradients live in the workspace as bf16 (the same float* fields then
-  // point at bf16 data; act_off() does their pointer arithmetic); bf16 weight images of every bf16-MFMA GEMM, rebuilt from
-  // the fp32 master weights inside each call: shared-centre forms [48][N][K] and their tap-reordered input-gradient
-  // stack, critic layers 2-4 forward [27][Cout][Cin] / input gradient [27][Cin][Cout], generator block 1 collapsed forms
-  // [64][Cout][Cin] and (re-ordered by tap) [64][Cin][Cout], the first critic kernel [ldp1][64]
-  void *bU[4], *bUT;
-  void *bWF[5], *bWB[5];
-  void *bG1F[4], *bG1B, *bW1B;
-  void *fWF[5], *fWB[5], *fG1F[4], *fG1B;    // the same images in fragment order (rdgan_gemm_f16.hip.h: rd_wfrag_index), written beside them
-  int wgrad_wide = 0;             // 1: bf16 weight gradients of N % 128 == 0 layers with >= 32768 rows on 256 x 128 tiles, three stages (k_wgrad_gemm_ws16<256,128>): measured SLOWER, default off
-  int conv_f16 = 1;               // 1: bf16 storage mode: the large gather GEMMs by k_conv_gemm_f16 (weights global -> VGPR, 256 x 128 tiles)
-  void* bW3I;                     // weight image of the slab kernel of generator block 3 (rdgan_upconv16.hip.h): 1 MB, MFMA-fragment order
-  int upconv_slab = 1;            // 1: bf16 storage mode, ndomain 16: block 3 forward (collapsed form) by the slab kernel k_upconv_slab16
-  void* bW3T = nullptr;           // weight image of the TILED slab kernel of generator block 3 (rdgan_upconv16t.hip.h): 1 MB, [phase][half][tap][j]
-  int upconv_slab_t = 1;          // 1: bf16 storage mode, source planes larger than 8 x 8 (ndomain 32, 64, ...: multiples of 16): block 3 forward by k_upconv_slab_t16
-  void* bW2I = nullptr;           // weight image of the slab kernel of generator block 2 (rdgan_upconv16b.hip.h): 4 MB
-  int upconv2_slab = 1;           // 1: the same for block 2 (k_upconv2_slab16)
-  int g9_fused = 1;               // 1: with the block-3 slab kernel, the last conv's tap products come out of that kernel's epilogue
-                                  // (no pass over h3; critic steps do not store h3 at all)
-  void* bW9I;                     // A-fragment image of the 64 -> 1 kernel for that epilogue (k_g9_wimg): 4 KB
-  void* bW2S;                     // weight image of the slab kernel of critic layer 2's input gradient (rdgan_d2slab16.hip.h): 432 KB
-  int d3_wgrad_slab = 1;          // 1: bf16 storage mode, ndomain 16: weight gradient of critic layer 3 by k_d3_wgrad_slab16
-  int d2_wgrad_slab = 1;          // 1: bf16 storage mode, ndomain 16: weight gradient of critic layer 2 by k_d2_wgrad_slab16
-  int upwgrad_slab = 1;           // 1: bf16 storage mode, ndomain 16, collapsed form: weight gradient of generator block 3 by k_upconv_wgrad_slab16
-  int d1_dgrad_fused = 1;         // 1: ndomain 16: dD/d(sample) of layer 1 in one pass per sample (k_d1_dgrad_sample16; fp32 storage: k_d1_dgrad_sample32,
-                                  // which in the critic step also takes the penalty's norm pass k_gp_norm_r0)
-  int combine_dx_fused = 1;       // 1: fp32 storage, shared-centre backward: the next PixelNorm backward folds the difference part's gradient into dx itself (no k_combine_dx)
-  int d1_wgrad16 = 1;             // 1: bf16 storage mode: layer-1 weight gradient + bias gradient on the bf16 matrix pipe (k_d1_wgrad16)
-  void* bW2F = nullptr;           // weight image of the slab kernel of critic layer 2's forward (rdgan_d2fwd16.hip.h): 448 KB
-  int d2_fwd_slab = 0;            // 1: bf16 storage mode, ndomain 16: forward of critic layer 2 by k_d2_fwd_slab16 (measured: no faster than the streaming GEMM, default off)
-  unsigned char* g1bits = nullptr; // layer 1's gate in 2 bits per element (written by k_d1_gemm_fwd, read by k_d2_dgrad_slab16): 16 B per row
-  int dense16 = 1;                // 1: bf16 storage mode: the generator's Dense layer on the bf16 matrix pipe (inputs and kernel rounded to bf16, K padded to 64)
-  int dense_skinny = 1;           // 1: ... and, on a handle of max_batch <= 128, by k_dense16_skinny (weights and inputs streamed in fragment order, no LDS)
-  void* xcat16 = nullptr;         // [MB][KP0] bf16
-  void* bW0 = nullptr;            // [n_nodes][KP0] bf16
-  int g9_bwd_mfma = 1;            // 1: bf16 storage mode: input gradient of the last conv + block 3's PixelNorm backward on the fp32 matrix pipe (k_g9_bwd_mfma16)
-  int d1_fwd_sample = 1;          // 1: bf16 storage mode, ndomain 16: layer-1 forward / second sweep with a sample resident in LDS (k_d1_fwd_sample16)
-  int wgrad_boxes = 1;            // 1: the weight gradients of critic layers 2-4 (streaming kernels) on the border-class boxes too
-  int border_boxes = 1;           // 1: forward / second-sweep GEMMs of critic layers 2-4 skip the taps that leave the picture (plan_conv_fwd_boxes)
-  int d2_gate_bits = 1;           // 1: the slab kernel of layer 2's input gradient reads the packed gate instead of layer 1's output
-  int d2_slab = 1;                // 1: bf16 storage mode, ndomain 16: input gradient of critic layer 2 by k_d2_dgrad_slab16
-  int a16 = 0;                    // 1: bf16 storage mode (option "bf16"; needs the collapsed + shared-centre forms)
-  int g9_direct = 1;              // 1: backward of the 64 -> 1 conv straight from the dlogits (no im2col matrix), fused with block 3's PixelNorm backward
-  int fast_fwd = -1;              // 1: forward of generator blocks 2, 3 as shared part T = S x + difference part (48 instead of 64 tap products); -1: by storage mode
-  int fast_bwd = -1;              // 1: generator blocks' weight/input gradients in the shared-centre form along d (48 instead of 64 tap products); -1: by storage mode
-  float *GWC[4], *GWD[4], *dWc;   // collapsed generator weights, their dgrad form, collapsed wgrad scratch
-  int collapse = 1;               // 1: 8-tap collapsed generator blocks (default); 0: direct 27-tap form
-  int tapgather = 1;              // 1: last generator conv sums its in-tile taps in the GEMM epilogue; 0: full column matrix + gather kernel
-  int ws_ksplit = 1;              // 1: split K of mid-size producer/consumer launches to fill whole rounds of workgroups; 0: off; >1: force (tests)
-  int wave_spec = 1;              // 1: producer/consumer (wave-specialised, LDS-DMA) kernel for the big clean GEMMs
-  int resident = 1;               // 1: bf16 forward GEMMs of the shared-centre form keep the tile's source rows resident in LDS (k_conv_gemm_ws<..., RES>)
-  int edge_kernels = 1;           // 1: dedicated streaming kernels for the generator's last conv (rdgan_edge.hip.h); 0: the tiled GEMM kernels
-  int sample_offset = 0;          // global index of this rank's first sample: RandomWeightedAverage's alpha of sample k is uniform(key, sample_offset + k)
-  float* g9b_tmp;                 // 64 partial sums of the last conv's bias gradient
-  float* gp_part;                 // [max_batch][64] partial sums of squares of the penalty's per-sample gradient norm
-  float* dw6_part;                // [16][F] row-slice partial sums of the critic Dense weight gradient
-  // Side stream (option "side_stream", default on): weight-only kernels (generator weight forms, critic weight transposes /
-  // bf16 images) and the bias-gradient column sums run beside the caller's stream, ordered by events: ~50 launches of 5-30 us
-  // per iteration that would otherwise sit between the GEMMs.  Same kernels, same arithmetic: results are bit-identical.
-  int side_on = 1;
-  int split3 = 0;                 // 1: fp32 conv GEMMs of the producer/consumer kernel multiply on the bf16 matrix pipe from 3-way split operands (optional data point)
-  int dense_slices = 0;           // tests: force the row-slice count of the critic Dense weight gradient (0 = by batch size)
-  // test hook "keep_gates": the critic step's second sweep overwrites the x_hat third of h_l in place; with the option on, that
-  // third is copied here first, so that rdgan_debug_activation can return the activations (= LeakyReLU / dropout pattern) of
-  // all 3B samples of the last critic step.  Allocated when the option is set, never inside a step.
-  // Weight-form cache (rdgan_set_weight_versions): the forward forms of the generator (W9T, collapsed / shared-centre forms, their
-  // bf16 images) and the critic's forms (transposes, padded / bf16 images) are functions of the weights alone.  The caller may
-  // assert a content version for each slab; a call whose (pointer, version, form options) equal those the forms in the
-  // workspace were built from skips the weight-only kernels.  Version 0 = unknown: rebuild (the default).
-  uint64_t gver_in = 0, cver_in = 0;
-  const float* gcache_ptr = nullptr; uint64_t gcache_ver = 0; int gcache_cfg = -1;
-  const float* ccache_ptr = nullptr; uint64_t ccache_ver = 0; int ccache_cfg = -1;
-  long form_builds[2] = {0, 0};   // how many times the generator / critic forms were (re)built (tests)
-  int keep_gates = 0;
-  void* gate_keep[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  int gate_keep_B = 0;            // samples held (0: the last call was not a critic step)
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_cw = nullptr, ev_g[4] = {nullptr, nullptr, nullptr, nullptr};
-  int* d_flag;
-  // Generator forward ahead (option "gen_fwd_ahead", default on with fp32 storage; rdgan_critic_grad_ahead): the last critic
-  // step of an iteration issues the NEXT generator step's forward on a stream of its own, forked right after the critic input
-  // is built (from there
-  // on the critic step reads neither h->fake nor any generator activation), beside the critic step's tail and the caller's
-  // Adam.  The generator step then skips its forward and waits for ev_ahead_done in front of its critic forward.  Same kernels,
-  // same plans and splits: results are bit-identical to the option off.  What the early forward writes, against what the rest
-  // of the critic step touches (compute stream st, side stream for the column sums):
-  //   buffer                                   early forward (stream `ahead`)   critic step tail (st / side)
-  //   xcat, xcat16, h0..h3, r1..r3, fE, fgS, P9, fake   written                  not touched (fake read only by the build, before the fork)
-  //   generator weight forms (uncached only)    written                          not touched
-  //   kpartial (split-K partials)               kpartial_ahead (own copy)        kpartial
-  //   non-finite flag                           flag_ahead (own copy)            d_flag (read by k_critic_losses)
-  //   cin, dh, du, v, P1, g0, gpv, gp_part, wpartial, cpartial, dW1P, dw6_part, g1bits, critic forms: tail only
-  // Every other entry that uses the workspace first waits for a forward still pending (ahead_drain).
-  int fwd_ahead = -1;             // 1 on, 0 off, -1 by storage mode: on with fp32 storage (the metric: 11.03 -> 10.77 ms), off in the
-                                  // bf16 mode, whose critic tail leaves no CUs idle (BASELINE configs[2] / [4] shard 0.3-0.6 % slower)
-  hipStream_t ahead = nullptr;
-  hipEvent_t ev_ahead_fork = nullptr, ev_ahead_done = nullptr;
-  float* kpartial_ahead = nullptr;
-  int* flag_ahead = nullptr;
-  bool ahead_pending = false;     // a forward has been issued and not yet consumed / waited for
-  const float *ahead_gp = nullptr, *ahead_z = nullptr, *ahead_cond = nullptr;
-  int ahead_B = 0;
-  uint64_t ahead_gver = 0;
-  // kernels whose dynamic-LDS limit has been raised on THIS handle's device (hipFuncSetAttribute is per device; keeping the
-  // record per handle rather than per process makes two handles on two devices, or on two threads, independent)
-  std::unordered_set<const void*> lds_attr_done;
-  // per-launch profiling (rdgan_profile_launches / rdgan_launch_table): HIP events around every GEMM launch
-  int prof_launches = 0;
-  std::vector<RdLaunchRec> launch_recs;
-  size_t launch_used = 0;
-  char cur_kernel[48] = {0};      // tile name of the launch being issued (set by the launchers while prof_launches is on)
-  // profiling
-  double flops_acc = 0;           // algorithmic FLOPs (2 * rows * taps * K * N of the forms actually run) of every GEMM launched so far
-  unsigned prof_mask = 0;
-  std::vector<hipEvent_t> ev_start[RDGAN_NUM_TAGS], ev_stop[RDGAN_NUM_TAGS];
-  size_t ev_used[RDGAN_NUM_TAGS] = {0};
-};
-
-#define RD_CHECK(h, call)                                                        \
-  do {                                                                           \
-    hipError_t e_ = (call);                                                      \
-    if (e_ != hipSuccess) {                                                      \
-      char b_[512];                                                              \
-      snprintf(b_, sizeof b_, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
-      if (h) (h)->err = b_;                                                      \
-      return (int)e_;                                                            \
-    }                                                                            \
-  } while (0)
-#define RD_TRY(expr)            \
-  do {                          \
-    int r_ = (expr);            \
-    if (r_ != 0) return r_;     \
-  } while (0)
-
-static int bad_arg(rdgan_handle* h, const char* msg) {
-  if (h) h->err = msg;
-  return -2;
-}
-
-// side stream ordered behind everything issued on `st` so far (or `st` itself with the option off)
-static hipStream_t side_fork(rdgan_handle* h, hipStream_t st) {
-  if (!h || !h->side_on || !h->side) return st;
-  if (hipEventRecord(h->ev_fork, st) != hipSuccess || hipStreamWaitEvent(h->side, h->ev_fork, 0) != hipSuccess) return st;
-  return h->side;
-}
-// `st` waits for everything issued on the side stream so far
-static int side_join(rdgan_handle* h, hipStream_t st, hipEvent_t ev);
-
-// raise a kernel's dynamic shared-memory limit once per handle (always, for the handle-less op-level entry points)
-static int ensure_lds(rdgan_handle* h, const void* kern, size_t lds) {
-  if (h && h->lds_attr_done.count(kern)) return 0;
-  RD_CHECK(h, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (h) h->lds_attr_done.insert(kern);
-  return 0;
-}
-
-static int side_join(rdgan_handle* h, hipStream_t st, hipEvent_t ev) {
-  if (!h || !h->side_on || !h->side || st == h->side) return 0;
-  RD_CHECK(h, hipEventRecord(ev, h->side));
-  RD_CHECK(h, hipStreamWaitEvent(st, ev, 0));
-  return 0;
-}
-
-struct ProfScope {
-  rdgan_handle* h; int tag; hipStream_t st; bool on;
-  ProfScope(rdgan_handle* h_, int tag_, hipStream_t st_) : h(h_), tag(tag_), st(st_), on(false) {
-    if (h && tag >= 0 && (h->prof_mask >> tag & 1u) && h->ev_used[tag] < h->ev_start[tag].size()) {
-      on = true;
-      (void)hipEventRecord(h->ev_start[tag][h->ev_used[tag]], st);
-    }
-  }
-  ~ProfScope() {
-    if (on) { (void)hipEventRecord(h->ev_stop[tag][h->ev_used[tag]], st); h->ev_used[tag]++; }
-  }
-};
-
-// plan index of a plan that lives in the handle's table (-1: a temporary plan of the op-level entry points)
-static int plan_index(const rdgan_handle* h, const RdPlan& hp) {
-  if (!h || h->plans.empty()) return -1;
-  const RdPlan* b = h->plans.data();
-  return (&hp >= b && &hp < b + h->plans.size()) ? (int)(&hp - b) : -1;
-}
-// kinds of a recorded launch
-enum { RD_KIND_CONV = 0, RD_KIND_WGRAD = 1, RD_KIND_EDGE = 2 };
-struct LaunchScope {
-  rdgan_handle* h; hipStream_t st; RdLaunchRec* r;
-  LaunchScope(rdgan_handle* h_, int plan, int kind, int batch, double flops, hipStream_t st_) : h(h_), st(st_), r(nullptr) {
-    if (h && h->prof_launches && h->launch_used < h->launch_recs.size()) {
-      r = &h->launch_recs[h->launch_used++];
-      r->plan = plan; r->kind = kind; r->batch = batch; r->flops = flops; r->kernel[0] = 0;
-      h->cur_kernel[0] = 0;
-      (void)hipEventRecord(r->e0, st);
-    }
-  }
-  ~LaunchScope() {
-    if (r) { (void)hipEventRecord(r->e1, st); memcpy(r->kernel, h->cur_kernel, sizeof(r->kernel)); }
-  }
-};
-#define RD_KNAME(h, ...) do { if ((h) && (h)->prof_launches) snprintf((h)->cur_kernel, sizeof((h)->cur_kernel), __VA_ARGS__); } while (0)
+#include "rdgan_handle.h"           // struct rdgan_handle by concern; RD_CHECK / RD_TRY, side_fork / side_join, ensure_lds, the profiling scopes
 #include "rdgan_slab_launch.h"      // one launcher per slab kernel of the bf16 storage mode
 
 // ------------------------------------------------------------------------------------
@@ -881,7 +653,7 @@ extern "C" int rdgan_create(rdgan_handle** out, int ndomain, int n_cond_channels
   if (!out) return -2;
   *out = nullptr;
   if (!rd_geometry_ok(ndomain, n_cond_channels, max_batch)) return -2;
-  rdgan_handle* h = new rdgan_handle();
+  rdgan_handle* h = new rdgan_handle();      // (zeroed, then the initialisers: from here every failure leaves through rdgan_destroy)
   rd_geometry(h, ndomain, n_cond_channels, max_batch);
   const int nd = ndomain;
   const int* gch = h->gch; const int* dch = h->dch;
@@ -889,14 +661,14 @@ extern "C" int rdgan_create(rdgan_handle** out, int ndomain, int n_cond_channels
   {
     std::vector<RdRow> tab;
     std::vector<size_t> first;
-    if (!rd_build_plans(h, h->plans, tab, first)) { delete h; return -2; }
+    if (!rd_build_plans(h, h->plans, tab, first)) { rdgan_destroy(h); return -2; }
     e = hipMalloc((void**)&h->d_tab, sizeof(RdRow) * tab.size());
     if (e == hipSuccess) e = hipMemcpy(h->d_tab, tab.data(), sizeof(RdRow) * tab.size(), hipMemcpyHostToDevice);
     for (int i = 0; i < PL_COUNT; ++i) h->plans[i].tab = h->d_tab + first[i];
   }
   if (e == hipSuccess) e = hipMalloc((void**)&h->d_plans, sizeof(RdPlan) * PL_COUNT);
   if (e == hipSuccess) e = hipMemcpy(h->d_plans, h->plans.data(), sizeof(RdPlan) * PL_COUNT, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { if (h->d_tab) (void)hipFree(h->d_tab); if (h->d_plans) (void)hipFree(h->d_plans); delete h; return (int)e; }
+  if (e != hipSuccess) { rdgan_destroy(h); return (int)e; }
 
   // workspace carve (two passes: size, then assign)
   const long MB = h->MB, NB = h->NB;
@@ -1016,7 +788,7 @@ extern "C" int rdgan_create(rdgan_handle** out, int ndomain, int n_cond_channels
     if (pass == 0) {
       h->ws_bytes = off + 256;
       e = hipMalloc((void**)&h->ws, h->ws_bytes);
-      if (e != hipSuccess) { (void)hipFree(h->d_plans); delete h; return (int)e; }
+      if (e != hipSuccess) { rdgan_destroy(h); return (int)e; }
       (void)hipMemset(h->ws, 0, h->ws_bytes);
     }
   }
@@ -1074,58 +846,33 @@ extern "C" int rdgan_critic_param_layout(const rdgan_handle* h, long* offsets, l
 static bool a16_geometry_ok(int nd) { return 4 * (size_t)(nd + 2) * (nd + 2) * sizeof(float) <= 96 * 1024; }
 #define RD_A16_TOO_LARGE "bf16 storage mode: ndomain too large (the mode supports ndomain <= 72; fp32 storage runs every accepted ndomain)"
 
+// ---- what setting an option does beyond its table row (RD_OPTIONS, rdgan_options.h)
+// "bf16": refused here, not at the first step, on a geometry the mode does not support: the mode stays off
+static int opt_bf16_admit(rdgan_handle* h, int v) {
+  return v && !a16_geometry_ok(h->nd) ? bad_arg(h, RD_A16_TOO_LARGE) : 0;
+}
+// "side_stream": on only where the stream exists
+static int opt_side_stream_value(const rdgan_handle* h, int v) { return (v && h->side) ? 1 : 0; }
+// "keep_gates": the copies are allocated when the option is set, never inside a step
+static int opt_keep_gates_buffers(rdgan_handle* h) {
+  h->gate_keep_B = 0;
+  for (int l = 1; l <= 4 && h->keep_gates; ++l)
+    if (!h->gate_keep[l]) RD_CHECK(h, hipMalloc(&h->gate_keep[l], (size_t)h->MB * h->dL[l] * h->dch[l] * sizeof(float)));
+  return 0;
+}
+
+// (an option that shapes weight forms needs nothing here: its row's flag puts it into rd_form_key, which the form builders compare)
 extern "C" int rdgan_set_option(rdgan_handle* h, const char* name, int value) {
   if (!h || !name) return -2;
-  if (!strcmp(name, "collapse")) { h->collapse = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "wave_specialized")) { h->wave_spec = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }   // 2 = also for small problems (tests)
-  if (!strcmp(name, "bf16") || !strcmp(name, "mfma_bf16")) {      // ("mfma_bf16": round-1 name)
-    if (value && !a16_geometry_ok(h->nd)) return bad_arg(h, RD_A16_TOO_LARGE);       // (refused here, not at the first step: the mode stays off)
-    h->a16 = value ? 1 : 0; return 0;
-  }
-  if (!strcmp(name, "g9_direct")) { h->g9_direct = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "fast_fwd")) { h->fast_fwd = value < 0 ? -1 : (value ? 1 : 0); return 0; }     // -1 = by storage mode
-  if (!strcmp(name, "fast_bwd")) { h->fast_bwd = value < 0 ? -1 : (value ? 1 : 0); return 0; }
-  if (!strcmp(name, "tapgather")) { h->tapgather = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "resident")) { h->resident = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "upconv_slab")) { h->upconv_slab = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "upconv_slab_t")) { h->upconv_slab_t = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "upconv2_slab")) { h->upconv2_slab = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "g9_fused")) { h->g9_fused = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "d1_fwd_sample")) { h->d1_fwd_sample = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "g9_bwd_mfma")) { h->g9_bwd_mfma = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "dense16")) { h->dense16 = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "dense_skinny")) { h->dense_skinny = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "wgrad_boxes")) { h->wgrad_boxes = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "border_boxes")) { h->border_boxes = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }    // 2 = at every size (tests)
-  if (!strcmp(name, "d3_wgrad_slab")) { h->d3_wgrad_slab = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "d2_wgrad_slab")) { h->d2_wgrad_slab = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "upwgrad_slab")) { h->upwgrad_slab = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "d1_dgrad_fused")) { h->d1_dgrad_fused = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "combine_dx_fused")) { h->combine_dx_fused = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "d1_wgrad16")) { h->d1_wgrad16 = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "wgrad_wide")) { h->wgrad_wide = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "conv_f16")) {      // (the forms are rebuilt: their fragment-order twins exist only while the option is on)
-    if (value < 0 || value > 2) return bad_arg(h, "conv_f16: 0, 1 or 2 (2: regardless of the launch size)");
-    h->conv_f16 = value; h->ccache_ver = 0; h->gcache_ver = 0; return 0;
-  }
-  if (!strcmp(name, "d2_fwd_slab")) { h->d2_fwd_slab = value ? 1 : 0; h->ccache_ver = 0; return 0; }
-  if (!strcmp(name, "d2_gate_bits")) { h->d2_gate_bits = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "d2_slab")) { h->d2_slab = value ? 1 : 0; h->ccache_ver = 0; return 0; }
-  if (!strcmp(name, "dense_wgrad_slices")) { h->dense_slices = value; return 0; }
-  if (!strcmp(name, "keep_gates")) {
-    h->keep_gates = value ? 1 : 0;
-    h->gate_keep_B = 0;
-    for (int l = 1; l <= 4 && h->keep_gates; ++l)
-      if (!h->gate_keep[l]) RD_CHECK(h, hipMalloc(&h->gate_keep[l], (size_t)h->MB * h->dL[l] * h->dch[l] * sizeof(float)));
-    return 0;
-  }
-  if (!strcmp(name, "split3")) { h->split3 = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "side_stream")) { h->side_on = (value && h->side) ? 1 : 0; return 0; }
-  if (!strcmp(name, "gen_fwd_ahead")) { h->fwd_ahead = value < 0 ? -1 : (value ? 1 : 0); return 0; }     // -1 = by storage mode
-  if (!strcmp(name, "edge_kernels")) { h->edge_kernels = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }
-  if (!strcmp(name, "sample_offset")) { if (value < 0) return bad_arg(h, "set_option: sample_offset < 0"); h->sample_offset = value; return 0; }
-  if (!strcmp(name, "ws_ksplit")) { h->ws_ksplit = value < 0 ? 0 : (value > 8 ? 8 : value); return 0; }   // > 1 = force (tests)
-  return bad_arg(h, "set_option: unknown option");
+  const RdOptionRow* row = rd_option_find(name);
+  if (!row) return bad_arg(h, "set_option: unknown option");
+  int v = 0;
+  if (!rd_option_normalise(*row, value, &v)) return bad_arg(h, row->refusal);      // ("conv_f16", "sample_offset": their messages)
+  if (row->field == &RdOptions::a16) RD_TRY(opt_bf16_admit(h, v));
+  if (row->field == &RdOptions::side_on) v = opt_side_stream_value(h, v);
+  h->*(row->field) = v;
+  if (row->field == &RdOptions::keep_gates) return opt_keep_gates_buffers(h);
+  return 0;
 }
 
 extern "C" int rdgan_set_weight_versions(rdgan_handle* h, uint64_t gen_version, uint64_t critic_version) {
@@ -1385,8 +1132,7 @@ static void launch_tapsum_softmax(rdgan_handle* h, int gq, float* out, const flo
 // these very weights (same slab, same content version, same form options).  *built: the form kernels were issued.
 static int gen_build_forms(rdgan_handle* h, const float* gp, hipStream_t st, hipStream_t ws, bool* built) {
   const bool a16 = h->a16 != 0;
-  const int gcfg = (h->collapse ? 1 : 0) | (fast_fwd_on(h) ? 2 : 0) | (a16 ? 4 : 0) | (h->upconv_slab ? 8 : 0) | (h->upconv2_slab ? 16 : 0) |
-                   (h->g9_fused && h->tapgather ? 32 : 0) | (h->dense16 ? 64 : 0) | (h->upconv_slab_t ? 128 : 0) | (h->dense_skinny ? 256 : 0);
+  const int gcfg = rd_form_key(h, RD_FORMS_GEN);       // every option this function reads, directly or through a predicate
   *built = !(h->gver_in != 0 && gp == h->gcache_ptr && h->gver_in == h->gcache_ver && gcfg == h->gcache_cfg);
   if (!*built) return 0;
   h->form_builds[0]++;
@@ -1699,7 +1445,7 @@ static bool d2_slab_t_on(const rdgan_handle* h) {
 static bool d2_fwd_slab_on(const rdgan_handle* h) { return h->d2_fwd_slab && h->a16 && h->nd == 16; }
 static int prep_critic_weights(rdgan_handle* h, const float* dp, hipStream_t st) {
   // (skipped when the forms in the workspace were built from these very weights: see rdgan_set_weight_versions)
-  const int ccfg = (h->a16 ? 1 : 0) | (h->d2_slab ? 2 : 0) | (h->d2_fwd_slab ? 4 : 0);
+  const int ccfg = rd_form_key(h, RD_FORMS_CRITIC);    // every option this function reads, directly or through a predicate
   if (h->cver_in != 0 && dp == h->ccache_ptr && h->cver_in == h->ccache_ver && ccfg == h->ccache_cfg) return 0;
   h->form_builds[1]++;
   h->ccache_ptr = nullptr; h->ccache_ver = 0; h->ccache_cfg = -1;     // (valid again only once every form kernel has been issued)
@@ -2920,786 +2666,7 @@ extern "C" int rdgan_op_rng(uint64_t seed, uint32_t stream_id, float* mask_out, 
   return (int)hipStreamSynchronize((hipStream_t)stream);
 }
 
-// ------------------------------------------------------------------------------------
-// input pipeline
-// ------------------------------------------------------------------------------------
-extern "C" int rdgan_data_gather(const float* data, int n_days, int ny, int nx, const int* indices, int n, int ndomain,
-                                 float norm_scale, float* batch_out, float* cond_out, int* flags, void* stream) {
-  if (!data || !indices || !cond_out || !flags || n_days < 1 || n < 1 || ndomain < 1 || ndomain > ny || ndomain > nx) return -2;
-  // *flags accumulates over calls (include/rdgan.h): the caller zeroes it before the first gather and after reading it
-  hipLaunchKernelGGL(k_gather_tiles, dim3(ew_blocks((long)n * ndomain * ndomain)), dim3(256), 0, (hipStream_t)stream, data, n_days,
-                     RDGAN_NHOURS, ny, nx, indices, n, ndomain, norm_scale, batch_out, cond_out, flags);
-  return (int)hipGetLastError();
-}
-
-extern "C" int rdgan_data_valid_tiles(const float* data, int n_days, int ny, int nx, int ndomain, int stride,
-                                      float tp_thresh_daily, int n_thresh, int* valid_out, void* stream) {
-  if (!data || !valid_out || n_days < 1 || ny < 1 || nx < 1 || stride < 1 || ndomain < 1 || ndomain > ny || ndomain > nx) return -2;
-  const int nbi = (ny - ndomain + stride - 1) / stride, nbj = (nx - ndomain + stride - 1) / stride;   // len(range(0, ny-nd, stride))
-  if (nbi < 1 || nbj < 1) return 0;
-  const long blocks = (long)n_days * nbi * nbj;
-  if (blocks > 0xFFFFFFL) return -2;       // one 256-thread block per box and no loop: a launch holds fewer than 2^32 threads
-  hipLaunchKernelGGL(k_valid_tiles, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, data, RDGAN_NHOURS, ny, nx,
-                     ndomain, stride, nbi, nbj, tp_thresh_daily, n_thresh, valid_out);
-  return (int)hipGetLastError();
-}
-
-// training set from raw radar frames (rdgan_radar.hip.h)
-template <int W, int FPH>
-static void launch_radar_hourly(const unsigned char* codes, const float* lut, long n_days, long plane, float* hourly, float* daily,
-                                unsigned long long* missing, hipStream_t st) {
-  const long groups = (plane + W - 1) / W;
-  // (a launch holds fewer than 2^32 threads; the kernel's grid-stride loop takes what lies beyond)
-  const long blocks = std::min<long>((n_days * groups + RD_RADAR_THREADS - 1) / RD_RADAR_THREADS, 0xFFFFFFL);
-  hipLaunchKernelGGL((k_radar_hourly<W, FPH>), dim3((unsigned)blocks), dim3(RD_RADAR_THREADS), 0, st, codes, lut, n_days, plane, groups,
-                     hourly, daily, missing);
-}
-template <int W>
-static void launch_radar_hourly_w(int fph, const unsigned char* codes, const float* lut, long n_days, long plane, float* hourly,
-                                  float* daily, unsigned long long* missing, hipStream_t st) {
-  switch (fph) {
-    case 1: launch_radar_hourly<W, 1>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
-    case 2: launch_radar_hourly<W, 2>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
-    case 3: launch_radar_hourly<W, 3>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
-    case 4: launch_radar_hourly<W, 4>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
-    case 6: launch_radar_hourly<W, 6>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
-    default: launch_radar_hourly<W, 12>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
-  }
-}
-
-extern "C" int rdgan_data_radar_hourly(const unsigned char* codes, const float* lut256, long n_days, int frames_per_hour, int ny, int nx,
-                                       float* hourly_out, float* daily_out, unsigned long long* missing_out, void* stream) {
-  const int f = frames_per_hour;
-  if (!codes || !lut256 || !hourly_out || n_days < 1 || ny < 1 || nx < 1) return -2;
-  if (f != 1 && f != 2 && f != 3 && f != 4 && f != 6 && f != 12) return -2;
-  const long plane = (long)ny * nx;
-  hipStream_t st = (hipStream_t)stream;
-  // 16 codes per lane: every frame and every output row group starts on a 16-byte boundary; 4 per lane: dword loads, float4 stores
-  const uintptr_t out_bits = (uintptr_t)hourly_out | (uintptr_t)daily_out;
-  if (plane % 16 == 0 && (((uintptr_t)codes | out_bits) & 15) == 0)
-    launch_radar_hourly_w<16>(f, codes, lut256, n_days, plane, hourly_out, daily_out, missing_out, st);
-  else if (plane % 4 == 0 && ((uintptr_t)codes & 3) == 0 && (out_bits & 15) == 0)
-    launch_radar_hourly_w<4>(f, codes, lut256, n_days, plane, hourly_out, daily_out, missing_out, st);
-  else
-    launch_radar_hourly_w<1>(f, codes, lut256, n_days, plane, hourly_out, daily_out, missing_out, st);
-  return (int)hipGetLastError();
-}
-
-extern "C" int rdgan_data_daily_sum(const float* hourly, long n_days, int ny, int nx, float* daily_out, void* stream) {
-  if (!hourly || !daily_out || n_days < 1 || ny < 1 || nx < 1) return -2;
-  const long plane = (long)ny * nx;
-  hipLaunchKernelGGL(k_daily_sum, dim3(ew_blocks(n_days * plane)), dim3(256), 0, (hipStream_t)stream, hourly, n_days, plane, daily_out);
-  return (int)hipGetLastError();
-}
-
-extern "C" int rdgan_data_valid_tiles_daily(const float* daily, long n_days, int ny, int nx, int ndomain, int stride,
-                                            float tp_thresh_daily, int n_thresh, int* valid_out, void* stream) {
-  if (!daily || !valid_out || n_days < 1 || ny < 1 || nx < 1 || stride < 1 || ndomain < 1 || ndomain > ny || ndomain > nx) return -2;
-  const int nbi = (ny - ndomain + stride - 1) / stride, nbj = (nx - ndomain + stride - 1) / stride;   // len(range(0, ny-nd, stride))
-  if (nbi < 1 || nbj < 1) return 0;
-  const long boxes = n_days * nbi * nbj;
-  const long blocks = std::min<long>((boxes + 3) / 4, 0xFFFFFFL);      // fewer than 2^32 threads per launch; the kernel loops over the rest
-  hipLaunchKernelGGL(k_valid_tiles_daily, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, daily, boxes, ny, nx, ndomain,
-                     stride, nbi, nbj, tp_thresh_daily, n_thresh, valid_out);
-  return (int)hipGetLastError();
-}
-
-extern "C" int rdgan_crps_ensemble(const float* ens, const float* obs, const float* scale, float* crps_out, int n,
-                                   long npix, void* stream) {
-  if (!ens || !obs || !crps_out || n < 1 || n > 8192 || npix < 1 || npix > 0x7FFFFFFFL) return -2;
-  int npow2 = 2;
-  while (npow2 < n) npow2 <<= 1;
-  hipLaunchKernelGGL(k_crps_ensemble, dim3((unsigned)npix), dim3(256), npow2 * sizeof(float), (hipStream_t)stream, ens, obs,
-                     scale, crps_out, n, npow2, npix);
-  return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// CRPS experiment (rdgan_crps.hip.h): fixed-ensemble CRPS, bootstrapped means, moments
-// ------------------------------------------------------------------------------------
-extern "C" int rdgan_crps_fixed_ensemble(const float* ens, const float* obs, float* crps_out, float* hourly_out, int n,
-                                         long n_days, int nd, void* stream) {
-  if (!ens || !obs || (!crps_out && !hourly_out) || n < 1 || n > RD_CRPS_MAXN || n_days < 1 || nd < 1 || nd > 1024) return -2;
-  const long npos = (long)RDGAN_NHOURS * nd * nd;
-  if (npos > 0x7FFFFFFFL || n_days > 0x7FFFFFFFL / npos) return -2;       // D * npos < 2^31, and the grids below fit
-  hipStream_t st = (hipStream_t)stream;
-  int npow2 = 2;
-  while (npow2 < n) npow2 <<= 1;
-  const size_t lds = (size_t)(n + 1 + RD_CRPS_THREADS) * sizeof(double) + (size_t)npow2 * sizeof(float);
-  RD_TRY(ensure_lds(nullptr, (const void*)k_crps_fixed, lds));
-  // the hourly means are taken over the per-position values: without a caller's buffer they live in a stream-ordered temporary
-  float* per_pos = crps_out;
-  if (!per_pos) {
-    hipError_t e = hipMallocAsync((void**)&per_pos, (size_t)n_days * npos * sizeof(float), st);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(k_crps_fixed, dim3((unsigned)npos), dim3(RD_CRPS_THREADS), lds, st, ens, obs, per_pos, n, npow2, n_days, npos);
-  if (hourly_out)
-    hipLaunchKernelGGL(k_crps_hourly, dim3((unsigned)(n_days * RDGAN_NHOURS)), dim3(256), 0, st, per_pos, hourly_out, nd * nd);
-  hipError_t e = hipGetLastError();
-  if (!crps_out) {
-    hipError_t f = hipFreeAsync(per_pos, st);
-    if (e == hipSuccess) e = f;
-  }
-  return (int)e;
-}
-
-extern "C" int rdgan_bootstrap_means(const double* x, long n, uint64_t seed, long first_resample, long n_resamples,
-                                     double* means_out, void* stream) {
-  if (!x || !means_out || n < 1 || n > 0xFFFFFFFFL || first_resample < 0 || n_resamples < 1 || n_resamples > 0x7FFFFFFFL) return -2;
-  hipLaunchKernelGGL(k_bootstrap_means, dim3((unsigned)n_resamples), dim3(RD_CRPS_THREADS), 0, (hipStream_t)stream, x, (uint32_t)n,
-                     rd_make_key(seed, RD_STREAM_BOOTSTRAP), (uint64_t)first_resample, means_out);
-  return (int)hipGetLastError();
-}
-
-extern "C" int rdgan_moments_f64(const double* x, long n, double* out3, void* stream) {
-  if (!x || !out3 || n < 1) return -2;
-  hipLaunchKernelGGL(k_moments_f64, dim3(1), dim3(RD_CRPS_THREADS), 0, (hipStream_t)stream, x, n, out3);
-  return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// distribution checks (rdgan_dist.hip.h): two-sample KS, box-plot statistics, ECDF on a grid
-// ------------------------------------------------------------------------------------
-static int rd_pow2_at_least(int n) {
-  int p = 2;
-  while (p < n) p <<= 1;
-  return p;
-}
-
-extern "C" int rdgan_ks_2samp(const float* a, const float* b, int n, int m, int ncol, long batch, int* counts_out, double* d_out,
-                              void* stream) {
-  if (!a || !b || !counts_out || !d_out || n < 1 || n > RD_DIST_MAXN || m < 1 || m > RD_DIST_MAXN || ncol < 1 || batch < 1) return -2;
-  if (batch > 0x7FFFFFFFL / ncol) return -2;
-  const int npa = rd_pow2_at_least(n), npb = rd_pow2_at_least(m);
-  RD_TRY(ensure_lds(nullptr, (const void*)k_ks_2samp, RD_KS_LDS_MAX));
-  hipLaunchKernelGGL(k_ks_2samp, dim3((unsigned)(batch * ncol)), dim3(RD_DIST_THREADS),
-                     RD_KS_LDS_HEAD + (size_t)(npa + npb) * sizeof(float), (hipStream_t)stream, a, b, n, m, npa, npb, ncol, counts_out,
-                     d_out);
-  return (int)hipGetLastError();
-}
-
-extern "C" int rdgan_box_stats(const float* x, int n, int ncol, long batch, double* stats_out, float* sorted_out, void* stream) {
-  if (!x || !stats_out || n < 1 || n > RD_DIST_MAXN || ncol < 1 || batch < 1) return -2;
-  if (batch > 0x7FFFFFFFL / ncol) return -2;
-  const int npow2 = rd_pow2_at_least(n);
-  RD_TRY(ensure_lds(nullptr, (const void*)k_box_stats, RD_BOX_LDS_MAX));
-  hipLaunchKernelGGL(k_box_stats, dim3((unsigned)(batch * ncol)), dim3(RD_DIST_THREADS), RD_BOX_LDS_HEAD + (size_t)npow2 * sizeof(float),
-                     (hipStream_t)stream, x, n, npow2, ncol, stats_out, sorted_out);
-  return (int)hipGetLastError();
-}
-
-extern "C" long rdgan_ecdf_workspace_bytes(int n_grid) {
-  if (n_grid < 1 || n_grid > RD_ECDF_MAXT) return -2;
-  return (long)(n_grid + 2) * (long)sizeof(unsigned long long);
-}
-
-extern "C" int rdgan_ecdf_grid(const float* x, long n_values, const float* grid, int n_grid, long long* counts_out, void* workspace,
-                               long workspace_bytes, void* stream) {
-  if (!x || !grid || !counts_out || !workspace || n_values < 1 || n_values > (1L << 40) || n_grid < 1 || n_grid > RD_ECDF_MAXT) return -2;
-  if (((unsigned long long)x & 3) || workspace_bytes < rdgan_ecdf_workspace_bytes(n_grid)) return -2;
-  hipStream_t st = (hipStream_t)stream;
-  unsigned long long* hist = (unsigned long long*)workspace;
-  hipError_t e = hipMemsetAsync(hist, 0, (size_t)(n_grid + 2) * sizeof(unsigned long long), st);
-  if (e != hipSuccess) return (int)e;
-  const long per_block = (long)RD_ECDF_THREADS * 16;                     // four float4 per thread
-  const long blocks = std::max<long>(1, std::min<long>(RD_ECDF_MAXBLOCKS, (n_values + per_block - 1) / per_block));
-  hipLaunchKernelGGL(k_ecdf_grid, dim3((unsigned)blocks), dim3(RD_ECDF_THREADS), (size_t)(2 * n_grid + 2) * sizeof(float), st, x,
-                     n_values, grid, n_grid, hist);
-  hipLaunchKernelGGL(k_ecdf_scan, dim3(1), dim3(RD_DIST_THREADS), 0, st, hist, n_grid, counts_out);
-  return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// whole daily fields (rdgan_field.hip.h): tile scan, condition batch, blend
-// ------------------------------------------------------------------------------------
-static bool rd_field_geometry_ok(long n_days, int ny, int nx, int nd, int overlap) {
-  return rd_geometry_ok(nd, 1, 1) && overlap >= 0 && overlap <= nd / 2 && ny >= nd && nx >= nd && n_days >= 1;
-}
-
-// a small host table for the next launch: a stream-ordered device copy, freed behind the launch by the caller
-static int rd_field_upload(const int* host, size_t n, int** dev, hipStream_t st) {
-  hipError_t e = hipMallocAsync((void**)dev, n * sizeof(int), st);
-  if (e != hipSuccess) return (int)e;
-  e = hipMemcpyAsync(*dev, host, n * sizeof(int), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) {
-    (void)hipFreeAsync(*dev, st);
-    return (int)e;
-  }
-  return 0;
-}
-
-extern "C" int rdgan_field_scan(const float* daily, long n_days, int ny, int nx, int nd, int overlap, int* counts_out, void* stream) {
-  if (!daily || !counts_out || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
-  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
-  if ((long)n_ty * n_tx > 0x7FFFFFFFL / n_days) return -2;                 // an entry number day * T + tile is an int32
-  const long entries = n_days * n_ty * n_tx;
-  const long blocks = std::min<long>((entries + 3) / 4, 0xFFFFFFL);        // the kernel loops over the rest
-  hipLaunchKernelGGL(k_field_scan, dim3((unsigned)blocks), dim3(RD_FIELD_THREADS), 0, (hipStream_t)stream, daily, entries, ny, nx, nd,
-                     step, n_ty, n_tx, counts_out);
-  return (int)hipGetLastError();
-}
-
-extern "C" int rdgan_field_cond(const float* daily, long n_days, int ny, int nx, int nd, int overlap, const int* entries, long m,
-                                double norm_scale, float* cond_out, void* stream) {
-  if (!daily || !entries || !cond_out || m < 1 || !(norm_scale > 0.0) || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
-  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
-  if ((long)n_ty * n_tx > 0x7FFFFFFFL / n_days) return -2;
-  const long n_entries = n_days * n_ty * n_tx;
-  for (long i = 0; i < m; ++i)
-    if (entries[i] < 0 || entries[i] >= n_entries) return -2;
-  hipStream_t st = (hipStream_t)stream;
-  int* dev = nullptr;
-  RD_TRY(rd_field_upload(entries, (size_t)m, &dev, st));
-  hipLaunchKernelGGL(k_field_cond, dim3(ew_blocks(m * nd * nd, RD_FIELD_THREADS)), dim3(RD_FIELD_THREADS), 0, st, daily, dev, m, ny, nx,
-                     nd, step, n_ty, n_tx, norm_scale, cond_out);
-  hipError_t e = hipGetLastError();
-  hipError_t f = hipFreeAsync(dev, st);
-  return (int)(e != hipSuccess ? e : f);
-}
-
-extern "C" int rdgan_field_blend(const float* frac, long m, const int* slots, long units, long first_unit, const int* ytab_idx,
-                                 const float* ytab_w, const int* xtab_idx, const float* xtab_w, const float* daily, long n_days,
-                                 int ny, int nx, int nd, int overlap, float* out, void* stream) {
-  if (!frac || !slots || !ytab_idx || !ytab_w || !xtab_idx || !xtab_w || !daily || !out) return -2;
-  if (m < 1 || m > 0x7FFFFFFFL || units < 1 || first_unit < 0 || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
-  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
-  const long T = (long)n_ty * n_tx;
-  if (T > 0x7FFFFFFFL || units > 0x7FFFFFFFL / T) return -2;
-  for (long i = 0; i < units * T; ++i)
-    if (slots[i] < -1 || slots[i] >= m) return -2;
-  hipStream_t st = (hipStream_t)stream;
-  int* dev = nullptr;
-  RD_TRY(rd_field_upload(slots, (size_t)(units * T), &dev, st));
-  const long nb = units * ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * ((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
-  hipLaunchKernelGGL(k_field_blend, dim3((unsigned)std::min<long>(nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0, st, frac, dev, ytab_idx,
-                     ytab_w, xtab_idx, xtab_w, daily, out, units, first_unit, n_days, ny, nx, nd, step, n_ty, n_tx);
-  hipError_t e = hipGetLastError();
-  hipError_t f = hipFreeAsync(dev, st);
-  return (int)(e != hipSuccess ? e : f);
-}
-
-// ------------------------------------------------------------------------------------
-// ensemble products (rdgan_products.hip.h): k-hour peaks of hourly maps, the blend fused with them, member statistics
-// ------------------------------------------------------------------------------------
-// the window list as the kernels take it: bit w - 1 set for every window w; false for a list that is not strictly increasing in 1 .. 24
-static bool rd_peaks_mask(const int* windows, int n_windows, unsigned* mask) {
-  if (!windows || n_windows < 1 || n_windows > RD_PEAKS_MAXK) return false;
-  unsigned m = 0;
-  for (int i = 0; i < n_windows; ++i) {
-    if (windows[i] < 1 || windows[i] > RD_FIELD_HOURS || (i > 0 && windows[i] <= windows[i - 1])) return false;
-    m |= 1u << (windows[i] - 1);
-  }
-  *mask = m;
-  return true;
-}
-
-extern "C" int rdgan_hourly_peaks(const float* hourly, long units, int ny, int nx, const int* windows, int n_windows, float* peaks_out,
-                                  unsigned char* peak_hour_out, void* stream) {
-  unsigned mask = 0;
-  if (!hourly || !peaks_out || !peak_hour_out || units < 1 || ny < 1 || nx < 1 || !rd_peaks_mask(windows, n_windows, &mask)) return -2;
-  const long nb = ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * (long)((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
-  if (units > (1L << 40) / nb) return -2;
-  hipLaunchKernelGGL(k_hourly_peaks, dim3((unsigned)std::min<long>(units * nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0,
-                     (hipStream_t)stream, hourly, units, ny, nx, mask, windows[0], peaks_out, peak_hour_out);
-  return (int)hipGetLastError();
-}
-
-extern "C" int rdgan_field_blend_peaks(const float* frac, long m, const int* slots, long units, long first_unit, const int* ytab_idx,
-                                       const float* ytab_w, const int* xtab_idx, const float* xtab_w, const float* daily, long n_days,
-                                       int ny, int nx, int nd, int overlap, const int* windows, int n_windows, float* peaks_out,
-                                       unsigned char* peak_hour_out, void* stream) {
-  unsigned mask = 0;
-  if (!frac || !slots || !ytab_idx || !ytab_w || !xtab_idx || !xtab_w || !daily || !peaks_out || !peak_hour_out) return -2;
-  if (m < 1 || m > 0x7FFFFFFFL || units < 1 || first_unit < 0 || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
-  if (!rd_peaks_mask(windows, n_windows, &mask)) return -2;
-  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
-  const long T = (long)n_ty * n_tx;
-  if (T > 0x7FFFFFFFL || units > 0x7FFFFFFFL / T) return -2;
-  for (long i = 0; i < units * T; ++i)
-    if (slots[i] < -1 || slots[i] >= m) return -2;
-  hipStream_t st = (hipStream_t)stream;
-  int* dev = nullptr;
-  RD_TRY(rd_field_upload(slots, (size_t)(units * T), &dev, st));
-  const long nb = units * ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * ((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
-  hipLaunchKernelGGL(k_field_blend_peaks, dim3((unsigned)std::min<long>(nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0, st, frac, dev,
-                     ytab_idx, ytab_w, xtab_idx, xtab_w, daily, peaks_out, peak_hour_out, units, first_unit, n_days, ny, nx, nd, step,
-                     n_ty, n_tx, mask, windows[0]);
-  hipError_t e = hipGetLastError();
-  hipError_t f = hipFreeAsync(dev, st);
-  return (int)(e != hipSuccess ? e : f);
-}
-
-extern "C" int rdgan_member_stats(const float* x, int n_members, long member_stride, long n_positions, const double* probs, int n_probs,
-                                  const double* thresholds, int n_thresholds, float* quantiles_out, float* mean_out, float* exceed_out,
-                                  long long* n_nan_positions_out, void* stream) {
-  if (!x || !probs || !quantiles_out || !mean_out || !n_nan_positions_out) return -2;
-  if (n_members < 1 || n_members > RD_MS_MAXS || n_positions < 1 || n_positions > (1L << 40) || member_stride < n_positions) return -2;
-  if (n_probs < 1 || n_probs > RD_MS_MAXQ || n_thresholds < 0 || n_thresholds > RD_MS_MAXT) return -2;
-  if (n_thresholds > 0 && (!thresholds || !exceed_out)) return -2;
-  rd_ms_args a;
-  memset(&a, 0, sizeof(a));
-  for (int i = 0; i < n_probs; ++i) {
-    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return -2;
-    a.probs[i] = probs[i];
-  }
-  for (int i = 0; i < n_thresholds; ++i) {
-    if (!std::isfinite(thresholds[i])) return -2;
-    a.thr[i] = thresholds[i];
-  }
-  const int np2 = rd_pow2_at_least(n_members);
-  const int px = rd_ms_run_width(np2);
-  int lpx = 0;
-  while ((1 << lpx) < px) ++lpx;
-  hipStream_t st = (hipStream_t)stream;
-  RD_TRY(ensure_lds(nullptr, (const void*)k_member_stats, RD_MS_LDS_MAX));
-  hipError_t e = hipMemsetAsync(n_nan_positions_out, 0, sizeof(long long), st);
-  if (e != hipSuccess) return (int)e;
-  const long runs = (n_positions + px - 1) / px;
-  hipLaunchKernelGGL(k_member_stats, dim3((unsigned)std::min<long>(runs, 1L << 16)), dim3(RD_MS_THREADS),
-                     RD_MS_LDS_HEAD + (size_t)np2 * px * sizeof(float), st, x, member_stride, n_members, np2, lpx, n_positions, n_probs,
-                     n_thresholds, a, quantiles_out, mean_out, exceed_out, (unsigned long long*)n_nan_positions_out);
-  return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// verification of field ensembles (rdgan_verify.hip.h): state accumulation, rank / reliability / Brier reduction, FSS
-// ------------------------------------------------------------------------------------
-// the thresholds as the kernels compare them: each rounded once to fp32; false unless finite, >= 0 and strictly increasing there
-static bool rd_vf_thresholds(const double* thresholds, int n, rd_vf_thr* out) {
-  if (!thresholds || n < 1 || n > RD_VF_MAXT) return false;
-  memset(out, 0, sizeof(*out));
-  for (int i = 0; i < n; ++i) {
-    if (!(thresholds[i] >= 0.0 && thresholds[i] <= 3.4028234663852886e38)) return false;        // (a NaN fails both)
-    const float f = (float)thresholds[i];
-    if (i > 0 && !(f > out->v[i - 1])) return false;
-    out->v[i] = f;
-  }
-  return true;
-}
-
-static bool rd_vf_widths_ok(const int* widths, int n, int S, rd_vf_widths* out) {
-  if (!widths || n < 1 || n > RD_VF_MAXW) return false;
-  memset(out, 0, sizeof(*out));
-  for (int i = 0; i < n; ++i) {
-    if (widths[i] < 1 || widths[i] % 2 == 0 || (i > 0 && widths[i] <= widths[i - 1])) return false;
-    if (widths[i] > 8192 || (long)S * widths[i] * widths[i] >= (1L << 26)) return false;
-    out->v[i] = widths[i];
-  }
-  return true;
-}
-
-template <int V>
-static void rd_vf_launch_accumulate(int T, unsigned blocks, hipStream_t st, const float* x, long stride, int n, long P, const float* obs,
-                                    const rd_vf_thr& thr, int* exceed, int* below, int* equal, unsigned char* bad) {
-#define RD_VF_CASE(TT)                                                                                                              \
-  case TT:                                                                                                                          \
-    hipLaunchKernelGGL((k_verify_accumulate<TT, V>), dim3(blocks), dim3(RD_VF_THREADS), 0, st, x, stride, n, P, obs, thr, exceed,    \
-                       below, equal, bad);                                                                                          \
-    break;
-  switch (T) {
-    RD_VF_CASE(1) RD_VF_CASE(2) RD_VF_CASE(3) RD_VF_CASE(4) RD_VF_CASE(5) RD_VF_CASE(6) RD_VF_CASE(7) RD_VF_CASE(8)
-  }
-#undef RD_VF_CASE
-}
-
-extern "C" int rdgan_verify_accumulate(const float* members, int n_members, long member_stride, long n_positions, const float* obs,
-                                       const double* thresholds, int n_thresholds, int* exceed, int* below, int* equal,
-                                       unsigned char* bad, void* stream) {
-  rd_vf_thr thr;
-  if (!members || !obs || !exceed || !below || !equal || !bad) return -2;
-  if (n_members < 1 || n_members > RD_VF_MAXS || n_positions < 1 || n_positions > (1L << 40) || member_stride < n_positions) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
-  const unsigned long long align = (unsigned long long)members | (unsigned long long)obs | (unsigned long long)exceed |
-                                   (unsigned long long)below | (unsigned long long)equal;
-  if (align & 3) return -2;
-  // 16-byte loads where every row of every array starts on 16 bytes: the member rows (base and stride), the T planes of exceed (P)
-  const bool vec = !(align & 15) && !((unsigned long long)bad & 3) && member_stride % 4 == 0 && n_positions % 4 == 0;
-  const long groups = vec ? n_positions / 4 : n_positions;
-  const unsigned blocks = (unsigned)std::min<long>((groups + RD_VF_THREADS - 1) / RD_VF_THREADS, 1L << 16);
-  if (vec)
-    rd_vf_launch_accumulate<4>(n_thresholds, blocks, (hipStream_t)stream, members, member_stride, n_members, n_positions, obs, thr,
-                               exceed, below, equal, bad);
-  else
-    rd_vf_launch_accumulate<1>(n_thresholds, blocks, (hipStream_t)stream, members, member_stride, n_members, n_positions, obs, thr,
-                               exceed, below, equal, bad);
-  return (int)hipGetLastError();
-}
-
-extern "C" int rdgan_verify_reduce(const float* obs, const int* exceed, const int* below, const int* equal, const unsigned char* bad,
-                                   long n_positions, long plane, int n_members, const double* thresholds, int n_thresholds, int n_bins,
-                                   uint64_t seed, long long* rank_hist_out, long long* reliability_out, long long* brier_out,
-                                   void* stream) {
-  rd_vf_thr thr;
-  if (!obs || !exceed || !below || !equal || !bad || !rank_hist_out || !reliability_out || !brier_out) return -2;
-  if (n_members < 1 || n_members > RD_VF_MAXS || n_bins < 2 || n_bins > std::min(n_members + 1, RD_VF_MAXBINS)) return -2;
-  if (plane < 1 || n_positions < 1 || n_positions > (1L << 40) || n_positions % plane) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
-  const int S = n_members, T = n_thresholds;
-  const long n_planes = n_positions / plane;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(rank_hist_out, 0, (size_t)RD_VF_HOURS * (S + 1) * sizeof(long long), st);
-  if (e == hipSuccess) e = hipMemsetAsync(reliability_out, 0, (size_t)T * RD_VF_HOURS * n_bins * 3 * sizeof(long long), st);
-  if (e == hipSuccess) e = hipMemsetAsync(brier_out, 0, (size_t)T * RD_VF_HOURS * 4 * sizeof(long long), st);
-  if (e != hipSuccess) return (int)e;
-  const long units = ((n_planes + RD_VF_HOURS - 1) / RD_VF_HOURS) * ((plane + RD_VF_CHUNK - 1) / RD_VF_CHUNK);       // per hour
-  // at most RD_VF_MAXUNITS chunks per workgroup (the 32-bit LDS counters), at least 64 workgroups per hour where there is work
-  const long nbx = std::max<long>((units + RD_VF_MAXUNITS - 1) / RD_VF_MAXUNITS, std::min<long>(units, 64));
-  const size_t lds = RD_VF_MAXT * 4 * sizeof(unsigned long long) + (size_t)(T * n_bins * 3 + S + 1) * sizeof(unsigned);
-  hipLaunchKernelGGL(k_verify_reduce, dim3((unsigned)nbx, RD_VF_HOURS), dim3(RD_VF_THREADS), lds, st, obs, exceed, below, equal, bad,
-                     n_positions, plane, n_planes, S, T, thr, n_bins, rd_make_key(seed, RD_STREAM_VERIFY),
-                     (unsigned long long*)rank_hist_out, (unsigned long long*)reliability_out, (unsigned long long*)brier_out);
-  return (int)hipGetLastError();
-}
-
-static long rd_vf_box_blocks(long plane) { return std::min<long>((plane + RD_VF_THREADS - 1) / RD_VF_THREADS, RD_VF_BOX_MAXBLOCKS); }
-
-extern "C" long rdgan_verify_fss_workspace_bytes(int ny, int nx, int n_thresholds, int n_widths) {
-  if (ny < 1 || nx < 1 || n_thresholds < 1 || n_thresholds > RD_VF_MAXT || n_widths < 1 || n_widths > RD_VF_MAXW) return -2;
-  const long plane = (long)ny * nx, planes = (long)RD_VF_HOURS * n_thresholds;
-  if (plane > (1L << 36)) return -2;
-  return planes * rd_vf_box_blocks(plane) * n_widths * 2 * (long)sizeof(double) + 2 * planes * plane * (long)sizeof(unsigned);
-}
-
-extern "C" int rdgan_verify_fss(const float* obs, const int* exceed, const unsigned char* bad, long n_days, int ny, int nx,
-                                int n_members, const double* thresholds, int n_thresholds, const int* widths, int n_widths,
-                                double* fss_sums_out, void* workspace, long workspace_bytes, void* stream) {
-  rd_vf_thr thr;
-  rd_vf_widths wd;
-  if (!obs || !exceed || !bad || !fss_sums_out || !workspace || ((unsigned long long)workspace & 7)) return -2;
-  if (n_days < 1 || ny < 1 || nx < 1 || n_members < 1 || n_members > RD_VF_MAXS) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr) || !rd_vf_widths_ok(widths, n_widths, n_members, &wd)) return -2;
-  const long need = rdgan_verify_fss_workspace_bytes(ny, nx, n_thresholds, n_widths);
-  if (need < 0 || workspace_bytes < need) return -2;
-  const int T = n_thresholds, W = n_widths;
-  const long plane = (long)ny * nx, planes = (long)RD_VF_HOURS * T;
-  if (n_days > (1L << 40) / (plane * RD_VF_HOURS)) return -2;
-  const long P = n_days * RD_VF_HOURS * plane, rows = planes * ny, cols = planes * nx;
-  if ((rows + 3) / 4 > 0x7FFFFFFFL || (cols + RD_VF_THREADS - 1) / RD_VF_THREADS > 0x7FFFFFFFL) return -2;
-  const int nblk = (int)rd_vf_box_blocks(plane);
-  double* partial = (double*)workspace;
-  unsigned* satC = (unsigned*)(partial + planes * nblk * W * 2);
-  unsigned* satE = satC + planes * plane;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(fss_sums_out, 0, (size_t)T * W * RD_VF_HOURS * 2 * sizeof(double), st);
-  if (e != hipSuccess) return (int)e;
-  for (long day = 0; day < n_days; ++day) {                 // the days one after another: the workspace holds one day's tables
-    hipLaunchKernelGGL(k_verify_fss_rows, dim3((unsigned)((rows + 3) / 4)), dim3(RD_VF_THREADS), 0, st, obs, exceed, bad, P, day, ny, nx,
-                       n_members, T, thr, satC, satE);
-    hipLaunchKernelGGL(k_verify_fss_cols, dim3((unsigned)((cols + RD_VF_THREADS - 1) / RD_VF_THREADS)), dim3(RD_VF_THREADS), 0, st, satC,
-                       satE, planes, ny, nx);
-    hipLaunchKernelGGL(k_verify_fss_box, dim3((unsigned)nblk, (unsigned)planes), dim3(RD_VF_THREADS), 0, st, satC, satE, ny, nx,
-                       n_members, wd, W, partial);
-    hipLaunchKernelGGL(k_verify_fss_final, dim3((unsigned)((planes * W + RD_VF_THREADS - 1) / RD_VF_THREADS)), dim3(RD_VF_THREADS), 0,
-                       st, partial, nblk, T, W, fss_sums_out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------
-// temporal structure of hourly fields (rdgan_temporal.hip.h): spells, transitions, wet hours, lagged products
-// ------------------------------------------------------------------------------------
-// workgroups of k_temporal_accumulate for `groups` threads' worth of work
-static long rd_ts_blocks(long groups) { return std::min<long>((groups + RD_TS_THREADS - 1) / RD_TS_THREADS, RD_TS_MAXBLOCKS); }
-
-static bool rd_ts_shape_ok(long n, long plane, int n_thresholds, int max_lag) {
-  if (n < 1 || plane < 1 || n_thresholds < 1 || n_thresholds > RD_TS_MAXT || max_lag < 1 || max_lag > RD_TS_MAXK) return false;
-  return plane <= RD_TS_MAXELEMS / RD_TS_HOURS && n <= RD_TS_MAXELEMS / (RD_TS_HOURS * plane);
-}
-
-extern "C" long rdgan_temporal_workspace_bytes(long n, long plane, int n_thresholds, int max_lag) {
-  if (!rd_ts_shape_ok(n, plane, n_thresholds, max_lag)) return -2;
-  return rd_ts_blocks(n * plane) * rd_ts_nsums(n_thresholds, max_lag) * (long)sizeof(double);       // (the scalar path has the most)
-}
-
-extern "C" int rdgan_temporal_accumulate(const float* x, long n, long day_stride, long plane, const double* thresholds,
-                                         int n_thresholds, int max_lag, long long* counts_inout, double* sums_inout, void* workspace,
-                                         long workspace_bytes, void* stream) {
-  rd_vf_thr thr;
-  if (!x || !counts_inout || !sums_inout || !workspace) return -2;
-  if (((unsigned long long)x & 3) || (((unsigned long long)counts_inout | (unsigned long long)sums_inout | (unsigned long long)workspace) & 7))
-    return -2;
-  if (!rd_ts_shape_ok(n, plane, n_thresholds, max_lag) || day_stride < RD_TS_HOURS * plane || day_stride > (1L << 50) / n) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
-  if (workspace_bytes < rdgan_temporal_workspace_bytes(n, plane, n_thresholds, max_lag)) return -2;
-  const bool vec = !((unsigned long long)x & 15) && plane % 4 == 0 && day_stride % 4 == 0;
-  const int nblk = (int)rd_ts_blocks(vec ? n * (plane / 4) : n * plane), nsums = rd_ts_nsums(n_thresholds, max_lag);
-  const size_t lds = rd_ts_lds_bytes(n_thresholds);
-  hipStream_t st = (hipStream_t)stream;
-#define RD_TS_LAUNCH(VV, KK)                                                                                                        \
-  do {                                                                                                                              \
-    RD_TRY(ensure_lds(nullptr, (const void*)k_temporal_accumulate<VV, KK>, rd_ts_lds_bytes(RD_TS_MAXT)));                           \
-    hipLaunchKernelGGL((k_temporal_accumulate<VV, KK>), dim3((unsigned)nblk), dim3(RD_TS_THREADS), lds, st, x, n, day_stride, plane, \
-                       thr, n_thresholds, max_lag, (unsigned long long*)counts_inout, (double*)workspace);                          \
-  } while (0)
-  if (vec && max_lag <= 6) RD_TS_LAUNCH(4, 6);
-  else if (vec) RD_TS_LAUNCH(4, 12);
-  else if (max_lag <= 6) RD_TS_LAUNCH(1, 6);
-  else RD_TS_LAUNCH(1, 12);
-#undef RD_TS_LAUNCH
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(k_temporal_final, dim3((unsigned)nsums), dim3(RD_TS_THREADS), 0, st, (const double*)workspace, nblk, nsums,
-                     sums_inout);
-  return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// rain cells of hourly fields (rdgan_cells.hip.h): connected wet areas, labelled and counted
-// ------------------------------------------------------------------------------------
-static bool rd_cl_shape_ok(long ny, long nx) {
-  return ny >= 1 && nx >= 1 && ny <= RD_CL_MAXPLANE && nx <= RD_CL_MAXPLANE && ny * nx <= RD_CL_MAXPLANE;
-}
-
-extern "C" long rdgan_cells_workspace_bytes(long ny, long nx, long planes_per_pass) {
-  if (!rd_cl_shape_ok(ny, nx) || planes_per_pass < 1 || planes_per_pass > RD_CL_MAXPASS) return -2;
-  return rd_cl_ws_bytes(ny * nx, planes_per_pass);
-}
-
-extern "C" int rdgan_cells_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds,
-                                      int n_thresholds, int connectivity, long long* counts_inout, int* labels_out,
-                                      int label_threshold, void* workspace, long workspace_bytes, void* stream) {
-  rd_vf_thr thr;
-  if (!x || !counts_inout || !workspace) return -2;
-  if (((unsigned long long)x & 3) || ((unsigned long long)labels_out & 3) ||
-      (((unsigned long long)counts_inout | (unsigned long long)workspace) & 7))
-    return -2;
-  if (n < 1 || !rd_cl_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8)) return -2;
-  const long plane = ny * nx;
-  if (n > RD_CL_MAXELEMS / (RD_CL_HOURS * plane) || day_stride < RD_CL_HOURS * plane || day_stride > (1L << 50) / n) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
-  if (labels_out && (label_threshold < 0 || label_threshold >= n_thresholds)) return -2;
-  // the planes of a pass: as many as the workspace holds
-  const long n_planes = n * RD_CL_HOURS;
-  const long per_pass = std::min<long>(std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / rd_cl_ws_bytes(plane, 1), n_planes), RD_CL_MAXPASS);
-  if (per_pass < 1) return -2;
-  unsigned long long* vol = (unsigned long long*)workspace;
-  int* parent = (int*)(vol + per_pass * plane);
-  unsigned* area = (unsigned*)(parent + per_pass * plane);
-  unsigned* words = area + per_pass * plane;
-  unsigned long long* counts = (unsigned long long*)counts_inout;
-  hipStream_t st = (hipStream_t)stream;
-  RD_TRY(ensure_lds(nullptr, (const void*)k_cells_label_tile, RD_CL_LDS_BYTES));
-  const int tiles_x = (int)((nx + RD_CL_TILE - 1) / RD_CL_TILE), tiles_y = (int)((ny + RD_CL_TILE - 1) / RD_CL_TILE);
-  const long border = (long)(tiles_x - 1) * ny + (long)(tiles_y - 1) * nx;
-  const int conn8 = connectivity == 8;
-  for (long p0 = 0; p0 < n_planes; p0 += per_pass) {
-    const unsigned P = (unsigned)std::min<long>(per_pass, n_planes - p0);
-    for (int t = 0; t < n_thresholds; ++t) {
-      unsigned long long* ct = counts + (long)t * RD_CL_NC;
-      hipLaunchKernelGGL(k_cells_label_tile, dim3((unsigned)(tiles_x * tiles_y), P), dim3(RD_CL_THREADS), RD_CL_LDS_BYTES, st, x, day_stride,
-                         (int)ny, (int)nx, p0, thr.v[t], conn8, (int)(t == 0), ct + RD_CL_WET,
-                         counts + (long)n_thresholds * RD_CL_NC + 1, vol, parent, area, words);
-      if (border > 0)
-        hipLaunchKernelGGL(k_cells_merge, dim3((unsigned)((border + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st,
-                           (int)ny, (int)nx, conn8, parent);
-      hipLaunchKernelGGL(k_cells_resolve, dim3((unsigned)((plane + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st, plane,
-                         p0, vol, parent, area, labels_out && t == label_threshold ? labels_out : (int*)nullptr);
-      hipLaunchKernelGGL(k_cells_reduce, dim3((unsigned)((plane + RD_CL_RCHUNK - 1) / RD_CL_RCHUNK), P), dim3(RD_CL_THREADS), 0, st, plane, p0,
-                         (const unsigned long long*)vol, (const int*)parent, (const unsigned*)area, words, ct);
-      hipLaunchKernelGGL(k_cells_planes, dim3((P + RD_CL_THREADS - 1) / RD_CL_THREADS), dim3(RD_CL_THREADS), 0, st, (int)P,
-                         (const unsigned*)words, ct, t == 0 ? counts + (long)n_thresholds * RD_CL_NC : (unsigned long long*)nullptr);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return (int)e;
-    }
-  }
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------
-// log-spectral distance (rdgan_spectral.hip.h)
-// ------------------------------------------------------------------------------------
-extern "C" int rdgan_spectra_bins(int nd) {
-  if (nd < 8 || nd > RD_SPEC_MAXND || nd % 2) return -2;
-  return rd_spec_bin(nd - 1, nd - 1) - 1;               // bins 1 .. max - 1: the first and the last group are dropped
-}
-
-extern "C" int rdgan_radial_spectra(const float* fields, float* out, long n, int nd, int log_out, void* stream) {
-  const int K = rdgan_spectra_bins(nd);
-  if (!fields || !out || n < 1 || n > (1L << 26) || K < 1) return -2;
-  rd_spec_args a;
-  memset(&a, 0, sizeof(a));
-  for (int j = 0; j < nd; ++j) {
-    const double th = -2.0 * M_PI * (double)j / (double)nd;
-    a.tw_re[j] = (float)cos(th);
-    a.tw_im[j] = (float)sin(th);
-  }
-  for (int i = 0; i < nd; ++i)
-    for (int j = 0; j < nd; ++j) {
-      const int b = rd_spec_bin(2 * j - (nd - 1), 2 * i - (nd - 1));
-      if (b >= 1 && b <= K) a.cnt[b - 1]++;
-    }
-  for (int b = 0; b < K; ++b)
-    if (a.cnt[b] == 0) return -2;
-  hipStream_t st = (hipStream_t)stream;
-  const int lo = log_out ? 1 : 0;
-  switch (nd) {
-#define RD_SPEC_CASE(ND)                                                                                                     \
-  case ND: {                                                                                                                 \
-    constexpr int FPB = ND * ND >= 256 ? 1 : 256 / (ND * ND);                                                                \
-    hipLaunchKernelGGL(k_radial_spectra<ND>, dim3((unsigned)((n + FPB - 1) / FPB)), dim3(256), 0, st, fields, out, (int)n, K, \
-                       lo, a);                                                                                               \
-    break;                                                                                                                   \
-  }
-    RD_SPEC_CASE(8) RD_SPEC_CASE(16) RD_SPEC_CASE(24) RD_SPEC_CASE(32) RD_SPEC_CASE(48) RD_SPEC_CASE(64)
-#undef RD_SPEC_CASE
-    default: return -2;
-  }
-  return (int)hipGetLastError();
-}
-
-static void rd_lsd_grid(long n, long m, int* gx, int* gy) {
-  const long nti = (n + RD_LSD_TILE - 1) / RD_LSD_TILE, ntj = (m + RD_LSD_TILE - 1) / RD_LSD_TILE;
-  *gy = (int)nti;
-  *gx = (int)std::max(1L, std::min(ntj, (2048 + nti - 1) / nti));     // ~2048 workgroups; a function of (n, m) alone
-}
-
-extern "C" long rdgan_lsd_workspace_bytes(long n, long m) {
-  if (n < 1 || m < 1 || n > RD_LSD_MAXROWS || m > RD_LSD_MAXROWS) return -2;
-  int gx, gy;
-  rd_lsd_grid(n, m, &gx, &gy);
-  return (long)gx * gy * (long)sizeof(rd_lsd_partial);
-}
-
-extern "C" int rdgan_lsd_pairwise(const float* spec_a, const float* spec_b, long n, long m, int k, int exclude_diagonal,
-                                  float* dist, unsigned long long* hist, int nbins, float lo, float hi, double* moments,
-                                  void* workspace, long workspace_bytes, void* stream) {
-  if (!spec_a || !spec_b || n < 1 || m < 1 || n > RD_LSD_MAXROWS || m > RD_LSD_MAXROWS || k < 1 || k > RD_SPEC_MAXK) return -2;
-  if (!dist && !hist && !moments) return -2;
-  long lds = 2L * k * RD_LSD_TILE * (long)sizeof(float);
-  float scale = 0.f;
-  if (hist) {
-    if (nbins < 1 || !(lo < hi) || !std::isfinite(lo) || !std::isfinite(hi)) return -2;
-    scale = (float)nbins / (hi - lo);
-    if (!std::isfinite(scale)) return -2;
-    lds += 4L * (nbins + 4);
-  }
-  if (lds > RD_LSD_MAX_DYN_LDS) return -2;
-  int gx, gy;
-  rd_lsd_grid(n, m, &gx, &gy);
-  if (moments && (!workspace || workspace_bytes < rdgan_lsd_workspace_bytes(n, m))) return -2;
-  hipStream_t st = (hipStream_t)stream;
-  if (hist) {
-    hipError_t e = hipMemsetAsync(hist, 0, sizeof(unsigned long long) * (nbins + 4), st);
-    if (e != hipSuccess) return (int)e;
-  }
-  rd_lsd_partial* part = moments ? (rd_lsd_partial*)workspace : nullptr;
-  hipLaunchKernelGGL(k_lsd_pairwise, dim3(gx, gy), dim3(256), (size_t)lds, st, spec_a, spec_b, (int)n, (int)m, k,
-                     exclude_diagonal ? 1 : 0, dist, hist, nbins, lo, hi, scale, part);
-  if (moments) hipLaunchKernelGGL(k_lsd_reduce, dim3(1), dim3(256), 0, st, part, gx * gy, moments);
-  return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// RainFARM baseline (rdgan_rainfarm.hip.h)
-// ------------------------------------------------------------------------------------
-extern "C" int rdgan_rainfarm_classes(int nd) {
-  if (!rd_rf_nd_ok(nd)) return -2;
-  return (nd / 2 + 1) * (nd / 2 + 1) + RD_RF_TCLASS;
-}
-
-static void rd_rf_stat_grid(long n, int* gs, int* gt) {
-  *gs = (int)std::min((long)RD_RF_STAT_WG, n * RD_RF_NT);
-  *gt = (int)std::min((long)RD_RF_STAT_WG, n);
-}
-
-extern "C" long rdgan_rainfarm_stats_workspace_bytes(long n, int nd) {
-  if (!rd_rf_nd_ok(nd) || n < 1 || n > RD_RF_MAXN) return -2;
-  int gs, gt;
-  rd_rf_stat_grid(n, &gs, &gt);
-  const long nc = (long)(nd / 2 + 1) * (nd / 2 + 1);
-  return ((long)gs * nc + (long)gt * RD_RF_TCLASS) * (long)sizeof(rd_rf_stat);
-}
-
-extern "C" int rdgan_rainfarm_slope_stats(const float* samples, long n, int nd, unsigned long long* counts, double* sums,
-                                          void* workspace, long workspace_bytes, void* stream) {
-  if (!samples || !counts || !sums || !workspace || ((uintptr_t)samples & 15)) return -2;
-  const long need = rdgan_rainfarm_stats_workspace_bytes(n, nd);
-  if (need < 0 || workspace_bytes < need) return -2;
-  rd_rf_slope_args a;
-  memset(&a, 0, sizeof(a));
-  for (int j = 0; j < nd; ++j) {
-    const double th = -2.0 * M_PI * (double)j / (double)nd;
-    a.tw_re[j] = cos(th);
-    a.tw_im[j] = sin(th);
-  }
-  for (int j = 0; j < RD_RF_NT; ++j) {
-    const double th = -2.0 * M_PI * (double)j / (double)RD_RF_NT;
-    a.t24_re[j] = cos(th);
-    a.t24_im[j] = sin(th);
-  }
-  int gs, gt;
-  rd_rf_stat_grid(n, &gs, &gt);
-  const int nc = (nd / 2 + 1) * (nd / 2 + 1);
-  rd_rf_stat* ps = (rd_rf_stat*)workspace;
-  rd_rf_stat* pt = ps + (long)gs * nc;
-  hipStream_t st = (hipStream_t)stream;
-  const long nplanes = n * RD_RF_NT;
-  switch (nd) {
-#define RD_RF_STATS_CASE(ND)                                                                                                 \
-  case ND:                                                                                                                   \
-    hipLaunchKernelGGL(k_rf_spatial_stats<ND>, dim3(gs), dim3(256), 0, st, samples, nplanes, ps, a);                        \
-    hipLaunchKernelGGL(k_rf_temporal_stats<ND>, dim3(gt), dim3(256), 0, st, samples, n, pt, a);                             \
-    break;
-    RD_RF_STATS_CASE(8) RD_RF_STATS_CASE(16) RD_RF_STATS_CASE(24) RD_RF_STATS_CASE(32) RD_RF_STATS_CASE(48) RD_RF_STATS_CASE(64)
-#undef RD_RF_STATS_CASE
-    default: return -2;
-  }
-  hipLaunchKernelGGL(k_rf_stats_reduce, dim3((nc + 255) / 256), dim3(256), 0, st, ps, gs, nc, counts, sums);
-  hipLaunchKernelGGL(k_rf_stats_reduce, dim3(1), dim3(256), 0, st, pt, gt, RD_RF_TCLASS, counts + nc, sums + nc);
-  return (int)hipGetLastError();
-}
-
-extern "C" long rdgan_rainfarm_gen_workspace_bytes(long n) {
-  if (n < 1 || n > RD_RF_MAXN) return -2;
-  return n * RD_RF_NT * (long)sizeof(float2);
-}
-
-extern "C" int rdgan_rainfarm_generate(const float* amplitudes, const float* precip, int precip_per_member, const void* uniforms,
-                                       int uniforms_fp64, uint64_t seed, long first_member, float* out, long n, int nd,
-                                       void* workspace, long workspace_bytes, void* stream) {
-  if (!rd_rf_nd_ok(nd) || !amplitudes || !precip || !out || !workspace || first_member < 0) return -2;
-  const long need = rdgan_rainfarm_gen_workspace_bytes(n);
-  if (need < 0 || workspace_bytes < need || ((uintptr_t)amplitudes & 7)) return -2;
-  rd_rf_gen_args a;
-  memset(&a, 0, sizeof(a));
-  for (int j = 0; j < nd; ++j) {
-    const double th = 2.0 * M_PI * (double)j / (double)nd;
-    a.tw_re[j] = (float)cos(th);
-    a.tw_im[j] = (float)sin(th);
-  }
-  for (int j = 0; j < RD_RF_NT; ++j) {
-    const double th = 2.0 * M_PI * (double)j / (double)RD_RF_NT;
-    a.t24_re[j] = (float)cos(th);
-    a.t24_im[j] = (float)sin(th);
-  }
-  const int usrc = uniforms ? (uniforms_fp64 ? 2 : 1) : 0;
-  const uint32_t key = rd_make_key(seed, RD_STREAM_RAINFARM);
-  const float2* amp = (const float2*)amplitudes;
-  float2* stats = (float2*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned nb = (unsigned)(n * RD_RF_NT);
-  switch (nd) {
-#define RD_RF_GEN_CASE(ND)                                                                                                   \
-  case ND: {                                                                                                                 \
-    constexpr int NT = rd_rf_gen_shape<ND>::NT;                                                                              \
-    if (usrc == 0)                                                                                                           \
-      hipLaunchKernelGGL((k_rf_gen_planes<ND, 0>), dim3(nb), dim3(NT), 0, st, amp, uniforms, key, first_member, out, stats, a); \
-    else if (usrc == 1)                                                                                                      \
-      hipLaunchKernelGGL((k_rf_gen_planes<ND, 1>), dim3(nb), dim3(NT), 0, st, amp, uniforms, key, first_member, out, stats, a); \
-    else                                                                                                                     \
-      hipLaunchKernelGGL((k_rf_gen_planes<ND, 2>), dim3(nb), dim3(NT), 0, st, amp, uniforms, key, first_member, out, stats, a); \
-    hipLaunchKernelGGL(k_rf_gen_finish<ND>, dim3((unsigned)n), dim3(NT), 0, st, out, precip, precip_per_member ? 1 : 0, stats); \
-    break;                                                                                                                   \
-  }
-    RD_RF_GEN_CASE(8) RD_RF_GEN_CASE(16) RD_RF_GEN_CASE(24) RD_RF_GEN_CASE(32) RD_RF_GEN_CASE(48) RD_RF_GEN_CASE(64)
-#undef RD_RF_GEN_CASE
-    default: return -2;
-  }
-  return (int)hipGetLastError();
-}
+#include "rdgan_eval_entries.h"   // rdgan_data_* ... rdgan_rainfarm_generate: the entry points that take no handle
 
 #ifdef RD_STAMP
 extern "C" int rdgan_debug_stamps(unsigned long long* out, int reset) {

@@ -1,0 +1,786 @@
+// The handle-free entry points of include/rdgan.h: input pipeline, CRPS experiment, distribution checks, whole fields, ensemble
+// products, verification, temporal structure, rain cells, spectra and RainFARM.  They take no rdgan_handle and use nothing of the
+// step engine but RD_TRY, ensure_lds(nullptr, ...) and ew_blocks.  Host code, included by rdgan_api.hip at one point, behind the
+// op-level test entries (the library stays one translation unit: one code object for the ISA lint).
+#pragma once
+
+// ------------------------------------------------------------------------------------
+// input pipeline
+// ------------------------------------------------------------------------------------
+extern "C" int rdgan_data_gather(const float* data, int n_days, int ny, int nx, const int* indices, int n, int ndomain,
+                                 float norm_scale, float* batch_out, float* cond_out, int* flags, void* stream) {
+  if (!data || !indices || !cond_out || !flags || n_days < 1 || n < 1 || ndomain < 1 || ndomain > ny || ndomain > nx) return -2;
+  // *flags accumulates over calls (include/rdgan.h): the caller zeroes it before the first gather and after reading it
+  hipLaunchKernelGGL(k_gather_tiles, dim3(ew_blocks((long)n * ndomain * ndomain)), dim3(256), 0, (hipStream_t)stream, data, n_days,
+                     RDGAN_NHOURS, ny, nx, indices, n, ndomain, norm_scale, batch_out, cond_out, flags);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_data_valid_tiles(const float* data, int n_days, int ny, int nx, int ndomain, int stride,
+                                      float tp_thresh_daily, int n_thresh, int* valid_out, void* stream) {
+  if (!data || !valid_out || n_days < 1 || ny < 1 || nx < 1 || stride < 1 || ndomain < 1 || ndomain > ny || ndomain > nx) return -2;
+  const int nbi = (ny - ndomain + stride - 1) / stride, nbj = (nx - ndomain + stride - 1) / stride;   // len(range(0, ny-nd, stride))
+  if (nbi < 1 || nbj < 1) return 0;
+  const long blocks = (long)n_days * nbi * nbj;
+  if (blocks > 0xFFFFFFL) return -2;       // one 256-thread block per box and no loop: a launch holds fewer than 2^32 threads
+  hipLaunchKernelGGL(k_valid_tiles, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, data, RDGAN_NHOURS, ny, nx,
+                     ndomain, stride, nbi, nbj, tp_thresh_daily, n_thresh, valid_out);
+  return (int)hipGetLastError();
+}
+
+// training set from raw radar frames (rdgan_radar.hip.h)
+template <int W, int FPH>
+static void launch_radar_hourly(const unsigned char* codes, const float* lut, long n_days, long plane, float* hourly, float* daily,
+                                unsigned long long* missing, hipStream_t st) {
+  const long groups = (plane + W - 1) / W;
+  // (a launch holds fewer than 2^32 threads; the kernel's grid-stride loop takes what lies beyond)
+  const long blocks = std::min<long>((n_days * groups + RD_RADAR_THREADS - 1) / RD_RADAR_THREADS, 0xFFFFFFL);
+  hipLaunchKernelGGL((k_radar_hourly<W, FPH>), dim3((unsigned)blocks), dim3(RD_RADAR_THREADS), 0, st, codes, lut, n_days, plane, groups,
+                     hourly, daily, missing);
+}
+template <int W>
+static void launch_radar_hourly_w(int fph, const unsigned char* codes, const float* lut, long n_days, long plane, float* hourly,
+                                  float* daily, unsigned long long* missing, hipStream_t st) {
+  switch (fph) {
+    case 1: launch_radar_hourly<W, 1>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+    case 2: launch_radar_hourly<W, 2>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+    case 3: launch_radar_hourly<W, 3>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+    case 4: launch_radar_hourly<W, 4>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+    case 6: launch_radar_hourly<W, 6>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+    default: launch_radar_hourly<W, 12>(codes, lut, n_days, plane, hourly, daily, missing, st); break;
+  }
+}
+
+extern "C" int rdgan_data_radar_hourly(const unsigned char* codes, const float* lut256, long n_days, int frames_per_hour, int ny, int nx,
+                                       float* hourly_out, float* daily_out, unsigned long long* missing_out, void* stream) {
+  const int f = frames_per_hour;
+  if (!codes || !lut256 || !hourly_out || n_days < 1 || ny < 1 || nx < 1) return -2;
+  if (f != 1 && f != 2 && f != 3 && f != 4 && f != 6 && f != 12) return -2;
+  const long plane = (long)ny * nx;
+  hipStream_t st = (hipStream_t)stream;
+  // 16 codes per lane: every frame and every output row group starts on a 16-byte boundary; 4 per lane: dword loads, float4 stores
+  const uintptr_t out_bits = (uintptr_t)hourly_out | (uintptr_t)daily_out;
+  if (plane % 16 == 0 && (((uintptr_t)codes | out_bits) & 15) == 0)
+    launch_radar_hourly_w<16>(f, codes, lut256, n_days, plane, hourly_out, daily_out, missing_out, st);
+  else if (plane % 4 == 0 && ((uintptr_t)codes & 3) == 0 && (out_bits & 15) == 0)
+    launch_radar_hourly_w<4>(f, codes, lut256, n_days, plane, hourly_out, daily_out, missing_out, st);
+  else
+    launch_radar_hourly_w<1>(f, codes, lut256, n_days, plane, hourly_out, daily_out, missing_out, st);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_data_daily_sum(const float* hourly, long n_days, int ny, int nx, float* daily_out, void* stream) {
+  if (!hourly || !daily_out || n_days < 1 || ny < 1 || nx < 1) return -2;
+  const long plane = (long)ny * nx;
+  hipLaunchKernelGGL(k_daily_sum, dim3(ew_blocks(n_days * plane)), dim3(256), 0, (hipStream_t)stream, hourly, n_days, plane, daily_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_data_valid_tiles_daily(const float* daily, long n_days, int ny, int nx, int ndomain, int stride,
+                                            float tp_thresh_daily, int n_thresh, int* valid_out, void* stream) {
+  if (!daily || !valid_out || n_days < 1 || ny < 1 || nx < 1 || stride < 1 || ndomain < 1 || ndomain > ny || ndomain > nx) return -2;
+  const int nbi = (ny - ndomain + stride - 1) / stride, nbj = (nx - ndomain + stride - 1) / stride;   // len(range(0, ny-nd, stride))
+  if (nbi < 1 || nbj < 1) return 0;
+  const long boxes = n_days * nbi * nbj;
+  const long blocks = std::min<long>((boxes + 3) / 4, 0xFFFFFFL);      // fewer than 2^32 threads per launch; the kernel loops over the rest
+  hipLaunchKernelGGL(k_valid_tiles_daily, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, daily, boxes, ny, nx, ndomain,
+                     stride, nbi, nbj, tp_thresh_daily, n_thresh, valid_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_crps_ensemble(const float* ens, const float* obs, const float* scale, float* crps_out, int n,
+                                   long npix, void* stream) {
+  if (!ens || !obs || !crps_out || n < 1 || n > 8192 || npix < 1 || npix > 0x7FFFFFFFL) return -2;
+  int npow2 = 2;
+  while (npow2 < n) npow2 <<= 1;
+  hipLaunchKernelGGL(k_crps_ensemble, dim3((unsigned)npix), dim3(256), npow2 * sizeof(float), (hipStream_t)stream, ens, obs,
+                     scale, crps_out, n, npow2, npix);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// CRPS experiment (rdgan_crps.hip.h): fixed-ensemble CRPS, bootstrapped means, moments
+// ------------------------------------------------------------------------------------
+extern "C" int rdgan_crps_fixed_ensemble(const float* ens, const float* obs, float* crps_out, float* hourly_out, int n,
+                                         long n_days, int nd, void* stream) {
+  if (!ens || !obs || (!crps_out && !hourly_out) || n < 1 || n > RD_CRPS_MAXN || n_days < 1 || nd < 1 || nd > 1024) return -2;
+  const long npos = (long)RDGAN_NHOURS * nd * nd;
+  if (npos > 0x7FFFFFFFL || n_days > 0x7FFFFFFFL / npos) return -2;       // D * npos < 2^31, and the grids below fit
+  hipStream_t st = (hipStream_t)stream;
+  int npow2 = 2;
+  while (npow2 < n) npow2 <<= 1;
+  const size_t lds = (size_t)(n + 1 + RD_CRPS_THREADS) * sizeof(double) + (size_t)npow2 * sizeof(float);
+  RD_TRY(ensure_lds(nullptr, (const void*)k_crps_fixed, lds));
+  // the hourly means are taken over the per-position values: without a caller's buffer they live in a stream-ordered temporary
+  float* per_pos = crps_out;
+  if (!per_pos) {
+    hipError_t e = hipMallocAsync((void**)&per_pos, (size_t)n_days * npos * sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(k_crps_fixed, dim3((unsigned)npos), dim3(RD_CRPS_THREADS), lds, st, ens, obs, per_pos, n, npow2, n_days, npos);
+  if (hourly_out)
+    hipLaunchKernelGGL(k_crps_hourly, dim3((unsigned)(n_days * RDGAN_NHOURS)), dim3(256), 0, st, per_pos, hourly_out, nd * nd);
+  hipError_t e = hipGetLastError();
+  if (!crps_out) {
+    hipError_t f = hipFreeAsync(per_pos, st);
+    if (e == hipSuccess) e = f;
+  }
+  return (int)e;
+}
+
+extern "C" int rdgan_bootstrap_means(const double* x, long n, uint64_t seed, long first_resample, long n_resamples,
+                                     double* means_out, void* stream) {
+  if (!x || !means_out || n < 1 || n > 0xFFFFFFFFL || first_resample < 0 || n_resamples < 1 || n_resamples > 0x7FFFFFFFL) return -2;
+  hipLaunchKernelGGL(k_bootstrap_means, dim3((unsigned)n_resamples), dim3(RD_CRPS_THREADS), 0, (hipStream_t)stream, x, (uint32_t)n,
+                     rd_make_key(seed, RD_STREAM_BOOTSTRAP), (uint64_t)first_resample, means_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_moments_f64(const double* x, long n, double* out3, void* stream) {
+  if (!x || !out3 || n < 1) return -2;
+  hipLaunchKernelGGL(k_moments_f64, dim3(1), dim3(RD_CRPS_THREADS), 0, (hipStream_t)stream, x, n, out3);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// distribution checks (rdgan_dist.hip.h): two-sample KS, box-plot statistics, ECDF on a grid
+// ------------------------------------------------------------------------------------
+static int rd_pow2_at_least(int n) {
+  int p = 2;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+extern "C" int rdgan_ks_2samp(const float* a, const float* b, int n, int m, int ncol, long batch, int* counts_out, double* d_out,
+                              void* stream) {
+  if (!a || !b || !counts_out || !d_out || n < 1 || n > RD_DIST_MAXN || m < 1 || m > RD_DIST_MAXN || ncol < 1 || batch < 1) return -2;
+  if (batch > 0x7FFFFFFFL / ncol) return -2;
+  const int npa = rd_pow2_at_least(n), npb = rd_pow2_at_least(m);
+  RD_TRY(ensure_lds(nullptr, (const void*)k_ks_2samp, RD_KS_LDS_MAX));
+  hipLaunchKernelGGL(k_ks_2samp, dim3((unsigned)(batch * ncol)), dim3(RD_DIST_THREADS),
+                     RD_KS_LDS_HEAD + (size_t)(npa + npb) * sizeof(float), (hipStream_t)stream, a, b, n, m, npa, npb, ncol, counts_out,
+                     d_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_box_stats(const float* x, int n, int ncol, long batch, double* stats_out, float* sorted_out, void* stream) {
+  if (!x || !stats_out || n < 1 || n > RD_DIST_MAXN || ncol < 1 || batch < 1) return -2;
+  if (batch > 0x7FFFFFFFL / ncol) return -2;
+  const int npow2 = rd_pow2_at_least(n);
+  RD_TRY(ensure_lds(nullptr, (const void*)k_box_stats, RD_BOX_LDS_MAX));
+  hipLaunchKernelGGL(k_box_stats, dim3((unsigned)(batch * ncol)), dim3(RD_DIST_THREADS), RD_BOX_LDS_HEAD + (size_t)npow2 * sizeof(float),
+                     (hipStream_t)stream, x, n, npow2, ncol, stats_out, sorted_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" long rdgan_ecdf_workspace_bytes(int n_grid) {
+  if (n_grid < 1 || n_grid > RD_ECDF_MAXT) return -2;
+  return (long)(n_grid + 2) * (long)sizeof(unsigned long long);
+}
+
+extern "C" int rdgan_ecdf_grid(const float* x, long n_values, const float* grid, int n_grid, long long* counts_out, void* workspace,
+                               long workspace_bytes, void* stream) {
+  if (!x || !grid || !counts_out || !workspace || n_values < 1 || n_values > (1L << 40) || n_grid < 1 || n_grid > RD_ECDF_MAXT) return -2;
+  if (((unsigned long long)x & 3) || workspace_bytes < rdgan_ecdf_workspace_bytes(n_grid)) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* hist = (unsigned long long*)workspace;
+  hipError_t e = hipMemsetAsync(hist, 0, (size_t)(n_grid + 2) * sizeof(unsigned long long), st);
+  if (e != hipSuccess) return (int)e;
+  const long per_block = (long)RD_ECDF_THREADS * 16;                     // four float4 per thread
+  const long blocks = std::max<long>(1, std::min<long>(RD_ECDF_MAXBLOCKS, (n_values + per_block - 1) / per_block));
+  hipLaunchKernelGGL(k_ecdf_grid, dim3((unsigned)blocks), dim3(RD_ECDF_THREADS), (size_t)(2 * n_grid + 2) * sizeof(float), st, x,
+                     n_values, grid, n_grid, hist);
+  hipLaunchKernelGGL(k_ecdf_scan, dim3(1), dim3(RD_DIST_THREADS), 0, st, hist, n_grid, counts_out);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// whole daily fields (rdgan_field.hip.h): tile scan, condition batch, blend
+// ------------------------------------------------------------------------------------
+static bool rd_field_geometry_ok(long n_days, int ny, int nx, int nd, int overlap) {
+  return rd_geometry_ok(nd, 1, 1) && overlap >= 0 && overlap <= nd / 2 && ny >= nd && nx >= nd && n_days >= 1;
+}
+
+// a small host table for the next launch: a stream-ordered device copy, freed behind the launch by the caller
+static int rd_field_upload(const int* host, size_t n, int** dev, hipStream_t st) {
+  hipError_t e = hipMallocAsync((void**)dev, n * sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  e = hipMemcpyAsync(*dev, host, n * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) {
+    (void)hipFreeAsync(*dev, st);
+    return (int)e;
+  }
+  return 0;
+}
+
+extern "C" int rdgan_field_scan(const float* daily, long n_days, int ny, int nx, int nd, int overlap, int* counts_out, void* stream) {
+  if (!daily || !counts_out || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
+  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
+  if ((long)n_ty * n_tx > 0x7FFFFFFFL / n_days) return -2;                 // an entry number day * T + tile is an int32
+  const long entries = n_days * n_ty * n_tx;
+  const long blocks = std::min<long>((entries + 3) / 4, 0xFFFFFFL);        // the kernel loops over the rest
+  hipLaunchKernelGGL(k_field_scan, dim3((unsigned)blocks), dim3(RD_FIELD_THREADS), 0, (hipStream_t)stream, daily, entries, ny, nx, nd,
+                     step, n_ty, n_tx, counts_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_field_cond(const float* daily, long n_days, int ny, int nx, int nd, int overlap, const int* entries, long m,
+                                double norm_scale, float* cond_out, void* stream) {
+  if (!daily || !entries || !cond_out || m < 1 || !(norm_scale > 0.0) || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
+  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
+  if ((long)n_ty * n_tx > 0x7FFFFFFFL / n_days) return -2;
+  const long n_entries = n_days * n_ty * n_tx;
+  for (long i = 0; i < m; ++i)
+    if (entries[i] < 0 || entries[i] >= n_entries) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  int* dev = nullptr;
+  RD_TRY(rd_field_upload(entries, (size_t)m, &dev, st));
+  hipLaunchKernelGGL(k_field_cond, dim3(ew_blocks(m * nd * nd, RD_FIELD_THREADS)), dim3(RD_FIELD_THREADS), 0, st, daily, dev, m, ny, nx,
+                     nd, step, n_ty, n_tx, norm_scale, cond_out);
+  hipError_t e = hipGetLastError();
+  hipError_t f = hipFreeAsync(dev, st);
+  return (int)(e != hipSuccess ? e : f);
+}
+
+extern "C" int rdgan_field_blend(const float* frac, long m, const int* slots, long units, long first_unit, const int* ytab_idx,
+                                 const float* ytab_w, const int* xtab_idx, const float* xtab_w, const float* daily, long n_days,
+                                 int ny, int nx, int nd, int overlap, float* out, void* stream) {
+  if (!frac || !slots || !ytab_idx || !ytab_w || !xtab_idx || !xtab_w || !daily || !out) return -2;
+  if (m < 1 || m > 0x7FFFFFFFL || units < 1 || first_unit < 0 || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
+  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
+  const long T = (long)n_ty * n_tx;
+  if (T > 0x7FFFFFFFL || units > 0x7FFFFFFFL / T) return -2;
+  for (long i = 0; i < units * T; ++i)
+    if (slots[i] < -1 || slots[i] >= m) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  int* dev = nullptr;
+  RD_TRY(rd_field_upload(slots, (size_t)(units * T), &dev, st));
+  const long nb = units * ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * ((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
+  hipLaunchKernelGGL(k_field_blend, dim3((unsigned)std::min<long>(nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0, st, frac, dev, ytab_idx,
+                     ytab_w, xtab_idx, xtab_w, daily, out, units, first_unit, n_days, ny, nx, nd, step, n_ty, n_tx);
+  hipError_t e = hipGetLastError();
+  hipError_t f = hipFreeAsync(dev, st);
+  return (int)(e != hipSuccess ? e : f);
+}
+
+// ------------------------------------------------------------------------------------
+// ensemble products (rdgan_products.hip.h): k-hour peaks of hourly maps, the blend fused with them, member statistics
+// ------------------------------------------------------------------------------------
+// the window list as the kernels take it: bit w - 1 set for every window w; false for a list that is not strictly increasing in 1 .. 24
+static bool rd_peaks_mask(const int* windows, int n_windows, unsigned* mask) {
+  if (!windows || n_windows < 1 || n_windows > RD_PEAKS_MAXK) return false;
+  unsigned m = 0;
+  for (int i = 0; i < n_windows; ++i) {
+    if (windows[i] < 1 || windows[i] > RD_FIELD_HOURS || (i > 0 && windows[i] <= windows[i - 1])) return false;
+    m |= 1u << (windows[i] - 1);
+  }
+  *mask = m;
+  return true;
+}
+
+extern "C" int rdgan_hourly_peaks(const float* hourly, long units, int ny, int nx, const int* windows, int n_windows, float* peaks_out,
+                                  unsigned char* peak_hour_out, void* stream) {
+  unsigned mask = 0;
+  if (!hourly || !peaks_out || !peak_hour_out || units < 1 || ny < 1 || nx < 1 || !rd_peaks_mask(windows, n_windows, &mask)) return -2;
+  const long nb = ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * (long)((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
+  if (units > (1L << 40) / nb) return -2;
+  hipLaunchKernelGGL(k_hourly_peaks, dim3((unsigned)std::min<long>(units * nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0,
+                     (hipStream_t)stream, hourly, units, ny, nx, mask, windows[0], peaks_out, peak_hour_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_field_blend_peaks(const float* frac, long m, const int* slots, long units, long first_unit, const int* ytab_idx,
+                                       const float* ytab_w, const int* xtab_idx, const float* xtab_w, const float* daily, long n_days,
+                                       int ny, int nx, int nd, int overlap, const int* windows, int n_windows, float* peaks_out,
+                                       unsigned char* peak_hour_out, void* stream) {
+  unsigned mask = 0;
+  if (!frac || !slots || !ytab_idx || !ytab_w || !xtab_idx || !xtab_w || !daily || !peaks_out || !peak_hour_out) return -2;
+  if (m < 1 || m > 0x7FFFFFFFL || units < 1 || first_unit < 0 || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
+  if (!rd_peaks_mask(windows, n_windows, &mask)) return -2;
+  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
+  const long T = (long)n_ty * n_tx;
+  if (T > 0x7FFFFFFFL || units > 0x7FFFFFFFL / T) return -2;
+  for (long i = 0; i < units * T; ++i)
+    if (slots[i] < -1 || slots[i] >= m) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  int* dev = nullptr;
+  RD_TRY(rd_field_upload(slots, (size_t)(units * T), &dev, st));
+  const long nb = units * ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * ((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
+  hipLaunchKernelGGL(k_field_blend_peaks, dim3((unsigned)std::min<long>(nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0, st, frac, dev,
+                     ytab_idx, ytab_w, xtab_idx, xtab_w, daily, peaks_out, peak_hour_out, units, first_unit, n_days, ny, nx, nd, step,
+                     n_ty, n_tx, mask, windows[0]);
+  hipError_t e = hipGetLastError();
+  hipError_t f = hipFreeAsync(dev, st);
+  return (int)(e != hipSuccess ? e : f);
+}
+
+extern "C" int rdgan_member_stats(const float* x, int n_members, long member_stride, long n_positions, const double* probs, int n_probs,
+                                  const double* thresholds, int n_thresholds, float* quantiles_out, float* mean_out, float* exceed_out,
+                                  long long* n_nan_positions_out, void* stream) {
+  if (!x || !probs || !quantiles_out || !mean_out || !n_nan_positions_out) return -2;
+  if (n_members < 1 || n_members > RD_MS_MAXS || n_positions < 1 || n_positions > (1L << 40) || member_stride < n_positions) return -2;
+  if (n_probs < 1 || n_probs > RD_MS_MAXQ || n_thresholds < 0 || n_thresholds > RD_MS_MAXT) return -2;
+  if (n_thresholds > 0 && (!thresholds || !exceed_out)) return -2;
+  rd_ms_args a;
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < n_probs; ++i) {
+    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return -2;
+    a.probs[i] = probs[i];
+  }
+  for (int i = 0; i < n_thresholds; ++i) {
+    if (!std::isfinite(thresholds[i])) return -2;
+    a.thr[i] = thresholds[i];
+  }
+  const int np2 = rd_pow2_at_least(n_members);
+  const int px = rd_ms_run_width(np2);
+  int lpx = 0;
+  while ((1 << lpx) < px) ++lpx;
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ensure_lds(nullptr, (const void*)k_member_stats, RD_MS_LDS_MAX));
+  hipError_t e = hipMemsetAsync(n_nan_positions_out, 0, sizeof(long long), st);
+  if (e != hipSuccess) return (int)e;
+  const long runs = (n_positions + px - 1) / px;
+  hipLaunchKernelGGL(k_member_stats, dim3((unsigned)std::min<long>(runs, 1L << 16)), dim3(RD_MS_THREADS),
+                     RD_MS_LDS_HEAD + (size_t)np2 * px * sizeof(float), st, x, member_stride, n_members, np2, lpx, n_positions, n_probs,
+                     n_thresholds, a, quantiles_out, mean_out, exceed_out, (unsigned long long*)n_nan_positions_out);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// verification of field ensembles (rdgan_verify.hip.h): state accumulation, rank / reliability / Brier reduction, FSS
+// ------------------------------------------------------------------------------------
+// the thresholds as the kernels compare them: each rounded once to fp32; false unless finite, >= 0 and strictly increasing there
+static bool rd_vf_thresholds(const double* thresholds, int n, rd_vf_thr* out) {
+  if (!thresholds || n < 1 || n > RD_VF_MAXT) return false;
+  memset(out, 0, sizeof(*out));
+  for (int i = 0; i < n; ++i) {
+    if (!(thresholds[i] >= 0.0 && thresholds[i] <= 3.4028234663852886e38)) return false;        // (a NaN fails both)
+    const float f = (float)thresholds[i];
+    if (i > 0 && !(f > out->v[i - 1])) return false;
+    out->v[i] = f;
+  }
+  return true;
+}
+
+static bool rd_vf_widths_ok(const int* widths, int n, int S, rd_vf_widths* out) {
+  if (!widths || n < 1 || n > RD_VF_MAXW) return false;
+  memset(out, 0, sizeof(*out));
+  for (int i = 0; i < n; ++i) {
+    if (widths[i] < 1 || widths[i] % 2 == 0 || (i > 0 && widths[i] <= widths[i - 1])) return false;
+    if (widths[i] > 8192 || (long)S * widths[i] * widths[i] >= (1L << 26)) return false;
+    out->v[i] = widths[i];
+  }
+  return true;
+}
+
+template <int V>
+static void rd_vf_launch_accumulate(int T, unsigned blocks, hipStream_t st, const float* x, long stride, int n, long P, const float* obs,
+                                    const rd_vf_thr& thr, int* exceed, int* below, int* equal, unsigned char* bad) {
+#define RD_VF_CASE(TT)                                                                                                              \
+  case TT:                                                                                                                          \
+    hipLaunchKernelGGL((k_verify_accumulate<TT, V>), dim3(blocks), dim3(RD_VF_THREADS), 0, st, x, stride, n, P, obs, thr, exceed,    \
+                       below, equal, bad);                                                                                          \
+    break;
+  switch (T) {
+    RD_VF_CASE(1) RD_VF_CASE(2) RD_VF_CASE(3) RD_VF_CASE(4) RD_VF_CASE(5) RD_VF_CASE(6) RD_VF_CASE(7) RD_VF_CASE(8)
+  }
+#undef RD_VF_CASE
+}
+
+extern "C" int rdgan_verify_accumulate(const float* members, int n_members, long member_stride, long n_positions, const float* obs,
+                                       const double* thresholds, int n_thresholds, int* exceed, int* below, int* equal,
+                                       unsigned char* bad, void* stream) {
+  rd_vf_thr thr;
+  if (!members || !obs || !exceed || !below || !equal || !bad) return -2;
+  if (n_members < 1 || n_members > RD_VF_MAXS || n_positions < 1 || n_positions > (1L << 40) || member_stride < n_positions) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  const unsigned long long align = (unsigned long long)members | (unsigned long long)obs | (unsigned long long)exceed |
+                                   (unsigned long long)below | (unsigned long long)equal;
+  if (align & 3) return -2;
+  // 16-byte loads where every row of every array starts on 16 bytes: the member rows (base and stride), the T planes of exceed (P)
+  const bool vec = !(align & 15) && !((unsigned long long)bad & 3) && member_stride % 4 == 0 && n_positions % 4 == 0;
+  const long groups = vec ? n_positions / 4 : n_positions;
+  const unsigned blocks = (unsigned)std::min<long>((groups + RD_VF_THREADS - 1) / RD_VF_THREADS, 1L << 16);
+  if (vec)
+    rd_vf_launch_accumulate<4>(n_thresholds, blocks, (hipStream_t)stream, members, member_stride, n_members, n_positions, obs, thr,
+                               exceed, below, equal, bad);
+  else
+    rd_vf_launch_accumulate<1>(n_thresholds, blocks, (hipStream_t)stream, members, member_stride, n_members, n_positions, obs, thr,
+                               exceed, below, equal, bad);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_verify_reduce(const float* obs, const int* exceed, const int* below, const int* equal, const unsigned char* bad,
+                                   long n_positions, long plane, int n_members, const double* thresholds, int n_thresholds, int n_bins,
+                                   uint64_t seed, long long* rank_hist_out, long long* reliability_out, long long* brier_out,
+                                   void* stream) {
+  rd_vf_thr thr;
+  if (!obs || !exceed || !below || !equal || !bad || !rank_hist_out || !reliability_out || !brier_out) return -2;
+  if (n_members < 1 || n_members > RD_VF_MAXS || n_bins < 2 || n_bins > std::min(n_members + 1, RD_VF_MAXBINS)) return -2;
+  if (plane < 1 || n_positions < 1 || n_positions > (1L << 40) || n_positions % plane) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  const int S = n_members, T = n_thresholds;
+  const long n_planes = n_positions / plane;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(rank_hist_out, 0, (size_t)RD_VF_HOURS * (S + 1) * sizeof(long long), st);
+  if (e == hipSuccess) e = hipMemsetAsync(reliability_out, 0, (size_t)T * RD_VF_HOURS * n_bins * 3 * sizeof(long long), st);
+  if (e == hipSuccess) e = hipMemsetAsync(brier_out, 0, (size_t)T * RD_VF_HOURS * 4 * sizeof(long long), st);
+  if (e != hipSuccess) return (int)e;
+  const long units = ((n_planes + RD_VF_HOURS - 1) / RD_VF_HOURS) * ((plane + RD_VF_CHUNK - 1) / RD_VF_CHUNK);       // per hour
+  // at most RD_VF_MAXUNITS chunks per workgroup (the 32-bit LDS counters), at least 64 workgroups per hour where there is work
+  const long nbx = std::max<long>((units + RD_VF_MAXUNITS - 1) / RD_VF_MAXUNITS, std::min<long>(units, 64));
+  const size_t lds = RD_VF_MAXT * 4 * sizeof(unsigned long long) + (size_t)(T * n_bins * 3 + S + 1) * sizeof(unsigned);
+  hipLaunchKernelGGL(k_verify_reduce, dim3((unsigned)nbx, RD_VF_HOURS), dim3(RD_VF_THREADS), lds, st, obs, exceed, below, equal, bad,
+                     n_positions, plane, n_planes, S, T, thr, n_bins, rd_make_key(seed, RD_STREAM_VERIFY),
+                     (unsigned long long*)rank_hist_out, (unsigned long long*)reliability_out, (unsigned long long*)brier_out);
+  return (int)hipGetLastError();
+}
+
+static long rd_vf_box_blocks(long plane) { return std::min<long>((plane + RD_VF_THREADS - 1) / RD_VF_THREADS, RD_VF_BOX_MAXBLOCKS); }
+
+extern "C" long rdgan_verify_fss_workspace_bytes(int ny, int nx, int n_thresholds, int n_widths) {
+  if (ny < 1 || nx < 1 || n_thresholds < 1 || n_thresholds > RD_VF_MAXT || n_widths < 1 || n_widths > RD_VF_MAXW) return -2;
+  const long plane = (long)ny * nx, planes = (long)RD_VF_HOURS * n_thresholds;
+  if (plane > (1L << 36)) return -2;
+  return planes * rd_vf_box_blocks(plane) * n_widths * 2 * (long)sizeof(double) + 2 * planes * plane * (long)sizeof(unsigned);
+}
+
+extern "C" int rdgan_verify_fss(const float* obs, const int* exceed, const unsigned char* bad, long n_days, int ny, int nx,
+                                int n_members, const double* thresholds, int n_thresholds, const int* widths, int n_widths,
+                                double* fss_sums_out, void* workspace, long workspace_bytes, void* stream) {
+  rd_vf_thr thr;
+  rd_vf_widths wd;
+  if (!obs || !exceed || !bad || !fss_sums_out || !workspace || ((unsigned long long)workspace & 7)) return -2;
+  if (n_days < 1 || ny < 1 || nx < 1 || n_members < 1 || n_members > RD_VF_MAXS) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr) || !rd_vf_widths_ok(widths, n_widths, n_members, &wd)) return -2;
+  const long need = rdgan_verify_fss_workspace_bytes(ny, nx, n_thresholds, n_widths);
+  if (need < 0 || workspace_bytes < need) return -2;
+  const int T = n_thresholds, W = n_widths;
+  const long plane = (long)ny * nx, planes = (long)RD_VF_HOURS * T;
+  if (n_days > (1L << 40) / (plane * RD_VF_HOURS)) return -2;
+  const long P = n_days * RD_VF_HOURS * plane, rows = planes * ny, cols = planes * nx;
+  if ((rows + 3) / 4 > 0x7FFFFFFFL || (cols + RD_VF_THREADS - 1) / RD_VF_THREADS > 0x7FFFFFFFL) return -2;
+  const int nblk = (int)rd_vf_box_blocks(plane);
+  double* partial = (double*)workspace;
+  unsigned* satC = (unsigned*)(partial + planes * nblk * W * 2);
+  unsigned* satE = satC + planes * plane;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(fss_sums_out, 0, (size_t)T * W * RD_VF_HOURS * 2 * sizeof(double), st);
+  if (e != hipSuccess) return (int)e;
+  for (long day = 0; day < n_days; ++day) {                 // the days one after another: the workspace holds one day's tables
+    hipLaunchKernelGGL(k_verify_fss_rows, dim3((unsigned)((rows + 3) / 4)), dim3(RD_VF_THREADS), 0, st, obs, exceed, bad, P, day, ny, nx,
+                       n_members, T, thr, satC, satE);
+    hipLaunchKernelGGL(k_verify_fss_cols, dim3((unsigned)((cols + RD_VF_THREADS - 1) / RD_VF_THREADS)), dim3(RD_VF_THREADS), 0, st, satC,
+                       satE, planes, ny, nx);
+    hipLaunchKernelGGL(k_verify_fss_box, dim3((unsigned)nblk, (unsigned)planes), dim3(RD_VF_THREADS), 0, st, satC, satE, ny, nx,
+                       n_members, wd, W, partial);
+    hipLaunchKernelGGL(k_verify_fss_final, dim3((unsigned)((planes * W + RD_VF_THREADS - 1) / RD_VF_THREADS)), dim3(RD_VF_THREADS), 0,
+                       st, partial, nblk, T, W, fss_sums_out);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// temporal structure of hourly fields (rdgan_temporal.hip.h): spells, transitions, wet hours, lagged products
+// ------------------------------------------------------------------------------------
+// workgroups of k_temporal_accumulate for `groups` threads' worth of work
+static long rd_ts_blocks(long groups) { return std::min<long>((groups + RD_TS_THREADS - 1) / RD_TS_THREADS, RD_TS_MAXBLOCKS); }
+
+static bool rd_ts_shape_ok(long n, long plane, int n_thresholds, int max_lag) {
+  if (n < 1 || plane < 1 || n_thresholds < 1 || n_thresholds > RD_TS_MAXT || max_lag < 1 || max_lag > RD_TS_MAXK) return false;
+  return plane <= RD_TS_MAXELEMS / RD_TS_HOURS && n <= RD_TS_MAXELEMS / (RD_TS_HOURS * plane);
+}
+
+extern "C" long rdgan_temporal_workspace_bytes(long n, long plane, int n_thresholds, int max_lag) {
+  if (!rd_ts_shape_ok(n, plane, n_thresholds, max_lag)) return -2;
+  return rd_ts_blocks(n * plane) * rd_ts_nsums(n_thresholds, max_lag) * (long)sizeof(double);       // (the scalar path has the most)
+}
+
+extern "C" int rdgan_temporal_accumulate(const float* x, long n, long day_stride, long plane, const double* thresholds,
+                                         int n_thresholds, int max_lag, long long* counts_inout, double* sums_inout, void* workspace,
+                                         long workspace_bytes, void* stream) {
+  rd_vf_thr thr;
+  if (!x || !counts_inout || !sums_inout || !workspace) return -2;
+  if (((unsigned long long)x & 3) || (((unsigned long long)counts_inout | (unsigned long long)sums_inout | (unsigned long long)workspace) & 7))
+    return -2;
+  if (!rd_ts_shape_ok(n, plane, n_thresholds, max_lag) || day_stride < RD_TS_HOURS * plane || day_stride > (1L << 50) / n) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  if (workspace_bytes < rdgan_temporal_workspace_bytes(n, plane, n_thresholds, max_lag)) return -2;
+  const bool vec = !((unsigned long long)x & 15) && plane % 4 == 0 && day_stride % 4 == 0;
+  const int nblk = (int)rd_ts_blocks(vec ? n * (plane / 4) : n * plane), nsums = rd_ts_nsums(n_thresholds, max_lag);
+  const size_t lds = rd_ts_lds_bytes(n_thresholds);
+  hipStream_t st = (hipStream_t)stream;
+#define RD_TS_LAUNCH(VV, KK)                                                                                                        \
+  do {                                                                                                                              \
+    RD_TRY(ensure_lds(nullptr, (const void*)k_temporal_accumulate<VV, KK>, rd_ts_lds_bytes(RD_TS_MAXT)));                           \
+    hipLaunchKernelGGL((k_temporal_accumulate<VV, KK>), dim3((unsigned)nblk), dim3(RD_TS_THREADS), lds, st, x, n, day_stride, plane, \
+                       thr, n_thresholds, max_lag, (unsigned long long*)counts_inout, (double*)workspace);                          \
+  } while (0)
+  if (vec && max_lag <= 6) RD_TS_LAUNCH(4, 6);
+  else if (vec) RD_TS_LAUNCH(4, 12);
+  else if (max_lag <= 6) RD_TS_LAUNCH(1, 6);
+  else RD_TS_LAUNCH(1, 12);
+#undef RD_TS_LAUNCH
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(k_temporal_final, dim3((unsigned)nsums), dim3(RD_TS_THREADS), 0, st, (const double*)workspace, nblk, nsums,
+                     sums_inout);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// rain cells of hourly fields (rdgan_cells.hip.h): connected wet areas, labelled and counted
+// ------------------------------------------------------------------------------------
+static bool rd_cl_shape_ok(long ny, long nx) {
+  return ny >= 1 && nx >= 1 && ny <= RD_CL_MAXPLANE && nx <= RD_CL_MAXPLANE && ny * nx <= RD_CL_MAXPLANE;
+}
+
+extern "C" long rdgan_cells_workspace_bytes(long ny, long nx, long planes_per_pass) {
+  if (!rd_cl_shape_ok(ny, nx) || planes_per_pass < 1 || planes_per_pass > RD_CL_MAXPASS) return -2;
+  return rd_cl_ws_bytes(ny * nx, planes_per_pass);
+}
+
+extern "C" int rdgan_cells_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds,
+                                      int n_thresholds, int connectivity, long long* counts_inout, int* labels_out,
+                                      int label_threshold, void* workspace, long workspace_bytes, void* stream) {
+  rd_vf_thr thr;
+  if (!x || !counts_inout || !workspace) return -2;
+  if (((unsigned long long)x & 3) || ((unsigned long long)labels_out & 3) ||
+      (((unsigned long long)counts_inout | (unsigned long long)workspace) & 7))
+    return -2;
+  if (n < 1 || !rd_cl_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8)) return -2;
+  const long plane = ny * nx;
+  if (n > RD_CL_MAXELEMS / (RD_CL_HOURS * plane) || day_stride < RD_CL_HOURS * plane || day_stride > (1L << 50) / n) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  if (labels_out && (label_threshold < 0 || label_threshold >= n_thresholds)) return -2;
+  // the planes of a pass: as many as the workspace holds
+  const long n_planes = n * RD_CL_HOURS;
+  const long per_pass = std::min<long>(std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / rd_cl_ws_bytes(plane, 1), n_planes), RD_CL_MAXPASS);
+  if (per_pass < 1) return -2;
+  unsigned long long* vol = (unsigned long long*)workspace;
+  int* parent = (int*)(vol + per_pass * plane);
+  unsigned* area = (unsigned*)(parent + per_pass * plane);
+  unsigned* words = area + per_pass * plane;
+  unsigned long long* counts = (unsigned long long*)counts_inout;
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ensure_lds(nullptr, (const void*)k_cells_label_tile, RD_CL_LDS_BYTES));
+  const int tiles_x = (int)((nx + RD_CL_TILE - 1) / RD_CL_TILE), tiles_y = (int)((ny + RD_CL_TILE - 1) / RD_CL_TILE);
+  const long border = (long)(tiles_x - 1) * ny + (long)(tiles_y - 1) * nx;
+  const int conn8 = connectivity == 8;
+  for (long p0 = 0; p0 < n_planes; p0 += per_pass) {
+    const unsigned P = (unsigned)std::min<long>(per_pass, n_planes - p0);
+    for (int t = 0; t < n_thresholds; ++t) {
+      unsigned long long* ct = counts + (long)t * RD_CL_NC;
+      hipLaunchKernelGGL(k_cells_label_tile, dim3((unsigned)(tiles_x * tiles_y), P), dim3(RD_CL_THREADS), RD_CL_LDS_BYTES, st, x, day_stride,
+                         (int)ny, (int)nx, p0, thr.v[t], conn8, (int)(t == 0), ct + RD_CL_WET,
+                         counts + (long)n_thresholds * RD_CL_NC + 1, vol, parent, area, words);
+      if (border > 0)
+        hipLaunchKernelGGL(k_cells_merge, dim3((unsigned)((border + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st,
+                           (int)ny, (int)nx, conn8, parent);
+      hipLaunchKernelGGL(k_cells_resolve, dim3((unsigned)((plane + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st, plane,
+                         p0, vol, parent, area, labels_out && t == label_threshold ? labels_out : (int*)nullptr);
+      hipLaunchKernelGGL(k_cells_reduce, dim3((unsigned)((plane + RD_CL_RCHUNK - 1) / RD_CL_RCHUNK), P), dim3(RD_CL_THREADS), 0, st, plane, p0,
+                         (const unsigned long long*)vol, (const int*)parent, (const unsigned*)area, words, ct);
+      hipLaunchKernelGGL(k_cells_planes, dim3((P + RD_CL_THREADS - 1) / RD_CL_THREADS), dim3(RD_CL_THREADS), 0, st, (int)P,
+                         (const unsigned*)words, ct, t == 0 ? counts + (long)n_thresholds * RD_CL_NC : (unsigned long long*)nullptr);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return (int)e;
+    }
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// log-spectral distance (rdgan_spectral.hip.h)
+// ------------------------------------------------------------------------------------
+extern "C" int rdgan_spectra_bins(int nd) {
+  if (nd < 8 || nd > RD_SPEC_MAXND || nd % 2) return -2;
+  return rd_spec_bin(nd - 1, nd - 1) - 1;               // bins 1 .. max - 1: the first and the last group are dropped
+}
+
+extern "C" int rdgan_radial_spectra(const float* fields, float* out, long n, int nd, int log_out, void* stream) {
+  const int K = rdgan_spectra_bins(nd);
+  if (!fields || !out || n < 1 || n > (1L << 26) || K < 1) return -2;
+  rd_spec_args a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < nd; ++j) {
+    const double th = -2.0 * M_PI * (double)j / (double)nd;
+    a.tw_re[j] = (float)cos(th);
+    a.tw_im[j] = (float)sin(th);
+  }
+  for (int i = 0; i < nd; ++i)
+    for (int j = 0; j < nd; ++j) {
+      const int b = rd_spec_bin(2 * j - (nd - 1), 2 * i - (nd - 1));
+      if (b >= 1 && b <= K) a.cnt[b - 1]++;
+    }
+  for (int b = 0; b < K; ++b)
+    if (a.cnt[b] == 0) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  const int lo = log_out ? 1 : 0;
+  switch (nd) {
+#define RD_SPEC_CASE(ND)                                                                                                     \
+  case ND: {                                                                                                                 \
+    constexpr int FPB = ND * ND >= 256 ? 1 : 256 / (ND * ND);                                                                \
+    hipLaunchKernelGGL(k_radial_spectra<ND>, dim3((unsigned)((n + FPB - 1) / FPB)), dim3(256), 0, st, fields, out, (int)n, K, \
+                       lo, a);                                                                                               \
+    break;                                                                                                                   \
+  }
+    RD_SPEC_CASE(8) RD_SPEC_CASE(16) RD_SPEC_CASE(24) RD_SPEC_CASE(32) RD_SPEC_CASE(48) RD_SPEC_CASE(64)
+#undef RD_SPEC_CASE
+    default: return -2;
+  }
+  return (int)hipGetLastError();
+}
+
+static void rd_lsd_grid(long n, long m, int* gx, int* gy) {
+  const long nti = (n + RD_LSD_TILE - 1) / RD_LSD_TILE, ntj = (m + RD_LSD_TILE - 1) / RD_LSD_TILE;
+  *gy = (int)nti;
+  *gx = (int)std::max(1L, std::min(ntj, (2048 + nti - 1) / nti));     // ~2048 workgroups; a function of (n, m) alone
+}
+
+extern "C" long rdgan_lsd_workspace_bytes(long n, long m) {
+  if (n < 1 || m < 1 || n > RD_LSD_MAXROWS || m > RD_LSD_MAXROWS) return -2;
+  int gx, gy;
+  rd_lsd_grid(n, m, &gx, &gy);
+  return (long)gx * gy * (long)sizeof(rd_lsd_partial);
+}
+
+extern "C" int rdgan_lsd_pairwise(const float* spec_a, const float* spec_b, long n, long m, int k, int exclude_diagonal,
+                                  float* dist, unsigned long long* hist, int nbins, float lo, float hi, double* moments,
+                                  void* workspace, long workspace_bytes, void* stream) {
+  if (!spec_a || !spec_b || n < 1 || m < 1 || n > RD_LSD_MAXROWS || m > RD_LSD_MAXROWS || k < 1 || k > RD_SPEC_MAXK) return -2;
+  if (!dist && !hist && !moments) return -2;
+  long lds = 2L * k * RD_LSD_TILE * (long)sizeof(float);
+  float scale = 0.f;
+  if (hist) {
+    if (nbins < 1 || !(lo < hi) || !std::isfinite(lo) || !std::isfinite(hi)) return -2;
+    scale = (float)nbins / (hi - lo);
+    if (!std::isfinite(scale)) return -2;
+    lds += 4L * (nbins + 4);
+  }
+  if (lds > RD_LSD_MAX_DYN_LDS) return -2;
+  int gx, gy;
+  rd_lsd_grid(n, m, &gx, &gy);
+  if (moments && (!workspace || workspace_bytes < rdgan_lsd_workspace_bytes(n, m))) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  if (hist) {
+    hipError_t e = hipMemsetAsync(hist, 0, sizeof(unsigned long long) * (nbins + 4), st);
+    if (e != hipSuccess) return (int)e;
+  }
+  rd_lsd_partial* part = moments ? (rd_lsd_partial*)workspace : nullptr;
+  hipLaunchKernelGGL(k_lsd_pairwise, dim3(gx, gy), dim3(256), (size_t)lds, st, spec_a, spec_b, (int)n, (int)m, k,
+                     exclude_diagonal ? 1 : 0, dist, hist, nbins, lo, hi, scale, part);
+  if (moments) hipLaunchKernelGGL(k_lsd_reduce, dim3(1), dim3(256), 0, st, part, gx * gy, moments);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// RainFARM baseline (rdgan_rainfarm.hip.h)
+// ------------------------------------------------------------------------------------
+extern "C" int rdgan_rainfarm_classes(int nd) {
+  if (!rd_rf_nd_ok(nd)) return -2;
+  return (nd / 2 + 1) * (nd / 2 + 1) + RD_RF_TCLASS;
+}
+
+static void rd_rf_stat_grid(long n, int* gs, int* gt) {
+  *gs = (int)std::min((long)RD_RF_STAT_WG, n * RD_RF_NT);
+  *gt = (int)std::min((long)RD_RF_STAT_WG, n);
+}
+
+extern "C" long rdgan_rainfarm_stats_workspace_bytes(long n, int nd) {
+  if (!rd_rf_nd_ok(nd) || n < 1 || n > RD_RF_MAXN) return -2;
+  int gs, gt;
+  rd_rf_stat_grid(n, &gs, &gt);
+  const long nc = (long)(nd / 2 + 1) * (nd / 2 + 1);
+  return ((long)gs * nc + (long)gt * RD_RF_TCLASS) * (long)sizeof(rd_rf_stat);
+}
+
+extern "C" int rdgan_rainfarm_slope_stats(const float* samples, long n, int nd, unsigned long long* counts, double* sums,
+                                          void* workspace, long workspace_bytes, void* stream) {
+  if (!samples || !counts || !sums || !workspace || ((uintptr_t)samples & 15)) return -2;
+  const long need = rdgan_rainfarm_stats_workspace_bytes(n, nd);
+  if (need < 0 || workspace_bytes < need) return -2;
+  rd_rf_slope_args a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < nd; ++j) {
+    const double th = -2.0 * M_PI * (double)j / (double)nd;
+    a.tw_re[j] = cos(th);
+    a.tw_im[j] = sin(th);
+  }
+  for (int j = 0; j < RD_RF_NT; ++j) {
+    const double th = -2.0 * M_PI * (double)j / (double)RD_RF_NT;
+    a.t24_re[j] = cos(th);
+    a.t24_im[j] = sin(th);
+  }
+  int gs, gt;
+  rd_rf_stat_grid(n, &gs, &gt);
+  const int nc = (nd / 2 + 1) * (nd / 2 + 1);
+  rd_rf_stat* ps = (rd_rf_stat*)workspace;
+  rd_rf_stat* pt = ps + (long)gs * nc;
+  hipStream_t st = (hipStream_t)stream;
+  const long nplanes = n * RD_RF_NT;
+  switch (nd) {
+#define RD_RF_STATS_CASE(ND)                                                                                                 \
+  case ND:                                                                                                                   \
+    hipLaunchKernelGGL(k_rf_spatial_stats<ND>, dim3(gs), dim3(256), 0, st, samples, nplanes, ps, a);                        \
+    hipLaunchKernelGGL(k_rf_temporal_stats<ND>, dim3(gt), dim3(256), 0, st, samples, n, pt, a);                             \
+    break;
+    RD_RF_STATS_CASE(8) RD_RF_STATS_CASE(16) RD_RF_STATS_CASE(24) RD_RF_STATS_CASE(32) RD_RF_STATS_CASE(48) RD_RF_STATS_CASE(64)
+#undef RD_RF_STATS_CASE
+    default: return -2;
+  }
+  hipLaunchKernelGGL(k_rf_stats_reduce, dim3((nc + 255) / 256), dim3(256), 0, st, ps, gs, nc, counts, sums);
+  hipLaunchKernelGGL(k_rf_stats_reduce, dim3(1), dim3(256), 0, st, pt, gt, RD_RF_TCLASS, counts + nc, sums + nc);
+  return (int)hipGetLastError();
+}
+
+extern "C" long rdgan_rainfarm_gen_workspace_bytes(long n) {
+  if (n < 1 || n > RD_RF_MAXN) return -2;
+  return n * RD_RF_NT * (long)sizeof(float2);
+}
+
+extern "C" int rdgan_rainfarm_generate(const float* amplitudes, const float* precip, int precip_per_member, const void* uniforms,
+                                       int uniforms_fp64, uint64_t seed, long first_member, float* out, long n, int nd,
+                                       void* workspace, long workspace_bytes, void* stream) {
+  if (!rd_rf_nd_ok(nd) || !amplitudes || !precip || !out || !workspace || first_member < 0) return -2;
+  const long need = rdgan_rainfarm_gen_workspace_bytes(n);
+  if (need < 0 || workspace_bytes < need || ((uintptr_t)amplitudes & 7)) return -2;
+  rd_rf_gen_args a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < nd; ++j) {
+    const double th = 2.0 * M_PI * (double)j / (double)nd;
+    a.tw_re[j] = (float)cos(th);
+    a.tw_im[j] = (float)sin(th);
+  }
+  for (int j = 0; j < RD_RF_NT; ++j) {
+    const double th = 2.0 * M_PI * (double)j / (double)RD_RF_NT;
+    a.t24_re[j] = (float)cos(th);
+    a.t24_im[j] = (float)sin(th);
+  }
+  const int usrc = uniforms ? (uniforms_fp64 ? 2 : 1) : 0;
+  const uint32_t key = rd_make_key(seed, RD_STREAM_RAINFARM);
+  const float2* amp = (const float2*)amplitudes;
+  float2* stats = (float2*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned nb = (unsigned)(n * RD_RF_NT);
+  switch (nd) {
+#define RD_RF_GEN_CASE(ND)                                                                                                   \
+  case ND: {                                                                                                                 \
+    constexpr int NT = rd_rf_gen_shape<ND>::NT;                                                                              \
+    if (usrc == 0)                                                                                                           \
+      hipLaunchKernelGGL((k_rf_gen_planes<ND, 0>), dim3(nb), dim3(NT), 0, st, amp, uniforms, key, first_member, out, stats, a); \
+    else if (usrc == 1)                                                                                                      \
+      hipLaunchKernelGGL((k_rf_gen_planes<ND, 1>), dim3(nb), dim3(NT), 0, st, amp, uniforms, key, first_member, out, stats, a); \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((k_rf_gen_planes<ND, 2>), dim3(nb), dim3(NT), 0, st, amp, uniforms, key, first_member, out, stats, a); \
+    hipLaunchKernelGGL(k_rf_gen_finish<ND>, dim3((unsigned)n), dim3(NT), 0, st, out, precip, precip_per_member ? 1 : 0, stats); \
+    break;                                                                                                                   \
+  }
+    RD_RF_GEN_CASE(8) RD_RF_GEN_CASE(16) RD_RF_GEN_CASE(24) RD_RF_GEN_CASE(32) RD_RF_GEN_CASE(48) RD_RF_GEN_CASE(64)
+#undef RD_RF_GEN_CASE
+    default: return -2;
+  }
+  return (int)hipGetLastError();
+}

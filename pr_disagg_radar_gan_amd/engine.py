@@ -207,9 +207,8 @@ class Engine:
                                        float(grad_scale), self._stream()), self._h, "rdgan_adam")
 
     def set_option(self, name, value):
-        """rdgan_set_option (include/rdgan.h): "collapse", "fast_fwd", "fast_bwd" (exact algebraic forms), "bf16" (bf16 storage
-        mode), "wave_specialized", "ws_ksplit", "tapgather", "g9_direct" (kernel variants), "sample_offset" (data-parallel
-        tests)."""
+        """rdgan_set_option: include/rdgan.h documents every option; csrc/rdgan_options.h lists them one row each (name,
+        normalisation of `value`, the weight forms the option shapes, default)."""
         _lib.check(self.lib.rdgan_set_option(self._h, name.encode(), int(value)), self._h, "rdgan_set_option")
 
     def profile(self, tag_mask):

@@ -235,6 +235,89 @@ def test_weight_form_cache_is_bit_identical_and_builds_once_per_update(bf16):
         eng.close()
 
 
+def _form_option_rows():
+    """(name, admitted values, default, shapes generator forms, shapes critic forms) of every RD_OPTIONS row flagged
+    RD_FORMS_GEN or RD_FORMS_CRITIC, read from csrc/rdgan_options.h"""
+    import re
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pr_disagg_radar_gan_amd", "csrc", "rdgan_options.h")
+    rows = []
+    for name, kind, forms, default in re.findall(
+            r'^\s*\{"(\w+)",\s*(?:nullptr|"\w+"),\s*&RdOptions::\w+,\s*(RD_\w+(?:\([^)]*\))?),\s*([^,]+),\s*(-?\d+),', open(path).read(), flags=re.M):
+        if "RD_FORMS" not in forms:
+            continue
+        if kind == "RD_BOOL":
+            lo, hi = 0, 1
+        elif kind == "RD_TRISTATE":
+            lo, hi = -1, 1
+        else:
+            lo, hi = (int(v) for v in re.match(r"RD_(?:CLAMP|RANGE)\((-?\d+),\s*(-?\d+)\)", kind).groups())
+        rows.append((name, list(range(lo, hi + 1)), int(default), "RD_FORMS_GEN" in forms, "RD_FORMS_CRITIC" in forms))
+    return rows
+
+
+@pytest.mark.parametrize("bf16", [0, 1])
+def test_form_cache_follows_every_form_option(bf16):
+    """Every option whose table row says it shapes cached weight forms (csrc/rdgan_options.h): with the caller vouching for
+    both slabs (fixed non-zero versions), a generator step, then the option set to each other value it admits, then the same
+    step again -- the second result equals, bit for bit, that of a fresh engine created in that option state (whose forms
+    were never built under another), and the counter of the network(s) the row names has advanced.  A state the engine
+    refuses (the bf16 storage mode without "collapse") is refused on both engines."""
+    from pr_disagg_radar_gan_amd import Engine, _lib
+    from pr_disagg_radar_gan_amd.engine import new_version
+    rows = _form_option_rows()
+    names = {r[0] for r in rows}
+    assert {"collapse", "fast_fwd", "bf16", "upconv_slab", "upconv2_slab", "upconv_slab_t", "g9_fused", "tapgather", "dense16",
+            "dense_skinny", "conv_f16", "d2_slab", "d2_fwd_slab"} <= names
+    B, seed = 2, 31
+    rng = np.random.default_rng(14)
+    g, d = W.init_generator(rng, 16), W.init_critic(rng, 16)
+    x, cond, z = ot.synthetic_batch(B, 16, 9)
+    dv = lambda a: torch.from_numpy(a).cuda()
+    zd, cd = dv(z), dv(cond)
+    eng = Engine(ndomain=16, max_batch=B)
+    try:
+        gs, ds = eng.to_slab(g), eng.to_slab(d)
+        vg, vc = new_version(), new_version()
+        step = lambda e, **kw: e.gen_grad(ds, gs, zd, cd, seed, **kw).clone()
+        base = {"bf16": bf16}
+        eng.set_option("bf16", bf16)
+        for name, values, default, shapes_gen, shapes_critic in rows:
+            start = base.get(name, default)
+            for value in values:
+                if value == start:
+                    continue
+                state = dict(base, **{name: value})
+                fresh = Engine(ndomain=16, max_batch=B)
+                try:
+                    for k, v in state.items():
+                        fresh.set_option(k, v)
+                    try:
+                        want = step(fresh)
+                    except _lib.RdganError:
+                        want = None
+                finally:
+                    fresh.close()
+                step(eng, gen_version=vg, critic_version=vc)              # the forms of the start state, vouched for
+                before = eng.form_builds()
+                eng.set_option(name, value)
+                try:
+                    if want is None:
+                        with pytest.raises(_lib.RdganError):
+                            step(eng, gen_version=vg, critic_version=vc)
+                        continue
+                    got = step(eng, gen_version=vg, critic_version=vc)
+                    after = eng.form_builds()
+                    assert torch.equal(got, want), (name, value)
+                    if shapes_gen:
+                        assert after[0] > before[0], (name, value, before, after)
+                    if shapes_critic:
+                        assert after[1] > before[1], (name, value, before, after)
+                finally:
+                    eng.set_option(name, start)
+    finally:
+        eng.close()
+
+
 def test_weight_form_cache_cannot_go_stale_through_the_model_and_trainer_api(tmp_path):
     """Whoever writes a slab takes a fresh version: Generator.set_weights / load_weights drop the device slab (a new slab, a
     new version), a trainer-owned slab adopted by a model is passed with version 0 (rebuild), load_checkpoint bumps both
