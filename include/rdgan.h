@@ -590,6 +590,50 @@ int rdgan_cells_accumulate(const float* x, long n, long day_stride, long ny, lon
                            int connectivity, long long* counts_inout, int* labels_out, int label_threshold, void* workspace,
                            long workspace_bytes, void* stream);
 
+/* Space-time structure of hourly fields: does the rain move?  The wet/dry agreement between hour h at
+ * pixel p and hour h + k at pixel p + d for every small displacement d, and for every pair of hours the displacement that best
+ * maps one wet mask onto the other (the cross-correlation tracking radar nowcasting calls TREC).
+ * x, n, day_stride, ny, nx, thresholds, wet and bad pixels: as for rdgan_cells_accumulate above.  W_t[i,h] is the wet mask of plane
+ * (i, h) at threshold t.  radius R in 1 .. 8, max_lag K in 1 .. 6; ny, nx >= 2R + 1, ny nx <= 2^24, n 24 ny nx <= 2^40.
+ * A displacement is d = (dy, dx), |dy|, |dx| <= R, dy counting rows and dx columns, with the flat index (dy + R)(2R + 1) + dx + R;
+ * there are D = (2R + 1)^2 of them.  d points from the earlier hour to the later one: a positive dx means the rain moved towards
+ * larger x.  Hours pair inside a day only, h = 0 .. 23 - k; days and scenarios never pair with each other.
+ * Pooled counts, over every (i, h <= 23 - k), k = 0 .. K; P(d) is the set of pixels p with p and p + d both inside the plane:
+ *   pairs[k][d]         p in P(d) with neither x[i,h](p) nor x[i,h+k](p + d) bad
+ *   wet_first[t][k][d]  those pairs with W_t[i,h](p)
+ *   wet_second[t][k][d] those pairs with W_t[i,h+k](p + d)
+ *   joint[t][k][d]      those pairs with both
+ * Best shift, per threshold, for k = 1 .. K and every (i, h <= 23 - k): the core C is the set of pixels with R <= y < ny - R and
+ * R <= x < nx - R; A = W_t[i,h], B = W_t[i,h+k]; dist(d) = #{p in C : A(p) != B(p + d)} (a bad pixel is simply dry here).  If A
+ * has no wet pixel in C or B has none in the plane, the pair is uninformative: it adds 1 to no_shift[t][k - 1] and nothing else.
+ * Otherwise its shift d* minimises dist, ties going to the smaller dy^2 + dx^2, then the smaller dy, then the smaller dx; the pair
+ * adds 1 to shift_hist[t][k - 1][d*], dist(d*) to dist_best[t][k - 1] and dist(0) to dist_zero[t][k - 1].
+ * counts_inout [rdgan_spacetime_state_count(T, R, K)] 64-bit integers (device), flat:
+ *     0                  pairs[K + 1][D]
+ *     (K + 1) D + t PT   the block of threshold t, PT = (3 (K + 1) + K) D + 3 K words:
+ *        + 0               wet_first[K + 1][D]
+ *        + (K + 1) D       wet_second[K + 1][D]
+ *        + 2 (K + 1) D     joint[K + 1][D]
+ *        + 3 (K + 1) D     shift_hist[K][D]
+ *        + (3 (K + 1) + K) D         no_shift[K]
+ *        + (3 (K + 1) + K) D + K     dist_best[K]
+ *        + (3 (K + 1) + K) D + 2 K   dist_zero[K]
+ *     (K + 1) D + T PT   n_days, then n_bad_pixels, once per state
+ * The array ACCUMULATES over any number of calls; the caller zeroes it before the first.  Everything is an integer merged with
+ * integer atomics, so the state does not depend on how the days are split into calls, on the workspace size or on the launch
+ * geometry.  The state-count entry returns -2 for T, R or K out of range.
+ * workspace: device memory, 8-byte aligned; it holds the bit masks of a pass, (T + 1) ny ceil(nx / 64) 8 bytes per plane.
+ * rdgan_spacetime_workspace_bytes(ny, nx, n_thresholds, planes_per_pass) is the size for planes_per_pass planes (1 .. 65520; -2
+ * for an argument out of range); the entry takes as many whole DAYS per pass as the workspace holds, at least one, loops over the
+ * passes, and the result does not depend on it.  16-byte loads when x is 16-byte aligned and nx and day_stride are multiples of
+ * 4, a scalar path otherwise (4-byte alignment is required).  Asynchronous on the stream; 0 = success, -2 = bad argument (a null
+ * or misaligned pointer, n < 1, ny or nx < 2R + 1, a size above the limits, a threshold list, radius or max_lag out of range,
+ * day_stride < 24 ny nx, a workspace too small for one day) with nothing launched and no output touched.  All offsets are 64-bit. */
+long rdgan_spacetime_state_count(int n_thresholds, int radius, int max_lag);
+long rdgan_spacetime_workspace_bytes(long ny, long nx, int n_thresholds, long planes_per_pass);
+int rdgan_spacetime_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds, int n_thresholds,
+                               int radius, int max_lag, long long* counts_inout, void* workspace, long workspace_bytes, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

@@ -10,6 +10,7 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
   * ``field_products`` -- k-hour peaks of hourly maps and statistics across an ensemble's members, the hourly ensemble never held
   * ``verification`` -- rank histogram, Brier score with reliability table and fractions skill score of field ensembles against the
     observed hours, accumulated over groups of scenarios
+  * ``spacetime`` -- displaced wet/dry agreement of hour pairs and the shift that best maps one hour's wet mask onto the next
 """
 from .engine import Engine, require_gpu  # noqa: F401
 from . import weights  # noqa: F401

@@ -1,5 +1,5 @@
 // The handle-free entry points of include/rdgan.h: input pipeline, CRPS experiment, distribution checks, whole fields, ensemble
-// products, verification, temporal structure, rain cells, spectra and RainFARM.  They take no rdgan_handle and use nothing of the
+// products, verification, temporal structure, rain cells, space-time structure, spectra and RainFARM.  They take no rdgan_handle and use nothing of the
 // step engine but RD_TRY, ensure_lds(nullptr, ...) and ew_blocks.  Host code, included by rdgan_api.hip at one point, behind the
 // op-level test entries (the library stays one translation unit: one code object for the ISA lint).
 #pragma once
@@ -588,6 +588,70 @@ extern "C" int rdgan_cells_accumulate(const float* x, long n, long day_stride, l
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return (int)e;
     }
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// space-time structure of hourly fields (rdgan_spacetime.hip.h): displaced wet/dry agreement and the best shift of hour pairs
+// ------------------------------------------------------------------------------------
+static bool rd_st_params_ok(int n_thresholds, int radius, int max_lag) {
+  return n_thresholds >= 1 && n_thresholds <= RD_ST_MAXT && radius >= 1 && radius <= RD_ST_MAXR && max_lag >= 1 && max_lag <= RD_ST_MAXK;
+}
+
+static bool rd_st_shape_ok(long ny, long nx, long least) {
+  return ny >= least && nx >= least && ny <= RD_ST_MAXPLANE && nx <= RD_ST_MAXPLANE && ny * nx <= RD_ST_MAXPLANE;
+}
+
+extern "C" long rdgan_spacetime_state_count(int n_thresholds, int radius, int max_lag) {
+  if (!rd_st_params_ok(n_thresholds, radius, max_lag)) return -2;
+  return rd_st_state_count(n_thresholds, radius, max_lag);
+}
+
+extern "C" long rdgan_spacetime_workspace_bytes(long ny, long nx, int n_thresholds, long planes_per_pass) {
+  if (!rd_st_shape_ok(ny, nx, 1) || n_thresholds < 1 || n_thresholds > RD_ST_MAXT || planes_per_pass < 1 || planes_per_pass > RD_ST_MAXPASS)
+    return -2;
+  return planes_per_pass * rd_st_plane_bytes(ny, nx, n_thresholds);
+}
+
+extern "C" int rdgan_spacetime_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds,
+                                          int n_thresholds, int radius, int max_lag, long long* counts_inout, void* workspace,
+                                          long workspace_bytes, void* stream) {
+  rd_vf_thr thr;
+  if (!x || !counts_inout || !workspace) return -2;
+  if (((unsigned long long)x & 3) || (((unsigned long long)counts_inout | (unsigned long long)workspace) & 7)) return -2;
+  if (n < 1 || !rd_vf_thresholds(thresholds, n_thresholds, &thr) || !rd_st_params_ok(n_thresholds, radius, max_lag)) return -2;
+  if (!rd_st_shape_ok(ny, nx, 2 * radius + 1)) return -2;
+  const long plane = ny * nx;
+  if (n > RD_ST_MAXELEMS / (RD_ST_HOURS * plane) || day_stride < RD_ST_HOURS * plane || day_stride > (1L << 50) / n) return -2;
+  // the days of a pass: as many whole days as the workspace holds
+  const long day_bytes = RD_ST_HOURS * rd_st_plane_bytes(ny, nx, n_thresholds);
+  const long per_pass = std::min<long>(std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / day_bytes, n), RD_ST_MAXPASS / RD_ST_HOURS);
+  if (per_pass < 1) return -2;
+  const int W = (int)((nx + 63) / 64), T = n_thresholds;
+  int cw, bh;
+  rd_st_tile(ny, nx, radius, &cw, &bh);
+  const int ns = rd_st_slices(radius, bh);
+  const size_t lds = rd_st_lds_bytes(radius, cw, bh);
+  const bool vec = !((unsigned long long)x & 15) && nx % 4 == 0 && day_stride % 4 == 0;
+  unsigned long long* counts = (unsigned long long*)counts_inout;
+  unsigned long long* tail = counts + rd_st_thr_base(radius, max_lag, T);                 // n_days, n_bad_pixels
+  unsigned long long* masks = (unsigned long long*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  for (long d0 = 0; d0 < n; d0 += per_pass) {
+    const long days = std::min<long>(per_pass, n - d0);
+    const long waves = days * RD_ST_HOURS * ny * (vec ? (W + 3) / 4 : W);
+    const unsigned blocks = (unsigned)std::min<long>((waves + RD_ST_THREADS / 64 - 1) / (RD_ST_THREADS / 64), RD_ST_PACK_MAXBLOCKS);
+    if (vec)
+      hipLaunchKernelGGL(k_st_pack<4>, dim3(blocks), dim3(RD_ST_THREADS), 0, st, x, day_stride, (int)ny, (int)nx, W, d0, days, thr, T, masks,
+                         tail, tail + 1);
+    else
+      hipLaunchKernelGGL(k_st_pack<1>, dim3(blocks), dim3(RD_ST_THREADS), 0, st, x, day_stride, (int)ny, (int)nx, W, d0, days, thr, T, masks,
+                         tail, tail + 1);
+    hipLaunchKernelGGL(k_st_correlate, dim3((unsigned)(days * (max_lag + 1) * RD_ST_GROUPS), (unsigned)T), dim3(RD_ST_THREADS), lds, st,
+                       (const unsigned long long*)masks, (int)ny, (int)nx, W, T, radius, max_lag, cw, bh, ns, counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
   }
   return 0;
 }

@@ -136,6 +136,22 @@ def cell_structure_field(daily, n_scenarios, thresholds, connectivity=8, overlap
                                       overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
 
+def spacetime_structure_field(daily, n_scenarios, thresholds, radius=4, max_lag=1, overlap=4, latent_mode="shared", scenario_chunk=16):
+    """The space-time structure of n_scenarios scenarios of a whole daily map (spacetime.spacetime_structure_field on the module's
+    ``gen`` and ``norm_scale``): the wet/dry agreement of hour h at pixel p with hour h + k at pixel p + d, and the displacement
+    that best maps one hour's wet mask onto the next -- does the rain travel or jump.  daily as generate_scenarios_field takes it;
+    thresholds: the wet-pixel events in mm/h.  Returns a spacetime.SpaceTimeStats (numpy); spacetime.compare sets it against the
+    same statistics of observed days.  The latent noise comes from the global numpy RNG as in generate_scenarios_field; the hourly
+    scenarios are produced scenario_chunk at a time and never held together."""
+    from . import spacetime
+    daily = np.asarray(daily)
+    if daily.ndim >= 3 and daily.shape[-1] == 1:
+        daily = daily[..., 0]
+    return spacetime.spacetime_structure_field(gen, daily, n_scenarios, thresholds, radius=radius, max_lag=max_lag,
+                                               scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode,
+                                               norm_scale=norm_scale)
+
+
 def plot_scenarios(scenarios):
     """reference :68-90: one row per scenario, 24 hourly panels, LogNorm(0.01, 50), gist_earth_r.
     Keeps the reference's indexing ``scenarios[iplot, jplot - 1]`` (the column labelled 00:00 shows

@@ -48,7 +48,8 @@ NO_SPILL = re.compile(r"k_conv_gemm_f16|k_upconv_slab16|k_upconv2_slab16|k_d2_dg
                       r"k_field_scan|k_field_cond|k_field_blend|k_hourly_peaks|k_field_blend_peaks|k_member_stats|"
                       r"k_verify_accumulate|k_verify_reduce|k_verify_fss_rows|k_verify_fss_cols|k_verify_fss_box|k_verify_fss_final|"
                       r"k_temporal_accumulate|k_temporal_final|"
-                      r"k_cells_label_tile|k_cells_merge|k_cells_resolve|k_cells_reduce|k_cells_planes")
+                      r"k_cells_label_tile|k_cells_merge|k_cells_resolve|k_cells_reduce|k_cells_planes|"
+                      r"k_st_pack|k_st_correlate")
 # scratch a NO_SPILL kernel may still use, with the reason (bytes)
 SCRATCH_ALLOWED = {
     r"^k_upconv2_slab16$": 16,     # three per-sample addresses stored in the prologue and reloaded once per sample, outside the K loop
