@@ -590,6 +590,49 @@ int rdgan_cells_accumulate(const float* x, long n, long day_stride, long ny, lon
                            int connectivity, long long* counts_inout, int* labels_out, int label_threshold, void* workspace,
                            long workspace_bytes, void* stream);
 
+/* Storms of hourly fields: wet volumes connected through the day's hours, labelled and counted -- how long
+ * a rain system lives, when it starts, and how much of the day's water falls in long-lived systems.
+ * x, n, day_stride, ny, nx, thresholds, wet and bad pixels, connectivity, q(x): as for the cells entry above.  A voxel (h, y, x)
+ * of day i has the day-local index v = h ny nx + y nx + x.  ny nx <= 2^24, 24 ny nx <= 2^27 and n 24 ny nx <= 2^40.
+ * Two wet voxels of the SAME day are linked when they lie in the same hour and are neighbours under `connectivity` (exactly the
+ * relation of the cells), or lie in consecutive hours h, h + 1 at pixels p, p + d with |dy|, |dx| <= reach, reach in 0 .. 4
+ * (0: the plain overlap rule of cell tracking; 1: rain may move one pixel per hour).  A storm is a maximal set of wet voxels of
+ * one day connected by links; days and scenarios never link.  Its canonical label is its smallest v; a voxel in no storm has
+ * label -1.  Per storm: size, its voxel count (pixel-hours); volume = sum of q(x); start, the hour of its smallest v; last, its
+ * largest hour; duration = last - start + 1 (links join consecutive hours only, so a storm's hours are contiguous).  Its class is
+ * c = space_edge + 2 time_edge: space_edge if any of its voxels lies in the first or last row or column of the plane or has a bad
+ * pixel in the 8-neighbourhood of its own hour (the edge flag of the cells); time_edge if start == 0 or last == 23 (the day
+ * censors the duration).
+ * counts_inout [T * 622 + 2] 64-bit integers (device); per threshold t, at t * 622 +
+ *     0  wet_pixels[h], h = 0 .. 23: wet voxels of hour h
+ *    24  storms[c], c = 0 .. 3: storms by class
+ *    28  duration_hist[c][duration - 1]
+ *   124  start_hour[c][start]
+ *   220  size_hist[c][b], b = floor(log2(size)) = 0 .. 27
+ *   332  size_sum[c]: the sum of the sizes
+ *   336  size_sq_sum[c]: the sum of the squared sizes
+ *   340  size_by_duration[c][duration - 1]: the sum of the sizes
+ *   436  volume_by_duration[c][duration - 1]: the sum of the volumes
+ *   532  storms_per_day[k], k = 0 .. 64: days with k storms, the last bin open (64 or more)
+ *   597  longest_duration[k], k = 0 .. 24: days whose longest storm lasts k hours, k = 0 a day without a wet voxel
+ * then n_days at T * 622 and n_bad_pixels at T * 622 + 1, once per state; the state-count entry returns T * 622 + 2, or -2 for T
+ * outside 1 .. 8.  The array ACCUMULATES over any number of calls; the caller zeroes it before the first.  Everything is an
+ * integer merged with integer atomics, so the state does not depend on how the days are split into calls, on the workspace size
+ * or on the launch geometry.  (The sums wrap modulo 2^64; a volume sum of one day stays below 2^63.)
+ * labels_out: null, or [n][24][ny][nx] int32 (device, dense): the canonical labels at threshold index label_threshold in 0 .. T-1.
+ * workspace: device memory, 8-byte aligned.  The workspace-bytes entry gives the size that lets a pass take days_per_pass whole
+ * days (1 .. 2730; 24 bytes per voxel, 8 per day and 8 per plane; -2 for an argument out of range); the accumulate entry takes as
+ * many whole days per pass as the workspace holds, loops over the passes and the thresholds, and the result does not depend on it.
+ * Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, n, ny or nx < 1, a size above the
+ * limits, a threshold list out of range, connectivity not 4 or 8, reach outside 0 .. 4, label_threshold out of range with
+ * labels_out given, day_stride < 24 ny nx, a workspace too small for one day) with nothing launched and no output touched.  All
+ * offsets are 64-bit. */
+long rdgan_storms_state_count(int n_thresholds);
+long rdgan_storms_workspace_bytes(long ny, long nx, long days_per_pass);
+int rdgan_storms_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds, int n_thresholds,
+                            int connectivity, int reach, long long* counts_inout, int* labels_out, int label_threshold,
+                            void* workspace, long workspace_bytes, void* stream);
+
 /* Space-time structure of hourly fields: does the rain move?  The wet/dry agreement between hour h at
  * pixel p and hour h + k at pixel p + d for every small displacement d, and for every pair of hours the displacement that best
  * maps one wet mask onto the other (the cross-correlation tracking radar nowcasting calls TREC).

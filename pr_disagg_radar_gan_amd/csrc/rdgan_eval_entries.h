@@ -1,5 +1,5 @@
 // The handle-free entry points of include/rdgan.h: input pipeline, CRPS experiment, distribution checks, whole fields, ensemble
-// products, verification, temporal structure, rain cells, space-time structure, spectra and RainFARM.  They take no rdgan_handle and use nothing of the
+// products, verification, temporal structure, rain cells, storms, space-time structure, spectra and RainFARM.  They take no rdgan_handle and use nothing of the
 // step engine but RD_TRY, ensure_lds(nullptr, ...) and ew_blocks.  Host code, included by rdgan_api.hip at one point, behind the
 // op-level test entries (the library stays one translation unit: one code object for the ISA lint).
 #pragma once
@@ -585,6 +585,77 @@ extern "C" int rdgan_cells_accumulate(const float* x, long n, long day_stride, l
                          (const unsigned long long*)vol, (const int*)parent, (const unsigned*)area, words, ct);
       hipLaunchKernelGGL(k_cells_planes, dim3((P + RD_CL_THREADS - 1) / RD_CL_THREADS), dim3(RD_CL_THREADS), 0, st, (int)P,
                          (const unsigned*)words, ct, t == 0 ? counts + (long)n_thresholds * RD_CL_NC : (unsigned long long*)nullptr);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return (int)e;
+    }
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// storms of hourly fields (rdgan_storms.hip.h): wet volumes connected through the day's hours, labelled and counted
+// ------------------------------------------------------------------------------------
+static bool rd_sm_shape_ok(long ny, long nx) { return rd_cl_shape_ok(ny, nx) && RD_CL_HOURS * ny * nx <= RD_SM_MAXDAY; }
+
+extern "C" long rdgan_storms_state_count(int n_thresholds) {
+  if (n_thresholds < 1 || n_thresholds > RD_CL_MAXT) return -2;
+  return (long)n_thresholds * RD_SM_NC + 2;
+}
+
+extern "C" long rdgan_storms_workspace_bytes(long ny, long nx, long days_per_pass) {
+  if (!rd_sm_shape_ok(ny, nx) || days_per_pass < 1 || days_per_pass > RD_SM_MAXPASS) return -2;
+  return rd_sm_ws_bytes(ny * nx, days_per_pass);
+}
+
+extern "C" int rdgan_storms_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds,
+                                       int n_thresholds, int connectivity, int reach, long long* counts_inout, int* labels_out,
+                                       int label_threshold, void* workspace, long workspace_bytes, void* stream) {
+  rd_vf_thr thr;
+  if (!x || !counts_inout || !workspace) return -2;
+  if (((unsigned long long)x & 3) || ((unsigned long long)labels_out & 3) ||
+      (((unsigned long long)counts_inout | (unsigned long long)workspace) & 7))
+    return -2;
+  if (n < 1 || !rd_sm_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8) || reach < 0 || reach > RD_SM_MAXREACH) return -2;
+  const long plane = ny * nx, V = RD_CL_HOURS * plane;
+  if (n > RD_CL_MAXELEMS / V || day_stride < V || day_stride > (1L << 50) / n) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  if (labels_out && (label_threshold < 0 || label_threshold >= n_thresholds)) return -2;
+  // the days of a pass: as many whole days as the workspace holds
+  const long per_pass = std::min<long>(std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / rd_sm_ws_bytes(plane, 1), n), RD_SM_MAXPASS);
+  if (per_pass < 1) return -2;
+  unsigned long long* vol = (unsigned long long*)workspace;
+  int* parent = (int*)(vol + per_pass * V);
+  unsigned* area = (unsigned*)(parent + per_pass * V);
+  unsigned* last = area + per_pass * V;
+  unsigned* day_words = last + 2 * per_pass * V;                          // (behind the spare word of every voxel)
+  unsigned* plane_words = day_words + 2 * per_pass;
+  unsigned long long* counts = (unsigned long long*)counts_inout;
+  unsigned long long* tail = counts + (long)n_thresholds * RD_SM_NC;      // n_days, n_bad_pixels
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ensure_lds(nullptr, (const void*)k_cells_label_tile, RD_CL_LDS_BYTES));
+  const int tiles_x = (int)((nx + RD_CL_TILE - 1) / RD_CL_TILE), tiles_y = (int)((ny + RD_CL_TILE - 1) / RD_CL_TILE);
+  const long border = (long)(tiles_x - 1) * ny + (long)(tiles_y - 1) * nx;
+  const int conn8 = connectivity == 8;
+  const unsigned vblocks = (unsigned)((V + RD_CL_THREADS - 1) / RD_CL_THREADS);
+  for (long d0 = 0; d0 < n; d0 += per_pass) {
+    const unsigned D = (unsigned)std::min<long>(per_pass, n - d0), P = D * RD_CL_HOURS;
+    for (int t = 0; t < n_thresholds; ++t) {
+      unsigned long long* ct = counts + (long)t * RD_SM_NC;
+      hipLaunchKernelGGL(k_cells_label_tile, dim3((unsigned)(tiles_x * tiles_y), P), dim3(RD_CL_THREADS), RD_CL_LDS_BYTES, st, x, day_stride,
+                         (int)ny, (int)nx, d0 * RD_CL_HOURS, thr.v[t], conn8, (int)(t == 0), ct + RD_SM_WET, tail + 1, vol, parent, area,
+                         plane_words);
+      if (border > 0)
+        hipLaunchKernelGGL(k_cells_merge, dim3((unsigned)((border + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st,
+                           (int)ny, (int)nx, conn8, parent);
+      hipLaunchKernelGGL(k_storm_lift, dim3(vblocks, D), dim3(RD_CL_THREADS), 0, st, plane, parent, last, day_words);
+      hipLaunchKernelGGL(k_storm_link, dim3((unsigned)((V - plane + RD_CL_THREADS - 1) / RD_CL_THREADS), D), dim3(RD_CL_THREADS), 0, st, (int)ny,
+                         (int)nx, reach, parent);
+      hipLaunchKernelGGL(k_storm_resolve, dim3(vblocks, D), dim3(RD_CL_THREADS), 0, st, plane, d0, vol, parent, area, last,
+                         labels_out && t == label_threshold ? labels_out : (int*)nullptr);
+      hipLaunchKernelGGL(k_storm_reduce, dim3((unsigned)((V + RD_SM_RCHUNK - 1) / RD_SM_RCHUNK), D), dim3(RD_CL_THREADS), 0, st, plane,
+                         (const unsigned long long*)vol, (const int*)parent, (const unsigned*)area, (const unsigned*)last, day_words, ct);
+      hipLaunchKernelGGL(k_storm_days, dim3((D + RD_CL_THREADS - 1) / RD_CL_THREADS), dim3(RD_CL_THREADS), 0, st, (int)D,
+                         (const unsigned*)day_words, ct, t == 0 ? tail : (unsigned long long*)nullptr);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return (int)e;
     }

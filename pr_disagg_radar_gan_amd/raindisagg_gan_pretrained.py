@@ -136,6 +136,21 @@ def cell_structure_field(daily, n_scenarios, thresholds, connectivity=8, overlap
                                       overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
 
+def storm_structure_field(daily, n_scenarios, thresholds, connectivity=8, reach=1, overlap=4, latent_mode="shared", scenario_chunk=16):
+    """The storms of n_scenarios scenarios of a whole daily map (storms.storm_structure_field on the module's ``gen`` and
+    ``norm_scale``): the wet volumes connected through the day's hours -- how long a rain system lives, when it starts, how much of
+    the day's water falls in long-lived systems.  daily as generate_scenarios_field takes it; thresholds: the wet-pixel events in
+    mm/h; reach: the pixels rain may move per hour and stay the same storm.  Returns a storms.StormStats (numpy); storms.compare
+    sets it against the same statistics of observed days.  The latent noise comes from the global numpy RNG as in
+    generate_scenarios_field; the hourly scenarios are produced scenario_chunk at a time and never held together."""
+    from . import storms
+    daily = np.asarray(daily)
+    if daily.ndim >= 3 and daily.shape[-1] == 1:
+        daily = daily[..., 0]
+    return storms.storm_structure_field(gen, daily, n_scenarios, thresholds, connectivity=connectivity, reach=reach,
+                                        scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
+
+
 def spacetime_structure_field(daily, n_scenarios, thresholds, radius=4, max_lag=1, overlap=4, latent_mode="shared", scenario_chunk=16):
     """The space-time structure of n_scenarios scenarios of a whole daily map (spacetime.spacetime_structure_field on the module's
     ``gen`` and ``norm_scale``): the wet/dry agreement of hour h at pixel p with hour h + k at pixel p + d, and the displacement
