@@ -633,6 +633,46 @@ int rdgan_storms_accumulate(const float* x, long n, long day_stride, long ny, lo
                             int connectivity, int reach, long long* counts_inout, int* labels_out, int label_threshold,
                             void* workspace, long workspace_bytes, void* stream);
 
+/* Areal extremes of hourly fields: depth-area-duration -- for every day the largest accumulation over any
+ * k consecutive hours and any w x w box of pixels, and statistics of those maxima over the days.
+ * x, n, day_stride, ny, nx and the size limits: as for rdgan_cells_accumulate above.  Everything is defined in integers:
+ * q(x) = (int) rintf(x * 1024), in units of 2^-10 mm (the product is exact in fp32, the rounding is half to even).  A pixel-hour is
+ * bad when x is NaN, +-inf, negative or >= 2048; so q < 2^21 and a box sum stays below 2^38.
+ * windows [n_windows] ints on the HOST, 1 <= n_windows = K <= 8, strictly increasing in 1 .. 24 (as for rdgan_hourly_peaks).
+ * widths [n_widths] ints on the HOST, 1 <= n_widths = W <= 8, strictly increasing in 1 .. 64, each <= min(ny, nx): boxes lie wholly
+ * inside the plane and are never clipped.  levels [n_levels] doubles in mm on the HOST, 0 <= n_levels = L <= 16 (null for 0),
+ * finite, strictly increasing, each in [0, 2048 * 24]; L_q[l] = llrint(levels[l] * 1024).
+ * For day u, window k, width w, start hour h0 <= 24 - k and corner (y0, x0), A(h0, y0, x0) is the sum of q over the k hours from h0
+ * and the w x w pixels from (y0, x0); a (window, box) that holds a bad pixel-hour is left out.  Amax[u][k][w] is the maximum of A over
+ * what remains, h*[u][k][w] the smallest h0 that attains it; Amax1[u][k] is Amax at w = 1, computed whether or not 1 is a width.
+ * counts_inout [K * W * (L + 53) + 2] 64-bit integers (device); the record of (k, w) lies at (k W + w) (L + 53) +
+ *     0       level_count[b], b = 0 .. L: days by b = #{l : Amax >= L_q[l] w^2}
+ *     L + 1   start_hour[h], h = 0 .. 23: days by h*
+ *     L + 25  arf_hist[r], r = 0 .. 20: days by min(20, (20 Amax) / (w^2 Amax1)), integer division; only days with Amax1 > 0
+ *     L + 46  sum_A: the sum of Amax over the days in arf_hist
+ *     L + 47  sum_A1: the sum of Amax1 over the same days (the pooled areal reduction factor is sum_A / (w^2 sum_A1))
+ *     L + 48  sum_A_all: the sum of Amax over all counted days
+ *     L + 49  max_A: the largest Amax seen (a running maximum, not a sum)
+ *     L + 50  n_days: days counted
+ *     L + 51  n_void: days with no admissible box; they enter nothing else
+ *     L + 52  n_dry: counted days with Amax1 == 0
+ * then n_days_total at K W (L + 53) and n_bad, the bad pixel-hours, behind it, once per state; the state-count entry returns
+ * K W (L + 53) + 2, or -2 for K, W or L out of range.  The array ACCUMULATES over any number of calls; the caller zeroes it before
+ * the first.  Everything is an integer merged with integer atomics, so the state does not depend on how the days are split into
+ * calls, on the workspace size or on the launch geometry.
+ * depths_out: null, or [n][K][W] 64-bit integers (device, dense): Amax, -1 for a day with no admissible box; written, not added to.
+ * workspace: device memory, 8-byte aligned.  The workspace-bytes entry gives the size that lets a pass take days_per_pass whole
+ * days (1 .. 65535; 576 bytes per day and 120 per pixel, rounded up to 8 per day; -2 for an argument out of range); the accumulate
+ * entry takes as many whole days per pass as the workspace holds, loops over the passes, and the result does not depend on it.
+ * Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, n, ny or nx < 1, a size above the
+ * limits, a list that is empty, unsorted or out of range, a width above min(ny, nx), day_stride < 24 ny nx, a workspace too small
+ * for one day) with nothing launched and no output touched.  All offsets are 64-bit. */
+long rdgan_areal_state_count(int n_windows, int n_widths, int n_levels);
+long rdgan_areal_workspace_bytes(long ny, long nx, long days_per_pass);
+int rdgan_areal_accumulate(const float* x, long n, long day_stride, long ny, long nx, const int* windows, int n_windows,
+                           const int* widths, int n_widths, const double* levels, int n_levels, long long* counts_inout,
+                           long long* depths_out, void* workspace, long workspace_bytes, void* stream);
+
 /* Space-time structure of hourly fields: does the rain move?  The wet/dry agreement between hour h at
  * pixel p and hour h + k at pixel p + d for every small displacement d, and for every pair of hours the displacement that best
  * maps one wet mask onto the other (the cross-correlation tracking radar nowcasting calls TREC).

@@ -111,6 +111,11 @@ SIGNATURES = {
     "rdgan_storms_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                ctypes.c_void_p, ctypes.c_long, c_stream]),
+    "rdgan_areal_state_count": (ctypes.c_long, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "rdgan_areal_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_long]),
+    "rdgan_areal_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,
+                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),
     "rdgan_spacetime_state_count": (ctypes.c_long, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "rdgan_spacetime_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_long]),
     "rdgan_spacetime_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,

@@ -1,5 +1,5 @@
 // The handle-free entry points of include/rdgan.h: input pipeline, CRPS experiment, distribution checks, whole fields, ensemble
-// products, verification, temporal structure, rain cells, storms, space-time structure, spectra and RainFARM.  They take no rdgan_handle and use nothing of the
+// products, verification, temporal structure, rain cells, storms, areal extremes, space-time structure, spectra and RainFARM.  They take no rdgan_handle and use nothing of the
 // step engine but RD_TRY, ensure_lds(nullptr, ...) and ew_blocks.  Host code, included by rdgan_api.hip at one point, behind the
 // op-level test entries (the library stays one translation unit: one code object for the ISA lint).
 #pragma once
@@ -659,6 +659,96 @@ extern "C" int rdgan_storms_accumulate(const float* x, long n, long day_stride, 
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return (int)e;
     }
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// areal extremes of hourly fields (rdgan_areal.hip.h): the largest k-hour accumulation over any w x w box, per day
+// ------------------------------------------------------------------------------------
+// a strictly increasing list of 1 .. n_max whole numbers in lo .. hi
+static bool rd_ar_increasing(const int* v, int n, int n_max, int lo, int hi) {
+  if (!v || n < 1 || n > n_max) return false;
+  for (int i = 0; i < n; ++i)
+    if (v[i] < lo || v[i] > hi || (i > 0 && v[i] <= v[i - 1])) return false;
+  return true;
+}
+
+// the three lists as the kernels take them; false for a list out of range.  The internal widths are 1 and then the caller's others.
+static bool rd_ar_make_lists(const int* windows, int K, const int* widths, int W, const double* levels, int L, long max_width,
+                             rd_ar_lists* out) {
+  if (!rd_ar_increasing(windows, K, RD_AR_MAXK, 1, RD_AR_HOURS) || !rd_ar_increasing(widths, W, RD_AR_MAXW, 1, RD_AR_MAXWIDTH)) return false;
+  if (widths[W - 1] > max_width || L < 0 || L > RD_AR_MAXL || (L > 0 && !levels)) return false;
+  rd_ar_lists a = {};
+  a.K = K, a.W = W, a.L = L, a.slots = 1;
+  a.slot_width[0] = 1;
+  for (int i = 0; i < K; ++i) a.windows[i] = windows[i];
+  for (int i = 0; i < W; ++i) {
+    a.widths[i] = widths[i];
+    a.slot_of[i] = widths[i] == 1 ? 0 : a.slots;
+    if (widths[i] != 1) a.slot_width[a.slots++] = widths[i];
+  }
+  for (int i = 0; i < L; ++i) {
+    if (!(levels[i] >= 0.0 && levels[i] <= 2048.0 * RD_AR_HOURS) || (i > 0 && !(levels[i] > levels[i - 1]))) return false;
+    a.level_q[i] = llrint(levels[i] * 1024.0);
+  }
+  *out = a;
+  return true;
+}
+
+static bool rd_ar_shape_ok(long ny, long nx) {
+  return ny >= 1 && nx >= 1 && ny <= RD_AR_MAXPLANE && nx <= RD_AR_MAXPLANE && ny * nx <= RD_AR_MAXPLANE;
+}
+
+extern "C" long rdgan_areal_state_count(int n_windows, int n_widths, int n_levels) {
+  if (n_windows < 1 || n_windows > RD_AR_MAXK || n_widths < 1 || n_widths > RD_AR_MAXW || n_levels < 0 || n_levels > RD_AR_MAXL) return -2;
+  return rd_ar_state_count(n_windows, n_widths, n_levels);
+}
+
+extern "C" long rdgan_areal_workspace_bytes(long ny, long nx, long days_per_pass) {
+  if (!rd_ar_shape_ok(ny, nx) || days_per_pass < 1 || days_per_pass > RD_AR_MAXPASS) return -2;
+  return days_per_pass * rd_ar_day_bytes(ny * nx);
+}
+
+extern "C" int rdgan_areal_accumulate(const float* x, long n, long day_stride, long ny, long nx, const int* windows, int n_windows,
+                                      const int* widths, int n_widths, const double* levels, int n_levels, long long* counts_inout,
+                                      long long* depths_out, void* workspace, long workspace_bytes, void* stream) {
+  rd_ar_lists lists;
+  if (!x || !counts_inout || !workspace) return -2;
+  if (((unsigned long long)x & 3) || (((unsigned long long)counts_inout | (unsigned long long)depths_out | (unsigned long long)workspace) & 7))
+    return -2;
+  if (n < 1 || !rd_ar_shape_ok(ny, nx)) return -2;
+  const long plane = ny * nx, V = RD_AR_HOURS * plane;
+  if (n > RD_AR_MAXELEMS / V || day_stride < V || day_stride > (1L << 50) / n) return -2;
+  if (!rd_ar_make_lists(windows, n_windows, widths, n_widths, levels, n_levels, std::min(ny, nx), &lists)) return -2;
+  // the days of a pass: as many whole days as the workspace holds
+  const long per_pass = std::min<long>(std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / rd_ar_day_bytes(plane), n), RD_AR_MAXPASS);
+  if (per_pass < 1) return -2;
+  unsigned long long* keys = (unsigned long long*)workspace;
+  int* S = (int*)(keys + per_pass * RD_AR_DAY_KEYS);
+  unsigned char* B = (unsigned char*)(S + per_pass * V);
+  unsigned long long* counts = (unsigned long long*)counts_inout;
+  unsigned long long* tail = counts + rd_ar_state_count(lists.K, lists.W, lists.L) - 2;   // n_days_total, n_bad
+  hipStream_t st = (hipStream_t)stream;
+  const int wmax = lists.slot_width[lists.slots - 1];
+  const size_t lds = rd_ar_lds_bytes(wmax);
+  RD_TRY(ensure_lds(nullptr, (const void*)k_areal_boxes, rd_ar_lds_bytes(RD_AR_MAXWIDTH)));
+  const bool vec = !(((unsigned long long)x | (unsigned long long)S) & 15) && plane % 4 == 0 && day_stride % 4 == 0;
+  const int tiles_x = (int)((nx + RD_AR_TILE - 1) / RD_AR_TILE), tiles_y = (int)((ny + RD_AR_TILE - 1) / RD_AR_TILE);
+  for (long d0 = 0; d0 < n; d0 += per_pass) {
+    const unsigned D = (unsigned)std::min<long>(per_pass, n - d0);
+    if (vec)
+      hipLaunchKernelGGL(k_areal_prefix<4>, dim3((unsigned)((plane / 4 + RD_AR_THREADS - 1) / RD_AR_THREADS), D), dim3(RD_AR_THREADS), 0, st, x,
+                         day_stride, plane, d0, keys, S, B, tail + 1);
+    else
+      hipLaunchKernelGGL(k_areal_prefix<1>, dim3((unsigned)((plane + RD_AR_THREADS - 1) / RD_AR_THREADS), D), dim3(RD_AR_THREADS), 0, st, x,
+                         day_stride, plane, d0, keys, S, B, tail + 1);
+    hipLaunchKernelGGL(k_areal_boxes, dim3((unsigned)(tiles_x * tiles_y), (unsigned)lists.K, D), dim3(RD_AR_THREADS), lds, st, (int)ny, (int)nx,
+                       tiles_x, lists, wmax, (const int*)S, (const unsigned char*)B, keys);
+    hipLaunchKernelGGL(k_areal_days, dim3((D + RD_AR_THREADS - 1) / RD_AR_THREADS, (unsigned)(lists.K * lists.W)), dim3(RD_AR_THREADS), 0, st,
+                       (int)D, d0, lists, (const unsigned long long*)keys, counts, depths_out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
   }
   return 0;
 }

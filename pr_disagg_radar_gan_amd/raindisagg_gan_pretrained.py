@@ -151,6 +151,24 @@ def storm_structure_field(daily, n_scenarios, thresholds, connectivity=8, reach=
                                         scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
 
+def areal_extremes_field(daily, n_scenarios, windows=(1, 3, 6, 12, 24), widths=(1, 5, 15, 31), levels=None, overlap=4, latent_mode="shared",
+                         scenario_chunk=16):
+    """The areal extremes of n_scenarios scenarios of a whole daily map (areal.areal_extremes_field on the module's ``gen`` and
+    ``norm_scale``): for every scenario the largest accumulation over any k consecutive hours and any w x w box of pixels -- the
+    depth-area-duration table and the storm-centred areal reduction factor, which say whether the generator's peaks are too
+    speckled or too smooth for a catchment.  daily as generate_scenarios_field takes it; windows: the durations in hours; widths:
+    the box widths in pixels; levels: areal-mean depths in mm whose exceedance is counted (None: areal.DEFAULT_LEVELS).  Returns an
+    areal.ArealStats (numpy); areal.compare sets it against the same statistics of observed days.  The latent noise comes from the
+    global numpy RNG as in generate_scenarios_field; the hourly scenarios are produced scenario_chunk at a time and never held
+    together."""
+    from . import areal
+    daily = np.asarray(daily)
+    if daily.ndim >= 3 and daily.shape[-1] == 1:
+        daily = daily[..., 0]
+    return areal.areal_extremes_field(gen, daily, n_scenarios, windows, widths, areal.DEFAULT_LEVELS if levels is None else levels,
+                                      scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
+
+
 def spacetime_structure_field(daily, n_scenarios, thresholds, radius=4, max_lag=1, overlap=4, latent_mode="shared", scenario_chunk=16):
     """The space-time structure of n_scenarios scenarios of a whole daily map (spacetime.spacetime_structure_field on the module's
     ``gen`` and ``norm_scale``): the wet/dry agreement of hour h at pixel p with hour h + k at pixel p + d, and the displacement
