@@ -717,6 +717,52 @@ long rdgan_spacetime_workspace_bytes(long ny, long nx, int n_thresholds, long pl
 int rdgan_spacetime_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds, int n_thresholds,
                                int radius, int max_lag, long long* counts_inout, void* workspace, long workspace_bytes, void* stream);
 
+/* Analog baseline, the method of fragments: the k library days whose daily field most resembles a daily
+ * condition, one of them picked per member, its hourly fractions scaled to the condition's daily amounts.
+ * The search is defined in integers.  q(x) = (int) rintf(x * 1024).  A pixel-hour of the library is bad when x is NaN, +-inf,
+ * negative or >= 2048; D[p] is the sum of q over the 24 hours (a bad hour adds 0), below 2^26; the feature is e[p] =
+ * floor(sqrt(D[p])), exact, below 2^13.  A library day is VOID when it holds a bad pixel-hour or the sum of its D is 0; a void day
+ * is never a neighbour.  A query is a daily sum in mm, Dq = (int) rintf(x * 1024), e = floor(sqrt(Dq)); a pixel of a query is MASKED
+ * when x is NaN, +-inf, negative or >= 2048 * 24.  dist(i, j) is the sum over the unmasked pixels of query i of (e_i[p] - e_j[p])^2,
+ * below 2^38, and key = dist * 2^24 + j: equal distances go to the smaller library index.  A library day whose group equals the
+ * query's group, and is >= 0, is skipped.
+ * Shapes: 1 <= ny nx = P <= 4096, Ppad = 8 ceil(P / 8), C = Ppad / 8; 1 <= n < 2^24 library days; 1 <= n_queries <= 2^18;
+ * 1 <= k <= 32; 1 <= n_members <= 65535.  All buffers lie on the device.
+ * rdgan_analog_features, hourly != 0: x [n][24][ny][nx] fp32, the leading stride day_stride >= 24 P (4-byte aligned; 16-byte loads
+ * when x is 16-byte aligned and P and day_stride are multiples of 4).  feat_out: 64 ceil(n / 64) Ppad uint16, 16-byte aligned, in
+ * blocks of 64 days: the 8 pixels 8c .. 8c + 7 of day j lie at byte 16 (((j / 64) C + c) 64 + j % 64); padding pixels are 0, the
+ * days behind n are not written.  total_out [n] 64-bit: the sum of q over the day's pixel-hours that are not bad.  void_out [n]
+ * bytes, 1 for a void day.  n_void_out [1] 64-bit: the count of void days (written, not added to).  mask_out must be null.
+ * rdgan_analog_features, hourly == 0: x [n][ny][nx] fp32, day_stride == P.  feat_out and mask_out [n][Ppad] uint16, 16-byte
+ * aligned: the feature, and 0xFFFF for a pixel that counts; both 0 for a masked or padding pixel.  The other outputs must be null.
+ * rdgan_analog_search: lib_feat, lib_void as written above for n days of `plane` = P pixels; query_feat, query_mask likewise.
+ * lib_groups [n], query_groups [n_queries] int32, null for no exclusion (both must be given to have one).  neighbours_out
+ * [n_queries][k] int32 and distances_out [n_queries][k] 64-bit, by ascending key, -1 in the slots behind the admissible days;
+ * found_out [n_queries] int32, the slots filled.  workspace: 8-byte aligned; rdgan_analog_workspace_bytes(n_queries, k, n_slices)
+ * = n_slices n_queries 64 k bytes holds the lists of n_slices slices (-2 for an argument out of range).  The search cuts the
+ * library into as many slices as the workspace holds lists for, at most one per block of 64 days, each ceil(blocks / slices)
+ * blocks long; the result does not depend on it, nor on the query tile (16 queries while Ppad <= 2048, 8 above) or the geometry.
+ * rdgan_analog_apply: lib [n][24][ny][nx] with day_stride, cond [n_queries][ny][nx], neighbours [n_queries][k] and found
+ * [n_queries] as the search wrote them.  For query i and member m, f = found[i]: bits = rd_bits(rd_member_key(rd_make_key(seed, 9),
+ * first_member + m), first_query + i) (csrc/rdgan_rng.h); weights 0 (uniform): r = (bits f) >> 32; weights 1 (1 / rank): c[r] =
+ * sum over s <= r of floor(2^20 / (s + 1)), r the first index with c[r] > (bits c[f - 1]) >> 32; the donor is j = neighbours[i][r].
+ * picks_out [n_queries][n_members] int32: j, -1 when f = 0.  out [n_queries][n_members][24][ny][nx] fp32: with d[p] the fp32 sum of
+ * the donor's hours 0 .. 23 in that order, cond[i][p] * (lib[j][h][p] / d[p]) where d[p] > 0 and cond[i][p] * (the donor's sum
+ * over the plane of hour h / its sum over the day) where d[p] = 0; NaN at a masked pixel and throughout when f = 0.
+ * Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, a size outside the limits above, an
+ * output that the mode does not write, day_stride below 24 P, a workspace too small for one slice, weights not 0 or 1, first_query
+ * + n_queries above 2^32) with nothing launched and no output touched.  All offsets are 64-bit. */
+long rdgan_analog_workspace_bytes(long n_queries, int k, long n_slices);
+int rdgan_analog_features(const float* x, long n, long day_stride, long ny, long nx, int hourly, unsigned short* feat_out,
+                          unsigned short* mask_out, long long* total_out, unsigned char* void_out, long long* n_void_out, void* stream);
+int rdgan_analog_search(const unsigned short* lib_feat, const unsigned char* lib_void, const int* lib_groups, long n, long plane,
+                        const unsigned short* query_feat, const unsigned short* query_mask, const int* query_groups, long n_queries,
+                        int k, int* neighbours_out, long long* distances_out, int* found_out, void* workspace, long workspace_bytes,
+                        void* stream);
+int rdgan_analog_apply(const float* lib, long n, long day_stride, long ny, long nx, const float* cond, long n_queries,
+                       long first_query, const int* neighbours, const int* found, int k, int n_members, long first_member,
+                       unsigned long long seed, int weights, float* out, int* picks_out, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

@@ -1,5 +1,5 @@
 // The handle-free entry points of include/rdgan.h: input pipeline, CRPS experiment, distribution checks, whole fields, ensemble
-// products, verification, temporal structure, rain cells, storms, areal extremes, space-time structure, spectra and RainFARM.  They take no rdgan_handle and use nothing of the
+// products, verification, temporal structure, rain cells, storms, areal extremes, space-time structure, analogs, spectra and RainFARM.  They take no rdgan_handle and use nothing of the
 // step engine but RD_TRY, ensure_lds(nullptr, ...) and ew_blocks.  Host code, included by rdgan_api.hip at one point, behind the
 // op-level test entries (the library stays one translation unit: one code object for the ISA lint).
 #pragma once
@@ -815,6 +815,100 @@ extern "C" int rdgan_spacetime_accumulate(const float* x, long n, long day_strid
     if (e != hipSuccess) return (int)e;
   }
   return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// analog baseline (rdgan_analog.hip.h): the nearest library days of a daily condition and their scaled hourly fractions
+// ------------------------------------------------------------------------------------
+static bool rd_an_shape_ok(long ny, long nx) { return ny >= 1 && nx >= 1 && ny <= RD_AN_MAXP && nx <= RD_AN_MAXP && ny * nx <= RD_AN_MAXP; }
+
+extern "C" long rdgan_analog_workspace_bytes(long n_queries, int k, long n_slices) {
+  if (n_queries < 1 || n_queries > RD_AN_MAXQ || k < 1 || k > RD_AN_MAXK || n_slices < 1 || n_slices > rd_an_blocks(RD_AN_MAXN)) return -2;
+  return n_slices * rd_an_list_bytes(n_queries, k);
+}
+
+extern "C" int rdgan_analog_features(const float* x, long n, long day_stride, long ny, long nx, int hourly, unsigned short* feat_out,
+                                     unsigned short* mask_out, long long* total_out, unsigned char* void_out, long long* n_void_out,
+                                     void* stream) {
+  if (!x || !feat_out || ((unsigned long long)x & 3) || ((unsigned long long)feat_out & 15)) return -2;
+  if (n < 1 || !rd_an_shape_ok(ny, nx)) return -2;
+  const long plane = ny * nx, ppad = rd_an_ppad(plane);
+  const int C = (int)(ppad / 8);
+  hipStream_t st = (hipStream_t)stream;
+  if (!hourly) {                                                           // the conditions of the queries, [n][plane]
+    if (!mask_out || ((unsigned long long)mask_out & 15) || total_out || void_out || n_void_out) return -2;
+    if (n > RD_AN_MAXQ || day_stride != plane) return -2;
+    hipLaunchKernelGGL(k_analog_query, dim3((unsigned)((n * ppad + 255) / 256)), dim3(256), 0, st, x, n, (int)plane, (int)ppad, feat_out, mask_out);
+    return (int)hipGetLastError();
+  }
+  if (mask_out || !total_out || !void_out || !n_void_out || (((unsigned long long)total_out | (unsigned long long)n_void_out) & 7)) return -2;
+  if (n > RD_AN_MAXN || day_stride < RD_AN_HOURS * plane || day_stride > (1L << 50) / n) return -2;
+  RD_TRY((int)hipMemsetAsync(total_out, 0, (size_t)n * 8, st));
+  RD_TRY((int)hipMemsetAsync(n_void_out, 0, 8, st));
+  const unsigned blocks = (unsigned)((n * C + 255) / 256);
+  if (!((unsigned long long)x & 15) && plane % 4 == 0 && day_stride % 4 == 0)
+    hipLaunchKernelGGL(k_analog_features<true>, dim3(blocks), dim3(256), 0, st, x, n, day_stride, (int)plane, C, (uint4*)feat_out,
+                       (unsigned long long*)total_out);
+  else
+    hipLaunchKernelGGL(k_analog_features<false>, dim3(blocks), dim3(256), 0, st, x, n, day_stride, (int)plane, C, (uint4*)feat_out,
+                       (unsigned long long*)total_out);
+  hipLaunchKernelGGL(k_analog_days, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (unsigned long long*)total_out, void_out,
+                     (unsigned long long*)n_void_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_analog_search(const unsigned short* lib_feat, const unsigned char* lib_void, const int* lib_groups, long n, long plane,
+                                   const unsigned short* query_feat, const unsigned short* query_mask, const int* query_groups,
+                                   long n_queries, int k, int* neighbours_out, long long* distances_out, int* found_out, void* workspace,
+                                   long workspace_bytes, void* stream) {
+  if (!lib_feat || !lib_void || !query_feat || !query_mask || !neighbours_out || !distances_out || !found_out || !workspace) return -2;
+  if ((((unsigned long long)lib_feat | (unsigned long long)query_feat | (unsigned long long)query_mask) & 15) ||
+      (((unsigned long long)distances_out | (unsigned long long)workspace) & 7) ||
+      (((unsigned long long)lib_groups | (unsigned long long)query_groups | (unsigned long long)neighbours_out | (unsigned long long)found_out) & 3))
+    return -2;
+  if (n < 1 || n > RD_AN_MAXN || plane < 1 || plane > RD_AN_MAXP || n_queries < 1 || n_queries > RD_AN_MAXQ || k < 1 || k > RD_AN_MAXK) return -2;
+  // the slices: as many lists per query as the workspace holds, at most one slice per block of 64 days
+  const long nblocks = rd_an_blocks(n);
+  const long held = std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / rd_an_list_bytes(n_queries, k), nblocks);
+  if (held < 1) return -2;
+  const long per_slice = (nblocks + held - 1) / held, slices = (nblocks + per_slice - 1) / per_slice;
+  const int C = (int)(rd_an_ppad(plane) / 8), QT = rd_an_query_tile(plane);
+  const size_t lds = rd_an_lds_bytes(plane);
+  const dim3 grid((unsigned)slices, (unsigned)((n_queries + QT - 1) / QT));
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* lists = (unsigned long long*)workspace;
+  if (QT == RD_AN_QT_SMALL) {
+    RD_TRY(ensure_lds(nullptr, (const void*)k_analog_search<RD_AN_QT_SMALL>, (size_t)RD_AN_QT_SMALL * RD_AN_QT_SPLIT * 4));
+    hipLaunchKernelGGL(k_analog_search<RD_AN_QT_SMALL>, grid, dim3(RD_AN_THREADS), lds, st, (const uint4*)lib_feat, lib_void, lib_groups,
+                       (const uint4*)query_feat, (const uint4*)query_mask, query_groups, (int)n, (int)n_queries, C, k, (int)nblocks,
+                       (int)per_slice, lists);
+  } else {
+    RD_TRY(ensure_lds(nullptr, (const void*)k_analog_search<RD_AN_QT_LARGE>, (size_t)RD_AN_QT_LARGE * RD_AN_MAXP * 4));
+    hipLaunchKernelGGL(k_analog_search<RD_AN_QT_LARGE>, grid, dim3(RD_AN_THREADS), lds, st, (const uint4*)lib_feat, lib_void, lib_groups,
+                       (const uint4*)query_feat, (const uint4*)query_mask, query_groups, (int)n, (int)n_queries, C, k, (int)nblocks,
+                       (int)per_slice, lists);
+  }
+  hipLaunchKernelGGL(k_analog_merge, dim3((unsigned)n_queries), dim3(64), 0, st, (const unsigned long long*)lists, slices * RD_AN_WAVES, k,
+                     neighbours_out, distances_out, found_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_analog_apply(const float* lib, long n, long day_stride, long ny, long nx, const float* cond, long n_queries,
+                                  long first_query, const int* neighbours, const int* found, int k, int n_members, long first_member,
+                                  unsigned long long seed, int weights, float* out, int* picks_out, void* stream) {
+  if (!lib || !cond || !neighbours || !found || !out || !picks_out) return -2;
+  if (((unsigned long long)lib | (unsigned long long)cond | (unsigned long long)neighbours | (unsigned long long)found | (unsigned long long)out |
+       (unsigned long long)picks_out) & 3)
+    return -2;
+  if (n < 1 || n > RD_AN_MAXN || !rd_an_shape_ok(ny, nx) || n_queries < 1 || n_queries > RD_AN_MAXQ || k < 1 || k > RD_AN_MAXK) return -2;
+  const long plane = ny * nx;
+  if (day_stride < RD_AN_HOURS * plane || day_stride > (1L << 50) / n || n_members < 1 || n_members > RD_AN_MAXS) return -2;
+  if (first_query < 0 || first_query > (1L << 32) - n_queries || first_member < 0 || first_member > (1L << 62)) return -2;
+  if (weights != RD_AN_UNIFORM && weights != RD_AN_RANK) return -2;
+  hipLaunchKernelGGL(k_analog_apply, dim3((unsigned)n_queries, (unsigned)n_members), dim3(RD_AN_APPLY_THREADS), (size_t)plane * 4,
+                     (hipStream_t)stream, lib, n, day_stride, (int)plane, cond, first_query, neighbours, found, k, first_member, seed, weights,
+                     out, picks_out);
+  return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------
