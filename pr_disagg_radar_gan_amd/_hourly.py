@@ -1,7 +1,13 @@
 """What the evaluations of hourly arrays share on the host: how an array (..., 24, ny, nx) is admitted -- kind, shape, layout --
-before any device call, and the two small quotients their statistics use."""
+before any device call, the accumulator they all are (HourlyAccumulator) with its driver for whole daily fields
+(evaluate_field), and the two small quotients their statistics use."""
 import numpy as np
 import torch
+
+from . import _lib
+from . import field as F
+from ._dev import ptr as _p, stream as _stream, workspace_bytes
+from .engine import require_gpu
 
 NHOURS = 24
 MAX_MEMBERS = 4096                                                           # RD_MS_MAXS, RD_VF_MAXS
@@ -99,6 +105,104 @@ def to_state_device(a, from_host, device, what="hourly"):
     if a.device != device:
         raise ValueError(f"{what} lies on {a.device}, the state on {device}")
     return a
+
+
+def check_out_tensor(t, name, dtype, shape):
+    """an optional output of an accumulate entry: None, or a contiguous CUDA tensor of this dtype and shape"""
+    if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+                              and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name}: expected a contiguous {str(dtype).split('.')[-1]} CUDA tensor of shape {tuple(shape)}")
+
+
+class HourlyAccumulator:
+    """What the accumulators of hourly arrays share: an integer state `counts` on the device that add() grows call by call, the
+    plane shape the first call pins, and one workspace.  A subclass names its two library entries and supplies what differs:
+
+      _state_tensors(device)            allocate the zeroed state: self.counts (temporal: and self.sums)
+      _check_plane(ny, nx, what)        ValueError for a plane the evaluation cannot take
+      _check_args(shape, n, out, ...)   ValueError for a bad out tensor or extra argument of add; -> the extra arguments, normalised
+      _pass_units(n, ny, nx)            how many of the entry's units (planes or days) one pass takes; None where there are no passes
+      _workspace_args(n, ny, nx)        the arguments of workspace_entry, (ny, nx, _pass_units) unless overridden
+      _entry_args(ny, nx, out, ...)     the arguments of `entry` between (x, n, day_stride) and the workspace
+      result()                          the state as statistics on the host
+
+    The workspace only grows, and the entry is told the bytes this call needs, not the size of the buffer: the entries take as many
+    units per pass as the bytes they are told hold, so a buffer left larger by an earlier call changes nothing (and the state does
+    not depend on the pass size in any case)."""
+    entry = workspace_entry = None
+    out_name = None                              # how add's optional out tensor is called in messages
+    device = None                                # where a numpy input goes (None: "cuda"); a tensor input fixes it
+
+    def reset(self):
+        """forget the days added so far (and the plane shape); returns self"""
+        self.plane_shape = None
+        self.lib = None
+        self.counts = self._ws = None
+        return self
+
+    def _start(self, device):
+        require_gpu()
+        self.lib = _lib.load()
+        self._state_tensors(device)
+
+    def _check_plane(self, ny, nx, what):
+        pass
+
+    def _check_args(self, shape, n, out):
+        return ()
+
+    def _pass_units(self, n, ny, nx):
+        return None
+
+    def _workspace_args(self, n, ny, nx):
+        return ny, nx, self._pass_units(n, ny, nx)
+
+    def add(self, hourly, out=None, *extra):
+        """hourly (..., 24, ny, nx) float32: a CUDA tensor, whose leading axis may have any stride >= the size of one of its
+        entries (a view of a wider buffer; tensor_layout has the rule, and refuses a crop, a step or a transpose at any rank), or
+        a numpy array.  The plane shape is fixed by the first call.  Returns self."""
+        hourly, from_host, shape, n, stride = admit(hourly, self.plane_shape)
+        ny, nx = shape[-2:]
+        self._check_plane(ny, nx, "hourly")
+        extra = self._check_args(shape, n, out, *extra)
+        if self.counts is None:
+            self._start((self.device or "cuda") if from_host else hourly.device)
+        device = self.counts.device
+        hourly = to_state_device(hourly, from_host, device)
+        if out is not None:
+            to_state_device(out, False, device, self.out_name)
+        self.plane_shape = shape[-2:]
+        with torch.cuda.device(device):
+            nbytes = workspace_bytes(self.lib, self.workspace_entry, *self._workspace_args(n, ny, nx))
+            if self._ws is None or self._ws.numel() * 8 < nbytes:
+                self._ws = None
+                self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+            rc = getattr(self.lib, self.entry)(_p(hourly), n, stride, *self._entry_args(ny, nx, out, *extra), _p(self._ws), nbytes,
+                                               _stream(self.counts))
+        _lib.check(rc, None, self.entry)
+        return self
+
+    def state(self):
+        """the state tensor itself, on the device, in the flat order of include/rdgan.h"""
+        if self.counts is None:
+            raise ValueError("nothing has been added")
+        return self.counts
+
+
+def evaluate_field(acc, gen, daily, n_scenarios, scenario_chunk, overlap, latent_mode, seed, latent, chunk, norm_scale):
+    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and add them to the accumulator `acc` without holding
+    them; -> acc.result().  The latent array is drawn once for all scenarios, exactly as field.disaggregate draws it for the same
+    seed, latent and numpy RNG state; disaggregate then runs for scenario_chunk scenarios at a time into one reused buffer and each
+    result is added.  The result is the evaluation of the hourly values those disaggregate calls produce.  The generator's fp32
+    output depends in its last bits on the batch of tiles it runs in, so against the evaluation of
+    disaggregate(...all scenarios...)[0] the integer states are equal (and temporal's sums within the reordering bound) when the
+    batches are the same (`chunk` at most one unit's wet tiles, or one scenario chunk); otherwise the two differ as disaggregate's
+    own outputs differ between values of `chunk`."""
+    S, step = F._check_scenarios(n_scenarios, scenario_chunk)
+    req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
+    acc._check_plane(req[3], req[4], "daily")
+    F._stream_scenarios(gen, req, req[0], S, step, acc.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
+    return acc.result()
 
 
 def div(a, b):

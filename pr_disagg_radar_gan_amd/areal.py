@@ -18,11 +18,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
-from . import field as F
 from . import weights as W
-from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import NHOURS, admit, div as _div, to_state_device, tv as _tv
+from ._dev import host_ptr as _hp, ptr as _p, whole_number
+from ._hourly import NHOURS, HourlyAccumulator, admit, check_out_tensor, div as _div, evaluate_field, tv as _tv
 from .engine import require_gpu
 
 UNIT = 1024                                                                  # depths are integers in 1 / UNIT mm
@@ -79,13 +77,6 @@ def check_levels(levels):
 
 def check_workspace_days(workspace_days):
     return None if workspace_days is None else whole_number(workspace_days, 1, MAX_PASS, "workspace_days, unless None,")
-
-
-def _check_plane(ny, nx, widths, what):
-    if ny * nx > MAX_PLANE:
-        raise ValueError(f"{what}: a plane has {ny * nx} pixels, the limit is {MAX_PLANE}")
-    if int(widths[-1]) > min(ny, nx):
-        raise ValueError(f"{what}: the width {int(widths[-1])} is larger than the plane {(ny, nx)}; boxes are never clipped")
 
 
 def state_count(n_windows, n_widths, n_levels):
@@ -180,12 +171,13 @@ def stats_from_state(counts, windows, widths, levels):
                       **split_state(counts, len(k), len(w), len(lv)))
 
 
-class ArealExtremes:
+class ArealExtremes(HourlyAccumulator):
     """The state of an areal-extremes evaluation on the device.  windows: the durations k in hours; widths: the box widths w in
     pixels, each at most the smaller side of the plane; levels: depths in mm of areal-mean accumulation whose exceedance is counted
     (may be empty); device: where a numpy input goes (None: "cuda"; a tensor input fixes it); workspace_days: how many days the
     workspace holds at a time, 120 bytes per pixel -- None: up to 2^22 pixels, 480 MB (one day if a day is larger).  The result does
-    not depend on it."""
+    not depend on it.  state(): counts (K W (L + 53) + 2,) int64."""
+    entry, workspace_entry, out_name = "rdgan_areal_accumulate", "rdgan_areal_workspace_bytes", "depths_out"
 
     def __init__(self, windows, widths, levels=(), device=None, workspace_days=None):
         self.windows, self.widths, self.levels = check_windows(windows), check_widths(widths), check_levels(levels)
@@ -193,54 +185,32 @@ class ArealExtremes:
         self.workspace_days = check_workspace_days(workspace_days)
         self.reset()
 
-    def reset(self):
-        """forget the days added so far (and the plane shape); returns self"""
-        self.plane_shape = None
-        self.lib = None
-        self.counts = self._ws = None
-        return self
-
-    def _start(self, device):
-        require_gpu()
-        self.lib = _lib.load()
-        self.counts = torch.zeros(state_count(len(self.windows), len(self.widths), len(self.levels)), dtype=torch.int64, device=device)
-
     def add(self, hourly, depths_out=None):
-        """hourly (..., 24, ny, nx) float32 in mm/h: a CUDA tensor or a numpy array, admitted as cells.CellStructure.add admits
+        """hourly (..., 24, ny, nx) float32 in mm/h: a CUDA tensor or a numpy array, admitted as HourlyAccumulator.add admits
         it.  The plane shape is fixed by the first call.  depths_out: None, or a contiguous int64 CUDA tensor (n, K, W), n the
         days of hourly, that receives the day's maxima in 1/1024 mm, -1 for a day with no admissible box.  Returns self."""
-        hourly, from_host, shape, n, stride = admit(hourly, self.plane_shape)
-        ny, nx = shape[-2:]
-        _check_plane(ny, nx, self.widths, "hourly")
-        K, Wn = len(self.windows), len(self.widths)
-        if depths_out is not None and not (isinstance(depths_out, torch.Tensor) and depths_out.is_cuda and depths_out.dtype == torch.int64
-                                           and depths_out.is_contiguous() and tuple(depths_out.shape) == (n, K, Wn)):
-            raise ValueError(f"depths_out: expected a contiguous int64 CUDA tensor of shape {(n, K, Wn)}")
-        if self.counts is None:
-            self._start((self.device or "cuda") if from_host else hourly.device)
-        hourly = to_state_device(hourly, from_host, self.counts.device)
-        if depths_out is not None and depths_out.device != self.counts.device:
-            raise ValueError(f"depths_out lies on {depths_out.device}, the state on {self.counts.device}")
-        self.plane_shape = shape[-2:]
-        per_pass = self.workspace_days or max(1, _DEFAULT_PASS_PIXELS // (ny * nx))
-        per_pass = min(per_pass, n, MAX_PASS)
-        with torch.cuda.device(self.counts.device):
-            nbytes = workspace_bytes(self.lib, "rdgan_areal_workspace_bytes", ny, nx, per_pass)
-            # (exactly this size: the entry takes as many days per pass as the workspace holds)
-            if self._ws is None or self._ws.numel() * 8 != nbytes:
-                self._ws = None
-                self._ws = torch.empty(nbytes // 8, dtype=torch.int64, device=self.counts.device)
-            rc = self.lib.rdgan_areal_accumulate(_p(hourly), n, stride, ny, nx, _hp(self.windows), K, _hp(self.widths), Wn,
-                                                 _hp(self.levels), len(self.levels), _p(self.counts), _p(depths_out), _p(self._ws),
-                                                 nbytes, _stream(self.counts))
-        _lib.check(rc, None, "rdgan_areal_accumulate")
-        return self
+        return super().add(hourly, depths_out)
 
-    def state(self):
-        """counts (K W (L + 53) + 2,) int64: the tensor itself, on the device, in the flat order of include/rdgan.h"""
-        if self.counts is None:
-            raise ValueError("nothing has been added")
-        return self.counts
+    def _state_tensors(self, device):
+        self.counts = torch.zeros(state_count(len(self.windows), len(self.widths), len(self.levels)), dtype=torch.int64, device=device)
+
+    def _check_plane(self, ny, nx, what):
+        if ny * nx > MAX_PLANE:
+            raise ValueError(f"{what}: a plane has {ny * nx} pixels, the limit is {MAX_PLANE}")
+        if int(self.widths[-1]) > min(ny, nx):
+            raise ValueError(f"{what}: the width {int(self.widths[-1])} is larger than the plane {(ny, nx)}; boxes are never clipped")
+
+    def _check_args(self, shape, n, depths_out):
+        check_out_tensor(depths_out, self.out_name, torch.int64, (n, len(self.windows), len(self.widths)))
+        return ()
+
+    def _pass_units(self, n, ny, nx):
+        per_pass = self.workspace_days or max(1, _DEFAULT_PASS_PIXELS // (ny * nx))
+        return min(per_pass, n, MAX_PASS)
+
+    def _entry_args(self, ny, nx, depths_out):
+        return (ny, nx, _hp(self.windows), len(self.windows), _hp(self.widths), len(self.widths), _hp(self.levels), len(self.levels),
+                _p(self.counts), _p(depths_out))
 
     def result(self):
         """-> ArealStats"""
@@ -255,7 +225,7 @@ def areal_extremes(hourly, windows, widths, levels=(), return_depths=False, work
     if not return_depths:
         return ae.add(hourly).result()
     hourly, from_host, shape, n, _ = admit(hourly)
-    _check_plane(shape[-2], shape[-1], ae.widths, "hourly")
+    ae._check_plane(shape[-2], shape[-1], "hourly")
     require_gpu()
     depths = torch.empty((n, len(ae.windows), len(ae.widths)), dtype=torch.int64, device="cuda" if from_host else hourly.device)
     return ae.add(hourly, depths_out=depths).result(), depths
@@ -263,16 +233,7 @@ def areal_extremes(hourly, windows, widths, levels=(), return_depths=False, work
 
 def areal_extremes_field(gen, daily, n_scenarios, windows, widths, levels=(), workspace_days=None, scenario_chunk=16, overlap=4,
                          latent_mode="shared", seed=None, latent=None, chunk=1024, norm_scale=W.NORM_SCALE):
-    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and take their areal extremes without holding them.  The
-    latent array is drawn once for all scenarios, exactly as field.disaggregate draws it for the same seed, latent and numpy RNG
-    state; disaggregate then runs for scenario_chunk scenarios at a time into one reused buffer and each result is added.  The
-    result is areal_extremes of the hourly values those disaggregate calls produce; as in cells.cell_structure_field, those values
-    equal the ones of a single disaggregate call only when the generator's batches are the same (`chunk` at most one unit's wet
-    tiles, or one scenario chunk).  -> ArealStats"""
-    ae = ArealExtremes(windows, widths, levels, workspace_days=workspace_days)
-    S, step = F._check_scenarios(n_scenarios, scenario_chunk)
-    req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
-    ny, nx = req[3:5]
-    _check_plane(ny, nx, ae.widths, "daily")
-    F._stream_scenarios(gen, req, req[0], S, step, ae.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
-    return ae.result()
+    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and take their areal extremes without holding them:
+    _hourly.evaluate_field, which says how the scenarios are drawn and what the result equals, on an ArealExtremes.  -> ArealStats"""
+    return evaluate_field(ArealExtremes(windows, widths, levels, workspace_days=workspace_days), gen, daily, n_scenarios, scenario_chunk,
+                          overlap, latent_mode, seed, latent, chunk, norm_scale)

@@ -15,11 +15,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
-from . import field as F
 from . import weights as W
-from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import NHOURS, admit, div as _div, to_state_device, tv as _tv
+from ._dev import host_ptr as _hp, ptr as _p, whole_number
+from ._hourly import NHOURS, HourlyAccumulator, admit, check_out_tensor, div as _div, evaluate_field, tv as _tv
 from .engine import require_gpu
 from .verification import check_event_thresholds
 
@@ -158,63 +156,47 @@ def stats_from_state(counts, thresholds, connectivity, n_pixels):
                      **split_state(counts, len(thr)))
 
 
-class CellStructure:
+class LabelAccumulator(HourlyAccumulator):
+    """An accumulator whose add() can also write the canonical labels at one of its thresholds (cells, storms)"""
+    out_name = "labels_out"
+
+    def add(self, hourly, labels_out=None, label_threshold=0):
+        """hourly (..., 24, ny, nx) float32: a CUDA tensor or a numpy array, admitted as HourlyAccumulator.add admits it.  The
+        plane shape is fixed by the first call.  labels_out: None, or a contiguous int32 CUDA tensor of hourly's shape that
+        receives the canonical labels at thresholds[label_threshold].  Returns self."""
+        return super().add(hourly, labels_out, label_threshold)
+
+    def _check_args(self, shape, n, labels_out, label_threshold):
+        label_threshold = whole_number(label_threshold, 0, len(self.thr) - 1, "label_threshold")
+        check_out_tensor(labels_out, self.out_name, torch.int32, shape)
+        return (label_threshold,)
+
+    def _state_tensors(self, device):
+        self.counts = torch.zeros(len(self.thr) * self.n_counts + 2, dtype=torch.int64, device=device)
+
+
+class CellStructure(LabelAccumulator):
     """The state of a cell evaluation on the device.  thresholds: the wet-pixel events in the unit of the data; connectivity: 4
     (edges) or 8 (edges and corners); planes_per_pass: how many (day, hour) planes the workspace holds at a time, 16 bytes per
-    pixel -- None: up to 2^24 pixels, 256 MB.  The result does not depend on it."""
+    pixel -- None: up to 2^24 pixels, 256 MB.  The result does not depend on it.  state(): counts (T * 317 + 2,) int64."""
+    entry, workspace_entry, n_counts = "rdgan_cells_accumulate", "rdgan_cells_workspace_bytes", N_COUNTS
 
     def __init__(self, thresholds, connectivity=8, planes_per_pass=None):
         self.thr = check_event_thresholds(thresholds)
         self.connectivity = check_connectivity(connectivity)
         self.planes_per_pass = check_planes_per_pass(planes_per_pass)
-        self.plane_shape = None
-        self.lib = None
-        self.counts = self._ws = None
+        self.reset()
 
-    def _start(self, device):
-        require_gpu()
-        self.lib = _lib.load()
-        self.counts = torch.zeros(len(self.thr) * N_COUNTS + 2, dtype=torch.int64, device=device)
+    def _check_plane(self, ny, nx, what):
+        if ny * nx > MAX_PLANE:
+            raise ValueError(f"{what}: a plane has {ny * nx} pixels, the limit is {MAX_PLANE}")
 
-    def add(self, hourly, labels_out=None, label_threshold=0):
-        """hourly (..., 24, ny, nx) float32: a CUDA tensor, whose leading axis may have any stride >= the size of one of its
-        entries (temporal.tensor_layout has the rule, and refuses a crop, a step or a transpose at any rank), or a numpy array.
-        The plane shape is fixed by the first call.  labels_out: None, or a contiguous int32 CUDA tensor of hourly's shape that
-        receives the canonical labels at thresholds[label_threshold].  Returns self."""
-        hourly, from_host, shape, n, stride = admit(hourly, self.plane_shape)
-        ny, nx = shape[-2:]
-        plane = ny * nx
-        if plane > MAX_PLANE:
-            raise ValueError(f"hourly: a plane has {plane} pixels, the limit is {MAX_PLANE}")
-        label_threshold = whole_number(label_threshold, 0, len(self.thr) - 1, "label_threshold")
-        if labels_out is not None and not (isinstance(labels_out, torch.Tensor) and labels_out.is_cuda and labels_out.dtype == torch.int32
-                                           and labels_out.is_contiguous() and tuple(labels_out.shape) == shape):
-            raise ValueError(f"labels_out: expected a contiguous int32 CUDA tensor of shape {shape}")
-        if self.counts is None:
-            self._start("cuda" if from_host else hourly.device)
-        hourly = to_state_device(hourly, from_host, self.counts.device)
-        if labels_out is not None and labels_out.device != self.counts.device:
-            raise ValueError(f"labels_out lies on {labels_out.device}, the state on {self.counts.device}")
-        self.plane_shape = shape[-2:]
-        per_pass = self.planes_per_pass or max(1, _DEFAULT_PASS_PIXELS // plane)
-        per_pass = min(per_pass, n * NHOURS, MAX_PASS)
-        with torch.cuda.device(self.counts.device):
-            nbytes = workspace_bytes(self.lib, "rdgan_cells_workspace_bytes", ny, nx, per_pass)
-            # (exactly this size: the entry takes as many planes per pass as the workspace holds)
-            if self._ws is None or self._ws.numel() * 8 != nbytes:
-                self._ws = None
-                self._ws = torch.empty(nbytes // 8, dtype=torch.int64, device=self.counts.device)
-            rc = self.lib.rdgan_cells_accumulate(_p(hourly), n, stride, ny, nx, _hp(self.thr), len(self.thr), self.connectivity,
-                                                 _p(self.counts), _p(labels_out), label_threshold, _p(self._ws), nbytes,
-                                                 _stream(self.counts))
-        _lib.check(rc, None, "rdgan_cells_accumulate")
-        return self
+    def _pass_units(self, n, ny, nx):
+        per_pass = self.planes_per_pass or max(1, _DEFAULT_PASS_PIXELS // (ny * nx))
+        return min(per_pass, n * NHOURS, MAX_PASS)
 
-    def state(self):
-        """counts (T * 317 + 2,) int64: the tensor itself, on the device, in the flat order of include/rdgan.h"""
-        if self.counts is None:
-            raise ValueError("nothing has been added")
-        return self.counts
+    def _entry_args(self, ny, nx, labels_out, label_threshold):
+        return ny, nx, _hp(self.thr), len(self.thr), self.connectivity, _p(self.counts), _p(labels_out), label_threshold
 
     def result(self):
         """-> CellStats"""
@@ -239,17 +221,7 @@ def label_cells(hourly, threshold, connectivity=8):
 
 def cell_structure_field(gen, daily, n_scenarios, thresholds, connectivity=8, planes_per_pass=None, scenario_chunk=16, overlap=4,
                          latent_mode="shared", seed=None, latent=None, chunk=1024, norm_scale=W.NORM_SCALE):
-    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and take their cells without holding them.  The latent
-    array is drawn once for all scenarios, exactly as field.disaggregate draws it for the same seed, latent and numpy RNG state;
-    disaggregate then runs for scenario_chunk scenarios at a time into one reused buffer and each result is added.  The result is
-    cell_structure of the hourly values those disaggregate calls produce; as in temporal.temporal_structure_field, those values
-    equal the ones of a single disaggregate call only when the generator's batches are the same (`chunk` at most one unit's wet
-    tiles, or one scenario chunk).  -> CellStats"""
-    cs = CellStructure(thresholds, connectivity, planes_per_pass)
-    S, step = F._check_scenarios(n_scenarios, scenario_chunk)
-    req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
-    ny, nx = req[3:5]
-    if ny * nx > MAX_PLANE:
-        raise ValueError(f"daily: a plane has {ny * nx} pixels, the limit is {MAX_PLANE}")
-    F._stream_scenarios(gen, req, req[0], S, step, cs.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
-    return cs.result()
+    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and take their cells without holding them:
+    _hourly.evaluate_field, which says how the scenarios are drawn and what the result equals, on a CellStructure.  -> CellStats"""
+    return evaluate_field(CellStructure(thresholds, connectivity, planes_per_pass), gen, daily, n_scenarios, scenario_chunk, overlap,
+                          latent_mode, seed, latent, chunk, norm_scale)

@@ -1,8 +1,29 @@
 // The handle-free entry points of include/rdgan.h: input pipeline, CRPS experiment, distribution checks, whole fields, ensemble
-// products, verification, temporal structure, rain cells, storms, areal extremes, space-time structure, analogs, spectra and RainFARM.  They take no rdgan_handle and use nothing of the
-// step engine but RD_TRY, ensure_lds(nullptr, ...) and ew_blocks.  Host code, included by rdgan_api.hip at one point, behind the
-// op-level test entries (the library stays one translation unit: one code object for the ISA lint).
+// products, verification, the five evaluations of hourly arrays (temporal structure, rain cells, storms, areal extremes, space-time
+// structure), analogs, spectra and RainFARM.  They take no rdgan_handle and use nothing of the step engine but RD_TRY,
+// ensure_lds(nullptr, ...) and ew_blocks.  Host code, included by rdgan_api.hip at one point, behind the op-level test entries (the
+// library stays one translation unit: one code object for the ISA lint).
+//
+// An *_accumulate entry of an hourly evaluation admits its array with rd_hourly_layout_ok and sizes its passes with rd_pass_units
+// (rdgan_hourly_host.h, host-only, tested on its own); the pass loop and its launches are the entry's own.
 #pragma once
+#include "rdgan_hourly_host.h"
+
+static int rd_pow2_at_least(int n) {
+  int p = 2;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+// the tables of a DFT of length nd: re[j] + i im[j] = exp(sign * 2 pi i j / nd), computed in fp64 and rounded once to T
+template <typename T>
+static void rd_twiddles(int nd, double sign, T* re, T* im) {
+  for (int j = 0; j < nd; ++j) {
+    const double th = sign * 2.0 * M_PI * (double)j / (double)nd;
+    re[j] = (T)cos(th);
+    im[j] = (T)sin(th);
+  }
+}
 
 // ------------------------------------------------------------------------------------
 // input pipeline
@@ -91,8 +112,7 @@ extern "C" int rdgan_data_valid_tiles_daily(const float* daily, long n_days, int
 extern "C" int rdgan_crps_ensemble(const float* ens, const float* obs, const float* scale, float* crps_out, int n,
                                    long npix, void* stream) {
   if (!ens || !obs || !crps_out || n < 1 || n > 8192 || npix < 1 || npix > 0x7FFFFFFFL) return -2;
-  int npow2 = 2;
-  while (npow2 < n) npow2 <<= 1;
+  const int npow2 = rd_pow2_at_least(n);
   hipLaunchKernelGGL(k_crps_ensemble, dim3((unsigned)npix), dim3(256), npow2 * sizeof(float), (hipStream_t)stream, ens, obs,
                      scale, crps_out, n, npow2, npix);
   return (int)hipGetLastError();
@@ -107,8 +127,7 @@ extern "C" int rdgan_crps_fixed_ensemble(const float* ens, const float* obs, flo
   const long npos = (long)RDGAN_NHOURS * nd * nd;
   if (npos > 0x7FFFFFFFL || n_days > 0x7FFFFFFFL / npos) return -2;       // D * npos < 2^31, and the grids below fit
   hipStream_t st = (hipStream_t)stream;
-  int npow2 = 2;
-  while (npow2 < n) npow2 <<= 1;
+  const int npow2 = rd_pow2_at_least(n);
   const size_t lds = (size_t)(n + 1 + RD_CRPS_THREADS) * sizeof(double) + (size_t)npow2 * sizeof(float);
   RD_TRY(ensure_lds(nullptr, (const void*)k_crps_fixed, lds));
   // the hourly means are taken over the per-position values: without a caller's buffer they live in a stream-ordered temporary
@@ -145,12 +164,6 @@ extern "C" int rdgan_moments_f64(const double* x, long n, double* out3, void* st
 // ------------------------------------------------------------------------------------
 // distribution checks (rdgan_dist.hip.h): two-sample KS, box-plot statistics, ECDF on a grid
 // ------------------------------------------------------------------------------------
-static int rd_pow2_at_least(int n) {
-  int p = 2;
-  while (p < n) p <<= 1;
-  return p;
-}
-
 extern "C" int rdgan_ks_2samp(const float* a, const float* b, int n, int m, int ncol, long batch, int* counts_out, double* d_out,
                               void* stream) {
   if (!a || !b || !counts_out || !d_out || n < 1 || n > RD_DIST_MAXN || m < 1 || m > RD_DIST_MAXN || ncol < 1 || batch < 1) return -2;
@@ -242,25 +255,44 @@ extern "C" int rdgan_field_cond(const float* daily, long n_days, int ny, int nx,
   return (int)(e != hipSuccess ? e : f);
 }
 
+// What the two blend entries share: the slot table of `units` units checked against m and the geometry, and uploaded for the launch
+struct rd_blend_plan {
+  int* dev;                 // the slot table on the device: rd_blend_done frees it behind the launch
+  int step, n_ty, n_tx;
+  long nb;                  // pixel blocks of all units
+};
+
+// the caller has checked its pointers; -2 for a bad size, geometry or slot, otherwise the upload's code
+static int rd_blend_slots(long m, const int* slots, long units, long first_unit, long n_days, int ny, int nx, int nd, int overlap,
+                          hipStream_t st, rd_blend_plan* p) {
+  if (m < 1 || m > 0x7FFFFFFFL || units < 1 || first_unit < 0 || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
+  p->step = nd - overlap, p->n_ty = rd_field_axis_tiles(ny, nd, p->step), p->n_tx = rd_field_axis_tiles(nx, nd, p->step);
+  const long T = (long)p->n_ty * p->n_tx;
+  if (T > 0x7FFFFFFFL || units > 0x7FFFFFFFL / T) return -2;
+  for (long i = 0; i < units * T; ++i)
+    if (slots[i] < -1 || slots[i] >= m) return -2;
+  p->nb = units * ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * ((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
+  p->dev = nullptr;
+  return rd_field_upload(slots, (size_t)(units * T), &p->dev, st);
+}
+
+// behind the blend launch: its error, or else the error of freeing the table (the first error wins)
+static int rd_blend_done(const rd_blend_plan& p, hipStream_t st) {
+  hipError_t e = hipGetLastError();
+  hipError_t f = hipFreeAsync(p.dev, st);
+  return (int)(e != hipSuccess ? e : f);
+}
+
 extern "C" int rdgan_field_blend(const float* frac, long m, const int* slots, long units, long first_unit, const int* ytab_idx,
                                  const float* ytab_w, const int* xtab_idx, const float* xtab_w, const float* daily, long n_days,
                                  int ny, int nx, int nd, int overlap, float* out, void* stream) {
   if (!frac || !slots || !ytab_idx || !ytab_w || !xtab_idx || !xtab_w || !daily || !out) return -2;
-  if (m < 1 || m > 0x7FFFFFFFL || units < 1 || first_unit < 0 || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
-  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
-  const long T = (long)n_ty * n_tx;
-  if (T > 0x7FFFFFFFL || units > 0x7FFFFFFFL / T) return -2;
-  for (long i = 0; i < units * T; ++i)
-    if (slots[i] < -1 || slots[i] >= m) return -2;
   hipStream_t st = (hipStream_t)stream;
-  int* dev = nullptr;
-  RD_TRY(rd_field_upload(slots, (size_t)(units * T), &dev, st));
-  const long nb = units * ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * ((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
-  hipLaunchKernelGGL(k_field_blend, dim3((unsigned)std::min<long>(nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0, st, frac, dev, ytab_idx,
-                     ytab_w, xtab_idx, xtab_w, daily, out, units, first_unit, n_days, ny, nx, nd, step, n_ty, n_tx);
-  hipError_t e = hipGetLastError();
-  hipError_t f = hipFreeAsync(dev, st);
-  return (int)(e != hipSuccess ? e : f);
+  rd_blend_plan p;
+  RD_TRY(rd_blend_slots(m, slots, units, first_unit, n_days, ny, nx, nd, overlap, st, &p));
+  hipLaunchKernelGGL(k_field_blend, dim3((unsigned)std::min<long>(p.nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0, st, frac, p.dev, ytab_idx,
+                     ytab_w, xtab_idx, xtab_w, daily, out, units, first_unit, n_days, ny, nx, nd, p.step, p.n_ty, p.n_tx);
+  return rd_blend_done(p, st);
 }
 
 // ------------------------------------------------------------------------------------
@@ -295,23 +327,14 @@ extern "C" int rdgan_field_blend_peaks(const float* frac, long m, const int* slo
                                        unsigned char* peak_hour_out, void* stream) {
   unsigned mask = 0;
   if (!frac || !slots || !ytab_idx || !ytab_w || !xtab_idx || !xtab_w || !daily || !peaks_out || !peak_hour_out) return -2;
-  if (m < 1 || m > 0x7FFFFFFFL || units < 1 || first_unit < 0 || !rd_field_geometry_ok(n_days, ny, nx, nd, overlap)) return -2;
   if (!rd_peaks_mask(windows, n_windows, &mask)) return -2;
-  const int step = nd - overlap, n_ty = rd_field_axis_tiles(ny, nd, step), n_tx = rd_field_axis_tiles(nx, nd, step);
-  const long T = (long)n_ty * n_tx;
-  if (T > 0x7FFFFFFFL || units > 0x7FFFFFFFL / T) return -2;
-  for (long i = 0; i < units * T; ++i)
-    if (slots[i] < -1 || slots[i] >= m) return -2;
   hipStream_t st = (hipStream_t)stream;
-  int* dev = nullptr;
-  RD_TRY(rd_field_upload(slots, (size_t)(units * T), &dev, st));
-  const long nb = units * ((ny + RD_FIELD_BY - 1) / RD_FIELD_BY) * ((nx + RD_FIELD_BX - 1) / RD_FIELD_BX);
-  hipLaunchKernelGGL(k_field_blend_peaks, dim3((unsigned)std::min<long>(nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0, st, frac, dev,
-                     ytab_idx, ytab_w, xtab_idx, xtab_w, daily, peaks_out, peak_hour_out, units, first_unit, n_days, ny, nx, nd, step,
-                     n_ty, n_tx, mask, windows[0]);
-  hipError_t e = hipGetLastError();
-  hipError_t f = hipFreeAsync(dev, st);
-  return (int)(e != hipSuccess ? e : f);
+  rd_blend_plan p;
+  RD_TRY(rd_blend_slots(m, slots, units, first_unit, n_days, ny, nx, nd, overlap, st, &p));
+  hipLaunchKernelGGL(k_field_blend_peaks, dim3((unsigned)std::min<long>(p.nb, 1L << 20)), dim3(RD_FIELD_THREADS), 0, st, frac, p.dev,
+                     ytab_idx, ytab_w, xtab_idx, xtab_w, daily, peaks_out, peak_hour_out, units, first_unit, n_days, ny, nx, nd, p.step,
+                     p.n_ty, p.n_tx, mask, windows[0]);
+  return rd_blend_done(p, st);
 }
 
 extern "C" int rdgan_member_stats(const float* x, int n_members, long member_stride, long n_positions, const double* probs, int n_probs,
@@ -503,9 +526,9 @@ extern "C" int rdgan_temporal_accumulate(const float* x, long n, long day_stride
                                          long workspace_bytes, void* stream) {
   rd_vf_thr thr;
   if (!x || !counts_inout || !sums_inout || !workspace) return -2;
-  if (((unsigned long long)x & 3) || (((unsigned long long)counts_inout | (unsigned long long)sums_inout | (unsigned long long)workspace) & 7))
-    return -2;
-  if (!rd_ts_shape_ok(n, plane, n_thresholds, max_lag) || day_stride < RD_TS_HOURS * plane || day_stride > (1L << 50) / n) return -2;
+  static_assert(RD_TS_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
+  if (!rd_aligned(7, counts_inout, sums_inout, workspace) || !rd_ts_shape_ok(n, plane, n_thresholds, max_lag)) return -2;
+  if (!rd_hourly_layout_ok(x, n, day_stride, RD_TS_HOURS * plane)) return -2;
   if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
   if (workspace_bytes < rdgan_temporal_workspace_bytes(n, plane, n_thresholds, max_lag)) return -2;
   const bool vec = !((unsigned long long)x & 15) && plane % 4 == 0 && day_stride % 4 == 0;
@@ -542,22 +565,35 @@ extern "C" long rdgan_cells_workspace_bytes(long ny, long nx, long planes_per_pa
   return rd_cl_ws_bytes(ny * nx, planes_per_pass);
 }
 
+// The label front end cells and storms share: P planes from plane p0 on labelled tile by tile at one threshold, then the tiles
+// merged along their borders.  The caller has raised k_cells_label_tile's LDS limit (ensure_lds, once per entry call, not here).
+static void rd_cl_label_planes(hipStream_t st, const float* x, long day_stride, long ny, long nx, long p0, unsigned P, float thr,
+                               int conn8, int first, unsigned long long* wet, unsigned long long* bad, unsigned long long* vol,
+                               int* parent, unsigned* area, unsigned* words) {
+  const int tiles_x = (int)((nx + RD_CL_TILE - 1) / RD_CL_TILE), tiles_y = (int)((ny + RD_CL_TILE - 1) / RD_CL_TILE);
+  const long border = (long)(tiles_x - 1) * ny + (long)(tiles_y - 1) * nx;
+  hipLaunchKernelGGL(k_cells_label_tile, dim3((unsigned)(tiles_x * tiles_y), P), dim3(RD_CL_THREADS), RD_CL_LDS_BYTES, st, x, day_stride,
+                     (int)ny, (int)nx, p0, thr, conn8, first, wet, bad, vol, parent, area, words);
+  if (border > 0)
+    hipLaunchKernelGGL(k_cells_merge, dim3((unsigned)((border + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st,
+                       (int)ny, (int)nx, conn8, parent);
+}
+
 extern "C" int rdgan_cells_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds,
                                       int n_thresholds, int connectivity, long long* counts_inout, int* labels_out,
                                       int label_threshold, void* workspace, long workspace_bytes, void* stream) {
   rd_vf_thr thr;
   if (!x || !counts_inout || !workspace) return -2;
-  if (((unsigned long long)x & 3) || ((unsigned long long)labels_out & 3) ||
-      (((unsigned long long)counts_inout | (unsigned long long)workspace) & 7))
-    return -2;
-  if (n < 1 || !rd_cl_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8)) return -2;
+  if (!rd_aligned(3, labels_out) || !rd_aligned(7, counts_inout, workspace)) return -2;
+  if (!rd_cl_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8)) return -2;
   const long plane = ny * nx;
-  if (n > RD_CL_MAXELEMS / (RD_CL_HOURS * plane) || day_stride < RD_CL_HOURS * plane || day_stride > (1L << 50) / n) return -2;
+  static_assert(RD_CL_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
+  if (!rd_hourly_layout_ok(x, n, day_stride, RD_CL_HOURS * plane)) return -2;
   if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
   if (labels_out && (label_threshold < 0 || label_threshold >= n_thresholds)) return -2;
   // the planes of a pass: as many as the workspace holds
   const long n_planes = n * RD_CL_HOURS;
-  const long per_pass = std::min<long>(std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / rd_cl_ws_bytes(plane, 1), n_planes), RD_CL_MAXPASS);
+  const long per_pass = rd_pass_units(workspace_bytes, rd_cl_ws_bytes(plane, 1), n_planes, RD_CL_MAXPASS);
   if (per_pass < 1) return -2;
   unsigned long long* vol = (unsigned long long*)workspace;
   int* parent = (int*)(vol + per_pass * plane);
@@ -566,19 +602,13 @@ extern "C" int rdgan_cells_accumulate(const float* x, long n, long day_stride, l
   unsigned long long* counts = (unsigned long long*)counts_inout;
   hipStream_t st = (hipStream_t)stream;
   RD_TRY(ensure_lds(nullptr, (const void*)k_cells_label_tile, RD_CL_LDS_BYTES));
-  const int tiles_x = (int)((nx + RD_CL_TILE - 1) / RD_CL_TILE), tiles_y = (int)((ny + RD_CL_TILE - 1) / RD_CL_TILE);
-  const long border = (long)(tiles_x - 1) * ny + (long)(tiles_y - 1) * nx;
   const int conn8 = connectivity == 8;
   for (long p0 = 0; p0 < n_planes; p0 += per_pass) {
     const unsigned P = (unsigned)std::min<long>(per_pass, n_planes - p0);
     for (int t = 0; t < n_thresholds; ++t) {
       unsigned long long* ct = counts + (long)t * RD_CL_NC;
-      hipLaunchKernelGGL(k_cells_label_tile, dim3((unsigned)(tiles_x * tiles_y), P), dim3(RD_CL_THREADS), RD_CL_LDS_BYTES, st, x, day_stride,
-                         (int)ny, (int)nx, p0, thr.v[t], conn8, (int)(t == 0), ct + RD_CL_WET,
+      rd_cl_label_planes(st, x, day_stride, ny, nx, p0, P, thr.v[t], conn8, (int)(t == 0), ct + RD_CL_WET,
                          counts + (long)n_thresholds * RD_CL_NC + 1, vol, parent, area, words);
-      if (border > 0)
-        hipLaunchKernelGGL(k_cells_merge, dim3((unsigned)((border + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st,
-                           (int)ny, (int)nx, conn8, parent);
       hipLaunchKernelGGL(k_cells_resolve, dim3((unsigned)((plane + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st, plane,
                          p0, vol, parent, area, labels_out && t == label_threshold ? labels_out : (int*)nullptr);
       hipLaunchKernelGGL(k_cells_reduce, dim3((unsigned)((plane + RD_CL_RCHUNK - 1) / RD_CL_RCHUNK), P), dim3(RD_CL_THREADS), 0, st, plane, p0,
@@ -612,16 +642,15 @@ extern "C" int rdgan_storms_accumulate(const float* x, long n, long day_stride, 
                                        int label_threshold, void* workspace, long workspace_bytes, void* stream) {
   rd_vf_thr thr;
   if (!x || !counts_inout || !workspace) return -2;
-  if (((unsigned long long)x & 3) || ((unsigned long long)labels_out & 3) ||
-      (((unsigned long long)counts_inout | (unsigned long long)workspace) & 7))
-    return -2;
-  if (n < 1 || !rd_sm_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8) || reach < 0 || reach > RD_SM_MAXREACH) return -2;
+  if (!rd_aligned(3, labels_out) || !rd_aligned(7, counts_inout, workspace)) return -2;
+  if (!rd_sm_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8) || reach < 0 || reach > RD_SM_MAXREACH) return -2;
   const long plane = ny * nx, V = RD_CL_HOURS * plane;
-  if (n > RD_CL_MAXELEMS / V || day_stride < V || day_stride > (1L << 50) / n) return -2;
+  static_assert(RD_CL_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
+  if (!rd_hourly_layout_ok(x, n, day_stride, V)) return -2;
   if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
   if (labels_out && (label_threshold < 0 || label_threshold >= n_thresholds)) return -2;
   // the days of a pass: as many whole days as the workspace holds
-  const long per_pass = std::min<long>(std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / rd_sm_ws_bytes(plane, 1), n), RD_SM_MAXPASS);
+  const long per_pass = rd_pass_units(workspace_bytes, rd_sm_ws_bytes(plane, 1), n, RD_SM_MAXPASS);
   if (per_pass < 1) return -2;
   unsigned long long* vol = (unsigned long long*)workspace;
   int* parent = (int*)(vol + per_pass * V);
@@ -633,20 +662,14 @@ extern "C" int rdgan_storms_accumulate(const float* x, long n, long day_stride, 
   unsigned long long* tail = counts + (long)n_thresholds * RD_SM_NC;      // n_days, n_bad_pixels
   hipStream_t st = (hipStream_t)stream;
   RD_TRY(ensure_lds(nullptr, (const void*)k_cells_label_tile, RD_CL_LDS_BYTES));
-  const int tiles_x = (int)((nx + RD_CL_TILE - 1) / RD_CL_TILE), tiles_y = (int)((ny + RD_CL_TILE - 1) / RD_CL_TILE);
-  const long border = (long)(tiles_x - 1) * ny + (long)(tiles_y - 1) * nx;
   const int conn8 = connectivity == 8;
   const unsigned vblocks = (unsigned)((V + RD_CL_THREADS - 1) / RD_CL_THREADS);
   for (long d0 = 0; d0 < n; d0 += per_pass) {
     const unsigned D = (unsigned)std::min<long>(per_pass, n - d0), P = D * RD_CL_HOURS;
     for (int t = 0; t < n_thresholds; ++t) {
       unsigned long long* ct = counts + (long)t * RD_SM_NC;
-      hipLaunchKernelGGL(k_cells_label_tile, dim3((unsigned)(tiles_x * tiles_y), P), dim3(RD_CL_THREADS), RD_CL_LDS_BYTES, st, x, day_stride,
-                         (int)ny, (int)nx, d0 * RD_CL_HOURS, thr.v[t], conn8, (int)(t == 0), ct + RD_SM_WET, tail + 1, vol, parent, area,
-                         plane_words);
-      if (border > 0)
-        hipLaunchKernelGGL(k_cells_merge, dim3((unsigned)((border + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st,
-                           (int)ny, (int)nx, conn8, parent);
+      rd_cl_label_planes(st, x, day_stride, ny, nx, d0 * RD_CL_HOURS, P, thr.v[t], conn8, (int)(t == 0), ct + RD_SM_WET, tail + 1, vol,
+                         parent, area, plane_words);
       hipLaunchKernelGGL(k_storm_lift, dim3(vblocks, D), dim3(RD_CL_THREADS), 0, st, plane, parent, last, day_words);
       hipLaunchKernelGGL(k_storm_link, dim3((unsigned)((V - plane + RD_CL_THREADS - 1) / RD_CL_THREADS), D), dim3(RD_CL_THREADS), 0, st, (int)ny,
                          (int)nx, reach, parent);
@@ -715,14 +738,13 @@ extern "C" int rdgan_areal_accumulate(const float* x, long n, long day_stride, l
                                       long long* depths_out, void* workspace, long workspace_bytes, void* stream) {
   rd_ar_lists lists;
   if (!x || !counts_inout || !workspace) return -2;
-  if (((unsigned long long)x & 3) || (((unsigned long long)counts_inout | (unsigned long long)depths_out | (unsigned long long)workspace) & 7))
-    return -2;
-  if (n < 1 || !rd_ar_shape_ok(ny, nx)) return -2;
+  if (!rd_aligned(7, counts_inout, depths_out, workspace) || !rd_ar_shape_ok(ny, nx)) return -2;
   const long plane = ny * nx, V = RD_AR_HOURS * plane;
-  if (n > RD_AR_MAXELEMS / V || day_stride < V || day_stride > (1L << 50) / n) return -2;
+  static_assert(RD_AR_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
+  if (!rd_hourly_layout_ok(x, n, day_stride, V)) return -2;
   if (!rd_ar_make_lists(windows, n_windows, widths, n_widths, levels, n_levels, std::min(ny, nx), &lists)) return -2;
   // the days of a pass: as many whole days as the workspace holds
-  const long per_pass = std::min<long>(std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / rd_ar_day_bytes(plane), n), RD_AR_MAXPASS);
+  const long per_pass = rd_pass_units(workspace_bytes, rd_ar_day_bytes(plane), n, RD_AR_MAXPASS);
   if (per_pass < 1) return -2;
   unsigned long long* keys = (unsigned long long*)workspace;
   int* S = (int*)(keys + per_pass * RD_AR_DAY_KEYS);
@@ -780,14 +802,13 @@ extern "C" int rdgan_spacetime_accumulate(const float* x, long n, long day_strid
                                           long workspace_bytes, void* stream) {
   rd_vf_thr thr;
   if (!x || !counts_inout || !workspace) return -2;
-  if (((unsigned long long)x & 3) || (((unsigned long long)counts_inout | (unsigned long long)workspace) & 7)) return -2;
-  if (n < 1 || !rd_vf_thresholds(thresholds, n_thresholds, &thr) || !rd_st_params_ok(n_thresholds, radius, max_lag)) return -2;
+  if (!rd_aligned(7, counts_inout, workspace)) return -2;
+  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr) || !rd_st_params_ok(n_thresholds, radius, max_lag)) return -2;
   if (!rd_st_shape_ok(ny, nx, 2 * radius + 1)) return -2;
-  const long plane = ny * nx;
-  if (n > RD_ST_MAXELEMS / (RD_ST_HOURS * plane) || day_stride < RD_ST_HOURS * plane || day_stride > (1L << 50) / n) return -2;
+  static_assert(RD_ST_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
+  if (!rd_hourly_layout_ok(x, n, day_stride, RD_ST_HOURS * ny * nx)) return -2;
   // the days of a pass: as many whole days as the workspace holds
-  const long day_bytes = RD_ST_HOURS * rd_st_plane_bytes(ny, nx, n_thresholds);
-  const long per_pass = std::min<long>(std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / day_bytes, n), RD_ST_MAXPASS / RD_ST_HOURS);
+  const long per_pass = rd_pass_units(workspace_bytes, RD_ST_HOURS * rd_st_plane_bytes(ny, nx, n_thresholds), n, RD_ST_MAXPASS / RD_ST_HOURS);
   if (per_pass < 1) return -2;
   const int W = (int)((nx + 63) / 64), T = n_thresholds;
   int cw, bh;
@@ -842,7 +863,7 @@ extern "C" int rdgan_analog_features(const float* x, long n, long day_stride, lo
     return (int)hipGetLastError();
   }
   if (mask_out || !total_out || !void_out || !n_void_out || (((unsigned long long)total_out | (unsigned long long)n_void_out) & 7)) return -2;
-  if (n > RD_AN_MAXN || day_stride < RD_AN_HOURS * plane || day_stride > (1L << 50) / n) return -2;
+  if (n > RD_AN_MAXN || !rd_day_stride_ok(n, day_stride, RD_AN_HOURS * plane)) return -2;
   RD_TRY((int)hipMemsetAsync(total_out, 0, (size_t)n * 8, st));
   RD_TRY((int)hipMemsetAsync(n_void_out, 0, 8, st));
   const unsigned blocks = (unsigned)((n * C + 255) / 256);
@@ -869,7 +890,7 @@ extern "C" int rdgan_analog_search(const unsigned short* lib_feat, const unsigne
   if (n < 1 || n > RD_AN_MAXN || plane < 1 || plane > RD_AN_MAXP || n_queries < 1 || n_queries > RD_AN_MAXQ || k < 1 || k > RD_AN_MAXK) return -2;
   // the slices: as many lists per query as the workspace holds, at most one slice per block of 64 days
   const long nblocks = rd_an_blocks(n);
-  const long held = std::min<long>(workspace_bytes < 0 ? 0 : workspace_bytes / rd_an_list_bytes(n_queries, k), nblocks);
+  const long held = rd_pass_units(workspace_bytes, rd_an_list_bytes(n_queries, k), nblocks, nblocks);
   if (held < 1) return -2;
   const long per_slice = (nblocks + held - 1) / held, slices = (nblocks + per_slice - 1) / per_slice;
   const int C = (int)(rd_an_ppad(plane) / 8), QT = rd_an_query_tile(plane);
@@ -902,7 +923,7 @@ extern "C" int rdgan_analog_apply(const float* lib, long n, long day_stride, lon
     return -2;
   if (n < 1 || n > RD_AN_MAXN || !rd_an_shape_ok(ny, nx) || n_queries < 1 || n_queries > RD_AN_MAXQ || k < 1 || k > RD_AN_MAXK) return -2;
   const long plane = ny * nx;
-  if (day_stride < RD_AN_HOURS * plane || day_stride > (1L << 50) / n || n_members < 1 || n_members > RD_AN_MAXS) return -2;
+  if (!rd_day_stride_ok(n, day_stride, RD_AN_HOURS * plane) || n_members < 1 || n_members > RD_AN_MAXS) return -2;
   if (first_query < 0 || first_query > (1L << 32) - n_queries || first_member < 0 || first_member > (1L << 62)) return -2;
   if (weights != RD_AN_UNIFORM && weights != RD_AN_RANK) return -2;
   hipLaunchKernelGGL(k_analog_apply, dim3((unsigned)n_queries, (unsigned)n_members), dim3(RD_AN_APPLY_THREADS), (size_t)plane * 4,
@@ -924,11 +945,7 @@ extern "C" int rdgan_radial_spectra(const float* fields, float* out, long n, int
   if (!fields || !out || n < 1 || n > (1L << 26) || K < 1) return -2;
   rd_spec_args a;
   memset(&a, 0, sizeof(a));
-  for (int j = 0; j < nd; ++j) {
-    const double th = -2.0 * M_PI * (double)j / (double)nd;
-    a.tw_re[j] = (float)cos(th);
-    a.tw_im[j] = (float)sin(th);
-  }
+  rd_twiddles(nd, -1.0, a.tw_re, a.tw_im);
   for (int i = 0; i < nd; ++i)
     for (int j = 0; j < nd; ++j) {
       const int b = rd_spec_bin(2 * j - (nd - 1), 2 * i - (nd - 1));
@@ -1023,16 +1040,8 @@ extern "C" int rdgan_rainfarm_slope_stats(const float* samples, long n, int nd, 
   if (need < 0 || workspace_bytes < need) return -2;
   rd_rf_slope_args a;
   memset(&a, 0, sizeof(a));
-  for (int j = 0; j < nd; ++j) {
-    const double th = -2.0 * M_PI * (double)j / (double)nd;
-    a.tw_re[j] = cos(th);
-    a.tw_im[j] = sin(th);
-  }
-  for (int j = 0; j < RD_RF_NT; ++j) {
-    const double th = -2.0 * M_PI * (double)j / (double)RD_RF_NT;
-    a.t24_re[j] = cos(th);
-    a.t24_im[j] = sin(th);
-  }
+  rd_twiddles(nd, -1.0, a.tw_re, a.tw_im);
+  rd_twiddles(RD_RF_NT, -1.0, a.t24_re, a.t24_im);
   int gs, gt;
   rd_rf_stat_grid(n, &gs, &gt);
   const int nc = (nd / 2 + 1) * (nd / 2 + 1);
@@ -1068,16 +1077,8 @@ extern "C" int rdgan_rainfarm_generate(const float* amplitudes, const float* pre
   if (need < 0 || workspace_bytes < need || ((uintptr_t)amplitudes & 7)) return -2;
   rd_rf_gen_args a;
   memset(&a, 0, sizeof(a));
-  for (int j = 0; j < nd; ++j) {
-    const double th = 2.0 * M_PI * (double)j / (double)nd;
-    a.tw_re[j] = (float)cos(th);
-    a.tw_im[j] = (float)sin(th);
-  }
-  for (int j = 0; j < RD_RF_NT; ++j) {
-    const double th = 2.0 * M_PI * (double)j / (double)RD_RF_NT;
-    a.t24_re[j] = (float)cos(th);
-    a.t24_im[j] = (float)sin(th);
-  }
+  rd_twiddles(nd, 1.0, a.tw_re, a.tw_im);
+  rd_twiddles(RD_RF_NT, 1.0, a.t24_re, a.t24_im);
   const int usrc = uniforms ? (uniforms_fp64 ? 2 : 1) : 0;
   const uint32_t key = rd_make_key(seed, RD_STREAM_RAINFARM);
   const float2* amp = (const float2*)amplitudes;

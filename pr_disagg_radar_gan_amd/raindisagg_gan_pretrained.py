@@ -61,6 +61,12 @@ def generate_scenarios(cond, n_scenarios):
     return generated * cond.squeeze() * norm_scale
 
 
+def _daily_map(daily):
+    """daily as an ndarray, without the trailing axis of 1 that ``cond`` has"""
+    daily = np.asarray(daily)
+    return daily[..., 0] if daily.ndim >= 3 and daily.shape[-1] == 1 else daily
+
+
 def generate_scenarios_field(daily, n_scenarios, overlap=4, latent_mode="shared"):
     """generate_scenarios for a whole daily map instead of one tile (field.disaggregate on the module's ``gen`` and
     ``norm_scale``).  daily: ndarray (ny, nx) or (n_days, ny, nx), daily sums in mm/day, ny, nx >= ndomain; a trailing axis of 1, as
@@ -70,9 +76,7 @@ def generate_scenarios_field(daily, n_scenarios, overlap=4, latent_mode="shared"
     (``latent_mode="shared"``) or one per tile (``"independent"``).  On an (ndomain, ndomain) field with overlap 0 this is
     generate_scenarios."""
     from . import field
-    daily = np.asarray(daily)
-    if daily.ndim >= 3 and daily.shape[-1] == 1:
-        daily = daily[..., 0]
+    daily = _daily_map(daily)
     out, _ = field.disaggregate(gen, daily, n_scenarios, overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
     return out.cpu().numpy().astype(np.float64).squeeze()
 
@@ -86,9 +90,7 @@ def scenario_products_field(daily, n_scenarios, windows=(1, 3, 6, 12, 24), probs
     the hour at which each scenario's windows[0]-hour peak begins (255 at a NaN pixel).  thresholds: None, a sequence in mm (the
     same for every window) or a (K, T) array.  The hourly scenarios themselves are never held."""
     from . import field_products
-    daily = np.asarray(daily)
-    if daily.ndim >= 3 and daily.shape[-1] == 1:
-        daily = daily[..., 0]
+    daily = _daily_map(daily)
     r = field_products.ensemble_products(gen, daily, n_scenarios, windows=windows, probs=probs, thresholds=thresholds, overlap=overlap,
                                          latent_mode=latent_mode, norm_scale=norm_scale)
     host = lambda t: None if t is None else t.cpu().numpy()
@@ -115,9 +117,7 @@ def temporal_structure_field(daily, n_scenarios, thresholds, max_lag=6, overlap=
     temporal.compare sets it against the same statistics of observed days.  The latent noise comes from the global numpy RNG as in
     generate_scenarios_field; the hourly scenarios are produced scenario_chunk at a time and never held together."""
     from . import temporal
-    daily = np.asarray(daily)
-    if daily.ndim >= 3 and daily.shape[-1] == 1:
-        daily = daily[..., 0]
+    daily = _daily_map(daily)
     return temporal.temporal_structure_field(gen, daily, n_scenarios, thresholds, max_lag=max_lag, scenario_chunk=scenario_chunk,
                                              overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
@@ -129,9 +129,7 @@ def cell_structure_field(daily, n_scenarios, thresholds, connectivity=8, overlap
     cells.compare sets it against the same statistics of observed days.  The latent noise comes from the global numpy RNG as in
     generate_scenarios_field; the hourly scenarios are produced scenario_chunk at a time and never held together."""
     from . import cells
-    daily = np.asarray(daily)
-    if daily.ndim >= 3 and daily.shape[-1] == 1:
-        daily = daily[..., 0]
+    daily = _daily_map(daily)
     return cells.cell_structure_field(gen, daily, n_scenarios, thresholds, connectivity=connectivity, scenario_chunk=scenario_chunk,
                                       overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
@@ -144,9 +142,7 @@ def storm_structure_field(daily, n_scenarios, thresholds, connectivity=8, reach=
     sets it against the same statistics of observed days.  The latent noise comes from the global numpy RNG as in
     generate_scenarios_field; the hourly scenarios are produced scenario_chunk at a time and never held together."""
     from . import storms
-    daily = np.asarray(daily)
-    if daily.ndim >= 3 and daily.shape[-1] == 1:
-        daily = daily[..., 0]
+    daily = _daily_map(daily)
     return storms.storm_structure_field(gen, daily, n_scenarios, thresholds, connectivity=connectivity, reach=reach,
                                         scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
@@ -162,9 +158,7 @@ def areal_extremes_field(daily, n_scenarios, windows=(1, 3, 6, 12, 24), widths=(
     global numpy RNG as in generate_scenarios_field; the hourly scenarios are produced scenario_chunk at a time and never held
     together."""
     from . import areal
-    daily = np.asarray(daily)
-    if daily.ndim >= 3 and daily.shape[-1] == 1:
-        daily = daily[..., 0]
+    daily = _daily_map(daily)
     return areal.areal_extremes_field(gen, daily, n_scenarios, windows, widths, areal.DEFAULT_LEVELS if levels is None else levels,
                                       scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
@@ -177,9 +171,7 @@ def spacetime_structure_field(daily, n_scenarios, thresholds, radius=4, max_lag=
     same statistics of observed days.  The latent noise comes from the global numpy RNG as in generate_scenarios_field; the hourly
     scenarios are produced scenario_chunk at a time and never held together."""
     from . import spacetime
-    daily = np.asarray(daily)
-    if daily.ndim >= 3 and daily.shape[-1] == 1:
-        daily = daily[..., 0]
+    daily = _daily_map(daily)
     return spacetime.spacetime_structure_field(gen, daily, n_scenarios, thresholds, radius=radius, max_lag=max_lag,
                                                scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode,
                                                norm_scale=norm_scale)

@@ -16,12 +16,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
-from . import field as F
 from . import weights as W
-from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import NHOURS, admit, div as _div, to_state_device, tv as _tv
-from .engine import require_gpu
+from ._dev import host_ptr as _hp, ptr as _p, whole_number
+from ._hourly import NHOURS, HourlyAccumulator, div as _div, evaluate_field, tv as _tv
 from .verification import check_event_thresholds
 
 MAX_RADIUS = 8                                                               # RD_ST_MAXR
@@ -184,55 +181,36 @@ def stats_from_state(counts, thresholds, radius, max_lag):
                           **split_state(counts, len(thr), radius, max_lag))
 
 
-class SpaceTimeStructure:
+class SpaceTimeStructure(HourlyAccumulator):
     """The state of a space-time evaluation on the device.  thresholds: the wet-pixel events in the unit of the data; radius: the
     largest displacement, in pixels, along either axis (1 .. 8); max_lag: the largest lag in hours (1 .. 6); planes_per_pass: how
     many (day, hour) planes the workspace holds at a time, at least 24 and taken in whole days, (T + 1) bits per pixel -- None: up
-    to 2^28 pixels.  The result does not depend on it."""
+    to 2^28 pixels.  The result does not depend on it.  add(hourly) is HourlyAccumulator's; state(): counts
+    (state_count(T, radius, max_lag),) int64."""
+    entry, workspace_entry = "rdgan_spacetime_accumulate", "rdgan_spacetime_workspace_bytes"
 
     def __init__(self, thresholds, radius=4, max_lag=1, planes_per_pass=None):
         self.thr = check_event_thresholds(thresholds)
         self.radius = check_radius(radius)
         self.max_lag = check_max_lag(max_lag)
         self.planes_per_pass = check_planes_per_pass(planes_per_pass)
-        self.plane_shape = None
-        self.lib = None
-        self.counts = self._ws = None
+        self.reset()
 
-    def _start(self, device):
-        require_gpu()
-        self.lib = _lib.load()
+    def _state_tensors(self, device):
         self.counts = torch.zeros(state_count(len(self.thr), self.radius, self.max_lag), dtype=torch.int64, device=device)
 
-    def add(self, hourly):
-        """hourly (..., 24, ny, nx) float32: a CUDA tensor, whose leading axis may have any stride >= the size of one of its
-        entries (_hourly.tensor_layout has the rule, and refuses a crop, a step or a transpose at any rank), or a numpy array.
-        The plane shape is fixed by the first call.  Returns self."""
-        hourly, from_host, shape, n, stride = admit(hourly, self.plane_shape)
-        ny, nx = shape[-2:]
-        check_plane(ny, nx, self.radius)
-        if self.counts is None:
-            self._start("cuda" if from_host else hourly.device)
-        hourly = to_state_device(hourly, from_host, self.counts.device)
-        self.plane_shape = shape[-2:]
-        per_pass = self.planes_per_pass or max(NHOURS, _DEFAULT_PASS_PIXELS // (ny * nx))
-        per_pass = max(NHOURS, min(per_pass, n * NHOURS, MAX_PASS) // NHOURS * NHOURS)
-        with torch.cuda.device(self.counts.device):
-            nbytes = workspace_bytes(self.lib, "rdgan_spacetime_workspace_bytes", ny, nx, len(self.thr), per_pass)
-            # (exactly this size: the entry takes as many days per pass as the workspace holds)
-            if self._ws is None or self._ws.numel() * 8 != nbytes:
-                self._ws = None
-                self._ws = torch.empty(nbytes // 8, dtype=torch.int64, device=self.counts.device)
-            rc = self.lib.rdgan_spacetime_accumulate(_p(hourly), n, stride, ny, nx, _hp(self.thr), len(self.thr), self.radius,
-                                                     self.max_lag, _p(self.counts), _p(self._ws), nbytes, _stream(self.counts))
-        _lib.check(rc, None, "rdgan_spacetime_accumulate")
-        return self
+    def _check_plane(self, ny, nx, what):
+        check_plane(ny, nx, self.radius, what)
 
-    def state(self):
-        """counts (state_count(T, radius, max_lag),) int64: the tensor itself, on the device, in the flat order of include/rdgan.h"""
-        if self.counts is None:
-            raise ValueError("nothing has been added")
-        return self.counts
+    def _pass_units(self, n, ny, nx):
+        per_pass = self.planes_per_pass or max(NHOURS, _DEFAULT_PASS_PIXELS // (ny * nx))
+        return max(NHOURS, min(per_pass, n * NHOURS, MAX_PASS) // NHOURS * NHOURS)
+
+    def _workspace_args(self, n, ny, nx):
+        return ny, nx, len(self.thr), self._pass_units(n, ny, nx)
+
+    def _entry_args(self, ny, nx, out):
+        return ny, nx, _hp(self.thr), len(self.thr), self.radius, self.max_lag, _p(self.counts)
 
     def result(self):
         """-> SpaceTimeStats"""
@@ -246,16 +224,8 @@ def spacetime_structure(hourly, thresholds, radius=4, max_lag=1, planes_per_pass
 
 def spacetime_structure_field(gen, daily, n_scenarios, thresholds, radius=4, max_lag=1, planes_per_pass=None, scenario_chunk=16,
                               overlap=4, latent_mode="shared", seed=None, latent=None, chunk=1024, norm_scale=W.NORM_SCALE):
-    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and take their space-time structure without holding them.
-    The latent array is drawn once for all scenarios, exactly as field.disaggregate draws it for the same seed, latent and numpy
-    RNG state; disaggregate then runs for scenario_chunk scenarios at a time into one reused buffer and each result is added.  The
-    result is spacetime_structure of the hourly values those disaggregate calls produce; as in cells.cell_structure_field, those
-    values equal the ones of a single disaggregate call only when the generator's batches are the same (`chunk` at most one unit's
-    wet tiles, or one scenario chunk).  -> SpaceTimeStats"""
-    st = SpaceTimeStructure(thresholds, radius, max_lag, planes_per_pass)
-    S, step = F._check_scenarios(n_scenarios, scenario_chunk)
-    req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
-    ny, nx = req[3:5]
-    check_plane(ny, nx, st.radius, "daily")
-    F._stream_scenarios(gen, req, req[0], S, step, st.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
-    return st.result()
+    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and take their space-time structure without holding them:
+    _hourly.evaluate_field, which says how the scenarios are drawn and what the result equals, on a SpaceTimeStructure.
+    -> SpaceTimeStats"""
+    return evaluate_field(SpaceTimeStructure(thresholds, radius, max_lag, planes_per_pass), gen, daily, n_scenarios, scenario_chunk,
+                          overlap, latent_mode, seed, latent, chunk, norm_scale)

@@ -18,12 +18,10 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
-from . import field as F
 from . import weights as W
-from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import NHOURS, admit, div as _div, to_state_device, tv as _tv
-from .cells import MAX_PLANE, VOLUME_UNIT, check_connectivity
+from ._dev import host_ptr as _hp, ptr as _p, whole_number
+from ._hourly import NHOURS, admit, div as _div, evaluate_field, tv as _tv
+from .cells import MAX_PLANE, VOLUME_UNIT, LabelAccumulator, check_connectivity
 from .engine import require_gpu
 from .verification import check_event_thresholds
 
@@ -46,11 +44,6 @@ def check_reach(reach):
 
 def check_days_per_pass(days_per_pass):
     return None if days_per_pass is None else whole_number(days_per_pass, 1, MAX_PASS, "days_per_pass, unless None,")
-
-
-def _check_plane(ny, nx, what):
-    if ny * nx > MAX_PLANE or NHOURS * ny * nx > MAX_DAY:
-        raise ValueError(f"{what}: a day has {NHOURS * ny * nx} voxels, the limit is {MAX_DAY}")
 
 
 def split_state(counts, n_thresholds):
@@ -183,62 +176,31 @@ def stats_from_state(counts, thresholds, connectivity, reach, n_pixels):
                       n_pixels=int(n_pixels), **split_state(counts, len(thr)))
 
 
-class StormStructure:
+class StormStructure(LabelAccumulator):
     """The state of a storm evaluation on the device.  thresholds: the wet-voxel events in the unit of the data; connectivity: 4
     (edges) or 8 (edges and corners) inside an hour; reach: how many pixels (Chebyshev) rain may move from one hour to the next
     and stay the same storm, 0 .. 4; days_per_pass: how many days the workspace holds at a time, 24 bytes per voxel -- None: up to
-    2^24 voxels, 384 MB (one day if a day is larger).  The result does not depend on it."""
+    2^24 voxels, 384 MB (one day if a day is larger).  The result does not depend on it.  add() writes the labels as day-local
+    voxel indices, -1 where dry; state(): counts (T * 622 + 2,) int64."""
+    entry, workspace_entry, n_counts = "rdgan_storms_accumulate", "rdgan_storms_workspace_bytes", N_COUNTS
 
     def __init__(self, thresholds, connectivity=8, reach=1, days_per_pass=None):
         self.thr = check_event_thresholds(thresholds)
         self.connectivity = check_connectivity(connectivity)
         self.reach = check_reach(reach)
         self.days_per_pass = check_days_per_pass(days_per_pass)
-        self.plane_shape = None
-        self.lib = None
-        self.counts = self._ws = None
+        self.reset()
 
-    def _start(self, device):
-        require_gpu()
-        self.lib = _lib.load()
-        self.counts = torch.zeros(len(self.thr) * N_COUNTS + 2, dtype=torch.int64, device=device)
+    def _check_plane(self, ny, nx, what):
+        if ny * nx > MAX_PLANE or NHOURS * ny * nx > MAX_DAY:
+            raise ValueError(f"{what}: a day has {NHOURS * ny * nx} voxels, the limit is {MAX_DAY}")
 
-    def add(self, hourly, labels_out=None, label_threshold=0):
-        """hourly (..., 24, ny, nx) float32: a CUDA tensor or a numpy array, admitted as cells.CellStructure.add admits it.  The
-        plane shape is fixed by the first call.  labels_out: None, or a contiguous int32 CUDA tensor of hourly's shape that
-        receives the canonical labels (day-local voxel indices, -1 where dry) at thresholds[label_threshold].  Returns self."""
-        hourly, from_host, shape, n, stride = admit(hourly, self.plane_shape)
-        ny, nx = shape[-2:]
-        _check_plane(ny, nx, "hourly")
-        label_threshold = whole_number(label_threshold, 0, len(self.thr) - 1, "label_threshold")
-        if labels_out is not None and not (isinstance(labels_out, torch.Tensor) and labels_out.is_cuda and labels_out.dtype == torch.int32
-                                           and labels_out.is_contiguous() and tuple(labels_out.shape) == shape):
-            raise ValueError(f"labels_out: expected a contiguous int32 CUDA tensor of shape {shape}")
-        if self.counts is None:
-            self._start("cuda" if from_host else hourly.device)
-        hourly = to_state_device(hourly, from_host, self.counts.device)
-        if labels_out is not None and labels_out.device != self.counts.device:
-            raise ValueError(f"labels_out lies on {labels_out.device}, the state on {self.counts.device}")
-        self.plane_shape = shape[-2:]
+    def _pass_units(self, n, ny, nx):
         per_pass = self.days_per_pass or max(1, _DEFAULT_PASS_VOXELS // (NHOURS * ny * nx))
-        per_pass = min(per_pass, n, MAX_PASS)
-        with torch.cuda.device(self.counts.device):
-            nbytes = workspace_bytes(self.lib, "rdgan_storms_workspace_bytes", ny, nx, per_pass)
-            # (exactly this size: the entry takes as many days per pass as the workspace holds)
-            if self._ws is None or self._ws.numel() * 8 != nbytes:
-                self._ws = None
-                self._ws = torch.empty(nbytes // 8, dtype=torch.int64, device=self.counts.device)
-            rc = self.lib.rdgan_storms_accumulate(_p(hourly), n, stride, ny, nx, _hp(self.thr), len(self.thr), self.connectivity,
-                                                  self.reach, _p(self.counts), _p(labels_out), label_threshold, _p(self._ws), nbytes,
-                                                  _stream(self.counts))
-        _lib.check(rc, None, "rdgan_storms_accumulate")
-        return self
+        return min(per_pass, n, MAX_PASS)
 
-    def state(self):
-        """counts (T * 622 + 2,) int64: the tensor itself, on the device, in the flat order of include/rdgan.h"""
-        if self.counts is None:
-            raise ValueError("nothing has been added")
-        return self.counts
+    def _entry_args(self, ny, nx, labels_out, label_threshold):
+        return ny, nx, _hp(self.thr), len(self.thr), self.connectivity, self.reach, _p(self.counts), _p(labels_out), label_threshold
 
     def result(self):
         """-> StormStats"""
@@ -257,7 +219,7 @@ def label_storms(hourly, threshold, connectivity=8, reach=1):
     elsewhere"""
     ss = StormStructure((threshold,), connectivity, reach)
     hourly, from_host, shape, _, _ = admit(hourly)
-    _check_plane(shape[-2], shape[-1], "hourly")
+    ss._check_plane(shape[-2], shape[-1], "hourly")
     require_gpu()
     labels = torch.empty(shape, dtype=torch.int32, device="cuda" if from_host else hourly.device)
     ss.add(hourly, labels_out=labels)
@@ -266,16 +228,7 @@ def label_storms(hourly, threshold, connectivity=8, reach=1):
 
 def storm_structure_field(gen, daily, n_scenarios, thresholds, connectivity=8, reach=1, days_per_pass=None, scenario_chunk=16,
                           overlap=4, latent_mode="shared", seed=None, latent=None, chunk=1024, norm_scale=W.NORM_SCALE):
-    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and take their storms without holding them.  The latent
-    array is drawn once for all scenarios, exactly as field.disaggregate draws it for the same seed, latent and numpy RNG state;
-    disaggregate then runs for scenario_chunk scenarios at a time into one reused buffer and each result is added.  The result is
-    storm_structure of the hourly values those disaggregate calls produce; as in cells.cell_structure_field, those values equal
-    the ones of a single disaggregate call only when the generator's batches are the same (`chunk` at most one unit's wet tiles,
-    or one scenario chunk).  -> StormStats"""
-    ss = StormStructure(thresholds, connectivity, reach, days_per_pass)
-    S, step = F._check_scenarios(n_scenarios, scenario_chunk)
-    req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
-    ny, nx = req[3:5]
-    _check_plane(ny, nx, "daily")
-    F._stream_scenarios(gen, req, req[0], S, step, ss.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
-    return ss.result()
+    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and take their storms without holding them:
+    _hourly.evaluate_field, which says how the scenarios are drawn and what the result equals, on a StormStructure.  -> StormStats"""
+    return evaluate_field(StormStructure(thresholds, connectivity, reach, days_per_pass), gen, daily, n_scenarios, scenario_chunk,
+                          overlap, latent_mode, seed, latent, chunk, norm_scale)

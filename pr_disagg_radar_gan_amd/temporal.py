@@ -14,12 +14,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
-from . import field as F
 from . import weights as W
-from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import NHOURS, admit, div as _div, tensor_layout, to_state_device, tv as _tv    # noqa: F401 (tensor_layout is public here)
-from .engine import require_gpu
+from ._dev import host_ptr as _hp, ptr as _p, whole_number
+from ._hourly import NHOURS, HourlyAccumulator, div as _div, evaluate_field, tensor_layout, tv as _tv    # noqa: F401 (tensor_layout is public here)
 from .verification import check_event_thresholds
 
 MAX_LAG = 12                                                                 # RD_TS_MAXK
@@ -158,50 +155,32 @@ def stats_from_state(counts, sums, thresholds, max_lag):
     return TemporalStats(thresholds=tuple(float(t) for t in thr), max_lag=int(max_lag), **d)
 
 
-class TemporalStructure:
+class TemporalStructure(HourlyAccumulator):
     """The state of a temporal-structure evaluation on the device.  thresholds: the wet-hour events in the unit of the data;
-    max_lag: the lags 1 .. max_lag of the lagged products."""
+    max_lag: the lags 1 .. max_lag of the lagged products.  add(hourly) is HourlyAccumulator's."""
+    entry, workspace_entry = "rdgan_temporal_accumulate", "rdgan_temporal_workspace_bytes"
 
     def __init__(self, thresholds, max_lag=6):
         self.thr = check_event_thresholds(thresholds)
         self.max_lag = check_max_lag(max_lag)
-        self.plane_shape = None
-        self.lib = None
-        self.counts = self.sums = self._ws = None
+        self.sums = None
+        self.reset()
 
-    def _start(self, device):
-        require_gpu()
-        self.lib = _lib.load()
+    def _state_tensors(self, device):
         T = len(self.thr)
         self.counts = torch.zeros(T * N_COUNTS + 2, dtype=torch.int64, device=device)
         self.sums = torch.zeros(n_sums(T, self.max_lag), dtype=torch.float64, device=self.counts.device)
 
-    def add(self, hourly):
-        """hourly (..., 24, ny, nx) float32: a CUDA tensor, whose leading axis may have any stride >= the size of one of its
-        entries (a view of a wider buffer; tensor_layout has the rule, and refuses a crop, a step or a transpose at any rank), or
-        a numpy array.  The plane shape is fixed by the first call.  Returns self."""
-        hourly, from_host, shape, n, stride = admit(hourly, self.plane_shape)
-        plane = shape[-2] * shape[-1]
-        if self.counts is None:
-            self._start("cuda" if from_host else hourly.device)
-        hourly = to_state_device(hourly, from_host, self.counts.device)
-        self.plane_shape = shape[-2:]
-        T = len(self.thr)
-        with torch.cuda.device(self.counts.device):
-            nbytes = workspace_bytes(self.lib, "rdgan_temporal_workspace_bytes", n, plane, T, self.max_lag)
-            if self._ws is None or self._ws.numel() * 8 < nbytes:
-                self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.counts.device)
-            rc = self.lib.rdgan_temporal_accumulate(_p(hourly), n, stride, plane, _hp(self.thr), T, self.max_lag, _p(self.counts),
-                                                    _p(self.sums), _p(self._ws), self._ws.numel() * 8, _stream(self.counts))
-        _lib.check(rc, None, "rdgan_temporal_accumulate")
-        return self
+    def _workspace_args(self, n, ny, nx):
+        return n, ny * nx, len(self.thr), self.max_lag
+
+    def _entry_args(self, ny, nx, out):
+        return ny * nx, _hp(self.thr), len(self.thr), self.max_lag, _p(self.counts), _p(self.sums)
 
     def state(self):
         """(counts (T * 286 + 2,) int64, sums (48 + K + 24 T,) float64): the tensors themselves, on the device, in the flat order
         of include/rdgan.h"""
-        if self.counts is None:
-            raise ValueError("nothing has been added")
-        return self.counts, self.sums
+        return super().state(), self.sums
 
     def result(self):
         """-> TemporalStats"""
@@ -216,15 +195,8 @@ def temporal_structure(hourly, thresholds, max_lag=6):
 
 def temporal_structure_field(gen, daily, n_scenarios, thresholds, max_lag=6, scenario_chunk=16, overlap=4, latent_mode="shared",
                              seed=None, latent=None, chunk=1024, norm_scale=W.NORM_SCALE):
-    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and take their temporal structure without holding them.
-    The latent array is drawn once for all scenarios, exactly as field.disaggregate draws it for the same seed, latent and numpy
-    RNG state; disaggregate then runs for scenario_chunk scenarios at a time into one reused buffer and each result is added.  The
-    result is temporal_structure of the hourly values those disaggregate calls produce.  The generator's fp32 output depends in its
-    last bits on the batch of tiles it runs in, so against temporal_structure(disaggregate(...all scenarios...)[0], ...) the counts
-    are equal and the sums within the reordering bound when the batches are the same (`chunk` at most one unit's wet tiles, or one
-    scenario chunk); otherwise the two differ as disaggregate's own outputs differ between values of `chunk`.  -> TemporalStats"""
-    ts = TemporalStructure(thresholds, max_lag)
-    S, step = F._check_scenarios(n_scenarios, scenario_chunk)
-    req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
-    F._stream_scenarios(gen, req, req[0], S, step, ts.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
-    return ts.result()
+    """Disaggregate a daily map ([D,] ny, nx) into n_scenarios scenarios and take their temporal structure without holding them:
+    _hourly.evaluate_field, which says how the scenarios are drawn and what the result equals, on a TemporalStructure.
+    -> TemporalStats"""
+    return evaluate_field(TemporalStructure(thresholds, max_lag), gen, daily, n_scenarios, scenario_chunk, overlap, latent_mode, seed,
+                          latent, chunk, norm_scale)

@@ -1,10 +1,17 @@
-"""CPU: the one admission of hourly arrays (pr_disagg_radar_gan_amd/_hourly.py) and the two accumulators built on it refuse the
-same inputs, with ValueError, before any device call."""
+"""CPU: the one admission of hourly arrays (pr_disagg_radar_gan_amd/_hourly.py) and everything built on it -- the five
+accumulators of HourlyAccumulator (temporal, cells, storms, areal, space-time) and the one-call functions that allocate an output
+before they add (label_cells, label_storms, areal_extremes with return_depths) -- refuse the same inputs, with ValueError, before
+any device call, and let a good input through to it; and the per-pass arithmetic of each accumulator, against the numbers the
+expressions in the five modules gave before the base class existed."""
 import numpy as np
 import pytest
 import torch
 
-from pr_disagg_radar_gan_amd import _hourly as H, _lib, cells as CL, temporal as TS
+from pr_disagg_radar_gan_amd import _hourly as H, _lib, areal as AR, cells as CL, spacetime as ST, storms as SM, temporal as TS
+
+# one of each accumulator, with parameters under which the 4 x 5 and 6 x 8 planes of the rows below are admissible
+ACCUMULATORS = (lambda: TS.TemporalStructure((0.1,)), lambda: CL.CellStructure((0.1,)), lambda: SM.StormStructure((0.1,)),
+                lambda: AR.ArealExtremes((1,), (1, 3)), lambda: ST.SpaceTimeStructure((0.1,), radius=1))
 
 
 class AsIfOnDevice(torch.Tensor):
@@ -35,13 +42,16 @@ def _rows():
 def test_every_entry_refuses_the_same_inputs_before_the_device(monkeypatch):
     def device_call(*a, **k):
         raise AssertionError("the device was reached")
-    for mod in (TS, CL):
+    for mod in (H, CL, SM, AR):                     # the accumulators' add reaches it in _hourly, the one-call functions in their modules
         monkeypatch.setattr(mod, "require_gpu", device_call)
     monkeypatch.setattr(_lib, "load", device_call)
     rows, four = _rows()
     assert all(isinstance(t, AsIfOnDevice) and t.is_cuda for t, m in rows if "contig" in m)
-    entries = (("admit", lambda x: H.admit(x)), ("TemporalStructure.add", lambda x: TS.TemporalStructure((0.1,)).add(x)),
-               ("CellStructure.add", lambda x: CL.CellStructure((0.1,)).add(x)), ("label_cells", lambda x: CL.label_cells(x, 0.1)))
+    entries = (("admit", lambda x: H.admit(x)),) + tuple((f"{make().__class__.__name__}.add", lambda x, make=make: make().add(x))
+                                                          for make in ACCUMULATORS)
+    entries += (("label_cells", lambda x: CL.label_cells(x, 0.1)), ("label_storms", lambda x: SM.label_storms(x, 0.1)),
+                ("areal_extremes", lambda x: AR.areal_extremes(x, (1,), (1, 3), return_depths=True)))
+    assert len(entries) == 9
     for name, entry in entries:
         for i, (bad, message) in enumerate(rows):
             with pytest.raises(ValueError, match=message):
@@ -62,7 +72,8 @@ def test_every_entry_refuses_the_same_inputs_before_the_device(monkeypatch):
 def test_the_plane_shape_of_the_first_call_holds(monkeypatch):
     monkeypatch.setattr(_lib, "load", lambda: pytest.fail("the device was reached"))
     second = (np.zeros((24, 4, 6), np.float32), torch.zeros(3, 24, 5, 4).as_subclass(AsIfOnDevice))
-    for acc in (TS.TemporalStructure((0.1,)), CL.CellStructure((0.1,))):
+    for make in ACCUMULATORS:
+        acc = make()
         acc.plane_shape = (4, 5)                                    # as after a first add
         for x in second:
             with pytest.raises(ValueError, match="since the first call"):
@@ -71,6 +82,49 @@ def test_the_plane_shape_of_the_first_call_holds(monkeypatch):
         with pytest.raises(ValueError, match="since the first call"):
             H.admit(x, (4, 5))
     assert H.admit(np.zeros((7, 24, 4, 5)), (4, 5))[3] == 7          # more days of the same plane are welcome
+
+
+# (per_pass argument, plane, {n days: units of a pass}); the numbers are worked out by hand from the expressions each module's add
+# held before HourlyAccumulator: 2^24 // 63 = 266305, 2^24 // 4550 = 3687, 2^24 // (24 * 63) = 11096, 2^24 // (24 * 4550) = 153,
+# 2^22 // 63 = 66576, 2^22 // 4550 = 921, 2^28 // 63 = 4260880, 2^28 // 4550 = 58996 -- none of which binds below 3 days, so the
+# 2048 x 2048 rows are there for the default: 2^24 // 2^22 = 4 planes, 2^24 // (24 * 2^22) = 0 -> 1 day, 2^22 // 2^22 = 1 day, 2^28 //
+# 2^22 = 64 planes -> 48
+PASS_UNITS = {
+    "cells": (lambda per: CL.CellStructure((0.1,), planes_per_pass=per), [          # planes: min(per or default, 24 n, 65535)
+        (None, (9, 7), {1: 24, 3: 72}), (None, (70, 65), {1: 24, 3: 72}), (None, (2048, 2048), {1: 4, 3: 4}),
+        (1, (9, 7), {1: 1, 3: 1}), (1, (70, 65), {1: 1, 3: 1}), (100, (9, 7), {1: 24, 3: 72}), (100, (70, 65), {1: 24, 3: 72}),
+        (50, (9, 7), {1: 24, 3: 50})]),
+    "storms": (lambda per: SM.StormStructure((0.1,), days_per_pass=per), [          # days: min(per or default, n, 2730)
+        (None, (9, 7), {1: 1, 3: 3}), (None, (70, 65), {1: 1, 3: 3}), (None, (2048, 2048), {1: 1, 3: 1}),
+        (1, (9, 7), {1: 1, 3: 1}), (1, (70, 65), {1: 1, 3: 1}), (5, (9, 7), {1: 1, 3: 3}), (5, (70, 65), {1: 1, 3: 3}),
+        (2, (70, 65), {1: 1, 3: 2})]),
+    "areal": (lambda per: AR.ArealExtremes((1,), (1, 3), workspace_days=per), [     # days: min(per or default, n, 65535)
+        (None, (9, 7), {1: 1, 3: 3}), (None, (70, 65), {1: 1, 3: 3}), (None, (2048, 2048), {1: 1, 3: 1}),
+        (1, (9, 7), {1: 1, 3: 1}), (1, (70, 65), {1: 1, 3: 1}), (5, (9, 7), {1: 1, 3: 3}), (5, (70, 65), {1: 1, 3: 3}),
+        (2, (70, 65), {1: 1, 3: 2})]),
+    "spacetime": (lambda per: ST.SpaceTimeStructure((0.1,), radius=1, planes_per_pass=per), [   # planes, in whole days, one day at least
+        (None, (9, 7), {1: 24, 3: 72}), (None, (70, 65), {1: 24, 3: 72}), (None, (2048, 2048), {1: 24, 3: 48}),
+        (24, (9, 7), {1: 24, 3: 24}), (24, (70, 65), {1: 24, 3: 24}), (100, (9, 7), {1: 24, 3: 72}), (100, (70, 65), {1: 24, 3: 72}),
+        (71, (70, 65), {1: 24, 3: 48}), (48, (9, 7), {1: 24, 3: 48})]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PASS_UNITS))
+def test_pass_units_are_the_expressions_the_modules_held(name):
+    make, table = PASS_UNITS[name]
+    for per, (ny, nx), want in table:
+        acc = make(per)
+        assert {n: acc._pass_units(n, ny, nx) for n in want} == want, (name, per, ny, nx)
+
+
+def test_pass_units_of_temporal_and_the_smallest_pass_arguments():
+    assert TS.TemporalStructure((0.1,))._pass_units(3, 9, 7) is None          # one launch over the whole array: no passes
+    # an explicit per-pass of 1 is the least a caller can ask for, 24 planes (one day) for space-time
+    for make, _ in PASS_UNITS.values():
+        with pytest.raises(ValueError):
+            make(0)
+    with pytest.raises(ValueError):
+        ST.SpaceTimeStructure((0.1,), planes_per_pass=23)
 
 
 def test_upload_or_refusal_once_the_state_exists():

@@ -1,0 +1,51 @@
+"""What the five accumulate entries of the hourly evaluations check and size the same way (csrc/rdgan_hourly_host.h:
+rd_hourly_layout_ok, rd_pass_units, rd_aligned) checked without a GPU: tests/host/hourly_check.cpp, a stand-alone program built
+by the host C++ compiler from that header alone with the address and undefined-behaviour sanitizers, prints each helper at its
+edges, and the output equals the table below, which restates the checks the entries held inline: x on 4 bytes, n >= 1,
+n day_elems <= 2^40, day_elems <= day_stride <= 2^50 / n; min(min(max(workspace_bytes, 0) / unit, n_units), max_units)."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+WANT = {
+    # a day of 24 x 35 elements unless the name says otherwise
+    "layout_good": 1, "layout_n0": 0, "layout_n_negative": 0, "layout_day0": 0,
+    "layout_stride_below_day": 0, "layout_stride_is_day": 1,                        # day_stride = day_elems - 1, = day_elems
+    "layout_stride_at_span": 1, "layout_stride_above_span": 0,                      # day_stride = 2^50 / 3, and one above
+    "layout_one_day_any_stride": 1, "layout_one_day_above_span": 0,                 # n = 1: 2^50, and one above
+    "layout_elems_at_cap": 1, "layout_elems_one_day_over": 0,                       # 2^30 days of 1024: exactly 2^40; one day more
+    "layout_one_day_of_cap": 1, "layout_one_day_over_cap": 0,                       # one day of 2^40, of 2^40 + 1
+    "layout_x_misaligned": 0, "layout_x_on_4": 1,
+    # a unit of 35 * 16 + 8 bytes, 72 units of input, at most 65535 a pass unless the name says otherwise
+    "pass_negative": 0, "pass_zero": 0, "pass_below_unit": 0, "pass_one_unit": 1, "pass_below_two": 1, "pass_five": 5,
+    "pass_more_than_input": 72, "pass_more_than_max": 65535, "pass_at_max": 65535, "pass_largest_size": 2730,
+    "aligned_all": 1, "aligned_one_on_4": 0, "aligned_4_is_enough": 1,
+}
+
+
+@pytest.fixture(scope="module")
+def printed(tmp_path_factory):
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path_factory.mktemp("hourly") / "hourly_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "host", "hourly_check.cpp"), "-o", exe], check=True, cwd=ROOT)
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]       # (a sanitizer report ends the program with an error)
+    return {name: int(value) for name, value in (line.split() for line in res.stdout.splitlines() if line.strip())}
+
+
+def test_layout_and_pass_helpers_at_their_edges(printed):
+    assert printed == WANT, {k: (printed.get(k), WANT.get(k)) for k in set(printed) | set(WANT) if printed.get(k) != WANT.get(k)}
+
+
+def test_the_entries_use_the_helpers_and_hold_no_copy():
+    """the bounds live in the header alone: the entries' file spells neither of them out any more"""
+    entries = open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", "rdgan_eval_entries.h")).read()
+    assert "1L << 50" not in entries and "workspace_bytes < 0 ? 0" not in entries
+    assert entries.count("rd_hourly_layout_ok(x, n, day_stride") == 5          # temporal, cells, storms, areal, space-time
