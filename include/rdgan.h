@@ -763,6 +763,39 @@ int rdgan_analog_apply(const float* lib, long n, long day_stride, long ny, long 
                        long first_query, const int* neighbours, const int* found, int k, int n_members, long first_member,
                        unsigned long long seed, int weights, float* out, int* picks_out, void* stream);
 
+/* Joint-field scores of ensembles of hourly days: the energy score (Gneiting et al. 2008) and the variogram
+ * score of order p (Scheuerer & Hamill 2015) of an ensemble of whole days against the observed day, taken as one vector.
+ * An ensemble is x [m][24][ny][nx] fp32, every value finite, 1 <= m <= 8192; the observation y [24][ny][nx] fp32.  A position where y
+ * is NaN is left out of every sum of that day; a day without a valid position has NaN in every floating-point output (and counts of
+ * 0).  shared = 0: ens [n_days][m][24][ny][nx], one ensemble per day; shared = 1: ens [m][24][ny][nx], one ensemble for all days.
+ * obs [n_days][24][ny][nx].  1 <= n_days <= 2^20, 1 <= ny nx <= 2^24, at most 2^40 ensemble values per call.  All buffers lie on the
+ * device, dense; ens and obs 4-byte aligned, the outputs and the workspace 8-byte aligned.
+ * rdgan_mv_energy: with V the valid positions of the day and |a - b| = sqrt(sum over p in V of (a_p - b_p)^2), the values converted
+ * to fp64 and the differences formed and accumulated in fp64 (ascending p), obs_sum_out [n_days] = sum over i of |x_i - y| and
+ * pair_sum_out [n_days] = sum over i < j of |x_i - x_j|, fp64.  Two members equal at every valid position contribute exactly 0 (the
+ * difference form, not the Gram form).  The caller forms ES = obs_sum / m - pair_sum / m^2, or pair_sum / (m (m - 1)) for the fair
+ * score, whose spread term is 0 at m = 1.  The sums are formed per 64 x 64 tile of the distance matrix and the tiles added in a
+ * fixed order: two calls agree bit for bit and a day's sums do not depend on the other days of the call.  With shared = 1 the
+ * distances among members are computed once for the days without a NaN, and once more for each day that has one.
+ * rdgan_mv_variogram: p is 0.5 or 1, 0 <= radius <= 4 (pixels), 0 <= max_lag <= 3 (hours).  A displacement (l, di, dj) has 0 <= l <=
+ * max_lag and |di|, |dj| <= radius and lies in the half-space l > 0, or l = 0 and di > 0, or l = 0, di = 0 and dj > 0.  A pair is
+ * a = (h, i, j), b = (h + l, i + di, j + dj), both inside the day and the plane (no wrap) and both valid.  v_k = |x_k,a - x_k,b|^p in
+ * fp32 (the difference rounded to fp32, sqrtf for p = 0.5), mean = (sum over k = 0 .. m - 1, in that order, of v_k in fp64) / m,
+ * o = |y_a - y_b|^p likewise.  sq_out [n_days][max_lag + 1][2 radius + 1][2 radius + 1] fp64 = the sum over the pairs of
+ * (o - mean)^2 at [l][di + radius][dj + radius], count_out (same shape, 64-bit integers) the number of pairs; both 0 outside the
+ * half-space.  The pairs are added in a fixed order; the shared form equals the per-day form given the same ensemble n_days times,
+ * bit for bit.  The caller forms VS = sum of w sq, by default w = 1 / sqrt(l^2 + di^2 + dj^2).
+ * The *_workspace_bytes entries return the bytes a call with these arguments needs (-2 for an argument out of range); a larger
+ * workspace changes nothing.  Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, a size
+ * outside the limits above, shared not 0 or 1, p not 0.5 or 1, a workspace too small, more than 2^31 - 1 workgroups) with nothing
+ * launched and no output touched.  All offsets are 64-bit. */
+long rdgan_mv_energy_workspace_bytes(long m, long n_days, int shared);
+int rdgan_mv_energy(const float* ens, const float* obs, long m, long n_days, long ny, long nx, int shared, double* obs_sum_out,
+                    double* pair_sum_out, void* workspace, long workspace_bytes, void* stream);
+long rdgan_mv_variogram_workspace_bytes(long n_days, long ny, long nx, int radius, int max_lag, int shared);
+int rdgan_mv_variogram(const float* ens, const float* obs, long m, long n_days, long ny, long nx, int shared, double p, int radius,
+                       int max_lag, double* sq_out, long long* count_out, void* workspace, long workspace_bytes, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

@@ -14,8 +14,10 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
   * ``storms`` -- wet volumes connected through the day's hours: how long a rain system lives, when it starts, what it carries
   * ``areal`` -- depth-area-duration: the largest k-hour accumulation over any w x w box per day, and the areal reduction factor
   * ``analog`` -- the analog baseline (method of fragments): the k nearest library days of a daily condition, their scaled fractions
+  * ``multivariate`` -- energy and variogram score of ensembles of whole hourly days; the four-method experiment
 """
 from .engine import Engine, require_gpu  # noqa: F401
 from . import weights  # noqa: F401
 from . import field_products  # noqa: F401
 from . import verification  # noqa: F401
+from . import multivariate  # noqa: F401

@@ -130,6 +130,12 @@ SIGNATURES = {
     "rdgan_analog_apply": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, c_f32p, ctypes.c_long,
                                           ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_long,
                                           ctypes.c_uint64, ctypes.c_int, c_f32p, ctypes.c_void_p, c_stream]),
+    "rdgan_mv_energy_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_int]),
+    "rdgan_mv_energy": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),
+    "rdgan_mv_variogram_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "rdgan_mv_variogram": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_double,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),
     "rdgan_spectra_bins": (ctypes.c_int, [ctypes.c_int]),
     "rdgan_radial_spectra": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_stream]),
     "rdgan_lsd_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long]),

@@ -933,6 +933,100 @@ extern "C" int rdgan_analog_apply(const float* lib, long n, long day_stride, lon
 }
 
 // ------------------------------------------------------------------------------------
+// joint-field scores (rdgan_mvscore.hip.h): the sums of the energy score and the tables of the variogram score
+// ------------------------------------------------------------------------------------
+static bool rd_mv_shape_ok(long m, long n_days, long ny, long nx, int shared) {
+  if (m < 1 || m > RD_MV_MAXM || n_days < 1 || n_days > RD_MV_MAXDAYS || (shared != 0 && shared != 1)) return false;
+  if (ny < 1 || nx < 1 || ny > RD_MV_MAXPLANE || nx > RD_MV_MAXPLANE || ny * nx > RD_MV_MAXPLANE) return false;
+  return (shared ? 1 : n_days) * m <= RD_HOURLY_MAXELEMS / (RD_MV_HOURS * ny * nx);
+}
+// workgroups of the largest launch of an energy call
+static long rd_mv_energy_blocks(long m, long n_days, int shared) {
+  if (!shared) return n_days * rd_mv_tile_pairs(rd_mv_tiles(m + 1));
+  return std::max<long>((1 + n_days) * rd_mv_tile_pairs(rd_mv_tiles(m)), rd_mv_tiles(m) * rd_mv_tiles(n_days));
+}
+static bool rd_mv_variogram_ok(int radius, int max_lag) { return radius >= 0 && radius <= RD_MV_MAXR && max_lag >= 0 && max_lag <= RD_MV_MAXLAG; }
+
+extern "C" long rdgan_mv_energy_workspace_bytes(long m, long n_days, int shared) {
+  if (!rd_mv_shape_ok(m, n_days, 1, 1, shared) || rd_mv_energy_blocks(m, n_days, shared) > RD_MV_MAXBLOCKS) return -2;
+  return rd_mv_energy_words(m, n_days, shared) * 8;
+}
+
+extern "C" int rdgan_mv_energy(const float* ens, const float* obs, long m, long n_days, long ny, long nx, int shared, double* obs_sum_out,
+                               double* pair_sum_out, void* workspace, long workspace_bytes, void* stream) {
+  if (!ens || !obs || !obs_sum_out || !pair_sum_out || !workspace) return -2;
+  if (!rd_aligned(3, ens, obs) || !rd_aligned(7, obs_sum_out, pair_sum_out, workspace)) return -2;
+  if (!rd_mv_shape_ok(m, n_days, ny, nx, shared) || rd_mv_energy_blocks(m, n_days, shared) > RD_MV_MAXBLOCKS) return -2;
+  if (workspace_bytes < rd_mv_energy_words(m, n_days, shared) * 8) return -2;
+  const long P = RD_MV_HOURS * ny * nx;
+  hipStream_t st = (hipStream_t)stream;
+  long long* nvalid = (long long*)workspace;
+  double* slots = (double*)workspace + n_days;
+  hipLaunchKernelGGL(k_mv_valid, dim3((unsigned)n_days), dim3(RD_MV_THREADS), 0, st, obs, P, nvalid);
+  if (!shared) {
+    const long T = rd_mv_tiles(m + 1), NT = rd_mv_tile_pairs(T);
+    hipLaunchKernelGGL(k_mv_energy<false>, dim3((unsigned)(n_days * NT)), dim3(RD_MV_THREADS), 0, st, ens, m * P, obs, (int)m, n_days, P, 1, 0,
+                       (const long long*)nvalid, slots);
+    hipLaunchKernelGGL(k_mv_energy_reduce, dim3((unsigned)n_days), dim3(RD_MV_THREADS), 0, st, (const double*)slots, (const double*)nullptr, NT,
+                       (int)T, 0L, 0, P, (const long long*)nvalid, obs_sum_out, pair_sum_out);
+  } else {
+    const long T = rd_mv_tiles(m), NT = rd_mv_tile_pairs(T), TD = rd_mv_tiles(n_days);
+    double* obs_slots = slots + (1 + n_days) * NT;
+    hipLaunchKernelGGL(k_mv_energy<false>, dim3((unsigned)((1 + n_days) * NT)), dim3(RD_MV_THREADS), 0, st, ens, 0L, obs, (int)m, n_days, P, 0, 1,
+                       (const long long*)nvalid, slots);
+    hipLaunchKernelGGL(k_mv_energy<true>, dim3((unsigned)(T * TD)), dim3(RD_MV_THREADS), 0, st, ens, 0L, obs, (int)m, n_days, P, 0, 0,
+                       (const long long*)nvalid, obs_slots);
+    hipLaunchKernelGGL(k_mv_energy_reduce, dim3((unsigned)n_days), dim3(RD_MV_THREADS), 0, st, (const double*)slots, (const double*)obs_slots, NT,
+                       (int)T, TD * RD_MV_TILE, 1, P, (const long long*)nvalid, obs_sum_out, pair_sum_out);
+  }
+  return (int)hipGetLastError();
+}
+
+extern "C" long rdgan_mv_variogram_workspace_bytes(long n_days, long ny, long nx, int radius, int max_lag, int shared) {
+  if (!rd_mv_shape_ok(1, n_days, ny, nx, shared) || !rd_mv_variogram_ok(radius, max_lag)) return -2;
+  if (n_days > RD_MV_MAXBLOCKS / std::max<long>(rd_mv_units(ny, nx, radius, max_lag), 1)) return -2;
+  return rd_mv_variogram_words(n_days, ny, nx, radius, max_lag, shared) * 8;
+}
+
+template <bool HALF>
+static void rd_mv_variogram_launch(const float* ens, const float* obs, long m, long n_days, long ny, long nx, int shared, int R, int L,
+                                   double* table, rd_mv_slot* slots, hipStream_t st) {
+  const long U = rd_mv_units(ny, nx, R, L), P = RD_MV_HOURS * ny * nx;
+  if (U == 0) return;                                                      // radius 0 and no lag: no displacement at all
+  if (!shared) {
+    hipLaunchKernelGGL((k_mv_variogram<0, HALF>), dim3((unsigned)(n_days * U)), dim3(RD_MV_THREADS), 0, st, ens, m * P, obs, (int)m, (int)ny,
+                       (int)nx, R, L, table, slots);
+  } else {
+    hipLaunchKernelGGL((k_mv_variogram<1, HALF>), dim3((unsigned)U), dim3(RD_MV_THREADS), 0, st, ens, 0L, obs, (int)m, (int)ny, (int)nx, R, L,
+                       table, slots);
+    hipLaunchKernelGGL((k_mv_variogram<2, HALF>), dim3((unsigned)(n_days * U)), dim3(RD_MV_THREADS), 0, st, ens, 0L, obs, (int)m, (int)ny,
+                       (int)nx, R, L, table, slots);
+  }
+}
+
+extern "C" int rdgan_mv_variogram(const float* ens, const float* obs, long m, long n_days, long ny, long nx, int shared, double p, int radius,
+                                  int max_lag, double* sq_out, long long* count_out, void* workspace, long workspace_bytes, void* stream) {
+  if (!ens || !obs || !sq_out || !count_out || !workspace) return -2;
+  if (!rd_aligned(3, ens, obs) || !rd_aligned(7, sq_out, count_out, workspace)) return -2;
+  if (!rd_mv_shape_ok(m, n_days, ny, nx, shared) || !rd_mv_variogram_ok(radius, max_lag) || !(p == 0.5 || p == 1.0)) return -2;
+  const long U = rd_mv_units(ny, nx, radius, max_lag);
+  if (n_days > RD_MV_MAXBLOCKS / std::max<long>(U, 1) || workspace_bytes < rd_mv_variogram_words(n_days, ny, nx, radius, max_lag, shared) * 8) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  long long* nvalid = (long long*)workspace;
+  rd_mv_slot* slots = (rd_mv_slot*)((long long*)workspace + n_days);
+  double* table = (double*)(slots + n_days * U * RD_MV_VG);
+  hipLaunchKernelGGL(k_mv_valid, dim3((unsigned)n_days), dim3(RD_MV_THREADS), 0, st, obs, RD_MV_HOURS * ny * nx, nvalid);
+  if (p == 0.5)
+    rd_mv_variogram_launch<true>(ens, obs, m, n_days, ny, nx, shared, radius, max_lag, table, slots, st);
+  else
+    rd_mv_variogram_launch<false>(ens, obs, m, n_days, ny, nx, shared, radius, max_lag, table, slots, st);
+  const long entries = n_days * (max_lag + 1) * rd_mv_side(radius) * rd_mv_side(radius);
+  hipLaunchKernelGGL(k_mv_variogram_reduce, dim3((unsigned)((entries + RD_MV_THREADS - 1) / RD_MV_THREADS)), dim3(RD_MV_THREADS), 0, st,
+                     (const rd_mv_slot*)slots, n_days, (int)ny, (int)nx, radius, max_lag, (const long long*)nvalid, sq_out, count_out);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
 // log-spectral distance (rdgan_spectral.hip.h)
 // ------------------------------------------------------------------------------------
 extern "C" int rdgan_spectra_bins(int nd) {
