@@ -796,6 +796,58 @@ long rdgan_mv_variogram_workspace_bytes(long n_days, long ny, long nx, int radiu
 int rdgan_mv_variogram(const float* ens, const float* obs, long m, long n_days, long ny, long nx, int shared, double p, int radius,
                        int max_lag, double* sq_out, long long* count_out, void* workspace, long workspace_bytes, void* stream);
 
+/* Random-cascade baseline: the microcanonical multiplicative cascade (Olsson 1998; Guentner et al. 2001) with
+ * the three-way first split of a 24-hour day (Mueller & Haberlandt 2015).  rdgan_cascade_accumulate counts, over observed hourly
+ * data, how a wet box of rain splits into its parts; the caller turns the counts into a table of thresholds; rdgan_cascade_generate
+ * applies the splits recursively to daily sums: 24 h -> 3 x 8 h -> 4 h -> 2 h -> 1 h.  Everything is an integer.
+ * Units: q(x) = (int) rintf(x * 1024).  A pixel-hour is bad when x is NaN, +-inf, negative or >= 2048.  A pixel-day with a bad hour is
+ * left out whole and counted in n_bad; one with sum 0 is counted in n_dry and adds nothing else.
+ * Tree: node 0 is the day, split into thirds of 8 h; nodes 1 .. 3 the 8 h boxes (level 0), 4 .. 9 the 4 h boxes (level 1), 10 .. 21
+ * the 2 h boxes (level 2), each split into halves.  A node of volume V = 0 is not a sample.  edge_units [n_edges], host memory: the
+ * edges of the volume classes as integers per hour, rint(mm/h * 1024), strictly increasing in 1 .. 2^21, 0 <= n_edges <= 7 (null for
+ * none); the class of a box of `hours` hours is the number of edges e with V >= e * hours, NV = n_edges + 1.  Position class of a box
+ * of a binary level, from whether the previous and the next box of its level within the day are wet (beyond the day's ends: dry):
+ * 0 isolated, 1 starting (previous dry, next wet), 2 enclosed, 3 ending.  Type of a binary split with first half V1: 0 = 0/1 (V1 = 0),
+ * 1 = 1/0 (V1 = V), 2 = x/(1-x) with the weight bin b = (V1 * 32) / V.  The day: its pattern is the wet mask of the thirds (bit t:
+ * third t); two wet thirds: the bin of the first wet one, (V_first * 32) / V; three: b1 = (V1 * 32) / V and b2 = (V2 * 32) / (V - V1).
+ * State, rdgan_cascade_state_size(n_edges) = 748 NV + 3 64-bit counters (-2 for n_edges out of range), flat in this order:
+ *     0          type    [level 3][position 4][NV][3]
+ *     36 NV      weight  [level 3][position 4][NV][32]
+ *     420 NV     pattern [NV][8]
+ *     428 NV     w2      [NV][pattern 8][32]          (patterns 3, 5, 6)
+ *     684 NV     w3a     [NV][32]                     b1 of pattern 7
+ *     716 NV     w3b     [NV][32]                     b2 of pattern 7
+ *     748 NV     n_days, n_bad, n_dry                 pixel-days seen, left out for a bad hour, without rain
+ * rdgan_cascade_accumulate: hourly [n][24][ny][nx] fp32 on the device, the leading stride day_stride >= 24 ny nx (4-byte aligned; 16-byte
+ * loads when it is 16-byte aligned and ny nx and day_stride are multiples of 4), ny nx <= 2^24, at most 2^40 elements.  state_inout
+ * (device, 8-byte aligned) ACCUMULATES over any number of calls; the caller zeroes it before the first.  Integer atomics throughout:
+ * the state does not depend on how the days are split into calls or on the launch geometry.
+ * rdgan_cascade_generate: model [748 NV] uint32 on the device, the state's layout without the last three words: per row the
+ * cumulative thresholds c[j] = (cum[j] << 24) / total, non-decreasing, the last 2^24 (and c[0] = 0 in a pattern row); a draw r < 2^24
+ * picks the first j with c[j] > r.  cond [n_queries][ny][nx] fp32 daily sums in mm; a pixel is masked when it is NaN, +-inf, negative
+ * or >= 16384 and gets 24 NaNs (units -1); otherwise V = rint(cond * 1024) < 2^24 is split level by level, the position classes of a
+ * level taken from the wetness the level above produced, and the children of a node sum to its V exactly.
+ * Draws: key = rd_member_key(rd_member_key(rd_make_key(seed, 10), first_member + m), first_query + i) for member m of query i, r =
+ * rd_bits(key, (block * 32 + node) * 4 + draw) >> 8 (csrc/rdgan_rng.h), block = (y / patch) ceil(nx / patch) + x / patch: the pixels
+ * of a patch x patch block share their draws.  Draw 0 picks the type or the pattern, draw 1 the bin b, draw 2 the 24 bits u inside
+ * it: part(V, b, u, most) = min(max((V ((b << 24) + u)) >> 29, 1), most), a 64-bit product.  The day: while the pattern has more wet
+ * thirds than V has units, its highest wet third is dropped; two wet thirds: the first gets part(V, b, u, V - 1), b from w2; three:
+ * V1 = part(V, b1, u1, V - 2) with b1 from w3a, then of R = V - V1, V2 = part(R, b2, u2, R - 1) with b2 from w3b and the draws 1 and
+ * 2 of node 22.  A binary node of V >= 2: the type from its row; type 2 gives V1 = part(V, b, u, V - 1).  A binary node of V = 1 cannot
+ * split x/(1-x): with (c0, c1, 2^24) its row, type 0 where (r c1) >> 24 < c0 and type 1 otherwise; where c1 = 0, type 0 for r < 2^23.
+ * out [n_queries][n_members][24][ny][nx] fp32 = units * 2^-10, exact; a pixel's 24 hours sum to rint(cond * 1024) / 1024.  units_out:
+ * null, or int32 of the same shape.  16-byte stores when nx is a multiple of 4 and out and units_out are 16-byte aligned.
+ * 1 <= n_queries <= 2^18, 1 <= n_members <= 65535, at most 2^40 output values, 1 <= patch <= 2^24, first_query + n_queries <= 2^32,
+ * 0 <= first_member <= 2^62.  Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, a size, an
+ * edge list, patch, first_query or first_member outside the limits above, day_stride below 24 ny nx) with nothing launched and no
+ * output touched.  All offsets are 64-bit. */
+long rdgan_cascade_state_size(int n_edges);
+int rdgan_cascade_accumulate(const float* hourly, long n, long day_stride, long ny, long nx, const int* edge_units, int n_edges,
+                             long long* state_inout, void* stream);
+int rdgan_cascade_generate(const unsigned* model, const int* edge_units, int n_edges, const float* cond, long n_queries,
+                           long first_query, long ny, long nx, int n_members, long first_member, unsigned long long seed, int patch,
+                           float* out, int* units_out, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

@@ -15,6 +15,7 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
   * ``areal`` -- depth-area-duration: the largest k-hour accumulation over any w x w box per day, and the areal reduction factor
   * ``analog`` -- the analog baseline (method of fragments): the k nearest library days of a daily condition, their scaled fractions
   * ``multivariate`` -- energy and variogram score of ensembles of whole hourly days; the four-method experiment
+  * ``cascade`` -- the random-cascade baseline: splits of wet boxes calibrated on hourly data, applied to daily sums 24 h -> 1 h
 """
 from .engine import Engine, require_gpu  # noqa: F401
 from . import weights  # noqa: F401

@@ -1198,3 +1198,72 @@ extern "C" int rdgan_rainfarm_generate(const float* amplitudes, const float* pre
   }
   return (int)hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------
+// random-cascade baseline (rdgan_cascade.hip.h): the splits of wet boxes counted, and applied to daily sums
+// ------------------------------------------------------------------------------------
+// the edges as the kernels compare them: integers per hour, strictly increasing in 1 .. RD_CS_MAXEDGE; no edge needs no list
+static bool rd_cs_edges_ok(const int* edge_units, int n_edges, rd_cs_edges* out) {
+  if (n_edges < 0 || n_edges > RD_CS_MAXE || (n_edges > 0 && !edge_units)) return false;
+  memset(out, 0, sizeof(*out));
+  out->n = n_edges;
+  for (int i = 0; i < n_edges; ++i) {
+    if (edge_units[i] < 1 || edge_units[i] > RD_CS_MAXEDGE || (i > 0 && edge_units[i] <= edge_units[i - 1])) return false;
+    out->v[i] = edge_units[i];
+  }
+  return true;
+}
+
+static bool rd_cs_shape_ok(long ny, long nx) { return ny >= 1 && nx >= 1 && ny <= RD_CS_MAXPLANE && nx <= RD_CS_MAXPLANE && ny * nx <= RD_CS_MAXPLANE; }
+
+extern "C" long rdgan_cascade_state_size(int n_edges) {
+  if (n_edges < 0 || n_edges > RD_CS_MAXE) return -2;
+  return rd_cs_state_size(n_edges);
+}
+
+extern "C" int rdgan_cascade_accumulate(const float* hourly, long n, long day_stride, long ny, long nx, const int* edge_units, int n_edges,
+                                        long long* state_inout, void* stream) {
+  rd_cs_edges e;
+  if (!hourly || !state_inout || !rd_aligned(7, state_inout) || !rd_aligned(3, edge_units)) return -2;
+  if (!rd_cs_shape_ok(ny, nx) || !rd_cs_edges_ok(edge_units, n_edges, &e)) return -2;
+  const long plane = ny * nx;
+  static_assert(RD_CS_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
+  if (!rd_hourly_layout_ok(hourly, n, day_stride, RD_CS_HOURS * plane)) return -2;
+  // a counter of a workgroup grows by at most 12 per pixel-day: 12 * 2^40 / (24 * RD_CS_ACC_MAXBLOCKS) stays below 2^32
+  static_assert(12 * (RD_CS_MAXELEMS / RD_CS_HOURS / RD_CS_ACC_MAXBLOCKS + RD_CS_THREADS * 4) < (1L << 32), "32-bit LDS counters");
+  const bool vec = !((unsigned long long)hourly & 15) && plane % 4 == 0 && day_stride % 4 == 0;
+  const long items = n * (vec ? plane / 4 : plane);
+  const unsigned blocks = (unsigned)std::min<long>((items + RD_CS_THREADS - 1) / RD_CS_THREADS, RD_CS_ACC_MAXBLOCKS);
+  const size_t lds = (size_t)rd_cs_state_size(n_edges) * sizeof(unsigned);
+  if (vec)
+    hipLaunchKernelGGL(k_cascade_accumulate<4>, dim3(blocks), dim3(RD_CS_THREADS), lds, (hipStream_t)stream, hourly, n, day_stride, plane, e,
+                       (unsigned long long*)state_inout);
+  else
+    hipLaunchKernelGGL(k_cascade_accumulate<1>, dim3(blocks), dim3(RD_CS_THREADS), lds, (hipStream_t)stream, hourly, n, day_stride, plane, e,
+                       (unsigned long long*)state_inout);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_cascade_generate(const unsigned* model, const int* edge_units, int n_edges, const float* cond, long n_queries,
+                                      long first_query, long ny, long nx, int n_members, long first_member, unsigned long long seed,
+                                      int patch, float* out, int* units_out, void* stream) {
+  rd_cs_edges e;
+  if (!model || !cond || !out || !rd_aligned(3, model, edge_units, cond, out, units_out)) return -2;
+  if (!rd_cs_shape_ok(ny, nx) || !rd_cs_edges_ok(edge_units, n_edges, &e)) return -2;
+  if (n_queries < 1 || n_queries > RD_CS_MAXQ || n_members < 1 || n_members > RD_CS_MAXS || patch < 1 || patch > RD_CS_MAXPLANE) return -2;
+  if (first_query < 0 || first_query > (1L << 32) - n_queries || first_member < 0 || first_member > (1L << 62)) return -2;
+  const long plane = ny * nx;
+  if (n_queries * n_members > RD_CS_MAXELEMS / (RD_CS_HOURS * plane)) return -2;
+  const bool vec = nx % 4 == 0 && rd_aligned(15, out, units_out);
+  const long items = n_queries * n_members * (vec ? plane / 4 : plane);
+  const unsigned blocks = (unsigned)std::min<long>((items + RD_CS_THREADS - 1) / RD_CS_THREADS, RD_CS_GEN_MAXBLOCKS);
+  const size_t lds = (size_t)RD_CS_PER_CLASS * (n_edges + 1) * sizeof(unsigned);
+  const int nbx = (int)((nx + patch - 1) / patch);
+  if (vec)
+    hipLaunchKernelGGL(k_cascade_generate<4>, dim3(blocks), dim3(RD_CS_THREADS), lds, (hipStream_t)stream, model, e, cond, n_queries, first_query,
+                       (int)nx, plane, (long)n_members, first_member, seed, patch, nbx, out, units_out);
+  else
+    hipLaunchKernelGGL(k_cascade_generate<1>, dim3(blocks), dim3(RD_CS_THREADS), lds, (hipStream_t)stream, model, e, cond, n_queries, first_query,
+                       (int)nx, plane, (long)n_members, first_member, seed, patch, nbx, out, units_out);
+  return (int)hipGetLastError();
+}

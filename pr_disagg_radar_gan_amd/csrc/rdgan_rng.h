@@ -11,6 +11,7 @@
 #define RD_STREAM_BOOTSTRAP 7u      // resample indices of the bootstrapped means (rdgan_crps.hip.h)
 #define RD_STREAM_VERIFY 8u         // tie-breaking ranks of the verification (rdgan_verify.hip.h)
 #define RD_STREAM_ANALOG 9u         // picks among the nearest library days (rdgan_analog.hip.h)
+#define RD_STREAM_CASCADE 10u       // types, weight bins and weights of the random cascade (rdgan_cascade.hip.h)
 #define RD_DROP_THRESHOLD 64u         // 0.25 * 2^8: a byte of the hash word decides one element
 
 #if defined(__HIPCC__)

@@ -19,6 +19,7 @@ from . import _lib, crps_experiment, ensemble, rainfarm
 from . import weights as W
 from ._dev import device_f32, ptr as _p, stream as _stream, whole_number, workspace_bytes
 from .analog import AnalogLibrary
+from .cascade import MAX_PLANE as CASCADE_MAX_PLANE, CascadeModel
 from .engine import require_gpu
 
 NHOURS = 24
@@ -259,13 +260,16 @@ def gan_ensemble(gen, real, n_members, seed=None, norm_scale=W.NORM_SCALE):
 
 
 def multivariate_experiment(gen, reals_precip, climatology, slopes=None, library=None, n_members=1000, seed=0, fair=False, p=0.5,
-                            radius=2, max_lag=1, weights=None, normalised=False, k=10, analog_weights="rank", query_groups=None):
+                            radius=2, max_lag=1, weights=None, normalised=False, k=10, analog_weights="rank", query_groups=None, cascade=None,
+                            cascade_patch=1):
     """Energy and variogram score per real day for the competing methods.  reals_precip (D, 24, nd, nd) mm/h; climatology
     (n, 24, nd, nd), e.g. crps_experiment.climatology_sample(dataset), scored in the shared form.  Seed rules, those of the CRPS
     experiment: the GAN's day d uses the device generator seeded seed + d (crps_experiment.crps_for_days); RainFARM, with slopes =
     (alpha, beta), draws the members d n_members .. (d + 1) n_members - 1 of the counter RNG (rainfarm_crps_for_days); the analog
     baseline, with library = an AnalogLibrary, is library.generate(daily sum of day d, n_members, k, seed, analog_weights,
-    first_query=d), query_groups (D,) leaving the library's days of the same group out.  -> MultivariateExperimentResult."""
+    first_query=d), query_groups (D,) leaving the library's days of the same group out; the random cascade, with cascade = a
+    cascade.CascadeModel, is cascade.generate(daily sum of day d, n_members, seed, first_query=d, patch=cascade_patch) and adds
+    es["cascade"] and vs["cascade"].  -> MultivariateExperimentResult."""
     shape = _check_reals(reals_precip, "reals_precip")
     cs = _check_reals(climatology, "climatology")
     if shape[2] != shape[3] or cs[1:] != shape[1:] or cs[0] > MAX_MEMBERS:
@@ -278,6 +282,9 @@ def multivariate_experiment(gen, reals_precip, climatology, slopes=None, library
         raise ValueError(f"library: expected an AnalogLibrary of planes {shape[2:]}")
     if query_groups is not None and (library is None or len(query_groups) != shape[0]):
         raise ValueError(f"query_groups: {shape[0]} groups and a library expected")
+    if cascade is not None and not isinstance(cascade, CascadeModel):
+        raise ValueError("cascade: expected a cascade.CascadeModel")
+    cascade_patch = whole_number(cascade_patch, 1, CASCADE_MAX_PLANE, "cascade_patch")
     m = whole_number(n_members, 1, MAX_MEMBERS, "n_members")
     seed = whole_number(seed, 0, (1 << 62), "seed")
     score = dict(fair=fair, p=check_order(p), radius=check_radius(radius), max_lag=check_max_lag(max_lag),
@@ -302,4 +309,7 @@ def multivariate_experiment(gen, reals_precip, climatology, slopes=None, library
         res.es["analog"], res.vs["analog"] = scores_for_days(
             lambda d: library.generate(reals[d:d + 1].sum(1), m, k=k, seed=seed, weights=analog_weights, first_query=d,
                                        query_groups=None if groups is None else groups[d:d + 1])[0], reals, **score)
+    if cascade is not None:
+        res.es["cascade"], res.vs["cascade"] = scores_for_days(
+            lambda d: cascade.generate(reals[d:d + 1].sum(1), m, seed=seed, first_query=d, patch=cascade_patch)[0], reals, **score)
     return res
