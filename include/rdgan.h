@@ -673,6 +673,49 @@ int rdgan_areal_accumulate(const float* x, long n, long day_stride, long ny, lon
                            const int* widths, int n_widths, const double* levels, int n_levels, long long* counts_inout,
                            long long* depths_out, void* workspace, long workspace_bytes, void* stream);
 
+/* Catchment rainfall of hourly fields: the areal rainfall of every basin of a map, hour by hour, its largest
+ * k-hour accumulation per day, and statistics of those maxima over the days.
+ * hourly, n, day_stride, ny, nx and the size limits: as x for rdgan_areal_accumulate above (ny nx <= 2^24); q(x) and the bad
+ * pixel-hours are the ones defined there.  windows and levels: as there (K <= 8, L <= 16, on the HOST).
+ * The map: n_catch = C catchments, 1 <= C <= 65535.  pixels [n_entries] ints (device): the flat indices y nx + x of the pixels of
+ * catchment 0, then of catchment 1, ...; a pixel may stand in several catchments or in none; C <= n_entries = E <= 2^26.
+ * npix [C] ints (device): the number of pixels of each catchment, >= 1.  chunks [n_chunks][3] ints (device): (catchment, first
+ * entry, count), a run of 1 <= count <= 256 consecutive entries of ONE catchment; together the chunks cover every entry once;
+ * C <= n_chunks <= min(E, 2^19).  The kernels read the lists through the chunk table only, and nobody checks it on the device: the
+ * caller guarantees that no chunk crosses a catchment and that every entry lies in 0 .. ny nx - 1 (a chunk that would leave the
+ * lists or the state is skipped, an entry outside the plane adds nothing).
+ * For day u, catchment c and hour h, P[u][c][h] is the sum of q over the catchment's pixels (a bad pixel-hour adds 0) and
+ * B[u][c][h] the number of its bad pixel-hours; a catchment-hour with B > 0 is void.  For window k, A[u][c][k] is the largest
+ * P[h0] + .. + P[h0 + k - 1] over the start hours h0 <= 24 - k whose k hours are all clean, h* the smallest h0 that attains it;
+ * A < 2^50.  With no clean window the day is void for (c, k); with A == 0 it is dry.
+ * counts_inout [C * K * (L + 30) + 2] 64-bit integers (device); the record of (c, k) lies at (c K + k) (L + 30) +
+ *     0       level_count[b], b = 0 .. L: counted days by b = #{l : A >= L_q[l] npix[c]} (levels are catchment-MEAN depths)
+ *     L + 1   start_hour[h], h = 0 .. 23: days with A > 0 by h*
+ *     L + 25  sum_A: the sum of A over the counted days
+ *     L + 26  max_A: the largest A seen (a running maximum, not a sum)
+ *     L + 27  n_days: days counted (not void)
+ *     L + 28  n_void: days with no clean window; they enter nothing else
+ *     L + 29  n_dry: counted days with A == 0; they enter level_count, n_days and n_dry only
+ * then n_days_total at C K (L + 30) and n_bad, the sum of B (a bad pixel-hour counts once per catchment that lists the pixel),
+ * behind it, once per state; the state-count entry returns C K (L + 30) + 2, or -2 for C, K or L out of range.  The array
+ * ACCUMULATES over any number of calls; the caller zeroes it before the first.  Everything is an integer merged with integer
+ * atomics, so the state does not depend on how the days are split into calls, on the workspace size or on the launch geometry.
+ * series_out: null, or [n][C][24] 64-bit integers (device, dense): P, -1 at a void catchment-hour.  depths_out: null, or [n][C][K]:
+ * A, -1 for a void day.  Both written, not added to.
+ * workspace: device memory, 8-byte aligned; the entry zeroes what a pass uses.  The workspace-bytes entry gives the size that lets a
+ * pass take days_per_pass whole days (1 .. 65535; 288 bytes per catchment and day; -2 for an argument out of range); the accumulate
+ * entry takes as many whole days per pass as the workspace holds, at most (2^24 - 1) / n_chunks, loops over the passes, and the
+ * result does not depend on it.
+ * Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, n, ny, nx or n_catch < 1, a size above
+ * the limits, a list that is empty, unsorted or out of range, day_stride < 24 ny nx, a workspace too small for one day) with
+ * nothing launched and no output touched.  All offsets are 64-bit. */
+long rdgan_catchment_state_count(int n_catch, int n_windows, int n_levels);
+long rdgan_catchment_workspace_bytes(int n_catch, long days_per_pass);
+int rdgan_catchment_accumulate(const float* hourly, long n, long day_stride, long ny, long nx, const int* chunks, long n_chunks,
+                               const int* pixels, long n_entries, const int* npix, int n_catch, const int* windows, int n_windows,
+                               const double* levels, int n_levels, long long* counts_inout, long long* series_out,
+                               long long* depths_out, void* workspace, long workspace_bytes, void* stream);
+
 /* Space-time structure of hourly fields: does the rain move?  The wet/dry agreement between hour h at
  * pixel p and hour h + k at pixel p + d for every small displacement d, and for every pair of hours the displacement that best
  * maps one wet mask onto the other (the cross-correlation tracking radar nowcasting calls TREC).

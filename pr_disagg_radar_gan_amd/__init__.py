@@ -13,6 +13,7 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
   * ``spacetime`` -- displaced wet/dry agreement of hour pairs and the shift that best maps one hour's wet mask onto the next
   * ``storms`` -- wet volumes connected through the day's hours: how long a rain system lives, when it starts, what it carries
   * ``areal`` -- depth-area-duration: the largest k-hour accumulation over any w x w box per day, and the areal reduction factor
+  * ``catchments`` -- catchment rainfall: the hyetograph of every basin of a map and its largest k-hour accumulation per day
   * ``analog`` -- the analog baseline (method of fragments): the k nearest library days of a daily condition, their scaled fractions
   * ``multivariate`` -- energy and variogram score of ensembles of whole hourly days; the four-method experiment
   * ``cascade`` -- the random-cascade baseline: splits of wet boxes calibrated on hourly data, applied to daily sums 24 h -> 1 h

@@ -44,6 +44,7 @@
 #include "rdgan_cells.hip.h"
 #include "rdgan_storms.hip.h"
 #include "rdgan_areal.hip.h"
+#include "rdgan_catchment.hip.h"
 #include "rdgan_spacetime.hip.h"
 #include "rdgan_analog.hip.h"
 #include "rdgan_mvscore.hip.h"

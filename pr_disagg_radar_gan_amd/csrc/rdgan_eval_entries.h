@@ -1,6 +1,6 @@
 // The handle-free entry points of include/rdgan.h: input pipeline, CRPS experiment, distribution checks, whole fields, ensemble
-// products, verification, the five evaluations of hourly arrays (temporal structure, rain cells, storms, areal extremes, space-time
-// structure), analogs, spectra and RainFARM.  They take no rdgan_handle and use nothing of the step engine but RD_TRY,
+// products, verification, the evaluations of hourly arrays (temporal structure, rain cells, storms, areal extremes, catchment
+// rainfall, space-time structure), analogs, spectra and RainFARM.  They take no rdgan_handle and use nothing of the step engine but RD_TRY,
 // ensure_lds(nullptr, ...) and ew_blocks.  Host code, included by rdgan_api.hip at one point, behind the op-level test entries (the
 // library stays one translation unit: one code object for the ISA lint).
 //
@@ -769,6 +769,66 @@ extern "C" int rdgan_areal_accumulate(const float* x, long n, long day_stride, l
                        tiles_x, lists, wmax, (const int*)S, (const unsigned char*)B, keys);
     hipLaunchKernelGGL(k_areal_days, dim3((D + RD_AR_THREADS - 1) / RD_AR_THREADS, (unsigned)(lists.K * lists.W)), dim3(RD_AR_THREADS), 0, st,
                        (int)D, d0, lists, (const unsigned long long*)keys, counts, depths_out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// catchment rainfall of hourly fields (rdgan_catchment.hip.h): hyetographs and k-hour maxima per basin of a map, per day
+// ------------------------------------------------------------------------------------
+static bool rd_ct_make_lists(const int* windows, int K, const double* levels, int L, rd_ct_lists* out) {
+  if (!rd_ar_increasing(windows, K, RD_CT_MAXK, 1, RD_CT_HOURS) || L < 0 || L > RD_CT_MAXL || (L > 0 && !levels)) return false;
+  rd_ct_lists a = {};
+  a.K = K, a.L = L;
+  for (int i = 0; i < K; ++i) a.windows[i] = windows[i];
+  for (int i = 0; i < L; ++i) {
+    if (!(levels[i] >= 0.0 && levels[i] <= 2048.0 * RD_CT_HOURS) || (i > 0 && !(levels[i] > levels[i - 1]))) return false;
+    a.level_q[i] = llrint(levels[i] * 1024.0);
+  }
+  *out = a;
+  return true;
+}
+
+extern "C" long rdgan_catchment_state_count(int n_catch, int n_windows, int n_levels) {
+  if (n_catch < 1 || n_catch > RD_CT_MAXCATCH || n_windows < 1 || n_windows > RD_CT_MAXK || n_levels < 0 || n_levels > RD_CT_MAXL) return -2;
+  return rd_ct_state_count(n_catch, n_windows, n_levels);
+}
+
+extern "C" long rdgan_catchment_workspace_bytes(int n_catch, long days_per_pass) {
+  if (n_catch < 1 || n_catch > RD_CT_MAXCATCH || days_per_pass < 1 || days_per_pass > RD_CT_MAXPASS) return -2;
+  return days_per_pass * rd_ct_day_bytes(n_catch);
+}
+
+extern "C" int rdgan_catchment_accumulate(const float* hourly, long n, long day_stride, long ny, long nx, const int* chunks, long n_chunks,
+                                          const int* pixels, long n_entries, const int* npix, int n_catch, const int* windows,
+                                          int n_windows, const double* levels, int n_levels, long long* counts_inout,
+                                          long long* series_out, long long* depths_out, void* workspace, long workspace_bytes,
+                                          void* stream) {
+  rd_ct_lists lists;
+  if (!hourly || !chunks || !pixels || !npix || !counts_inout || !workspace) return -2;
+  if (!rd_aligned(3, chunks, pixels, npix) || !rd_aligned(7, counts_inout, series_out, depths_out, workspace)) return -2;
+  if (!rd_ar_shape_ok(ny, nx) || n_catch < 1 || n_catch > RD_CT_MAXCATCH) return -2;
+  if (n_entries < n_catch || n_entries > RD_CT_MAXENTRIES || n_chunks < n_catch || n_chunks > n_entries || n_chunks > RD_CT_MAXCHUNKS) return -2;
+  const long plane = ny * nx;
+  static_assert(RD_CT_MAXELEMS == RD_HOURLY_MAXELEMS && RD_CT_MAXPLANE == RD_AR_MAXPLANE, "rd_hourly_layout_ok bounds the array");
+  if (!rd_hourly_layout_ok(hourly, n, day_stride, RD_CT_HOURS * plane)) return -2;
+  if (!rd_ct_make_lists(windows, n_windows, levels, n_levels, &lists)) return -2;
+  // the days of a pass: as many whole days as the workspace holds and one launch has workgroups for
+  const long per_pass = rd_pass_units(workspace_bytes, rd_ct_day_bytes(n_catch), n, std::min<long>(RD_CT_MAXPASS, RD_CT_MAXGROUPS / n_chunks));
+  if (per_pass < 1) return -2;
+  unsigned long long* P = (unsigned long long*)workspace;
+  unsigned* B = (unsigned*)(P + per_pass * n_catch * RD_CT_HOURS);
+  hipStream_t st = (hipStream_t)stream;
+  for (long d0 = 0; d0 < n; d0 += per_pass) {
+    const long D = std::min<long>(per_pass, n - d0);
+    RD_TRY((int)hipMemsetAsync(workspace, 0, (size_t)(per_pass * rd_ct_day_bytes(n_catch)), st));     // P and B of the pass
+    hipLaunchKernelGGL(k_catch_sums, dim3((unsigned)n_chunks, (unsigned)D), dim3(RD_CT_THREADS), 0, st, hourly, day_stride, plane, d0, chunks,
+                       pixels, n_entries, n_catch, P, B);
+    hipLaunchKernelGGL(k_catch_days, dim3((unsigned)((D * n_catch + RD_CT_THREADS - 1) / RD_CT_THREADS)), dim3(RD_CT_THREADS), 0, st, (int)D, d0,
+                       n_catch, lists, npix, (const unsigned long long*)P, (const unsigned*)B, (unsigned long long*)counts_inout, series_out,
+                       depths_out);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
   }

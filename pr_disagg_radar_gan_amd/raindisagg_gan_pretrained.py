@@ -163,6 +163,23 @@ def areal_extremes_field(daily, n_scenarios, windows=(1, 3, 6, 12, 24), widths=(
                                       scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
 
+def catchment_rainfall_field(daily, n_scenarios, cmap, windows=(1, 3, 6, 12, 24), levels=None, return_series=False, overlap=4,
+                             latent_mode="shared", scenario_chunk=16):
+    """The catchment rainfall of n_scenarios scenarios of a whole daily map (catchments.catchment_rainfall_field on the module's
+    ``gen`` and ``norm_scale``): for every scenario and every basin of the catchments.CatchmentMap ``cmap`` the largest areal
+    rainfall over any k consecutive hours and the hour it starts -- what a rainfall-runoff model of the basin is driven by.  daily
+    as generate_scenarios_field takes it; windows: the durations in hours; levels: catchment-mean depths in mm whose exceedance is
+    counted (None: catchments.DEFAULT_LEVELS).  Returns a catchments.CatchmentStats (numpy), with return_series followed by the
+    hyetographs (n_scenarios, [D,] C, 24) int64 on the device (catchments.series_mm: in mm/h); catchments.compare sets the
+    statistics against those of observed days.  The latent noise comes from the global numpy RNG as in generate_scenarios_field;
+    the hourly scenarios are produced scenario_chunk at a time and never held together."""
+    from . import catchments
+    daily = _daily_map(daily)
+    return catchments.catchment_rainfall_field(gen, daily, n_scenarios, cmap, windows, catchments.DEFAULT_LEVELS if levels is None else levels,
+                                               return_series=return_series, scenario_chunk=scenario_chunk, overlap=overlap,
+                                               latent_mode=latent_mode, norm_scale=norm_scale)
+
+
 def spacetime_structure_field(daily, n_scenarios, thresholds, radius=4, max_lag=1, overlap=4, latent_mode="shared", scenario_chunk=16):
     """The space-time structure of n_scenarios scenarios of a whole daily map (spacetime.spacetime_structure_field on the module's
     ``gen`` and ``norm_scale``): the wet/dry agreement of hour h at pixel p with hour h + k at pixel p + d, and the displacement
