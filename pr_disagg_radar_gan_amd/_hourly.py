@@ -9,7 +9,11 @@ from . import field as F
 from ._dev import ptr as _p, stream as _stream, workspace_bytes
 from .engine import require_gpu
 
-NHOURS = 24
+NHOURS = 24                                                                  # RD_HOURS
+UNIT = 1024                                                                  # RD_DEPTH_UNIT: depths are integers in 1 / UNIT mm
+MAX_DEPTH = 2048                                                             # RD_DEPTH_MAX: mm an hour, from which a value is bad
+MAX_PLANE = 1 << 24                                                          # RD_HOURLY_MAXPLANE: pixels of a plane
+MAX_ELEMS = 1 << 40                                                          # RD_HOURLY_MAXELEMS: values of one call's array
 MAX_MEMBERS = 4096                                                           # RD_MS_MAXS, RD_VF_MAXS
 
 

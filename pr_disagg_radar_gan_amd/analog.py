@@ -21,11 +21,10 @@ import torch
 
 from . import _lib
 from ._dev import device_f32, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import NHOURS, admit, to_state_device
+from ._hourly import NHOURS, UNIT, admit, to_state_device
 from .engine import require_gpu
 from .ensemble import crps_ensemble_device
 
-UNIT = 1024                                                                  # depths are integers in 1 / UNIT mm
 MAX_PLANE = 4096                                                             # RD_AN_MAXP
 MAX_LIBRARY = (1 << 24) - 1                                                  # RD_AN_MAXN
 MAX_QUERIES = 1 << 18                                                        # RD_AN_MAXQ

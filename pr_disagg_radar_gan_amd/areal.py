@@ -20,18 +20,16 @@ import torch
 
 from . import weights as W
 from ._dev import host_ptr as _hp, ptr as _p, whole_number
-from ._hourly import NHOURS, HourlyAccumulator, admit, check_out_tensor, div as _div, evaluate_field, tv as _tv
+from ._hourly import MAX_DEPTH, MAX_PLANE, NHOURS, UNIT, HourlyAccumulator, admit, check_out_tensor, div as _div, evaluate_field, tv as _tv
 from .engine import require_gpu
 
-UNIT = 1024                                                                  # depths are integers in 1 / UNIT mm
 MAX_WINDOWS = 8                                                              # RD_AR_MAXK
 MAX_WIDTHS = 8                                                               # RD_AR_MAXW
 MAX_WIDTH = 64                                                               # RD_AR_MAXWIDTH
 MAX_LEVELS = 16                                                              # RD_AR_MAXL
-MAX_LEVEL = 2048.0 * NHOURS                                                  # mm: what a window can hold
+MAX_LEVEL = float(MAX_DEPTH * NHOURS)                                        # mm: what a window can hold
 N_ARF = 21                                                                   # RD_AR_NARF: arf_hist[0 .. 20]
 N_FIXED = 52                                                                 # RD_AR_FIXED: words of a record besides level_count
-MAX_PLANE = 1 << 24                                                          # RD_AR_MAXPLANE
 MAX_PASS = 65535                                                             # RD_AR_MAXPASS: days of a pass
 # offsets behind level_count[L + 1] in the record of one (k, w) (RD_AR_START ..)
 _START, _ARF, _SUM_A, _SUM_A1, _SUM_ALL, _MAX_A, _NDAYS, _NVOID, _NDRY = 0, 24, 45, 46, 47, 48, 49, 50, 51

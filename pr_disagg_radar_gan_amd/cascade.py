@@ -17,11 +17,10 @@ import torch
 from . import _lib
 from ._dev import device_f32, host_ptr, ptr as _p, stream as _stream, whole_number
 from .analog import _gather_tiles
-from ._hourly import NHOURS, HourlyAccumulator, admit, to_state_device
+from ._hourly import MAX_ELEMS, MAX_PLANE, NHOURS, UNIT, HourlyAccumulator, admit, to_state_device
 from .engine import require_gpu
 from .ensemble import crps_ensemble_device
 
-UNIT = 1024                                                                  # depths are integers in 1 / UNIT mm
 NB = 32                                                                      # RD_CS_NB: weight bins
 NP = 4                                                                       # RD_CS_NP: position classes
 NL = 3                                                                       # RD_CS_NL: binary levels, boxes of 8, 4 and 2 hours
@@ -30,8 +29,6 @@ MAX_EDGES = 7                                                                # R
 PER_CLASS = 748                                                              # RD_CS_PER_CLASS: counters per volume class
 TAIL = 3                                                                     # RD_CS_TAIL: n_days, n_bad, n_dry
 MAX_EDGE = 1 << 21                                                           # RD_CS_MAXEDGE
-MAX_PLANE = 1 << 24                                                          # RD_CS_MAXPLANE
-MAX_ELEMS = 1 << 40                                                          # RD_CS_MAXELEMS
 MAX_QUERIES = 1 << 18                                                        # RD_CS_MAXQ
 MAX_MEMBERS = 65535                                                          # RD_CS_MAXS
 MAX_COND = 16384                                                             # RD_CS_MAXCOND
@@ -63,7 +60,7 @@ def check_edges(edges):
     for e in edges:
         if isinstance(e, bool) or not isinstance(e, (int, float, np.integer, np.floating)) or not np.isfinite(e):
             raise ValueError(f"edges: expected finite numbers, got {e!r}")
-        u = int(np.rint(np.float64(e) * 1024.0))
+        u = int(np.rint(np.float64(e) * UNIT))
         if not 1 <= u <= MAX_EDGE or (units and u <= units[-1]):
             raise ValueError(f"edges: expected strictly increasing values in 1/1024 .. 2048 mm/h, got {edges!r}")
         units.append(u)

@@ -24,13 +24,12 @@ import torch
 
 from . import field as F, weights as W
 from ._dev import host_ptr as _hp, ptr as _p
-from ._hourly import NHOURS, HourlyAccumulator, admit, check_out_tensor, div as _div, tv as _tv
-from .areal import UNIT, check_levels, check_windows, check_workspace_days
+from ._hourly import MAX_PLANE, NHOURS, UNIT, HourlyAccumulator, admit, check_out_tensor, div as _div, tv as _tv
+from .areal import check_levels, check_windows, check_workspace_days
 from .engine import require_gpu
 
 CHUNK = 256                                                                  # RD_CT_CHUNK: list entries of a chunk
 MAX_CATCHMENTS = 65535                                                       # RD_CT_MAXCATCH
-MAX_PLANE = 1 << 24                                                          # RD_CT_MAXPLANE
 MAX_ENTRIES = 1 << 26                                                        # RD_CT_MAXENTRIES
 MAX_PASS = 65535                                                             # RD_CT_MAXPASS: days of a pass
 MAX_GROUPS = (1 << 24) - 1                                                   # RD_CT_MAXGROUPS: workgroups of a launch

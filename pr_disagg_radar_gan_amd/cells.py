@@ -17,14 +17,13 @@ import torch
 
 from . import weights as W
 from ._dev import host_ptr as _hp, ptr as _p, whole_number
-from ._hourly import NHOURS, HourlyAccumulator, admit, check_out_tensor, div as _div, evaluate_field, tv as _tv
+from ._hourly import MAX_PLANE, NHOURS, HourlyAccumulator, admit, check_out_tensor, div as _div, evaluate_field, tv as _tv
 from .engine import require_gpu
 from .verification import check_event_thresholds
 
 N_COUNTS = 317                                                               # RD_CL_NC: counters per threshold
 N_BINS = 25                                                                  # RD_CL_NBINS: floor(log2(area)) = 0 .. 24
 N_KPP = 65                                                                   # RD_CL_NKP: cells_per_plane[0 .. 64], the last bin open
-MAX_PLANE = 1 << 24                                                          # RD_CL_MAXPLANE
 MAX_PASS = 65535                                                             # RD_CL_MAXPASS
 VOLUME_UNIT = 2.0 ** -16                                                     # a volume counts 2^-16 of the data's unit
 # offsets of a threshold's counters (RD_CL_WET ..)

@@ -31,8 +31,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rdgan_rng.h"
+#include "rdgan_hourly.hip.h"
 
-#define RD_AN_HOURS 24
 #define RD_AN_MAXP 4096                  // pixels of a plane
 #define RD_AN_MAXN ((1L << 24) - 1)      // library days: the index takes the low 24 bits of a key
 #define RD_AN_MAXQ (1L << 18)            // queries of a call
@@ -56,8 +56,6 @@ __host__ __device__ inline long rd_an_blocks(long n) { return (n + RD_AN_BLOCK -
 __host__ __device__ inline int rd_an_query_tile(long plane) { return rd_an_ppad(plane) <= RD_AN_QT_SPLIT ? RD_AN_QT_SMALL : RD_AN_QT_LARGE; }
 __host__ __device__ inline size_t rd_an_lds_bytes(long plane) { return (size_t)rd_an_query_tile(plane) * rd_an_ppad(plane) * 4; }
 __host__ __device__ inline long rd_an_list_bytes(long n_queries, int k) { return n_queries * RD_AN_WAVES * k * 8; }   // per slice
-
-__device__ __forceinline__ bool rd_an_bad(float v) { return !(v >= 0.0f && v < 2048.0f); }
 
 // floor(sqrt(D)) for D < 2^27: the float estimate is off by one at most, the squares decide
 __device__ __forceinline__ unsigned rd_an_isqrt(unsigned D) {
@@ -84,7 +82,7 @@ k_analog_features(const float* __restrict__ x, long n, long day_stride, int plan
 #pragma unroll
     for (int i = 0; i < 8; ++i) sum[i] = 0u;
 #pragma unroll 4
-    for (int h = 0; h < RD_AN_HOURS; ++h) {
+    for (int h = 0; h < RD_HOURS; ++h) {
       float v[8];
       if constexpr (VEC) {
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
@@ -97,8 +95,8 @@ k_analog_features(const float* __restrict__ x, long n, long day_stride, int plan
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const bool b = rd_an_bad(v[i]);
-        sum[i] += b ? 0u : (unsigned)(int)rintf(v[i] * 1024.0f);
+        const bool b = rd_depth_bad(v[i]);
+        sum[i] += b ? 0u : (unsigned)rd_depth_q(v[i]);
         bad |= b;
       }
     }
@@ -140,7 +138,7 @@ k_analog_query(const float* __restrict__ x, long n, int plane, int ppad, unsigne
   unsigned e = 0u, m = 0u;
   if (p < plane) {
     const float v = x[i * plane + p];
-    if (v >= 0.0f && v < 2048.0f * RD_AN_HOURS) e = rd_an_isqrt((unsigned)(int)rintf(v * 1024.0f)), m = 0xFFFFu;
+    if (v >= 0.0f && v < (float)RD_DEPTH_MAX * RD_HOURS) e = rd_an_isqrt((unsigned)rd_depth_q(v)), m = 0xFFFFu;
   }
   feat[item] = (unsigned short)e;
   mask[item] = (unsigned short)m;
@@ -279,8 +277,8 @@ k_analog_apply(const float* __restrict__ lib, long n, long day_stride, int plane
                const int* __restrict__ neighbours, const int* __restrict__ found, int k, long first_member, unsigned long long seed,
                int weights, float* __restrict__ out, int* __restrict__ picks) {
   extern __shared__ __attribute__((aligned(16))) float rd_an_day[];           // the donor's pixel sums
-  __shared__ double part[RD_AN_APPLY_THREADS / 64][RD_AN_HOURS];
-  __shared__ float profile[RD_AN_HOURS];
+  __shared__ double part[RD_AN_APPLY_THREADS / 64][RD_HOURS];
+  __shared__ float profile[RD_HOURS];
   const int tid = threadIdx.x;
   const long i = blockIdx.x, m = blockIdx.y, S = gridDim.y;
   const int f = min(max(found[i], 0), k);
@@ -291,21 +289,21 @@ k_analog_apply(const float* __restrict__ lib, long n, long day_stride, int plane
     if (j < 0 || j >= n) j = -1;                                           // (a list that is not the search's: nothing is read)
   }
   if (tid == 0) picks[i * S + m] = (int)j;
-  float* o = out + (i * S + m) * RD_AN_HOURS * plane;
+  float* o = out + (i * S + m) * RD_HOURS * plane;
   const float* c = cond + i * plane;
   const float nan = __builtin_nanf("");
   if (j < 0) {                                                             // (uniform)
-    for (long e = tid; e < (long)RD_AN_HOURS * plane; e += RD_AN_APPLY_THREADS) o[e] = nan;
+    for (long e = tid; e < (long)RD_HOURS * plane; e += RD_AN_APPLY_THREADS) o[e] = nan;
     return;
   }
   const float* d = lib + j * day_stride;
-  double hsum[RD_AN_HOURS];
+  double hsum[RD_HOURS];
 #pragma unroll
-  for (int h = 0; h < RD_AN_HOURS; ++h) hsum[h] = 0.0;
+  for (int h = 0; h < RD_HOURS; ++h) hsum[h] = 0.0;
   for (int p = tid; p < plane; p += RD_AN_APPLY_THREADS) {
     float s = 0.0f;
 #pragma unroll
-    for (int h = 0; h < RD_AN_HOURS; ++h) {
+    for (int h = 0; h < RD_HOURS; ++h) {
       const float v = d[(long)h * plane + p];
       s += v;
       hsum[h] += (double)v;
@@ -313,7 +311,7 @@ k_analog_apply(const float* __restrict__ lib, long n, long day_stride, int plane
     rd_an_day[p] = s;
   }
 #pragma unroll
-  for (int h = 0; h < RD_AN_HOURS; ++h) {
+  for (int h = 0; h < RD_HOURS; ++h) {
     double v = hsum[h];
     for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
     if ((tid & 63) == 0) part[tid >> 6][h] = v;
@@ -321,18 +319,18 @@ k_analog_apply(const float* __restrict__ lib, long n, long day_stride, int plane
   __syncthreads();
   if (tid < 64) {
     double v = 0.0;
-    if (tid < RD_AN_HOURS)
+    if (tid < RD_HOURS)
       for (int w = 0; w < RD_AN_APPLY_THREADS / 64; ++w) v += part[w][tid];
     double all = v;
     for (int s = 32; s > 0; s >>= 1) all += __shfl_xor(all, s);
-    if (tid < RD_AN_HOURS) profile[tid] = (float)(v / all);                // (all > 0: the donor is not void)
+    if (tid < RD_HOURS) profile[tid] = (float)(v / all);                // (all > 0: the donor is not void)
   }
   __syncthreads();
   for (int p = tid; p < plane; p += RD_AN_APPLY_THREADS) {
     const float cv = c[p], dp = rd_an_day[p];
-    const bool masked = !(cv >= 0.0f && cv < 2048.0f * RD_AN_HOURS);
+    const bool masked = !(cv >= 0.0f && cv < (float)RD_DEPTH_MAX * RD_HOURS);
 #pragma unroll 4
-    for (int h = 0; h < RD_AN_HOURS; ++h) {
+    for (int h = 0; h < RD_HOURS; ++h) {
       const float frac = dp > 0.0f ? d[(long)h * plane + p] / dp : profile[h];
       o[(long)h * plane + p] = masked ? nan : cv * frac;
     }

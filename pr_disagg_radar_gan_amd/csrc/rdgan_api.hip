@@ -39,6 +39,7 @@
 #include "rdgan_radar.hip.h"
 #include "rdgan_field.hip.h"
 #include "rdgan_products.hip.h"
+#include "rdgan_hourly.hip.h"        // what the evaluations of hourly arrays below share
 #include "rdgan_verify.hip.h"
 #include "rdgan_temporal.hip.h"
 #include "rdgan_cells.hip.h"

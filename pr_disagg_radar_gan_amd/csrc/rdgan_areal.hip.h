@@ -24,8 +24,8 @@
 // offsets are 64-bit.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "rdgan_hourly.hip.h"
 
-#define RD_AR_HOURS 24
 #define RD_AR_THREADS 256
 #define RD_AR_TILE 64                    // box corners of a tile, each way
 #define RD_AR_MAXK 8                     // windows
@@ -34,8 +34,6 @@
 #define RD_AR_MAXL 16                    // levels
 #define RD_AR_SLOTS 9                    // internal widths: 1, then the caller's other widths
 #define RD_AR_DAY_KEYS (RD_AR_MAXK * RD_AR_SLOTS)
-#define RD_AR_MAXPLANE (1L << 24)
-#define RD_AR_MAXELEMS (1L << 40)
 #define RD_AR_MAXPASS 65535              // days of one pass: the grid's z
 #define RD_AR_NARF 21                    // arf_hist[0 .. 20]
 #define RD_AR_BADBIT 44                  // of an LDS word: bad windows are counted from this bit up
@@ -58,19 +56,17 @@ struct rd_ar_lists {
   int widths[RD_AR_MAXW];
   int slot_width[RD_AR_SLOTS];           // slot 0 is width 1
   int slot_of[RD_AR_MAXW];               // the slot of the caller's width
-  long long level_q[RD_AR_MAXL];         // llrint(level * 1024)
+  long long level_q[RD_AR_MAXL];         // rd_levels_q
 };
 
 __host__ __device__ inline long rd_ar_record(int L) { return L + 1 + RD_AR_FIXED; }
 __host__ __device__ inline long rd_ar_state_count(int K, int W, int L) { return (long)K * W * rd_ar_record(L) + 2; }
 // bytes of the workspace per day: the keys, 24 running sums and 24 running bad counts per pixel, rounded up to 8
-__host__ __device__ inline long rd_ar_day_bytes(long plane) { return RD_AR_DAY_KEYS * 8 + (RD_AR_HOURS * plane * 5 + 7) / 8 * 8; }
+__host__ __device__ inline long rd_ar_day_bytes(long plane) { return RD_AR_DAY_KEYS * 8 + (RD_HOURS * plane * 5 + 7) / 8 * 8; }
 // the summed-area table of a tile: rows and row stride (in 8-byte words, odd: the lanes of the row scan fall on distinct banks)
 __host__ __device__ inline int rd_ar_rows(int wmax) { return RD_AR_TILE + wmax; }
 __host__ __device__ inline int rd_ar_stride(int wmax) { return (RD_AR_TILE + wmax) | 1; }
 __host__ __device__ inline size_t rd_ar_lds_bytes(int wmax) { return (size_t)rd_ar_rows(wmax) * rd_ar_stride(wmax) * 8; }
-
-__device__ __forceinline__ bool rd_ar_bad(float v) { return !(v >= 0.0f && v < 2048.0f); }
 
 // grid (ceil(plane / (V 256)), D).  V = 4 needs x 16-byte aligned and plane and day_stride multiples of 4.
 template <int V>
@@ -83,25 +79,20 @@ k_areal_prefix(const float* __restrict__ x, long day_stride, long plane, long da
   unsigned bad_here = 0;
   if (p < plane) {
     const float* xd = x + (day0 + d) * day_stride + p;
-    int* Sd = S + d * RD_AR_HOURS * plane + p;
-    unsigned char* Bd = B + d * RD_AR_HOURS * plane + p;
+    int* Sd = S + d * RD_HOURS * plane + p;
+    unsigned char* Bd = B + d * RD_HOURS * plane + p;
     int sum[V];
     unsigned bad[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) sum[j] = 0, bad[j] = 0u;
 #pragma unroll 8
-    for (int h = 0; h < RD_AR_HOURS; ++h) {
+    for (int h = 0; h < RD_HOURS; ++h) {
       float v[V];
-      if constexpr (V == 4) {
-        const float4 f = *reinterpret_cast<const float4*>(xd + h * plane);
-        v[0] = f.x, v[1] = f.y, v[2] = f.z, v[3] = f.w;
-      } else {
-        v[0] = xd[h * plane];
-      }
+      rd_load<V>(xd + h * plane, v);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
-        const bool b = rd_ar_bad(v[j]);
-        sum[j] += b ? 0 : (int)rintf(v[j] * 1024.0f);
+        const bool b = rd_depth_bad(v[j]);
+        sum[j] += b ? 0 : rd_depth_q(v[j]);
         bad[j] += b ? 1u : 0u;
       }
       if constexpr (V == 4) {
@@ -130,8 +121,8 @@ k_areal_boxes(int ny, int nx, int tiles_x, rd_ar_lists lists, int wmax, const in
   const int ty0 = (int)(blockIdx.x / tiles_x) * RD_AR_TILE, tx0 = (int)(blockIdx.x % tiles_x) * RD_AR_TILE;
   const int k = lists.windows[blockIdx.y];
   const long plane = (long)ny * nx, d = blockIdx.z;
-  const int* Sd = S + d * RD_AR_HOURS * plane;
-  const unsigned char* Bd = B + d * RD_AR_HOURS * plane;
+  const int* Sd = S + d * RD_HOURS * plane;
+  const unsigned char* Bd = B + d * RD_HOURS * plane;
   // the pixels of the plane the tile's boxes can cover, and the corners of the tile inside the plane
   const int ry = min(RD_AR_TILE + wmax - 1, ny - ty0), rx = min(RD_AR_TILE + wmax - 1, nx - tx0);
   const int cy = min(RD_AR_TILE, ny - ty0), cx = min(RD_AR_TILE, nx - tx0);
@@ -142,7 +133,7 @@ k_areal_boxes(int ny, int nx, int tiles_x, rd_ar_lists lists, int wmax, const in
   unsigned long long best[RD_AR_SLOTS];
 #pragma unroll
   for (int s = 0; s < RD_AR_SLOTS; ++s) best[s] = 0ull;
-  for (int h0 = 0; h0 + k <= RD_AR_HOURS; ++h0) {
+  for (int h0 = 0; h0 + k <= RD_HOURS; ++h0) {
     const int* hi = Sd + (long)(h0 + k - 1) * plane;
     const unsigned char* bhi = Bd + (long)(h0 + k - 1) * plane;
     const long lo = h0 ? -(long)k * plane : 0;                             // S[h0 - 1] from S[h0 + k - 1]; nothing before hour 0

@@ -28,8 +28,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rdgan_rng.h"
+#include "rdgan_hourly.hip.h"
 
-#define RD_CS_HOURS 24
 #define RD_CS_NB 32                      // weight bins
 #define RD_CS_NP 4                       // position classes
 #define RD_CS_NL 3                       // binary levels
@@ -38,15 +38,16 @@
 #define RD_CS_PER_CLASS 748              // counters per volume class
 #define RD_CS_TAIL 3                     // n_days, n_bad, n_dry
 #define RD_CS_MAXEDGE (1 << 21)          // an edge in units per hour: 2048 mm/h
-#define RD_CS_MAXPLANE (1L << 24)        // pixels of a plane: a draw's counter (block * 32 + node) * 4 + draw stays below 2^31
-#define RD_CS_MAXELEMS (1L << 40)        // elements of one call's hourly array, and of one call's output
 #define RD_CS_MAXQ (1L << 18)            // queries of a call
 #define RD_CS_MAXS 65535                 // members of a call
-#define RD_CS_MAXCOND 16384              // a condition at or above it is masked: V = rint(cond * 1024) < 2^24
+#define RD_CS_MAXCOND 16384              // a condition at or above it is masked: V = rd_depth_q(cond) < 2^24
 #define RD_CS_THREADS 256
 #define RD_CS_ACC_MAXBLOCKS 2048         // workgroups of an accumulate call: 2^40 / 24 pixel-days over them is below 2^25 each
 #define RD_CS_GEN_MAXBLOCKS 8192
 #define RD_CS_NODE_DAY2 22               // the draws of a three-wet day's second split
+// RD_HOURLY_MAXPLANE pixels of a plane: a draw's counter (block * 32 + node) * 4 + draw stays below 2^31; RD_HOURLY_MAXELEMS bounds
+// one call's hourly array, and one call's output
+static_assert(RD_HOURLY_MAXPLANE * 32 * 4 <= (1L << 31) && RD_CS_MAXCOND * RD_DEPTH_UNIT <= (1 << 24), "the draw counter and V");
 
 struct rd_cs_edges {
   int n;
@@ -60,8 +61,6 @@ __host__ __device__ inline int rd_cs_off_w2(int NV) { return 428 * NV; }
 __host__ __device__ inline int rd_cs_off_w3a(int NV) { return 684 * NV; }
 __host__ __device__ inline int rd_cs_off_w3b(int NV) { return 716 * NV; }
 __host__ __device__ inline int rd_cs_off_tail(int NV) { return RD_CS_PER_CLASS * NV; }
-
-__device__ __forceinline__ bool rd_cs_bad(float v) { return !(v >= 0.0f && v < 2048.0f); }
 
 __device__ __forceinline__ int rd_cs_vclass(unsigned V, const rd_cs_edges& e, unsigned hours) {
   int c = 0;
@@ -100,7 +99,7 @@ __device__ __forceinline__ void rd_cs_count_level(const unsigned (&box)[NBOX], c
 }
 
 // one wet pixel-day: q the 24 hours, D > 0 their sum
-__device__ __forceinline__ void rd_cs_count_day(const unsigned (&q)[RD_CS_HOURS], unsigned D, const rd_cs_edges& e, int NV, unsigned* cnt) {
+__device__ __forceinline__ void rd_cs_count_day(const unsigned (&q)[RD_HOURS], unsigned D, const rd_cs_edges& e, int NV, unsigned* cnt) {
   unsigned v2[12], v4[6], v8[3];
 #pragma unroll
   for (int i = 0; i < 12; ++i) v2[i] = q[2 * i] + q[2 * i + 1];
@@ -108,7 +107,7 @@ __device__ __forceinline__ void rd_cs_count_day(const unsigned (&q)[RD_CS_HOURS]
   for (int i = 0; i < 6; ++i) v4[i] = v2[2 * i] + v2[2 * i + 1];
 #pragma unroll
   for (int i = 0; i < 3; ++i) v8[i] = v4[2 * i] + v4[2 * i + 1];
-  const int vc = rd_cs_vclass(D, e, RD_CS_HOURS);
+  const int vc = rd_cs_vclass(D, e, RD_HOURS);
   const int pat = (v8[0] > 0u ? 1 : 0) | (v8[1] > 0u ? 2 : 0) | (v8[2] > 0u ? 4 : 0);
   atomicAdd(&cnt[rd_cs_off_pattern(NV) + vc * 8 + pat], 1u);
   if (pat == 7) {
@@ -136,23 +135,18 @@ k_cascade_accumulate(const float* __restrict__ x, long n, long day_stride, long 
   for (long item = (long)blockIdx.x * RD_CS_THREADS + tid; item < items; item += (long)gridDim.x * RD_CS_THREADS) {
     const long j = item / groups;
     const float* xd = x + j * day_stride + (item - j * groups) * VEC;
-    unsigned q[VEC][RD_CS_HOURS], D[VEC];
+    unsigned q[VEC][RD_HOURS], D[VEC];
     bool bad[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) D[k] = 0u, bad[k] = false;
 #pragma unroll
-    for (int h = 0; h < RD_CS_HOURS; ++h) {
+    for (int h = 0; h < RD_HOURS; ++h) {
       float v[VEC];
-      if constexpr (VEC == 4) {
-        const float4 a = *reinterpret_cast<const float4*>(xd + (long)h * plane);
-        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
-      } else {
-        v[0] = xd[(long)h * plane];
-      }
+      rd_load<VEC>(xd + (long)h * plane, v);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        const bool b = rd_cs_bad(v[k]);
-        q[k][h] = b ? 0u : (unsigned)(int)rintf(v[k] * 1024.0f);
+        const bool b = rd_depth_bad(v[k]);
+        q[k][h] = b ? 0u : (unsigned)rd_depth_q(v[k]);
         D[k] += q[k][h];
         bad[k] |= b;
       }
@@ -227,9 +221,9 @@ __device__ __forceinline__ void rd_cs_split_level(const unsigned (&box)[NBOX], u
 
 // one pixel of volume V > 0 -> its 24 hours
 __device__ __forceinline__ void rd_cs_walk(unsigned V, uint32_t key, unsigned block, const rd_cs_edges& e, int NV, const unsigned* tab,
-                                           unsigned (&q)[RD_CS_HOURS]) {
+                                           unsigned (&q)[RD_HOURS]) {
   unsigned v8[3], v4[6], v2[12];
-  const int vc = rd_cs_vclass(V, e, RD_CS_HOURS);
+  const int vc = rd_cs_vclass(V, e, RD_HOURS);
   const unsigned* prow = tab + rd_cs_off_pattern(NV) + vc * 8;
   const unsigned r = rd_cs_draw(key, block, 0, 0);
   int pat = 7;
@@ -276,9 +270,9 @@ k_cascade_generate(const unsigned* __restrict__ model, rd_cs_edges e, const floa
     const long qm = item / groups, i = qm / S, m = qm - i * S;
     const int p0 = (int)(item - qm * groups) * VEC;
     const uint32_t key = rd_member_key(rd_member_key(base, (uint64_t)(first_member + m)), (uint64_t)(first_query + i));
-    unsigned u[RD_CS_HOURS][VEC];                                        // units; ~0 for a masked pixel
+    unsigned u[RD_HOURS][VEC];                                        // units; ~0 for a masked pixel
 #pragma unroll
-    for (int h = 0; h < RD_CS_HOURS; ++h) {
+    for (int h = 0; h < RD_HOURS; ++h) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) u[h][k] = 0u;
     }
@@ -286,29 +280,29 @@ k_cascade_generate(const unsigned* __restrict__ model, rd_cs_edges e, const floa
     for (int k = 0; k < VEC; ++k) {
       const int p = p0 + k, y = p / nx, xx = p - y * nx;
       const float c = cond[i * plane + p];
-      unsigned q[RD_CS_HOURS];
+      unsigned q[RD_HOURS];
       if (!(c >= 0.0f && c < (float)RD_CS_MAXCOND)) {
 #pragma unroll
-        for (int h = 0; h < RD_CS_HOURS; ++h) q[h] = ~0u;
+        for (int h = 0; h < RD_HOURS; ++h) q[h] = ~0u;
       } else {
-        const unsigned V = (unsigned)(int)rintf(c * 1024.0f);
+        const unsigned V = (unsigned)rd_depth_q(c);
 #pragma unroll
-        for (int h = 0; h < RD_CS_HOURS; ++h) q[h] = 0u;
+        for (int h = 0; h < RD_HOURS; ++h) q[h] = 0u;
         if (V > 0u) rd_cs_walk(V, key, (unsigned)((y / patch) * nbx + xx / patch), e, NV, rd_cs_tab, q);
       }
 #pragma unroll
-      for (int h = 0; h < RD_CS_HOURS; ++h) {
+      for (int h = 0; h < RD_HOURS; ++h) {
 #pragma unroll
         for (int kk = 0; kk < VEC; ++kk) u[h][kk] = kk == k ? q[h] : u[h][kk];
       }
     }
     const float nan = __builtin_nanf("");
-    const long o0 = qm * RD_CS_HOURS * plane + p0;
+    const long o0 = qm * RD_HOURS * plane + p0;
 #pragma unroll
-    for (int h = 0; h < RD_CS_HOURS; ++h) {
+    for (int h = 0; h < RD_HOURS; ++h) {
       float f[VEC];
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) f[k] = u[h][k] == ~0u ? nan : (float)u[h][k] * (1.0f / 1024.0f);
+      for (int k = 0; k < VEC; ++k) f[k] = u[h][k] == ~0u ? nan : (float)u[h][k] * (1.0f / (float)RD_DEPTH_UNIT);
       if constexpr (VEC == 4) {
         *reinterpret_cast<float4*>(out + o0 + (long)h * plane) = make_float4(f[0], f[1], f[2], f[3]);
         if (units) *reinterpret_cast<int4*>(units + o0 + (long)h * plane) = make_int4((int)u[h][0], (int)u[h][1], (int)u[h][2], (int)u[h][3]);

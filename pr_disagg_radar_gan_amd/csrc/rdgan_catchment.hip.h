@@ -1,7 +1,7 @@
 // Catchment rainfall of hourly fields: the areal rainfall of every basin of a map, hour by hour, its largest
 // k-hour accumulation per day and statistics of those maxima over the days.
 // hourly [n][24][ny][nx] fp32 with a leading stride day_stride >= 24 ny nx.  q = (int) rintf(x * 1024) in units of 2^-10 mm; a
-// pixel-hour is bad when x is NaN, +-inf, negative or >= 2048, as in rdgan_areal.hip.h (so q < 2^21).  A catchment is a list of
+// pixel-hour is bad when x is NaN, +-inf, negative or >= 2048: rd_depth_q and rd_depth_bad (so q < 2^21).  A catchment is a list of
 // pixels: pixels[E] holds the flat indices y nx + x of all catchments one behind the other, and a pixel may stand in several lists
 // (nested basins) or in none.  The kernels see the lists only through the chunk table chunks[n_chunks][3] = (catchment, first
 // entry, count): a run of 1 .. RD_CT_CHUNK consecutive entries of ONE catchment.
@@ -25,18 +25,16 @@
 // offsets are 64-bit.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "rdgan_hourly.hip.h"
 
-#define RD_CT_HOURS 24
 #define RD_CT_THREADS 256
 #define RD_CT_CHUNK 256                  // list entries of a chunk: one per lane of a workgroup
 #define RD_CT_MAXK 8                     // windows
 #define RD_CT_MAXL 16                    // levels
 #define RD_CT_MAXCATCH 65535
-#define RD_CT_MAXPLANE (1L << 24)
 #define RD_CT_MAXENTRIES (1L << 26)
 #define RD_CT_MAXCHUNKS (1L << 19)       // above MAXENTRIES / CHUNK + MAXCATCH, what a table with no needless cut holds
 #define RD_CT_MAXGROUPS ((1L << 24) - 1) // workgroups of a launch: fewer than 2^32 threads
-#define RD_CT_MAXELEMS (1L << 40)
 #define RD_CT_MAXPASS 65535              // days of one pass: the grid's y
 // the record of one (c, k), L levels: level_count[L + 1], then at L + 1 +
 #define RD_CT_START 0                    // start_hour[24]
@@ -50,20 +48,18 @@
 struct rd_ct_lists {
   int K, L;                              // windows, levels
   int windows[RD_CT_MAXK];
-  long long level_q[RD_CT_MAXL];         // llrint(level * 1024)
+  long long level_q[RD_CT_MAXL];         // rd_levels_q
 };
 
 __host__ __device__ inline long rd_ct_record(int L) { return L + 1 + RD_CT_FIXED; }
 __host__ __device__ inline long rd_ct_state_count(long C, int K, int L) { return C * K * rd_ct_record(L) + 2; }
 // bytes of the workspace per day: 24 sums of 8 bytes and 24 bad counts of 4 per catchment
-__host__ __device__ inline long rd_ct_day_bytes(long C) { return C * RD_CT_HOURS * 12; }
-
-__device__ __forceinline__ bool rd_ct_bad(float v) { return !(v >= 0.0f && v < 2048.0f); }
+__host__ __device__ inline long rd_ct_day_bytes(long C) { return C * RD_HOURS * 12; }
 
 // One step of the halving butterfly over N values: the lanes with bit M clear keep the sums of v[0 .. N/2 - 1], their partners
 // lane ^ M those of v[N/2 .. N - 1]; each hands the other half over.
 template <int N, int M>
-__device__ __forceinline__ void rd_ct_halve(unsigned (&v)[RD_CT_HOURS], bool upper) {
+__device__ __forceinline__ void rd_ct_halve(unsigned (&v)[RD_HOURS], bool upper) {
 #pragma unroll
   for (int i = 0; i < N / 2; ++i) {
     const unsigned keep = upper ? v[i + N / 2] : v[i], send = upper ? v[i] : v[i + N / 2];
@@ -75,33 +71,33 @@ __device__ __forceinline__ void rd_ct_halve(unsigned (&v)[RD_CT_HOURS], bool upp
 __global__ void __launch_bounds__(RD_CT_THREADS)
 k_catch_sums(const float* __restrict__ hourly, long day_stride, long plane, long day0, const int* __restrict__ chunks,
              const int* __restrict__ pixels, long n_entries, int n_catch, unsigned long long* __restrict__ P, unsigned* __restrict__ B) {
-  __shared__ unsigned long long sP[RD_CT_HOURS];
-  __shared__ unsigned sB[RD_CT_HOURS];
+  __shared__ unsigned long long sP[RD_HOURS];
+  __shared__ unsigned sB[RD_HOURS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int* ch = chunks + (long)blockIdx.x * 3;
   const int c = ch[0], count = ch[2];
   const long first = ch[1];
   // (the table is checked on the host; a chunk that would leave the lists or the state is skipped whole)
   if (c < 0 || c >= n_catch || first < 0 || count < 1 || count > RD_CT_CHUNK || first + count > n_entries) return;
-  if (tid < RD_CT_HOURS) sP[tid] = 0ull, sB[tid] = 0u;
+  if (tid < RD_HOURS) sP[tid] = 0ull, sB[tid] = 0u;
   __syncthreads();
   if (tid - lane < count) {                                                  // a wave with an entry
-    unsigned v[RD_CT_HOURS];
+    unsigned v[RD_HOURS];
     const long p = tid < count ? (long)pixels[first + tid] : -1;
     if (p >= 0 && p < plane) {
       const float* xd = hourly + (day0 + (long)blockIdx.y) * day_stride + p;
-      float f[RD_CT_HOURS];
+      float f[RD_HOURS];
 #pragma unroll
-      for (int h = 0; h < RD_CT_HOURS; ++h) f[h] = xd[h * plane];
+      for (int h = 0; h < RD_HOURS; ++h) f[h] = xd[h * plane];
 #pragma unroll
-      for (int h = 0; h < RD_CT_HOURS; ++h) {
-        const bool b = rd_ct_bad(f[h]);
-        v[h] = b ? 0u : (unsigned)(int)rintf(f[h] * 1024.0f);
+      for (int h = 0; h < RD_HOURS; ++h) {
+        const bool b = rd_depth_bad(f[h]);
+        v[h] = b ? 0u : (unsigned)rd_depth_q(f[h]);
         if (b) atomicAdd(&sB[h], 1u);
       }
     } else {
 #pragma unroll
-      for (int h = 0; h < RD_CT_HOURS; ++h) v[h] = 0u;
+      for (int h = 0; h < RD_HOURS; ++h) v[h] = 0u;
     }
     rd_ct_halve<24, 32>(v, lane & 32);
     rd_ct_halve<12, 16>(v, lane & 16);
@@ -118,8 +114,8 @@ k_catch_sums(const float* __restrict__ hourly, long day_stride, long plane, long
     }
   }
   __syncthreads();
-  if (tid < RD_CT_HOURS) {
-    const long at = (((long)blockIdx.y * n_catch) + c) * RD_CT_HOURS + tid;
+  if (tid < RD_HOURS) {
+    const long at = (((long)blockIdx.y * n_catch) + c) * RD_HOURS + tid;
     atomicAdd(&P[at], sP[tid]);
     if (sB[tid]) atomicAdd(&B[at], sB[tid]);
   }
@@ -139,21 +135,21 @@ k_catch_days(int D, long day0, int n_catch, rd_ct_lists lists, const int* __rest
   if (t >= (long)D * n_catch) return;
   const int c = (int)(t % n_catch);
   const long d = t / n_catch;
-  const unsigned long long* Pd = P + t * RD_CT_HOURS;
-  const unsigned* Bd = B + t * RD_CT_HOURS;
+  const unsigned long long* Pd = P + t * RD_HOURS;
+  const unsigned* Bd = B + t * RD_HOURS;
   unsigned long long bad = 0ull;
-  for (int h = 0; h < RD_CT_HOURS; ++h) bad += Bd[h];
+  for (int h = 0; h < RD_HOURS; ++h) bad += Bd[h];
   if (bad) atomicAdd(&tail[1], bad);
   if (series) {
-    long long* out = series + ((day0 + d) * n_catch + c) * RD_CT_HOURS;
-    for (int h = 0; h < RD_CT_HOURS; ++h) out[h] = Bd[h] ? -1ll : (long long)Pd[h];
+    long long* out = series + ((day0 + d) * n_catch + c) * RD_HOURS;
+    for (int h = 0; h < RD_HOURS; ++h) out[h] = Bd[h] ? -1ll : (long long)Pd[h];
   }
   const unsigned long long area = (unsigned long long)npix[c];
   for (int ki = 0; ki < K; ++ki) {
     const int k = lists.windows[ki];
     unsigned long long sum = 0ull, best = 0ull;
     unsigned nb = 0u;
-    for (int h = 0; h < RD_CT_HOURS; ++h) {
+    for (int h = 0; h < RD_HOURS; ++h) {
       sum += Pd[h], nb += Bd[h];
       if (h >= k) sum -= Pd[h - k], nb -= Bd[h - k];
       if (h >= k - 1 && !nb) {

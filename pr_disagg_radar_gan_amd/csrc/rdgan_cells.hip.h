@@ -25,14 +25,11 @@
 // between the phases: no spin-wait, no grid sync.  No floating-point atomics.  All global offsets are 64-bit.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "rdgan_verify.hip.h"
+#include "rdgan_hourly.hip.h"
 
-#define RD_CL_HOURS 24
-#define RD_CL_MAXT RD_VF_MAXT
+#define RD_CL_MAXT RD_THR_MAX
 #define RD_CL_TILE 64
 #define RD_CL_THREADS 256
-#define RD_CL_MAXPLANE (1L << 24)
-#define RD_CL_MAXELEMS (1L << 40)
 #define RD_CL_MAXPASS 65535              // planes of one pass: the grid's y
 #define RD_CL_NBINS 25                   // floor(log2(area)) = 0 .. 24
 #define RD_CL_NKP 65                     // cells_per_plane[0 .. 64], the last bin open
@@ -120,7 +117,7 @@ k_cells_label_tile(const float* __restrict__ x, long day_stride, int ny, int nx,
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
   const int y0 = ty * RD_CL_TILE, x0 = tx * RD_CL_TILE;
   const long pl = blockIdx.y, gp = plane0 + pl, plane = (long)ny * nx;
-  const float* src = x + (gp / RD_CL_HOURS) * day_stride + (gp % RD_CL_HOURS) * plane;
+  const float* src = x + (gp / RD_HOURS) * day_stride + (gp % RD_HOURS) * plane;
   const long wbase = pl * plane;
 
   if (tid < 10) halo[tid] = 0u;                                            // (halo[8], halo[9] are cnt)
@@ -140,7 +137,7 @@ k_cells_label_tile(const float* __restrict__ x, long day_stride, int ny, int nx,
     const int r = wave + 4 * i, gy = y0 + r;
     float v = 0.0f;
     if (gy < ny && gx < nx) v = src[(long)gy * nx + gx];
-    const bool bad = (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u;
+    const bool bad = ((__float_as_uint(v) & RD_F32_EXP) == RD_F32_EXP);
     const bool wet = !bad && v > thr;
     const unsigned long long wm = __ballot(wet), bm = __ballot(bad);
     q[i] = wet ? rd_cl_q(v) : 0ull;
@@ -155,14 +152,14 @@ k_cells_label_tile(const float* __restrict__ x, long day_stride, int ny, int nx,
     const int gy = wave == 0 ? y0 - 1 : y0 + RD_CL_TILE;
     float v = 0.0f;
     if (gy >= 0 && gy < ny && gx < nx) v = src[(long)gy * nx + gx];
-    const unsigned long long bm = __ballot((__float_as_uint(v) & 0x7F800000u) == 0x7F800000u);
+    const unsigned long long bm = __ballot(((__float_as_uint(v) & RD_F32_EXP) == RD_F32_EXP));
     if (lane == 0) badm[wave == 0 ? 0 : 65] = bm;
   }
   if (tid < 132) {                                                         // the columns left and right of the tile, rows -1 .. 64
     const int side = tid / 66, rr = tid % 66, gy = y0 + rr - 1, hx = side == 0 ? x0 - 1 : x0 + RD_CL_TILE;
     if (gy >= 0 && gy < ny && hx >= 0 && hx < nx) {
       const float v = src[(long)gy * nx + hx];
-      if ((__float_as_uint(v) & 0x7F800000u) == 0x7F800000u) atomicOr(&halo[side * 4 + (rr >> 5)], 1u << (rr & 31));
+      if (((__float_as_uint(v) & RD_F32_EXP) == RD_F32_EXP)) atomicOr(&halo[side * 4 + (rr >> 5)], 1u << (rr & 31));
     }
   }
   if (lane == 0) {
@@ -238,7 +235,7 @@ k_cells_label_tile(const float* __restrict__ x, long day_stride, int ny, int nx,
     if (is_root) vol_ws[g] = lvol[p];
   }
   if (tid == 0) {
-    if (cnt[0]) atomicAdd(&wet_counts[gp % RD_CL_HOURS], (unsigned long long)cnt[0]);
+    if (cnt[0]) atomicAdd(&wet_counts[gp % RD_HOURS], (unsigned long long)cnt[0]);
     if (count_bad && cnt[1]) atomicAdd(bad_count, (unsigned long long)cnt[1]);
   }
 }
@@ -334,12 +331,12 @@ k_cells_reduce(long plane, long plane0, const unsigned long long* __restrict__ v
     atomicMax(&plane_words[blockIdx.y * 2 + 1], amax);
   }
   __syncthreads();
-  const int h = (int)((plane0 + blockIdx.y) % RD_CL_HOURS);
+  const int h = (int)((plane0 + blockIdx.y) % RD_HOURS);
   for (int i = tid; i < RD_CL_NL; i += RD_CL_THREADS) {
     const unsigned long long v = tab[i];
     if (!v) continue;
     int dst;
-    if (i < RD_CL_LHIST) dst = RD_CL_CELLS + i * RD_CL_HOURS + h;
+    if (i < RD_CL_LHIST) dst = RD_CL_CELLS + i * RD_HOURS + h;
     else if (i < RD_CL_LASUM) dst = RD_CL_HIST + (i - RD_CL_LHIST);
     else if (i < RD_CL_LASQ) dst = RD_CL_ASUM + (i - RD_CL_LASUM);
     else if (i < RD_CL_LVBA) dst = RD_CL_ASQ + (i - RD_CL_LASQ);

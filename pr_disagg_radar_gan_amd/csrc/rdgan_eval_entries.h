@@ -303,7 +303,7 @@ static bool rd_peaks_mask(const int* windows, int n_windows, unsigned* mask) {
   if (!windows || n_windows < 1 || n_windows > RD_PEAKS_MAXK) return false;
   unsigned m = 0;
   for (int i = 0; i < n_windows; ++i) {
-    if (windows[i] < 1 || windows[i] > RD_FIELD_HOURS || (i > 0 && windows[i] <= windows[i - 1])) return false;
+    if (windows[i] < 1 || windows[i] > RD_HOURS || (i > 0 && windows[i] <= windows[i - 1])) return false;
     m |= 1u << (windows[i] - 1);
   }
   *mask = m;
@@ -373,8 +373,8 @@ extern "C" int rdgan_member_stats(const float* x, int n_members, long member_str
 // verification of field ensembles (rdgan_verify.hip.h): state accumulation, rank / reliability / Brier reduction, FSS
 // ------------------------------------------------------------------------------------
 // the thresholds as the kernels compare them: each rounded once to fp32; false unless finite, >= 0 and strictly increasing there
-static bool rd_vf_thresholds(const double* thresholds, int n, rd_vf_thr* out) {
-  if (!thresholds || n < 1 || n > RD_VF_MAXT) return false;
+static bool rd_thresholds(const double* thresholds, int n, rd_thr* out) {
+  if (!thresholds || n < 1 || n > RD_THR_MAX) return false;
   memset(out, 0, sizeof(*out));
   for (int i = 0; i < n; ++i) {
     if (!(thresholds[i] >= 0.0 && thresholds[i] <= 3.4028234663852886e38)) return false;        // (a NaN fails both)
@@ -398,7 +398,7 @@ static bool rd_vf_widths_ok(const int* widths, int n, int S, rd_vf_widths* out) 
 
 template <int V>
 static void rd_vf_launch_accumulate(int T, unsigned blocks, hipStream_t st, const float* x, long stride, int n, long P, const float* obs,
-                                    const rd_vf_thr& thr, int* exceed, int* below, int* equal, unsigned char* bad) {
+                                    const rd_thr& thr, int* exceed, int* below, int* equal, unsigned char* bad) {
 #define RD_VF_CASE(TT)                                                                                                              \
   case TT:                                                                                                                          \
     hipLaunchKernelGGL((k_verify_accumulate<TT, V>), dim3(blocks), dim3(RD_VF_THREADS), 0, st, x, stride, n, P, obs, thr, exceed,    \
@@ -413,10 +413,10 @@ static void rd_vf_launch_accumulate(int T, unsigned blocks, hipStream_t st, cons
 extern "C" int rdgan_verify_accumulate(const float* members, int n_members, long member_stride, long n_positions, const float* obs,
                                        const double* thresholds, int n_thresholds, int* exceed, int* below, int* equal,
                                        unsigned char* bad, void* stream) {
-  rd_vf_thr thr;
+  rd_thr thr;
   if (!members || !obs || !exceed || !below || !equal || !bad) return -2;
   if (n_members < 1 || n_members > RD_VF_MAXS || n_positions < 1 || n_positions > (1L << 40) || member_stride < n_positions) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr)) return -2;
   const unsigned long long align = (unsigned long long)members | (unsigned long long)obs | (unsigned long long)exceed |
                                    (unsigned long long)below | (unsigned long long)equal;
   if (align & 3) return -2;
@@ -437,23 +437,23 @@ extern "C" int rdgan_verify_reduce(const float* obs, const int* exceed, const in
                                    long n_positions, long plane, int n_members, const double* thresholds, int n_thresholds, int n_bins,
                                    uint64_t seed, long long* rank_hist_out, long long* reliability_out, long long* brier_out,
                                    void* stream) {
-  rd_vf_thr thr;
+  rd_thr thr;
   if (!obs || !exceed || !below || !equal || !bad || !rank_hist_out || !reliability_out || !brier_out) return -2;
   if (n_members < 1 || n_members > RD_VF_MAXS || n_bins < 2 || n_bins > std::min(n_members + 1, RD_VF_MAXBINS)) return -2;
   if (plane < 1 || n_positions < 1 || n_positions > (1L << 40) || n_positions % plane) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr)) return -2;
   const int S = n_members, T = n_thresholds;
   const long n_planes = n_positions / plane;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(rank_hist_out, 0, (size_t)RD_VF_HOURS * (S + 1) * sizeof(long long), st);
-  if (e == hipSuccess) e = hipMemsetAsync(reliability_out, 0, (size_t)T * RD_VF_HOURS * n_bins * 3 * sizeof(long long), st);
-  if (e == hipSuccess) e = hipMemsetAsync(brier_out, 0, (size_t)T * RD_VF_HOURS * 4 * sizeof(long long), st);
+  hipError_t e = hipMemsetAsync(rank_hist_out, 0, (size_t)RD_HOURS * (S + 1) * sizeof(long long), st);
+  if (e == hipSuccess) e = hipMemsetAsync(reliability_out, 0, (size_t)T * RD_HOURS * n_bins * 3 * sizeof(long long), st);
+  if (e == hipSuccess) e = hipMemsetAsync(brier_out, 0, (size_t)T * RD_HOURS * 4 * sizeof(long long), st);
   if (e != hipSuccess) return (int)e;
-  const long units = ((n_planes + RD_VF_HOURS - 1) / RD_VF_HOURS) * ((plane + RD_VF_CHUNK - 1) / RD_VF_CHUNK);       // per hour
+  const long units = ((n_planes + RD_HOURS - 1) / RD_HOURS) * ((plane + RD_VF_CHUNK - 1) / RD_VF_CHUNK);       // per hour
   // at most RD_VF_MAXUNITS chunks per workgroup (the 32-bit LDS counters), at least 64 workgroups per hour where there is work
   const long nbx = std::max<long>((units + RD_VF_MAXUNITS - 1) / RD_VF_MAXUNITS, std::min<long>(units, 64));
   const size_t lds = RD_VF_MAXT * 4 * sizeof(unsigned long long) + (size_t)(T * n_bins * 3 + S + 1) * sizeof(unsigned);
-  hipLaunchKernelGGL(k_verify_reduce, dim3((unsigned)nbx, RD_VF_HOURS), dim3(RD_VF_THREADS), lds, st, obs, exceed, below, equal, bad,
+  hipLaunchKernelGGL(k_verify_reduce, dim3((unsigned)nbx, RD_HOURS), dim3(RD_VF_THREADS), lds, st, obs, exceed, below, equal, bad,
                      n_positions, plane, n_planes, S, T, thr, n_bins, rd_make_key(seed, RD_STREAM_VERIFY),
                      (unsigned long long*)rank_hist_out, (unsigned long long*)reliability_out, (unsigned long long*)brier_out);
   return (int)hipGetLastError();
@@ -463,7 +463,7 @@ static long rd_vf_box_blocks(long plane) { return std::min<long>((plane + RD_VF_
 
 extern "C" long rdgan_verify_fss_workspace_bytes(int ny, int nx, int n_thresholds, int n_widths) {
   if (ny < 1 || nx < 1 || n_thresholds < 1 || n_thresholds > RD_VF_MAXT || n_widths < 1 || n_widths > RD_VF_MAXW) return -2;
-  const long plane = (long)ny * nx, planes = (long)RD_VF_HOURS * n_thresholds;
+  const long plane = (long)ny * nx, planes = (long)RD_HOURS * n_thresholds;
   if (plane > (1L << 36)) return -2;
   return planes * rd_vf_box_blocks(plane) * n_widths * 2 * (long)sizeof(double) + 2 * planes * plane * (long)sizeof(unsigned);
 }
@@ -471,24 +471,24 @@ extern "C" long rdgan_verify_fss_workspace_bytes(int ny, int nx, int n_threshold
 extern "C" int rdgan_verify_fss(const float* obs, const int* exceed, const unsigned char* bad, long n_days, int ny, int nx,
                                 int n_members, const double* thresholds, int n_thresholds, const int* widths, int n_widths,
                                 double* fss_sums_out, void* workspace, long workspace_bytes, void* stream) {
-  rd_vf_thr thr;
+  rd_thr thr;
   rd_vf_widths wd;
   if (!obs || !exceed || !bad || !fss_sums_out || !workspace || ((unsigned long long)workspace & 7)) return -2;
   if (n_days < 1 || ny < 1 || nx < 1 || n_members < 1 || n_members > RD_VF_MAXS) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr) || !rd_vf_widths_ok(widths, n_widths, n_members, &wd)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr) || !rd_vf_widths_ok(widths, n_widths, n_members, &wd)) return -2;
   const long need = rdgan_verify_fss_workspace_bytes(ny, nx, n_thresholds, n_widths);
   if (need < 0 || workspace_bytes < need) return -2;
   const int T = n_thresholds, W = n_widths;
-  const long plane = (long)ny * nx, planes = (long)RD_VF_HOURS * T;
-  if (n_days > (1L << 40) / (plane * RD_VF_HOURS)) return -2;
-  const long P = n_days * RD_VF_HOURS * plane, rows = planes * ny, cols = planes * nx;
+  const long plane = (long)ny * nx, planes = (long)RD_HOURS * T;
+  if (n_days > (1L << 40) / (plane * RD_HOURS)) return -2;
+  const long P = n_days * RD_HOURS * plane, rows = planes * ny, cols = planes * nx;
   if ((rows + 3) / 4 > 0x7FFFFFFFL || (cols + RD_VF_THREADS - 1) / RD_VF_THREADS > 0x7FFFFFFFL) return -2;
   const int nblk = (int)rd_vf_box_blocks(plane);
   double* partial = (double*)workspace;
   unsigned* satC = (unsigned*)(partial + planes * nblk * W * 2);
   unsigned* satE = satC + planes * plane;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(fss_sums_out, 0, (size_t)T * W * RD_VF_HOURS * 2 * sizeof(double), st);
+  hipError_t e = hipMemsetAsync(fss_sums_out, 0, (size_t)T * W * RD_HOURS * 2 * sizeof(double), st);
   if (e != hipSuccess) return (int)e;
   for (long day = 0; day < n_days; ++day) {                 // the days one after another: the workspace holds one day's tables
     hipLaunchKernelGGL(k_verify_fss_rows, dim3((unsigned)((rows + 3) / 4)), dim3(RD_VF_THREADS), 0, st, obs, exceed, bad, P, day, ny, nx,
@@ -513,7 +513,7 @@ static long rd_ts_blocks(long groups) { return std::min<long>((groups + RD_TS_TH
 
 static bool rd_ts_shape_ok(long n, long plane, int n_thresholds, int max_lag) {
   if (n < 1 || plane < 1 || n_thresholds < 1 || n_thresholds > RD_TS_MAXT || max_lag < 1 || max_lag > RD_TS_MAXK) return false;
-  return plane <= RD_TS_MAXELEMS / RD_TS_HOURS && n <= RD_TS_MAXELEMS / (RD_TS_HOURS * plane);
+  return plane <= RD_HOURLY_MAXELEMS / RD_HOURS && n <= RD_HOURLY_MAXELEMS / (RD_HOURS * plane);
 }
 
 extern "C" long rdgan_temporal_workspace_bytes(long n, long plane, int n_thresholds, int max_lag) {
@@ -524,14 +524,13 @@ extern "C" long rdgan_temporal_workspace_bytes(long n, long plane, int n_thresho
 extern "C" int rdgan_temporal_accumulate(const float* x, long n, long day_stride, long plane, const double* thresholds,
                                          int n_thresholds, int max_lag, long long* counts_inout, double* sums_inout, void* workspace,
                                          long workspace_bytes, void* stream) {
-  rd_vf_thr thr;
+  rd_thr thr;
   if (!x || !counts_inout || !sums_inout || !workspace) return -2;
-  static_assert(RD_TS_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
   if (!rd_aligned(7, counts_inout, sums_inout, workspace) || !rd_ts_shape_ok(n, plane, n_thresholds, max_lag)) return -2;
-  if (!rd_hourly_layout_ok(x, n, day_stride, RD_TS_HOURS * plane)) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  if (!rd_hourly_layout_ok(x, n, day_stride, RD_HOURS * plane)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr)) return -2;
   if (workspace_bytes < rdgan_temporal_workspace_bytes(n, plane, n_thresholds, max_lag)) return -2;
-  const bool vec = !((unsigned long long)x & 15) && plane % 4 == 0 && day_stride % 4 == 0;
+  const bool vec = rd_vec4_ok(x, plane, day_stride);
   const int nblk = (int)rd_ts_blocks(vec ? n * (plane / 4) : n * plane), nsums = rd_ts_nsums(n_thresholds, max_lag);
   const size_t lds = rd_ts_lds_bytes(n_thresholds);
   hipStream_t st = (hipStream_t)stream;
@@ -557,7 +556,7 @@ extern "C" int rdgan_temporal_accumulate(const float* x, long n, long day_stride
 // rain cells of hourly fields (rdgan_cells.hip.h): connected wet areas, labelled and counted
 // ------------------------------------------------------------------------------------
 static bool rd_cl_shape_ok(long ny, long nx) {
-  return ny >= 1 && nx >= 1 && ny <= RD_CL_MAXPLANE && nx <= RD_CL_MAXPLANE && ny * nx <= RD_CL_MAXPLANE;
+  return ny >= 1 && nx >= 1 && ny <= RD_HOURLY_MAXPLANE && nx <= RD_HOURLY_MAXPLANE && ny * nx <= RD_HOURLY_MAXPLANE;
 }
 
 extern "C" long rdgan_cells_workspace_bytes(long ny, long nx, long planes_per_pass) {
@@ -582,17 +581,16 @@ static void rd_cl_label_planes(hipStream_t st, const float* x, long day_stride, 
 extern "C" int rdgan_cells_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds,
                                       int n_thresholds, int connectivity, long long* counts_inout, int* labels_out,
                                       int label_threshold, void* workspace, long workspace_bytes, void* stream) {
-  rd_vf_thr thr;
+  rd_thr thr;
   if (!x || !counts_inout || !workspace) return -2;
   if (!rd_aligned(3, labels_out) || !rd_aligned(7, counts_inout, workspace)) return -2;
   if (!rd_cl_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8)) return -2;
   const long plane = ny * nx;
-  static_assert(RD_CL_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
-  if (!rd_hourly_layout_ok(x, n, day_stride, RD_CL_HOURS * plane)) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  if (!rd_hourly_layout_ok(x, n, day_stride, RD_HOURS * plane)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr)) return -2;
   if (labels_out && (label_threshold < 0 || label_threshold >= n_thresholds)) return -2;
   // the planes of a pass: as many as the workspace holds
-  const long n_planes = n * RD_CL_HOURS;
+  const long n_planes = n * RD_HOURS;
   const long per_pass = rd_pass_units(workspace_bytes, rd_cl_ws_bytes(plane, 1), n_planes, RD_CL_MAXPASS);
   if (per_pass < 1) return -2;
   unsigned long long* vol = (unsigned long long*)workspace;
@@ -625,7 +623,7 @@ extern "C" int rdgan_cells_accumulate(const float* x, long n, long day_stride, l
 // ------------------------------------------------------------------------------------
 // storms of hourly fields (rdgan_storms.hip.h): wet volumes connected through the day's hours, labelled and counted
 // ------------------------------------------------------------------------------------
-static bool rd_sm_shape_ok(long ny, long nx) { return rd_cl_shape_ok(ny, nx) && RD_CL_HOURS * ny * nx <= RD_SM_MAXDAY; }
+static bool rd_sm_shape_ok(long ny, long nx) { return rd_cl_shape_ok(ny, nx) && RD_HOURS * ny * nx <= RD_SM_MAXDAY; }
 
 extern "C" long rdgan_storms_state_count(int n_thresholds) {
   if (n_thresholds < 1 || n_thresholds > RD_CL_MAXT) return -2;
@@ -640,14 +638,13 @@ extern "C" long rdgan_storms_workspace_bytes(long ny, long nx, long days_per_pas
 extern "C" int rdgan_storms_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds,
                                        int n_thresholds, int connectivity, int reach, long long* counts_inout, int* labels_out,
                                        int label_threshold, void* workspace, long workspace_bytes, void* stream) {
-  rd_vf_thr thr;
+  rd_thr thr;
   if (!x || !counts_inout || !workspace) return -2;
   if (!rd_aligned(3, labels_out) || !rd_aligned(7, counts_inout, workspace)) return -2;
   if (!rd_sm_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8) || reach < 0 || reach > RD_SM_MAXREACH) return -2;
-  const long plane = ny * nx, V = RD_CL_HOURS * plane;
-  static_assert(RD_CL_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
+  const long plane = ny * nx, V = RD_HOURS * plane;
   if (!rd_hourly_layout_ok(x, n, day_stride, V)) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr)) return -2;
   if (labels_out && (label_threshold < 0 || label_threshold >= n_thresholds)) return -2;
   // the days of a pass: as many whole days as the workspace holds
   const long per_pass = rd_pass_units(workspace_bytes, rd_sm_ws_bytes(plane, 1), n, RD_SM_MAXPASS);
@@ -665,10 +662,10 @@ extern "C" int rdgan_storms_accumulate(const float* x, long n, long day_stride, 
   const int conn8 = connectivity == 8;
   const unsigned vblocks = (unsigned)((V + RD_CL_THREADS - 1) / RD_CL_THREADS);
   for (long d0 = 0; d0 < n; d0 += per_pass) {
-    const unsigned D = (unsigned)std::min<long>(per_pass, n - d0), P = D * RD_CL_HOURS;
+    const unsigned D = (unsigned)std::min<long>(per_pass, n - d0), P = D * RD_HOURS;
     for (int t = 0; t < n_thresholds; ++t) {
       unsigned long long* ct = counts + (long)t * RD_SM_NC;
-      rd_cl_label_planes(st, x, day_stride, ny, nx, d0 * RD_CL_HOURS, P, thr.v[t], conn8, (int)(t == 0), ct + RD_SM_WET, tail + 1, vol,
+      rd_cl_label_planes(st, x, day_stride, ny, nx, d0 * RD_HOURS, P, thr.v[t], conn8, (int)(t == 0), ct + RD_SM_WET, tail + 1, vol,
                          parent, area, plane_words);
       hipLaunchKernelGGL(k_storm_lift, dim3(vblocks, D), dim3(RD_CL_THREADS), 0, st, plane, parent, last, day_words);
       hipLaunchKernelGGL(k_storm_link, dim3((unsigned)((V - plane + RD_CL_THREADS - 1) / RD_CL_THREADS), D), dim3(RD_CL_THREADS), 0, st, (int)ny,
@@ -690,7 +687,7 @@ extern "C" int rdgan_storms_accumulate(const float* x, long n, long day_stride, 
 // areal extremes of hourly fields (rdgan_areal.hip.h): the largest k-hour accumulation over any w x w box, per day
 // ------------------------------------------------------------------------------------
 // a strictly increasing list of 1 .. n_max whole numbers in lo .. hi
-static bool rd_ar_increasing(const int* v, int n, int n_max, int lo, int hi) {
+static bool rd_increasing(const int* v, int n, int n_max, int lo, int hi) {
   if (!v || n < 1 || n > n_max) return false;
   for (int i = 0; i < n; ++i)
     if (v[i] < lo || v[i] > hi || (i > 0 && v[i] <= v[i - 1])) return false;
@@ -700,8 +697,8 @@ static bool rd_ar_increasing(const int* v, int n, int n_max, int lo, int hi) {
 // the three lists as the kernels take them; false for a list out of range.  The internal widths are 1 and then the caller's others.
 static bool rd_ar_make_lists(const int* windows, int K, const int* widths, int W, const double* levels, int L, long max_width,
                              rd_ar_lists* out) {
-  if (!rd_ar_increasing(windows, K, RD_AR_MAXK, 1, RD_AR_HOURS) || !rd_ar_increasing(widths, W, RD_AR_MAXW, 1, RD_AR_MAXWIDTH)) return false;
-  if (widths[W - 1] > max_width || L < 0 || L > RD_AR_MAXL || (L > 0 && !levels)) return false;
+  if (!rd_increasing(windows, K, RD_AR_MAXK, 1, RD_HOURS) || !rd_increasing(widths, W, RD_AR_MAXW, 1, RD_AR_MAXWIDTH)) return false;
+  if (widths[W - 1] > max_width) return false;
   rd_ar_lists a = {};
   a.K = K, a.W = W, a.L = L, a.slots = 1;
   a.slot_width[0] = 1;
@@ -711,16 +708,13 @@ static bool rd_ar_make_lists(const int* windows, int K, const int* widths, int W
     a.slot_of[i] = widths[i] == 1 ? 0 : a.slots;
     if (widths[i] != 1) a.slot_width[a.slots++] = widths[i];
   }
-  for (int i = 0; i < L; ++i) {
-    if (!(levels[i] >= 0.0 && levels[i] <= 2048.0 * RD_AR_HOURS) || (i > 0 && !(levels[i] > levels[i - 1]))) return false;
-    a.level_q[i] = llrint(levels[i] * 1024.0);
-  }
+  if (!rd_levels_q(levels, L, RD_AR_MAXL, a.level_q)) return false;
   *out = a;
   return true;
 }
 
 static bool rd_ar_shape_ok(long ny, long nx) {
-  return ny >= 1 && nx >= 1 && ny <= RD_AR_MAXPLANE && nx <= RD_AR_MAXPLANE && ny * nx <= RD_AR_MAXPLANE;
+  return ny >= 1 && nx >= 1 && ny <= RD_HOURLY_MAXPLANE && nx <= RD_HOURLY_MAXPLANE && ny * nx <= RD_HOURLY_MAXPLANE;
 }
 
 extern "C" long rdgan_areal_state_count(int n_windows, int n_widths, int n_levels) {
@@ -739,8 +733,7 @@ extern "C" int rdgan_areal_accumulate(const float* x, long n, long day_stride, l
   rd_ar_lists lists;
   if (!x || !counts_inout || !workspace) return -2;
   if (!rd_aligned(7, counts_inout, depths_out, workspace) || !rd_ar_shape_ok(ny, nx)) return -2;
-  const long plane = ny * nx, V = RD_AR_HOURS * plane;
-  static_assert(RD_AR_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
+  const long plane = ny * nx, V = RD_HOURS * plane;
   if (!rd_hourly_layout_ok(x, n, day_stride, V)) return -2;
   if (!rd_ar_make_lists(windows, n_windows, widths, n_widths, levels, n_levels, std::min(ny, nx), &lists)) return -2;
   // the days of a pass: as many whole days as the workspace holds
@@ -755,7 +748,7 @@ extern "C" int rdgan_areal_accumulate(const float* x, long n, long day_stride, l
   const int wmax = lists.slot_width[lists.slots - 1];
   const size_t lds = rd_ar_lds_bytes(wmax);
   RD_TRY(ensure_lds(nullptr, (const void*)k_areal_boxes, rd_ar_lds_bytes(RD_AR_MAXWIDTH)));
-  const bool vec = !(((unsigned long long)x | (unsigned long long)S) & 15) && plane % 4 == 0 && day_stride % 4 == 0;
+  const bool vec = rd_vec4_ok(x, plane, day_stride) && rd_aligned(15, S);
   const int tiles_x = (int)((nx + RD_AR_TILE - 1) / RD_AR_TILE), tiles_y = (int)((ny + RD_AR_TILE - 1) / RD_AR_TILE);
   for (long d0 = 0; d0 < n; d0 += per_pass) {
     const unsigned D = (unsigned)std::min<long>(per_pass, n - d0);
@@ -779,14 +772,11 @@ extern "C" int rdgan_areal_accumulate(const float* x, long n, long day_stride, l
 // catchment rainfall of hourly fields (rdgan_catchment.hip.h): hyetographs and k-hour maxima per basin of a map, per day
 // ------------------------------------------------------------------------------------
 static bool rd_ct_make_lists(const int* windows, int K, const double* levels, int L, rd_ct_lists* out) {
-  if (!rd_ar_increasing(windows, K, RD_CT_MAXK, 1, RD_CT_HOURS) || L < 0 || L > RD_CT_MAXL || (L > 0 && !levels)) return false;
+  if (!rd_increasing(windows, K, RD_CT_MAXK, 1, RD_HOURS)) return false;
   rd_ct_lists a = {};
   a.K = K, a.L = L;
   for (int i = 0; i < K; ++i) a.windows[i] = windows[i];
-  for (int i = 0; i < L; ++i) {
-    if (!(levels[i] >= 0.0 && levels[i] <= 2048.0 * RD_CT_HOURS) || (i > 0 && !(levels[i] > levels[i - 1]))) return false;
-    a.level_q[i] = llrint(levels[i] * 1024.0);
-  }
+  if (!rd_levels_q(levels, L, RD_CT_MAXL, a.level_q)) return false;
   *out = a;
   return true;
 }
@@ -812,14 +802,13 @@ extern "C" int rdgan_catchment_accumulate(const float* hourly, long n, long day_
   if (!rd_ar_shape_ok(ny, nx) || n_catch < 1 || n_catch > RD_CT_MAXCATCH) return -2;
   if (n_entries < n_catch || n_entries > RD_CT_MAXENTRIES || n_chunks < n_catch || n_chunks > n_entries || n_chunks > RD_CT_MAXCHUNKS) return -2;
   const long plane = ny * nx;
-  static_assert(RD_CT_MAXELEMS == RD_HOURLY_MAXELEMS && RD_CT_MAXPLANE == RD_AR_MAXPLANE, "rd_hourly_layout_ok bounds the array");
-  if (!rd_hourly_layout_ok(hourly, n, day_stride, RD_CT_HOURS * plane)) return -2;
+  if (!rd_hourly_layout_ok(hourly, n, day_stride, RD_HOURS * plane)) return -2;
   if (!rd_ct_make_lists(windows, n_windows, levels, n_levels, &lists)) return -2;
   // the days of a pass: as many whole days as the workspace holds and one launch has workgroups for
   const long per_pass = rd_pass_units(workspace_bytes, rd_ct_day_bytes(n_catch), n, std::min<long>(RD_CT_MAXPASS, RD_CT_MAXGROUPS / n_chunks));
   if (per_pass < 1) return -2;
   unsigned long long* P = (unsigned long long*)workspace;
-  unsigned* B = (unsigned*)(P + per_pass * n_catch * RD_CT_HOURS);
+  unsigned* B = (unsigned*)(P + per_pass * n_catch * RD_HOURS);
   hipStream_t st = (hipStream_t)stream;
   for (long d0 = 0; d0 < n; d0 += per_pass) {
     const long D = std::min<long>(per_pass, n - d0);
@@ -843,7 +832,7 @@ static bool rd_st_params_ok(int n_thresholds, int radius, int max_lag) {
 }
 
 static bool rd_st_shape_ok(long ny, long nx, long least) {
-  return ny >= least && nx >= least && ny <= RD_ST_MAXPLANE && nx <= RD_ST_MAXPLANE && ny * nx <= RD_ST_MAXPLANE;
+  return ny >= least && nx >= least && ny <= RD_HOURLY_MAXPLANE && nx <= RD_HOURLY_MAXPLANE && ny * nx <= RD_HOURLY_MAXPLANE;
 }
 
 extern "C" long rdgan_spacetime_state_count(int n_thresholds, int radius, int max_lag) {
@@ -860,29 +849,28 @@ extern "C" long rdgan_spacetime_workspace_bytes(long ny, long nx, int n_threshol
 extern "C" int rdgan_spacetime_accumulate(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds,
                                           int n_thresholds, int radius, int max_lag, long long* counts_inout, void* workspace,
                                           long workspace_bytes, void* stream) {
-  rd_vf_thr thr;
+  rd_thr thr;
   if (!x || !counts_inout || !workspace) return -2;
   if (!rd_aligned(7, counts_inout, workspace)) return -2;
-  if (!rd_vf_thresholds(thresholds, n_thresholds, &thr) || !rd_st_params_ok(n_thresholds, radius, max_lag)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr) || !rd_st_params_ok(n_thresholds, radius, max_lag)) return -2;
   if (!rd_st_shape_ok(ny, nx, 2 * radius + 1)) return -2;
-  static_assert(RD_ST_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
-  if (!rd_hourly_layout_ok(x, n, day_stride, RD_ST_HOURS * ny * nx)) return -2;
+  if (!rd_hourly_layout_ok(x, n, day_stride, RD_HOURS * ny * nx)) return -2;
   // the days of a pass: as many whole days as the workspace holds
-  const long per_pass = rd_pass_units(workspace_bytes, RD_ST_HOURS * rd_st_plane_bytes(ny, nx, n_thresholds), n, RD_ST_MAXPASS / RD_ST_HOURS);
+  const long per_pass = rd_pass_units(workspace_bytes, RD_HOURS * rd_st_plane_bytes(ny, nx, n_thresholds), n, RD_ST_MAXPASS / RD_HOURS);
   if (per_pass < 1) return -2;
   const int W = (int)((nx + 63) / 64), T = n_thresholds;
   int cw, bh;
   rd_st_tile(ny, nx, radius, &cw, &bh);
   const int ns = rd_st_slices(radius, bh);
   const size_t lds = rd_st_lds_bytes(radius, cw, bh);
-  const bool vec = !((unsigned long long)x & 15) && nx % 4 == 0 && day_stride % 4 == 0;
+  const bool vec = rd_vec4_ok(x, nx, day_stride);
   unsigned long long* counts = (unsigned long long*)counts_inout;
   unsigned long long* tail = counts + rd_st_thr_base(radius, max_lag, T);                 // n_days, n_bad_pixels
   unsigned long long* masks = (unsigned long long*)workspace;
   hipStream_t st = (hipStream_t)stream;
   for (long d0 = 0; d0 < n; d0 += per_pass) {
     const long days = std::min<long>(per_pass, n - d0);
-    const long waves = days * RD_ST_HOURS * ny * (vec ? (W + 3) / 4 : W);
+    const long waves = days * RD_HOURS * ny * (vec ? (W + 3) / 4 : W);
     const unsigned blocks = (unsigned)std::min<long>((waves + RD_ST_THREADS / 64 - 1) / (RD_ST_THREADS / 64), RD_ST_PACK_MAXBLOCKS);
     if (vec)
       hipLaunchKernelGGL(k_st_pack<4>, dim3(blocks), dim3(RD_ST_THREADS), 0, st, x, day_stride, (int)ny, (int)nx, W, d0, days, thr, T, masks,
@@ -923,11 +911,11 @@ extern "C" int rdgan_analog_features(const float* x, long n, long day_stride, lo
     return (int)hipGetLastError();
   }
   if (mask_out || !total_out || !void_out || !n_void_out || (((unsigned long long)total_out | (unsigned long long)n_void_out) & 7)) return -2;
-  if (n > RD_AN_MAXN || !rd_day_stride_ok(n, day_stride, RD_AN_HOURS * plane)) return -2;
+  if (n > RD_AN_MAXN || !rd_day_stride_ok(n, day_stride, RD_HOURS * plane)) return -2;
   RD_TRY((int)hipMemsetAsync(total_out, 0, (size_t)n * 8, st));
   RD_TRY((int)hipMemsetAsync(n_void_out, 0, 8, st));
   const unsigned blocks = (unsigned)((n * C + 255) / 256);
-  if (!((unsigned long long)x & 15) && plane % 4 == 0 && day_stride % 4 == 0)
+  if (rd_vec4_ok(x, plane, day_stride))
     hipLaunchKernelGGL(k_analog_features<true>, dim3(blocks), dim3(256), 0, st, x, n, day_stride, (int)plane, C, (uint4*)feat_out,
                        (unsigned long long*)total_out);
   else
@@ -983,7 +971,7 @@ extern "C" int rdgan_analog_apply(const float* lib, long n, long day_stride, lon
     return -2;
   if (n < 1 || n > RD_AN_MAXN || !rd_an_shape_ok(ny, nx) || n_queries < 1 || n_queries > RD_AN_MAXQ || k < 1 || k > RD_AN_MAXK) return -2;
   const long plane = ny * nx;
-  if (!rd_day_stride_ok(n, day_stride, RD_AN_HOURS * plane) || n_members < 1 || n_members > RD_AN_MAXS) return -2;
+  if (!rd_day_stride_ok(n, day_stride, RD_HOURS * plane) || n_members < 1 || n_members > RD_AN_MAXS) return -2;
   if (first_query < 0 || first_query > (1L << 32) - n_queries || first_member < 0 || first_member > (1L << 62)) return -2;
   if (weights != RD_AN_UNIFORM && weights != RD_AN_RANK) return -2;
   hipLaunchKernelGGL(k_analog_apply, dim3((unsigned)n_queries, (unsigned)n_members), dim3(RD_AN_APPLY_THREADS), (size_t)plane * 4,
@@ -997,8 +985,8 @@ extern "C" int rdgan_analog_apply(const float* lib, long n, long day_stride, lon
 // ------------------------------------------------------------------------------------
 static bool rd_mv_shape_ok(long m, long n_days, long ny, long nx, int shared) {
   if (m < 1 || m > RD_MV_MAXM || n_days < 1 || n_days > RD_MV_MAXDAYS || (shared != 0 && shared != 1)) return false;
-  if (ny < 1 || nx < 1 || ny > RD_MV_MAXPLANE || nx > RD_MV_MAXPLANE || ny * nx > RD_MV_MAXPLANE) return false;
-  return (shared ? 1 : n_days) * m <= RD_HOURLY_MAXELEMS / (RD_MV_HOURS * ny * nx);
+  if (ny < 1 || nx < 1 || ny > RD_HOURLY_MAXPLANE || nx > RD_HOURLY_MAXPLANE || ny * nx > RD_HOURLY_MAXPLANE) return false;
+  return (shared ? 1 : n_days) * m <= RD_HOURLY_MAXELEMS / (RD_HOURS * ny * nx);
 }
 // workgroups of the largest launch of an energy call
 static long rd_mv_energy_blocks(long m, long n_days, int shared) {
@@ -1018,7 +1006,7 @@ extern "C" int rdgan_mv_energy(const float* ens, const float* obs, long m, long 
   if (!rd_aligned(3, ens, obs) || !rd_aligned(7, obs_sum_out, pair_sum_out, workspace)) return -2;
   if (!rd_mv_shape_ok(m, n_days, ny, nx, shared) || rd_mv_energy_blocks(m, n_days, shared) > RD_MV_MAXBLOCKS) return -2;
   if (workspace_bytes < rd_mv_energy_words(m, n_days, shared) * 8) return -2;
-  const long P = RD_MV_HOURS * ny * nx;
+  const long P = RD_HOURS * ny * nx;
   hipStream_t st = (hipStream_t)stream;
   long long* nvalid = (long long*)workspace;
   double* slots = (double*)workspace + n_days;
@@ -1051,7 +1039,7 @@ extern "C" long rdgan_mv_variogram_workspace_bytes(long n_days, long ny, long nx
 template <bool HALF>
 static void rd_mv_variogram_launch(const float* ens, const float* obs, long m, long n_days, long ny, long nx, int shared, int R, int L,
                                    double* table, rd_mv_slot* slots, hipStream_t st) {
-  const long U = rd_mv_units(ny, nx, R, L), P = RD_MV_HOURS * ny * nx;
+  const long U = rd_mv_units(ny, nx, R, L), P = RD_HOURS * ny * nx;
   if (U == 0) return;                                                      // radius 0 and no lag: no displacement at all
   if (!shared) {
     hipLaunchKernelGGL((k_mv_variogram<0, HALF>), dim3((unsigned)(n_days * U)), dim3(RD_MV_THREADS), 0, st, ens, m * P, obs, (int)m, (int)ny,
@@ -1075,7 +1063,7 @@ extern "C" int rdgan_mv_variogram(const float* ens, const float* obs, long m, lo
   long long* nvalid = (long long*)workspace;
   rd_mv_slot* slots = (rd_mv_slot*)((long long*)workspace + n_days);
   double* table = (double*)(slots + n_days * U * RD_MV_VG);
-  hipLaunchKernelGGL(k_mv_valid, dim3((unsigned)n_days), dim3(RD_MV_THREADS), 0, st, obs, RD_MV_HOURS * ny * nx, nvalid);
+  hipLaunchKernelGGL(k_mv_valid, dim3((unsigned)n_days), dim3(RD_MV_THREADS), 0, st, obs, RD_HOURS * ny * nx, nvalid);
   if (p == 0.5)
     rd_mv_variogram_launch<true>(ens, obs, m, n_days, ny, nx, shared, radius, max_lag, table, slots, st);
   else
@@ -1274,7 +1262,7 @@ static bool rd_cs_edges_ok(const int* edge_units, int n_edges, rd_cs_edges* out)
   return true;
 }
 
-static bool rd_cs_shape_ok(long ny, long nx) { return ny >= 1 && nx >= 1 && ny <= RD_CS_MAXPLANE && nx <= RD_CS_MAXPLANE && ny * nx <= RD_CS_MAXPLANE; }
+static bool rd_cs_shape_ok(long ny, long nx) { return ny >= 1 && nx >= 1 && ny <= RD_HOURLY_MAXPLANE && nx <= RD_HOURLY_MAXPLANE && ny * nx <= RD_HOURLY_MAXPLANE; }
 
 extern "C" long rdgan_cascade_state_size(int n_edges) {
   if (n_edges < 0 || n_edges > RD_CS_MAXE) return -2;
@@ -1287,11 +1275,10 @@ extern "C" int rdgan_cascade_accumulate(const float* hourly, long n, long day_st
   if (!hourly || !state_inout || !rd_aligned(7, state_inout) || !rd_aligned(3, edge_units)) return -2;
   if (!rd_cs_shape_ok(ny, nx) || !rd_cs_edges_ok(edge_units, n_edges, &e)) return -2;
   const long plane = ny * nx;
-  static_assert(RD_CS_MAXELEMS == RD_HOURLY_MAXELEMS, "rd_hourly_layout_ok bounds the array");
-  if (!rd_hourly_layout_ok(hourly, n, day_stride, RD_CS_HOURS * plane)) return -2;
+  if (!rd_hourly_layout_ok(hourly, n, day_stride, RD_HOURS * plane)) return -2;
   // a counter of a workgroup grows by at most 12 per pixel-day: 12 * 2^40 / (24 * RD_CS_ACC_MAXBLOCKS) stays below 2^32
-  static_assert(12 * (RD_CS_MAXELEMS / RD_CS_HOURS / RD_CS_ACC_MAXBLOCKS + RD_CS_THREADS * 4) < (1L << 32), "32-bit LDS counters");
-  const bool vec = !((unsigned long long)hourly & 15) && plane % 4 == 0 && day_stride % 4 == 0;
+  static_assert(12 * (RD_HOURLY_MAXELEMS / RD_HOURS / RD_CS_ACC_MAXBLOCKS + RD_CS_THREADS * 4) < (1L << 32), "32-bit LDS counters");
+  const bool vec = rd_vec4_ok(hourly, plane, day_stride);
   const long items = n * (vec ? plane / 4 : plane);
   const unsigned blocks = (unsigned)std::min<long>((items + RD_CS_THREADS - 1) / RD_CS_THREADS, RD_CS_ACC_MAXBLOCKS);
   const size_t lds = (size_t)rd_cs_state_size(n_edges) * sizeof(unsigned);
@@ -1310,10 +1297,10 @@ extern "C" int rdgan_cascade_generate(const unsigned* model, const int* edge_uni
   rd_cs_edges e;
   if (!model || !cond || !out || !rd_aligned(3, model, edge_units, cond, out, units_out)) return -2;
   if (!rd_cs_shape_ok(ny, nx) || !rd_cs_edges_ok(edge_units, n_edges, &e)) return -2;
-  if (n_queries < 1 || n_queries > RD_CS_MAXQ || n_members < 1 || n_members > RD_CS_MAXS || patch < 1 || patch > RD_CS_MAXPLANE) return -2;
+  if (n_queries < 1 || n_queries > RD_CS_MAXQ || n_members < 1 || n_members > RD_CS_MAXS || patch < 1 || patch > RD_HOURLY_MAXPLANE) return -2;
   if (first_query < 0 || first_query > (1L << 32) - n_queries || first_member < 0 || first_member > (1L << 62)) return -2;
   const long plane = ny * nx;
-  if (n_queries * n_members > RD_CS_MAXELEMS / (RD_CS_HOURS * plane)) return -2;
+  if (n_queries * n_members > RD_HOURLY_MAXELEMS / (RD_HOURS * plane)) return -2;
   const bool vec = nx % 4 == 0 && rd_aligned(15, out, units_out);
   const long items = n_queries * n_members * (vec ? plane / 4 : plane);
   const unsigned blocks = (unsigned)std::min<long>((items + RD_CS_THREADS - 1) / RD_CS_THREADS, RD_CS_GEN_MAXBLOCKS);

@@ -15,12 +15,12 @@
 //    two calls agree bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "rdgan_hourly.hip.h"
 
 #define RD_FIELD_THREADS 256
 #define RD_FIELD_BX 64          // a wave takes 64 adjacent x of one field row,
 #define RD_FIELD_BY 4           // the four waves of a workgroup four adjacent rows: they share the tile rows they read
 #define RD_FIELD_COVER 3        // at most 3 tiles cover a coordinate per axis (overlap <= nd / 2)
-#define RD_FIELD_HOURS 24
 
 __host__ __device__ __forceinline__ int rd_field_origin(int i, int step, int L, int nd) {
   const long o = (long)i * step;
@@ -102,7 +102,7 @@ __device__ __forceinline__ void rd_field_resolve(const int* __restrict__ srow, c
       const int tx = x - rd_field_origin(okx ? ix : 0, step, nx, nd);
       const bool ok = oky && okx && ty >= 0 && ty < nd && tx >= 0 && tx < nd;
       const int slot = ok ? srow[iy * n_tx + ix] : -1;
-      off[a * RD_FIELD_COVER + c] = slot >= 0 ? ((long)slot * RD_FIELD_HOURS * nd + ty) * nd + tx : -1;
+      off[a * RD_FIELD_COVER + c] = slot >= 0 ? ((long)slot * RD_HOURS * nd + ty) * nd + tx : -1;
       w[a * RD_FIELD_COVER + c] = wy * wx;
     }
   }
@@ -144,16 +144,16 @@ k_field_blend(const float* __restrict__ frac, const int* __restrict__ slots, con
     const int y = (int)((b / nbx) % nby) * RD_FIELD_BY + ly, x = (int)(b % nbx) * RD_FIELD_BX + lx;
     if (y >= ny || x >= nx) continue;
     const float d = daily[((first_unit + u) % n_days) * plane + (long)y * nx + x];
-    float* dst = out + u * RD_FIELD_HOURS * plane + (long)y * nx + x;
+    float* dst = out + u * RD_HOURS * plane + (long)y * nx + x;
     if (d == 0.f || d != d) {
 #pragma unroll
-      for (int h = 0; h < RD_FIELD_HOURS; ++h) dst[h * plane] = d;         // 0 stays 0, NaN stays NaN
+      for (int h = 0; h < RD_HOURS; ++h) dst[h * plane] = d;         // 0 stays 0, NaN stays NaN
       continue;
     }
     long off[RD_FIELD_COVER * RD_FIELD_COVER];
     float w[RD_FIELD_COVER * RD_FIELD_COVER];
     rd_field_resolve(slots + u * T, ytab_i, ytab_w, xtab_i, xtab_w, y, x, ny, nx, nd, step, n_ty, n_tx, off, w);
 #pragma unroll 4
-    for (int h = 0; h < RD_FIELD_HOURS; ++h) dst[h * plane] = rd_field_hour(frac, off, w, h, tile, d);
+    for (int h = 0; h < RD_HOURS; ++h) dst[h * plane] = rd_field_hour(frac, off, w, h, tile, d);
   }
 }

@@ -24,10 +24,9 @@
 // No floating-point atomics, no spin-waits.  All global offsets are 64-bit.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "rdgan_hourly.hip.h"
 
-#define RD_MV_HOURS 24
 #define RD_MV_MAXM 8192                  // members (RD_CRPS_MAXN)
-#define RD_MV_MAXPLANE (1L << 24)        // pixels of a plane
 #define RD_MV_MAXDAYS (1L << 20)         // observed days of a call
 #define RD_MV_MAXR 4
 #define RD_MV_MAXLAG 3
@@ -58,7 +57,7 @@ __host__ __device__ inline long rd_mv_vtiles(long ny, long nx) { return ((ny + R
 // units (workgroups) of a day: lag-major, then hour, group, tile
 __host__ __device__ inline long rd_mv_unit_base(long ny, long nx, int R, int l) {
   long u = 0;
-  for (int k = 0; k < l; ++k) u += (long)(RD_MV_HOURS - k) * rd_mv_groups(R, k) * rd_mv_vtiles(ny, nx);
+  for (int k = 0; k < l; ++k) u += (long)(RD_HOURS - k) * rd_mv_groups(R, k) * rd_mv_vtiles(ny, nx);
   return u;
 }
 __host__ __device__ inline long rd_mv_units(long ny, long nx, int R, int L) { return rd_mv_unit_base(ny, nx, R, L + 1); }
@@ -354,14 +353,14 @@ k_mv_variogram(const float* __restrict__ ens, long ens_day_stride, const float* 
   __shared__ double wsq[RD_MV_THREADS / 64][RD_MV_VG];
   __shared__ int wcnt[RD_MV_THREADS / 64][RD_MV_VG];
   const int tid = threadIdx.x, tx = tid & (RD_MV_VT - 1), ty = tid / RD_MV_VT;
-  const long plane = (long)ny * nx, P = RD_MV_HOURS * plane;
+  const long plane = (long)ny * nx, P = RD_HOURS * plane;
   const int ntx = (nx + RD_MV_VT - 1) / RD_MV_VT;
   const long nt = rd_mv_vtiles(ny, nx), U = rd_mv_units(ny, nx, R, L);
   const long day = blockIdx.x / U;
   long u = blockIdx.x % U;
   int l = 0;
   for (;;) {                                                               // the unit -> lag, hour, group, tile
-    const long n = (long)(RD_MV_HOURS - l) * rd_mv_groups(R, l) * nt;
+    const long n = (long)(RD_HOURS - l) * rd_mv_groups(R, l) * nt;
     if (u < n) break;
     u -= n;
     ++l;
@@ -494,7 +493,7 @@ k_mv_variogram_reduce(const rd_mv_slot* __restrict__ slots, long n_days, int ny,
     const long nt = rd_mv_vtiles(ny, nx), U = rd_mv_units(ny, nx, R, L);
     const int ng = rd_mv_groups(R, l), g = (d - first) / RD_MV_VG, k = (d - first) % RD_MV_VG;
     const rd_mv_slot* base = slots + (day * U + rd_mv_unit_base(ny, nx, R, l)) * RD_MV_VG + k;
-    for (int h = 0; h < RD_MV_HOURS - l; ++h)
+    for (int h = 0; h < RD_HOURS - l; ++h)
       for (long t = 0; t < nt; ++t) {
         const rd_mv_slot s = base[(((long)h * ng + g) * nt + t) * RD_MV_VG];
         sq = __dadd_rn(sq, s.sq);

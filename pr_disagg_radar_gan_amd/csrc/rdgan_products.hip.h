@@ -33,25 +33,25 @@
 // The k-hour peaks of one pixel from its 24 hourly values in registers.  pk points at the pixel in the first of the K = popcount(mask)
 // output planes, `plane` apart; hr at its peak hour.  Every index into v and s is a compile-time constant (no scratch): window w is
 // reached by adding hour h0 + w - 1 to the running sum s[h0] of window w - 1, which IS the left-to-right sum of the definition.
-__device__ __forceinline__ void rd_window_peaks(const float (&v)[RD_FIELD_HOURS], unsigned mask, int w0, float* __restrict__ pk,
+__device__ __forceinline__ void rd_window_peaks(const float (&v)[RD_HOURS], unsigned mask, int w0, float* __restrict__ pk,
                                                 long plane, unsigned char* __restrict__ hr) {
 #pragma clang fp contract(off)
   bool nan = false;
 #pragma unroll
-  for (int h = 0; h < RD_FIELD_HOURS; ++h) nan |= v[h] != v[h];
-  float s[RD_FIELD_HOURS];
+  for (int h = 0; h < RD_HOURS; ++h) nan |= v[h] != v[h];
+  float s[RD_HOURS];
   int hour = 0;
   long k = 0;
 #pragma unroll
-  for (int w = 1; w <= RD_FIELD_HOURS; ++w) {
+  for (int w = 1; w <= RD_HOURS; ++w) {
     if ((mask >> (w - 1)) == 0u) break;                  // no window of w hours or more is asked for
 #pragma unroll
-    for (int h0 = 0; h0 + w <= RD_FIELD_HOURS; ++h0) s[h0] = w == 1 ? v[h0] : s[h0] + v[h0 + w - 1];
+    for (int h0 = 0; h0 + w <= RD_HOURS; ++h0) s[h0] = w == 1 ? v[h0] : s[h0] + v[h0 + w - 1];
     if ((mask >> (w - 1)) & 1u) {
       float best = s[0];
       int bh = 0;
 #pragma unroll
-      for (int h0 = 1; h0 + w <= RD_FIELD_HOURS; ++h0)
+      for (int h0 = 1; h0 + w <= RD_HOURS; ++h0)
         if (s[h0] > best) {
           best = s[h0];
           bh = h0;
@@ -79,10 +79,10 @@ k_hourly_peaks(const float* __restrict__ x, long units, int ny, int nx, unsigned
     const int y = (int)((b / nbx) % nby) * RD_FIELD_BY + ly, xx = (int)(b % nbx) * RD_FIELD_BX + lx;
     if (y >= ny || xx >= nx) continue;
     const long pix = (long)y * nx + xx;
-    const float* src = x + u * RD_FIELD_HOURS * plane + pix;
-    float v[RD_FIELD_HOURS];
+    const float* src = x + u * RD_HOURS * plane + pix;
+    float v[RD_HOURS];
 #pragma unroll
-    for (int h = 0; h < RD_FIELD_HOURS; ++h) v[h] = src[h * plane];
+    for (int h = 0; h < RD_HOURS; ++h) v[h] = src[h * plane];
     rd_window_peaks(v, mask, w0, peaks + u * K * plane + pix, plane, peak_hour + u * plane + pix);
   }
 }
@@ -116,9 +116,9 @@ k_field_blend_peaks(const float* __restrict__ frac, const int* __restrict__ slot
     long off[RD_FIELD_COVER * RD_FIELD_COVER];
     float w[RD_FIELD_COVER * RD_FIELD_COVER];
     rd_field_resolve(slots + u * T, ytab_i, ytab_w, xtab_i, xtab_w, y, x, ny, nx, nd, step, n_ty, n_tx, off, w);
-    float v[RD_FIELD_HOURS];
+    float v[RD_HOURS];
 #pragma unroll
-    for (int h = 0; h < RD_FIELD_HOURS; ++h) v[h] = rd_field_hour(frac, off, w, h, tile, d);
+    for (int h = 0; h < RD_HOURS; ++h) v[h] = rd_field_hour(frac, off, w, h, tile, d);
     rd_window_peaks(v, mask, w0, pk, plane, hr);
   }
 }

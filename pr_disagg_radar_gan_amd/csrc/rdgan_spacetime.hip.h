@@ -23,15 +23,12 @@
 // offsets are 64-bit.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "rdgan_verify.hip.h"
+#include "rdgan_hourly.hip.h"
 
-#define RD_ST_HOURS 24
-#define RD_ST_MAXT RD_VF_MAXT
+#define RD_ST_MAXT RD_THR_MAX
 #define RD_ST_MAXR 8
 #define RD_ST_MAXK 6
 #define RD_ST_THREADS 256
-#define RD_ST_MAXPLANE (1L << 24)
-#define RD_ST_MAXELEMS (1L << 40)
 #define RD_ST_MAXPASS 65520              // planes of one pass: 2730 whole days
 #define RD_ST_HPB 6                      // hours of one (day, k) a workgroup of k_st_correlate takes
 #define RD_ST_GROUPS 4                   // 24 / RD_ST_HPB
@@ -79,8 +76,6 @@ inline int rd_st_slices(int R, int bh) {
   return best;
 }
 
-__device__ __forceinline__ bool rd_st_bad(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
-
 // the core's columns R <= x < nx - R among the 64 of word w
 __device__ __forceinline__ unsigned long long rd_st_core_mask(int w, int nx, int R) {
   const int lo = R - 64 * w > 0 ? R - 64 * w : 0, hi = nx - R - 64 * w < 64 ? nx - R - 64 * w : 64;
@@ -91,27 +86,27 @@ __device__ __forceinline__ unsigned long long rd_st_core_mask(int w, int nx, int
 
 template <int V>
 __global__ void __launch_bounds__(RD_ST_THREADS)
-k_st_pack(const float* __restrict__ x, long day_stride, int ny, int nx, int W, long day0, long days, rd_vf_thr thr, int T,
+k_st_pack(const float* __restrict__ x, long day_stride, int ny, int nx, int W, long day0, long days, rd_thr thr, int T,
           unsigned long long* __restrict__ masks, unsigned long long* __restrict__ n_days, unsigned long long* __restrict__ bad_count) {
   const int lane = threadIdx.x & 63;
   const long wave = ((long)blockIdx.x * RD_ST_THREADS + threadIdx.x) >> 6, nwaves = (long)gridDim.x * (RD_ST_THREADS / 64);
   const long plane = (long)ny * nx;
   const int per_row = V == 4 ? (W + 3) / 4 : W;                          // items of a row: 256 or 64 pixels each
-  const long items = days * RD_ST_HOURS * ny * per_row;
+  const long items = days * RD_HOURS * ny * per_row;
   unsigned n_bad = 0;
   for (long it = wave; it < items; it += nwaves) {                        // (the same trip count in every lane of a wave)
     const int c = (int)(it % per_row);
     const long r = it / per_row;
     const int y = (int)(r % ny);
     const long pl = r / ny;                                               // the plane of the pass: day * 24 + hour
-    const float* src = x + (day0 + pl / RD_ST_HOURS) * day_stride + (pl % RD_ST_HOURS) * plane + (long)y * nx;
+    const float* src = x + (day0 + pl / RD_HOURS) * day_stride + (pl % RD_HOURS) * plane + (long)y * nx;
     unsigned long long* row = masks + (pl * (T + 1) * ny + y) * W;        // mask m of this row lies m * ny * W words on
     const long mstride = (long)ny * W;
     if constexpr (V == 1) {
       const int px = c * 64 + lane;
       const bool in = px < nx;
       const float v = in ? src[px] : 0.0f;
-      const bool bad = in && rd_st_bad(v), ok = in && !bad;
+      const bool bad = in && rd_nonfinite(v), ok = in && !bad;
       n_bad += bad;
       unsigned long long mine = __ballot(ok);                             // lane m keeps mask m
 #pragma unroll
@@ -124,11 +119,11 @@ k_st_pack(const float* __restrict__ x, long day_stride, int ny, int nx, int W, l
     } else {
       const int px = c * 256 + 4 * lane;
       float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (px < nx) rd_vf_load<4>(src + px, v);                            // (nx % 4 == 0: all four or none)
+      if (px < nx) rd_load<4>(src + px, v);                            // (nx % 4 == 0: all four or none)
       bool ok[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const bool bad = px < nx && rd_st_bad(v[j]);
+        const bool bad = px < nx && rd_nonfinite(v[j]);
         ok[j] = px < nx && !bad;
         n_bad += bad;
       }
@@ -171,7 +166,7 @@ k_st_correlate(const unsigned long long* __restrict__ masks, int ny, int nx, int
   const int tid = threadIdx.x, lane = tid & 63;
   const int t = blockIdx.y, g = blockIdx.x % RD_ST_GROUPS, k = (blockIdx.x / RD_ST_GROUPS) % (K + 1);
   const long day = blockIdx.x / (RD_ST_GROUPS * (K + 1));
-  const int h0 = g * RD_ST_HPB, h1 = h0 + RD_ST_HPB < RD_ST_HOURS - k ? h0 + RD_ST_HPB : RD_ST_HOURS - k;
+  const int h0 = g * RD_ST_HPB, h1 = h0 + RD_ST_HPB < RD_HOURS - k ? h0 + RD_ST_HPB : RD_HOURS - k;
   const bool first = t == 0;
   const long mplane = (long)ny * W;
   unsigned long long* tb = counts + rd_st_thr_base(R, K, t);
@@ -182,8 +177,8 @@ k_st_correlate(const unsigned long long* __restrict__ masks, int ny, int nx, int
     for (int i = tid; i < D; i += RD_ST_THREADS) acc[4 * D + i] = 0u;
     if (tid < 2) cnt[tid] = 0u;
     if (tid == 2) *key = ~0ull;
-    const unsigned long long* ga = masks + (day * RD_ST_HOURS + h) * (T + 1) * mplane;
-    const unsigned long long* gb = masks + (day * RD_ST_HOURS + h + k) * (T + 1) * mplane;
+    const unsigned long long* ga = masks + (day * RD_HOURS + h) * (T + 1) * mplane;
+    const unsigned long long* gb = masks + (day * RD_HOURS + h + k) * (T + 1) * mplane;
     for (int y0 = 0; y0 < ny; y0 += bh)
       for (int w0 = 0; w0 < W; w0 += cw) {
         __syncthreads();                                                   // the tile before this one is done with, the zeros are written

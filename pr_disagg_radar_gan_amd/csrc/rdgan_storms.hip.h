@@ -60,13 +60,13 @@
 // bytes of the workspace for D days of `plane` pixels: the four maps (and the spare word) per voxel, count and longest duration
 // per day, then the label kernel's two words per plane
 __host__ __device__ inline long rd_sm_ws_bytes(long plane, long D) {
-  return D * RD_CL_HOURS * plane * RD_SM_VOXEL_BYTES + D * 8 + D * RD_CL_HOURS * 8;
+  return D * RD_HOURS * plane * RD_SM_VOXEL_BYTES + D * 8 + D * RD_HOURS * 8;
 }
 
 // grid (ceil(V / 256), D), V = 24 plane
 __global__ void __launch_bounds__(RD_CL_THREADS)
 k_storm_lift(long plane, int* __restrict__ parent_ws, unsigned* __restrict__ last_ws, unsigned* __restrict__ day_words) {
-  const long V = RD_CL_HOURS * plane, v = (long)blockIdx.x * RD_CL_THREADS + threadIdx.x;
+  const long V = RD_HOURS * plane, v = (long)blockIdx.x * RD_CL_THREADS + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < 2) day_words[(long)blockIdx.y * 2 + threadIdx.x] = 0u;
   if (v >= V) return;
   const long g = (long)blockIdx.y * V + v;
@@ -82,7 +82,7 @@ k_storm_lift(long plane, int* __restrict__ parent_ws, unsigned* __restrict__ las
 // b's set.  Sets only grow, so the skipped union could change nothing.
 __global__ void __launch_bounds__(RD_CL_THREADS)
 k_storm_link(int ny, int nx, int reach, int* __restrict__ parent_ws) {
-  const long plane = (long)ny * nx, V = RD_CL_HOURS * plane;
+  const long plane = (long)ny * nx, V = RD_HOURS * plane;
   const long v = (long)blockIdx.x * RD_CL_THREADS + threadIdx.x;
   if (v >= V - plane) return;
   int* parent = parent_ws + (long)blockIdx.y * V;
@@ -107,7 +107,7 @@ k_storm_link(int ny, int nx, int reach, int* __restrict__ parent_ws) {
 __global__ void __launch_bounds__(RD_CL_THREADS)
 k_storm_resolve(long plane, long day0, unsigned long long* __restrict__ vol_ws, int* __restrict__ parent_ws,
                 unsigned* __restrict__ area_ws, unsigned* __restrict__ last_ws, int* __restrict__ labels) {
-  const long V = RD_CL_HOURS * plane, v = (long)blockIdx.x * RD_CL_THREADS + threadIdx.x;
+  const long V = RD_HOURS * plane, v = (long)blockIdx.x * RD_CL_THREADS + threadIdx.x;
   if (v >= V) return;
   const long base = (long)blockIdx.y * V;
   int* parent = parent_ws + base;
@@ -141,7 +141,7 @@ k_storm_reduce(long plane, const unsigned long long* __restrict__ vol_ws, const 
   const int tid = threadIdx.x;
   for (int i = tid; i < RD_SM_NL; i += RD_CL_THREADS) tab[i] = 0ull;
   __syncthreads();
-  const long V = RD_CL_HOURS * plane, base = (long)blockIdx.y * V, v0 = (long)blockIdx.x * RD_SM_RCHUNK;
+  const long V = RD_HOURS * plane, base = (long)blockIdx.y * V, v0 = (long)blockIdx.x * RD_SM_RCHUNK;
   unsigned n = 0, longest = 0;
 #pragma unroll 4
   for (int k = 0; k < RD_SM_RCHUNK / RD_CL_THREADS; ++k) {
@@ -149,13 +149,13 @@ k_storm_reduce(long plane, const unsigned long long* __restrict__ vol_ws, const 
     if (v >= V || parent_ws[base + v] != (int)v) continue;
     const unsigned w = area_ws[base + v], size = w & ~RD_CL_EDGE;          // (a root has size >= 1)
     const unsigned start = (unsigned)(v / plane), last = last_ws[base + v], dur = last - start + 1;
-    const int c = (int)(w >> 31) + 2 * (int)(start == 0 || last == RD_CL_HOURS - 1);
-    const int b = 31 - __builtin_clz(size), cd = c * RD_CL_HOURS + (int)dur - 1;
+    const int c = (int)(w >> 31) + 2 * (int)(start == 0 || last == RD_HOURS - 1);
+    const int b = 31 - __builtin_clz(size), cd = c * RD_HOURS + (int)dur - 1;
     ++n;
     longest = dur > longest ? dur : longest;
     atomicAdd(&tab[RD_SM_L(RD_SM_STORMS) + c], 1ull);
     atomicAdd(&tab[RD_SM_L(RD_SM_DUR) + cd], 1ull);
-    atomicAdd(&tab[RD_SM_L(RD_SM_START) + c * RD_CL_HOURS + (int)start], 1ull);
+    atomicAdd(&tab[RD_SM_L(RD_SM_START) + c * RD_HOURS + (int)start], 1ull);
     atomicAdd(&tab[RD_SM_L(RD_SM_HIST) + c * RD_SM_NBINS + b], 1ull);
     atomicAdd(&tab[RD_SM_L(RD_SM_SSUM) + c], (unsigned long long)size);
     atomicAdd(&tab[RD_SM_L(RD_SM_SSQ) + c], (unsigned long long)size * size);

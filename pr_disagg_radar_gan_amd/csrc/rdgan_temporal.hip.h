@@ -26,15 +26,13 @@
 // adds at most 12 to one word, so no LDS word passes 2^31.  All global offsets are 64-bit.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "rdgan_verify.hip.h"
+#include "rdgan_hourly.hip.h"
 
-#define RD_TS_HOURS 24
-#define RD_TS_MAXT RD_VF_MAXT
+#define RD_TS_MAXT RD_THR_MAX
 #define RD_TS_MAXK 12
 #define RD_TS_THREADS 256
 #define RD_TS_WAVES (RD_TS_THREADS / 64)
 #define RD_TS_MAXBLOCKS 1024
-#define RD_TS_MAXELEMS (1L << 40)
 // the state: counters per threshold, flat
 #define RD_TS_WH 0                       // wet_hours[25]
 #define RD_TS_LW 25                      // longest_wet[25]
@@ -51,7 +49,7 @@
 #define RD_TS_LD 65                      // doubles per tile row: lanes 0 .. 63 and one of padding (conflict-free transposed reads)
 #define RD_TS_TILE (16 * RD_TS_LD)       // doubles per wave
 
-__host__ __device__ inline int rd_ts_nsums(int T, int K) { return 2 * RD_TS_HOURS + K + T * RD_TS_HOURS; }
+__host__ __device__ inline int rd_ts_nsums(int T, int K) { return 2 * RD_HOURS + K + T * RD_HOURS; }
 __host__ __device__ inline size_t rd_ts_lds_bytes(int T) {
   return ((size_t)RD_TS_WAVES * RD_TS_TILE + (size_t)RD_TS_WAVES * T * 2 * 64) * sizeof(double) + ((size_t)T * RD_TS_NL + 2) * sizeof(unsigned);
 }
@@ -90,7 +88,7 @@ __device__ __forceinline__ int rd_ts_runs(unsigned* __restrict__ bins, unsigned 
   int longest = 0;
   while (s) {
     const int a = __builtin_ctz(s), b = __builtin_ctz(e), L = b - a + 1;
-    atomicAdd(&bins[((a == 0) | (b == RD_TS_HOURS - 1)) * RD_TS_HOURS + L - 1], 1u);
+    atomicAdd(&bins[((a == 0) | (b == RD_HOURS - 1)) * RD_HOURS + L - 1], 1u);
     longest = L > longest ? L : longest;
     s &= s - 1;
     e &= e - 1;
@@ -100,7 +98,7 @@ __device__ __forceinline__ int rd_ts_runs(unsigned* __restrict__ bins, unsigned 
 
 template <int V, int KMAX>
 __global__ void __launch_bounds__(RD_TS_THREADS)
-k_temporal_accumulate(const float* __restrict__ x, long n, long day_stride, long plane, rd_vf_thr thr, int T, int K,
+k_temporal_accumulate(const float* __restrict__ x, long n, long day_stride, long plane, rd_thr thr, int T, int K,
                       unsigned long long* __restrict__ counts, double* __restrict__ partial) {
   extern __shared__ double rd_ts_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -117,14 +115,14 @@ k_temporal_accumulate(const float* __restrict__ x, long n, long day_stride, long
   for (long g0 = (long)blockIdx.x * RD_TS_THREADS; g0 < groups; g0 += (long)gridDim.x * RD_TS_THREADS) {
     const long g = g0 + tid;
     const bool in = g < groups;
-    float v[RD_TS_HOURS][V];
+    float v[RD_HOURS][V];
     if (in) {
       const float* src = x + (g / gpp) * day_stride + (g % gpp) * V;
 #pragma unroll
-      for (int h = 0; h < RD_TS_HOURS; ++h) rd_vf_load<V>(src + (long)h * plane, v[h]);
+      for (int h = 0; h < RD_HOURS; ++h) rd_load<V>(src + (long)h * plane, v[h]);
     } else {
 #pragma unroll
-      for (int h = 0; h < RD_TS_HOURS; ++h)
+      for (int h = 0; h < RD_HOURS; ++h)
 #pragma unroll
         for (int j = 0; j < V; ++j) v[h][j] = 0.0f;
     }
@@ -134,17 +132,17 @@ k_temporal_accumulate(const float* __restrict__ x, long n, long day_stride, long
     for (int j = 0; j < V; ++j) {
       unsigned worst = 0;
 #pragma unroll
-      for (int h = 0; h < RD_TS_HOURS; ++h) {
-        const unsigned e = __float_as_uint(v[h][j]) & 0x7F800000u;
+      for (int h = 0; h < RD_HOURS; ++h) {
+        const unsigned e = __float_as_uint(v[h][j]) & RD_F32_EXP;
         worst = e > worst ? e : worst;
       }
-      const bool finite = worst != 0x7F800000u;
+      const bool finite = worst != RD_F32_EXP;
       ok[j] = in && finite;
       n_valid += ok[j];
       n_bad += in && !finite;
       if (!finite) {
 #pragma unroll
-        for (int h = 0; h < RD_TS_HOURS; ++h) v[h][j] = 0.0f;
+        for (int h = 0; h < RD_HOURS; ++h) v[h][j] = 0.0f;
       }
     }
 
@@ -169,11 +167,11 @@ k_temporal_accumulate(const float* __restrict__ x, long n, long day_stride, long
       for (int k = 0; k < KMAX; ++k) lg[k] = 0.0;
 #pragma unroll
       for (int j = 0; j < V; ++j) {
-        double d[RD_TS_HOURS];
+        double d[RD_HOURS];
 #pragma unroll
-        for (int h = 0; h < RD_TS_HOURS; ++h) d[h] = (double)rd_ts_again(v[h][j]);
+        for (int h = 0; h < RD_HOURS; ++h) d[h] = (double)rd_ts_again(v[h][j]);
 #pragma unroll
-        for (int h = 1; h < RD_TS_HOURS; ++h)                      // (hours outer: a widened hour is live for KMAX hours only)
+        for (int h = 1; h < RD_HOURS; ++h)                      // (hours outer: a widened hour is live for KMAX hours only)
 #pragma unroll
           for (int k = 1; k <= KMAX; ++k)
             if (h - k >= 0) lg[k - 1] = __builtin_fma(d[h - k], d[h], lg[k - 1]);
@@ -186,17 +184,17 @@ k_temporal_accumulate(const float* __restrict__ x, long n, long day_stride, long
 #pragma unroll
       for (int k = 1; k < RD_TS_MAXT; ++k) th = k == t ? thr.v[k] : th;
       unsigned* ct = tab + t * RD_TS_NL;
-      unsigned wet[RD_TS_HOURS], t11[RD_TS_HOURS - 1], n_dry = 0;          // the same in every lane: scalar registers
+      unsigned wet[RD_HOURS], t11[RD_HOURS - 1], n_dry = 0;          // the same in every lane: scalar registers
 #pragma unroll
-      for (int h = 0; h < RD_TS_HOURS; ++h) wet[h] = 0;
+      for (int h = 0; h < RD_HOURS; ++h) wet[h] = 0;
 #pragma unroll
-      for (int h = 0; h < RD_TS_HOURS - 1; ++h) t11[h] = 0;
+      for (int h = 0; h < RD_HOURS - 1; ++h) t11[h] = 0;
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         unsigned m = 0;
         unsigned long long prev = 0;
 #pragma unroll
-        for (int h = 0; h < RD_TS_HOURS; ++h) {
+        for (int h = 0; h < RD_HOURS; ++h) {
           const bool w = v[h][j] > th;
           const unsigned long long b = __ballot(w);
           m |= (unsigned)w << h;
@@ -217,13 +215,13 @@ k_temporal_accumulate(const float* __restrict__ x, long n, long day_stride, long
         if (n_dry) {
           atomicAdd(&ct[RD_TS_WH], n_dry);
           atomicAdd(&ct[RD_TS_LW], n_dry);
-          atomicAdd(&ct[RD_TS_DS + RD_TS_HOURS + RD_TS_HOURS - 1], n_dry);
+          atomicAdd(&ct[RD_TS_DS + RD_HOURS + RD_HOURS - 1], n_dry);
         }
 #pragma unroll
-        for (int h = 0; h < RD_TS_HOURS; ++h)
+        for (int h = 0; h < RD_HOURS; ++h)
           if (wet[h]) atomicAdd(&ct[RD_TS_LWET + h], wet[h]);
 #pragma unroll
-        for (int h = 0; h < RD_TS_HOURS - 1; ++h)
+        for (int h = 0; h < RD_HOURS - 1; ++h)
           if (t11[h]) atomicAdd(&ct[RD_TS_LT11 + h], t11[h]);
       }
       // wet_amount[t][h]: hours 0 .. 15, then 16 .. 23, onto the LDS slots this lane owns
@@ -255,12 +253,12 @@ k_temporal_accumulate(const float* __restrict__ x, long n, long day_stride, long
   const double* wall = rd_ts_lds + RD_TS_WAVES * RD_TS_TILE;             // [wave][t][2][64]
   for (int i = tid; i < nsums; i += RD_TS_THREADS) {
     double s = 0.0;
-    if (i < 2 * RD_TS_HOURS + K) {
-      const int b = i < 2 * RD_TS_HOURS ? i >> 4 : 3, r = i < 2 * RD_TS_HOURS ? i & 15 : i - 2 * RD_TS_HOURS;
+    if (i < 2 * RD_HOURS + K) {
+      const int b = i < 2 * RD_HOURS ? i >> 4 : 3, r = i < 2 * RD_HOURS ? i & 15 : i - 2 * RD_HOURS;
       for (int w = 0; w < RD_TS_WAVES; ++w)
         for (int sg = 0; sg < 4; ++sg) s += fin[b * RD_TS_THREADS + w * 64 + sg * 16 + r];
     } else {
-      const int t = (i - 2 * RD_TS_HOURS - K) / RD_TS_HOURS, h = (i - 2 * RD_TS_HOURS - K) % RD_TS_HOURS;
+      const int t = (i - 2 * RD_HOURS - K) / RD_HOURS, h = (i - 2 * RD_HOURS - K) % RD_HOURS;
       for (int w = 0; w < RD_TS_WAVES; ++w) {
         const double* a = wall + ((long)(w * T + t) * 2 + (h >= 16)) * 64;
         if (h < 16)
@@ -278,8 +276,8 @@ k_temporal_accumulate(const float* __restrict__ x, long n, long day_stride, long
     const unsigned val = tab[t * RD_TS_NL + c];
     if (val) atomicAdd(&counts[(long)t * RD_TS_NC + c], (unsigned long long)val);
   }
-  for (int i = tid; i < T * (RD_TS_HOURS - 1); i += RD_TS_THREADS) {
-    const int t = i / (RD_TS_HOURS - 1), h = i % (RD_TS_HOURS - 1);
+  for (int i = tid; i < T * (RD_HOURS - 1); i += RD_TS_THREADS) {
+    const int t = i / (RD_HOURS - 1), h = i % (RD_HOURS - 1);
     const unsigned* ct = tab + t * RD_TS_NL;
     const unsigned long long w0 = ct[RD_TS_LWET + h], w1 = ct[RD_TS_LWET + h + 1], b = ct[RD_TS_LT11 + h];
     unsigned long long* dst = counts + (long)t * RD_TS_NC + RD_TS_TR + h * 4;

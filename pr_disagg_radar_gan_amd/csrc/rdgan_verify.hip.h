@@ -23,32 +23,20 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rdgan_rng.h"
+#include "rdgan_hourly.hip.h"
 
-#define RD_VF_MAXT 8
+#define RD_VF_MAXT RD_THR_MAX
 #define RD_VF_MAXW 8
 #define RD_VF_MAXS 4096
 #define RD_VF_MAXBINS 64
-#define RD_VF_HOURS 24
 #define RD_VF_THREADS 256
 #define RD_VF_CHUNK 2048                 // positions of one (day, hour) plane a workgroup of k_verify_reduce takes at a time
 #define RD_VF_MAXUNITS 256               // chunks per workgroup at most: 2^19 positions, sum c <= 2^31 in a 32-bit LDS counter
 #define RD_VF_BOX_MAXBLOCKS 128          // workgroups of k_verify_fss_box per plane
 
-struct rd_vf_thr {
-  float v[RD_VF_MAXT];
-};
 struct rd_vf_widths {
   int v[RD_VF_MAXW];
 };
-
-template <int V> __device__ __forceinline__ void rd_vf_load(const float* __restrict__ p, float (&v)[V]) {
-  if constexpr (V == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-    v[0] = *p;
-  }
-}
 
 template <int V> __device__ __forceinline__ void rd_vf_add(int* __restrict__ p, const int (&a)[V]) {
   if constexpr (V == 4) {
@@ -62,13 +50,13 @@ template <int V> __device__ __forceinline__ void rd_vf_add(int* __restrict__ p, 
 
 template <int T, int V>
 __global__ void __launch_bounds__(RD_VF_THREADS)
-k_verify_accumulate(const float* __restrict__ x, long member_stride, int n, long P, const float* __restrict__ obs, rd_vf_thr thr,
+k_verify_accumulate(const float* __restrict__ x, long member_stride, int n, long P, const float* __restrict__ obs, rd_thr thr,
                     int* __restrict__ exceed, int* __restrict__ below, int* __restrict__ equal, unsigned char* __restrict__ bad) {
   const long groups = P / V;                                              // (V = 4 is chosen only for P % 4 == 0)
   for (long g = (long)blockIdx.x * RD_VF_THREADS + threadIdx.x; g < groups; g += (long)gridDim.x * RD_VF_THREADS) {
     const long p = g * V;
     float o[V];
-    rd_vf_load<V>(obs + p, o);
+    rd_load<V>(obs + p, o);
     int ex[T][V], bl[V], eq[V], nn[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
@@ -82,7 +70,7 @@ k_verify_accumulate(const float* __restrict__ x, long member_stride, int n, long
 #pragma unroll 4
     for (int s = 0; s < n; ++s) {
       float v[V];
-      rd_vf_load<V>(src + (long)s * member_stride, v);
+      rd_load<V>(src + (long)s * member_stride, v);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         bl[j] += v[j] < o[j];
@@ -110,7 +98,7 @@ k_verify_accumulate(const float* __restrict__ x, long member_stride, int n, long
 __global__ void __launch_bounds__(RD_VF_THREADS)
 k_verify_reduce(const float* __restrict__ obs, const int* __restrict__ exceed, const int* __restrict__ below,
                 const int* __restrict__ equal, const unsigned char* __restrict__ bad, long P, long plane, long n_planes, int S, int T,
-                rd_vf_thr thr, int n_bins, uint32_t key, unsigned long long* __restrict__ rank_hist,
+                rd_thr thr, int n_bins, uint32_t key, unsigned long long* __restrict__ rank_hist,
                 unsigned long long* __restrict__ reliability, unsigned long long* __restrict__ brier) {
   extern __shared__ unsigned long long rd_vf_lds[];
   unsigned long long* bs = rd_vf_lds;                                      // [T][4]
@@ -122,7 +110,7 @@ k_verify_reduce(const float* __restrict__ obs, const int* __restrict__ exceed, c
   for (int i = tid; i < n_rel + S + 1; i += RD_VF_THREADS) rel[i] = 0u;
   __syncthreads();
   // the planes of this hour are q = hour, hour + 24, ..: the last day may stop short of 24 hours
-  const long chunks = (plane + RD_VF_CHUNK - 1) / RD_VF_CHUNK, units = ((n_planes + RD_VF_HOURS - 1) / RD_VF_HOURS) * chunks;
+  const long chunks = (plane + RD_VF_CHUNK - 1) / RD_VF_CHUNK, units = ((n_planes + RD_HOURS - 1) / RD_HOURS) * chunks;
   unsigned n_valid = 0, se[RD_VF_MAXT], sce[RD_VF_MAXT];
   unsigned long long sc2[RD_VF_MAXT];
 #pragma unroll
@@ -132,7 +120,7 @@ k_verify_reduce(const float* __restrict__ obs, const int* __restrict__ exceed, c
     sc2[t] = 0;
   }
   for (long u = blockIdx.x; u < units; u += gridDim.x) {
-    const long q = (u / chunks) * RD_VF_HOURS + hour;
+    const long q = (u / chunks) * RD_HOURS + hour;
     if (q >= n_planes) continue;
     const long base = q * plane;
     const long i0 = (u % chunks) * RD_VF_CHUNK, i1 = i0 + RD_VF_CHUNK < plane ? i0 + RD_VF_CHUNK : plane;
@@ -175,10 +163,10 @@ k_verify_reduce(const float* __restrict__ obs, const int* __restrict__ exceed, c
   for (int i = tid; i < n_rel; i += RD_VF_THREADS)
     if (rel[i]) {
       const int t = i / (n_bins * 3), rest = i % (n_bins * 3);
-      atomicAdd(&reliability[((long)t * RD_VF_HOURS + hour) * n_bins * 3 + rest], (unsigned long long)rel[i]);
+      atomicAdd(&reliability[((long)t * RD_HOURS + hour) * n_bins * 3 + rest], (unsigned long long)rel[i]);
     }
   for (int i = tid; i < T * 4; i += RD_VF_THREADS)
-    if (bs[i]) atomicAdd(&brier[((long)(i >> 2) * RD_VF_HOURS + hour) * 4 + (i & 3)], bs[i]);
+    if (bs[i]) atomicAdd(&brier[((long)(i >> 2) * RD_HOURS + hour) * 4 + (i & 3)], bs[i]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -186,17 +174,17 @@ k_verify_reduce(const float* __restrict__ obs, const int* __restrict__ exceed, c
 // One wave per row (a workgroup takes 4): the inclusive scan of 64 values by shuffles, a carry from segment to segment.
 __global__ void __launch_bounds__(RD_VF_THREADS)
 k_verify_fss_rows(const float* __restrict__ obs, const int* __restrict__ exceed, const unsigned char* __restrict__ bad, long P,
-                  long day, int ny, int nx, int S, int T, rd_vf_thr thr, unsigned* __restrict__ satC, unsigned* __restrict__ satE) {
+                  long day, int ny, int nx, int S, int T, rd_thr thr, unsigned* __restrict__ satC, unsigned* __restrict__ satE) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * (RD_VF_THREADS / 64) + (threadIdx.x >> 6);      // the same in all lanes of a wave
-  if (row >= (long)RD_VF_HOURS * T * ny) return;
+  if (row >= (long)RD_HOURS * T * ny) return;
   const int y = (int)(row % ny);
   const long q = row / ny;
   const int t = (int)(q % T), hour = (int)(q / T);
   float th = thr.v[0];
 #pragma unroll
   for (int k = 1; k < RD_VF_MAXT; ++k) th = k == t ? thr.v[k] : th;
-  const long src = ((day * RD_VF_HOURS + hour) * ny + y) * (long)nx, dst = row * (long)nx;
+  const long src = ((day * RD_HOURS + hour) * ny + y) * (long)nx, dst = row * (long)nx;
   const int* ex = exceed + (long)t * P + src;
   unsigned carry_c = 0, carry_e = 0;
   for (int x0 = 0; x0 < nx; x0 += 64) {
@@ -308,7 +296,7 @@ k_verify_fss_box(const unsigned* __restrict__ satC, const unsigned* __restrict__
 __global__ void __launch_bounds__(RD_VF_THREADS)
 k_verify_fss_final(const double* __restrict__ partial, int nblk, int T, int W, double* __restrict__ fss_sums) {
   const int j = blockIdx.x * RD_VF_THREADS + threadIdx.x;
-  if (j >= RD_VF_HOURS * T * W) return;
+  if (j >= RD_HOURS * T * W) return;
   const int i = j % W, q = j / W, t = q % T, hour = q / T;
   double num = 0.0, den = 0.0;
   for (int b = 0; b < nblk; ++b) {
@@ -316,7 +304,7 @@ k_verify_fss_final(const double* __restrict__ partial, int nblk, int T, int W, d
     num += src[0];
     den += src[1];
   }
-  double* dst = fss_sums + (((long)t * W + i) * RD_VF_HOURS + hour) * 2;
+  double* dst = fss_sums + (((long)t * W + i) * RD_HOURS + hour) * 2;
   dst[0] += num;
   dst[1] += den;
 }

@@ -19,12 +19,11 @@ from . import _lib, crps_experiment, ensemble, rainfarm
 from . import weights as W
 from ._dev import device_f32, ptr as _p, stream as _stream, whole_number, workspace_bytes
 from .analog import AnalogLibrary
-from .cascade import MAX_PLANE as CASCADE_MAX_PLANE, CascadeModel
+from ._hourly import MAX_PLANE, NHOURS
+from .cascade import CascadeModel
 from .engine import require_gpu
 
-NHOURS = 24
 MAX_MEMBERS = crps_experiment.MAX_MEMBERS                                    # RD_MV_MAXM
-MAX_PLANE = 1 << 24                                                          # RD_MV_MAXPLANE
 MAX_DAYS = 1 << 20                                                           # RD_MV_MAXDAYS
 MAX_RADIUS = 4                                                               # RD_MV_MAXR
 MAX_LAG = 3                                                                  # RD_MV_MAXLAG
@@ -284,7 +283,7 @@ def multivariate_experiment(gen, reals_precip, climatology, slopes=None, library
         raise ValueError(f"query_groups: {shape[0]} groups and a library expected")
     if cascade is not None and not isinstance(cascade, CascadeModel):
         raise ValueError("cascade: expected a cascade.CascadeModel")
-    cascade_patch = whole_number(cascade_patch, 1, CASCADE_MAX_PLANE, "cascade_patch")
+    cascade_patch = whole_number(cascade_patch, 1, MAX_PLANE, "cascade_patch")
     m = whole_number(n_members, 1, MAX_MEMBERS, "n_members")
     seed = whole_number(seed, 0, (1 << 62), "seed")
     score = dict(fair=fair, p=check_order(p), radius=check_radius(radius), max_lag=check_max_lag(max_lag),

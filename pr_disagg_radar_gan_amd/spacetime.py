@@ -18,12 +18,11 @@ import torch
 
 from . import weights as W
 from ._dev import host_ptr as _hp, ptr as _p, whole_number
-from ._hourly import NHOURS, HourlyAccumulator, div as _div, evaluate_field, tv as _tv
+from ._hourly import MAX_PLANE, NHOURS, HourlyAccumulator, div as _div, evaluate_field, tv as _tv
 from .verification import check_event_thresholds
 
 MAX_RADIUS = 8                                                               # RD_ST_MAXR
 MAX_LAG = 6                                                                  # RD_ST_MAXK
-MAX_PLANE = 1 << 24                                                          # RD_ST_MAXPLANE
 MAX_PASS = 65520                                                             # RD_ST_MAXPASS: planes of a pass, 2730 days
 MAX_TILE_WORDS = 8                                                           # RD_ST_MAXCW
 LDS_WORDS = 4096                                                             # RD_ST_LDS_WORDS

@@ -20,8 +20,8 @@ import torch
 
 from . import weights as W
 from ._dev import host_ptr as _hp, ptr as _p, whole_number
-from ._hourly import NHOURS, admit, div as _div, evaluate_field, tv as _tv
-from .cells import MAX_PLANE, VOLUME_UNIT, LabelAccumulator, check_connectivity
+from ._hourly import MAX_PLANE, NHOURS, admit, div as _div, evaluate_field, tv as _tv
+from .cells import VOLUME_UNIT, LabelAccumulator, check_connectivity
 from .engine import require_gpu
 from .verification import check_event_thresholds
 

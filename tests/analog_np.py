@@ -5,20 +5,11 @@ is the definition.  tests/test_analog_host.py checks the two forms against each 
 import numpy as np
 
 from oracle import rng as orng
+from tests.hourly_np import quantise
 
 NHOURS = 24
 STREAM_ANALOG = 9
 NONE = np.int64(1) << np.int64(62)                                           # above every key
-
-
-def quantise(x, limit):
-    """x float32 -> (q int64, bad bool): q = rint(x * 1024), the product in fp32, ties to even, 0 where bad; bad where x is NaN,
-    +-inf, negative or >= limit"""
-    x = np.asarray(x, dtype=np.float32)
-    with np.errstate(invalid="ignore"):
-        bad = ~((x >= 0) & (x < limit))
-        q = np.rint(np.where(bad, np.float32(0), x) * np.float32(1024)).astype(np.int64)
-    return q, bad
 
 
 def isqrt(D):

@@ -5,6 +5,8 @@ checks them against each other and against answers worked out by hand.  No code 
 project has no such code, so this file is the definition."""
 import numpy as np
 
+from tests.hourly_np import levels_q as level_q, quantise
+
 NHOURS, NARF = 24, 21
 ORDER = ("level_count", "start_hour", "arf_hist", "sum_A", "sum_A1", "sum_A_all", "max_A", "n_days", "n_void", "n_dry")
 
@@ -14,20 +16,6 @@ def days_of(x):
     x = np.asarray(x, dtype=np.float32)
     assert x.ndim >= 3 and x.shape[-3] == NHOURS
     return x.reshape((-1,) + x.shape[-3:])
-
-
-def quantise(day):
-    """day float32 -> (q int64, bad bool): q = rint(x * 1024) with the product in fp32 and ties to even, 0 where bad; bad where x
-    is NaN, +-inf, negative or >= 2048"""
-    day = np.asarray(day, dtype=np.float32)
-    with np.errstate(invalid="ignore"):
-        bad = ~((day >= 0) & (day < 2048))
-        q = np.rint(np.where(bad, np.float32(0), day) * np.float32(1024)).astype(np.int64)
-    return q, bad
-
-
-def level_q(levels):
-    return [int(np.rint(np.float64(v) * 1024.0)) for v in levels]
 
 
 def day_maxima_brute(day, windows, widths):

@@ -21,9 +21,9 @@ last three words and holds, per row, cumulative 24-bit thresholds."""
 import numpy as np
 
 from oracle import rng as orng
+from tests.hourly_np import UNIT, levels_q, quantise
 
 NHOURS = 24
-UNIT = 1024
 NB = 32
 NP = 4
 NL = 3
@@ -50,17 +50,7 @@ def state_size(n_edges):
 
 def edge_units(edges):
     """the integer thresholds per hour: rint(e * 1024), the product in fp64"""
-    return [int(np.rint(np.float64(e) * 1024.0)) for e in edges]
-
-
-def quantise(x, limit):
-    """x float32 -> (q int64, bad bool): q = rint(x * 1024), the product in fp32, 0 where bad; bad where x is NaN, +-inf, negative or
-    >= limit"""
-    x = np.asarray(x, dtype=np.float32)
-    with np.errstate(invalid="ignore"):
-        bad = ~((x >= 0) & (x < limit))
-        q = np.rint(np.where(bad, np.float32(0), x) * np.float32(1024)).astype(np.int64)
-    return q, bad
+    return levels_q(edges)
 
 
 def vclass(V, eq, hours):

@@ -4,6 +4,8 @@ checks it against answers worked out by hand.  No code is shared with the module
 this file is the definition."""
 import numpy as np
 
+from tests.hourly_np import levels_q as level_q, quantise
+
 NHOURS = 24
 ORDER = ("level_count", "start_hour", "sum_A", "max_A", "n_days", "n_void", "n_dry")
 
@@ -24,20 +26,6 @@ def members_of(regions=None, masks=None, valid=None):
         masks = np.stack([regions == c for c in range(int(regions.max()) + 1)])
     ok = np.ones(masks.shape[1:], bool) if valid is None else np.asarray(valid, bool)
     return [np.flatnonzero(m & ok) for m in np.asarray(masks, bool)]
-
-
-def quantise(day):
-    """day float32 -> (q int64, bad bool): q = rint(x * 1024) with the product in fp32 and ties to even, 0 where bad; bad where x
-    is NaN, +-inf, negative or >= 2048"""
-    day = np.asarray(day, dtype=np.float32)
-    with np.errstate(invalid="ignore"):
-        bad = ~((day >= 0) & (day < 2048))
-        q = np.rint(np.where(bad, np.float32(0), np.float32(day)) * np.float32(1024)).astype(np.int64)
-    return q, bad
-
-
-def level_q(levels):
-    return [int(np.rint(np.float64(v) * 1024.0)) for v in levels]
 
 
 def window_maximum(P, B, k):

@@ -1,6 +1,6 @@
 // csrc/rdgan_hourly_host.h compiled WITHOUT HIP and with the address and undefined-behaviour sanitizers
-// (tests/test_hourly_host.py): one line "name value" per probe of rd_hourly_layout_ok, rd_pass_units and rd_aligned at their
-// edges; the test holds the expected values.
+// (tests/test_hourly_host.py): one line "name value" per probe of rd_hourly_layout_ok, rd_pass_units, rd_aligned and rd_vec4_ok at
+// their edges; the test holds the expected values.
 #include <stdio.h>
 #include "../../pr_disagg_radar_gan_amd/csrc/rdgan_hourly_host.h"
 
@@ -42,5 +42,10 @@ int main() {
   printf("aligned_all %d\n", rd_aligned(7, (const void*)buf, (const void*)(buf + 2), (const void*)nullptr));
   printf("aligned_one_on_4 %d\n", rd_aligned(7, (const void*)buf, (const void*)(buf + 1)));
   printf("aligned_4_is_enough %d\n", rd_aligned(3, (const void*)(buf + 1)));
+  // the 16-byte route: the pointer on 16 bytes, the row and the day stride multiples of 4
+  printf("vec4_aligned %d\n", rd_vec4_ok(x, 4 * 8, 24 * 32 + 4));
+  printf("vec4_off_by_4_bytes %d\n", rd_vec4_ok((const char*)buf + 4, 4 * 8, 24 * 32 + 4));
+  printf("vec4_plane_not_of_4 %d\n", rd_vec4_ok(x, 5 * 7, 24 * 35));
+  printf("vec4_stride_not_of_4 %d\n", rd_vec4_ok(x, 4 * 8, 24 * 32 + 2));
   return 0;
 }

@@ -227,9 +227,10 @@ def test_header_and_lib_agree_on_the_analog_entries():
 
 def test_python_constants_are_the_kernel_header_s():
     text = open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", "rdgan_analog.hip.h")).read()
+    text += "".join(open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", h)).read() for h in ("rdgan_hourly_host.h", "rdgan_hourly.hip.h"))
     value = lambda name: eval(re.search(r"^#define " + name + r"\s+(\S.*?)\s*(//.*)?$", text, re.M).group(1).replace("L", ""))
     assert (AN.MAX_PLANE, AN.MAX_LIBRARY, AN.MAX_QUERIES, AN.MAX_K, AN.MAX_MEMBERS, AN.BLOCK, AN.WAVES, AN.NHOURS) == tuple(
-        value(m) for m in ("RD_AN_MAXP", "RD_AN_MAXN", "RD_AN_MAXQ", "RD_AN_MAXK", "RD_AN_MAXS", "RD_AN_BLOCK", "RD_AN_WAVES", "RD_AN_HOURS"))
+        value(m) for m in ("RD_AN_MAXP", "RD_AN_MAXN", "RD_AN_MAXQ", "RD_AN_MAXK", "RD_AN_MAXS", "RD_AN_BLOCK", "RD_AN_WAVES", "RD_HOURS"))
     assert (AN.WEIGHTS["uniform"], AN.WEIGHTS["rank"]) == (value("RD_AN_UNIFORM"), value("RD_AN_RANK"))
     assert (AN.query_tile(256), AN.query_tile(4096), 2048) == (value("RD_AN_QT_SMALL"), value("RD_AN_QT_LARGE"), value("RD_AN_QT_SPLIT"))
     assert value("RD_AN_THREADS") == 64 * AN.WAVES and value("RD_AN_WIDEN") * 8 * 8191 ** 2 < 2 ** 32 and AN.UNIT == 1024

@@ -250,9 +250,10 @@ def test_header_and_lib_agree_on_the_areal_entries():
 
 def test_python_constants_are_the_kernel_header_s():
     text = open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", "rdgan_areal.hip.h")).read()
+    text += "".join(open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", h)).read() for h in ("rdgan_hourly_host.h", "rdgan_hourly.hip.h"))
     value = lambda name: eval(re.search(r"^#define " + name + r"\s+(\S.*?)\s*(//.*)?$", text, re.M).group(1).replace("L", ""))
     assert (AR.MAX_WINDOWS, AR.MAX_WIDTHS, AR.MAX_WIDTH, AR.MAX_LEVELS, AR.N_ARF, AR.N_FIXED, AR.MAX_PLANE, AR.MAX_PASS, AR.NHOURS) == tuple(
-        value(m) for m in ("RD_AR_MAXK", "RD_AR_MAXW", "RD_AR_MAXWIDTH", "RD_AR_MAXL", "RD_AR_NARF", "RD_AR_FIXED", "RD_AR_MAXPLANE", "RD_AR_MAXPASS", "RD_AR_HOURS"))
+        value(m) for m in ("RD_AR_MAXK", "RD_AR_MAXW", "RD_AR_MAXWIDTH", "RD_AR_MAXL", "RD_AR_NARF", "RD_AR_FIXED", "RD_HOURLY_MAXPLANE", "RD_AR_MAXPASS", "RD_HOURS"))
     offsets = (AR._START, AR._ARF, AR._SUM_A, AR._SUM_A1, AR._SUM_ALL, AR._MAX_A, AR._NDAYS, AR._NVOID, AR._NDRY)
     assert offsets == tuple(value(m) for m in ("RD_AR_START", "RD_AR_ARF", "RD_AR_SUM_A", "RD_AR_SUM_A1", "RD_AR_SUM_ALL", "RD_AR_MAX_A", "RD_AR_NDAYS",
                                                "RD_AR_NVOID", "RD_AR_NDRY"))

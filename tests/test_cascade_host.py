@@ -331,9 +331,10 @@ def test_header_and_lib_agree_on_the_cascade_entries():
 
 def test_python_constants_are_the_kernel_header_s():
     text = open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", "rdgan_cascade.hip.h")).read()
+    text += "".join(open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", h)).read() for h in ("rdgan_hourly_host.h", "rdgan_hourly.hip.h"))
     value = lambda name: eval(re.search(r"^#define " + name + r"\s+(\S.*?)\s*(//.*)?$", text, re.M).group(1).replace("L", ""))
-    names = ("RD_CS_HOURS", "RD_CS_NB", "RD_CS_NP", "RD_CS_NL", "RD_CS_NT", "RD_CS_MAXE", "RD_CS_PER_CLASS", "RD_CS_TAIL", "RD_CS_MAXEDGE", "RD_CS_MAXPLANE",
-             "RD_CS_MAXELEMS", "RD_CS_MAXQ", "RD_CS_MAXS", "RD_CS_MAXCOND")
+    names = ("RD_HOURS", "RD_CS_NB", "RD_CS_NP", "RD_CS_NL", "RD_CS_NT", "RD_CS_MAXE", "RD_CS_PER_CLASS", "RD_CS_TAIL", "RD_CS_MAXEDGE", "RD_HOURLY_MAXPLANE",
+             "RD_HOURLY_MAXELEMS", "RD_CS_MAXQ", "RD_CS_MAXS", "RD_CS_MAXCOND")
     ours = (C.NHOURS, C.NB, C.NP, C.NL, C.NT, C.MAX_EDGES, C.PER_CLASS, C.TAIL, C.MAX_EDGE, C.MAX_PLANE, C.MAX_ELEMS, C.MAX_QUERIES, C.MAX_MEMBERS, C.MAX_COND)
     assert ours == tuple(value(n) for n in names)
     assert ours[:8] + (C.MAX_COND,) == (cn.NHOURS, cn.NB, cn.NP, cn.NL, cn.NT, cn.MAX_EDGES, cn.PER_CLASS, cn.TAIL, cn.MAX_COND)

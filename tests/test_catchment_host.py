@@ -318,10 +318,11 @@ def test_header_lib_and_kernel_constants_agree():
     assert listed == {name: (off + 1 if name != "level_count" else 0) for name, off in zip(cn.ORDER, offsets)}
     assert f"C * K * (L + {CT.N_FIXED + 1}) + 2" in header
     text = open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", "rdgan_catchment.hip.h")).read()
+    text += "".join(open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", h)).read() for h in ("rdgan_hourly_host.h", "rdgan_hourly.hip.h"))
     value = lambda name: eval(re.search(r"^#define " + name + r"\s+(\S.*?)\s*(//.*)?$", text, re.M).group(1).replace("L", ""))
     assert (CT.CHUNK, CT.MAX_CATCHMENTS, CT.MAX_PLANE, CT.MAX_ENTRIES, CT.MAX_PASS, CT.MAX_GROUPS, CT.N_FIXED, CT.NHOURS) == tuple(
-        value(m) for m in ("RD_CT_CHUNK", "RD_CT_MAXCATCH", "RD_CT_MAXPLANE", "RD_CT_MAXENTRIES", "RD_CT_MAXPASS", "RD_CT_MAXGROUPS", "RD_CT_FIXED",
-                           "RD_CT_HOURS"))
+        value(m) for m in ("RD_CT_CHUNK", "RD_CT_MAXCATCH", "RD_HOURLY_MAXPLANE", "RD_CT_MAXENTRIES", "RD_CT_MAXPASS", "RD_CT_MAXGROUPS", "RD_CT_FIXED",
+                           "RD_HOURS"))
     assert offsets[1:] == tuple(value(m) for m in ("RD_CT_START", "RD_CT_SUM_A", "RD_CT_MAX_A", "RD_CT_NDAYS", "RD_CT_NVOID", "RD_CT_NDRY"))
     assert value("RD_CT_MAXCHUNKS") > CT.MAX_ENTRIES // CT.CHUNK + CT.MAX_CATCHMENTS and value("RD_CT_CHUNK") == value("RD_CT_THREADS")
     from pr_disagg_radar_gan_amd import areal as AR

@@ -239,9 +239,10 @@ def test_header_and_lib_agree_on_the_cells_entries():
 
 def test_python_constants_are_the_kernel_header_s():
     text = open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", "rdgan_cells.hip.h")).read()
+    text += "".join(open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", h)).read() for h in ("rdgan_hourly_host.h", "rdgan_hourly.hip.h"))
     value = lambda name: eval(re.search(r"^#define " + name + r"\s+(\S.*?)\s*(//.*)?$", text, re.M).group(1).replace("L", ""))
     assert (CL.N_COUNTS, CL.N_BINS, CL.N_KPP, CL.MAX_PLANE, CL.MAX_PASS, CL.NHOURS) == tuple(
-        value(m) for m in ("RD_CL_NC", "RD_CL_NBINS", "RD_CL_NKP", "RD_CL_MAXPLANE", "RD_CL_MAXPASS", "RD_CL_HOURS"))
+        value(m) for m in ("RD_CL_NC", "RD_CL_NBINS", "RD_CL_NKP", "RD_HOURLY_MAXPLANE", "RD_CL_MAXPASS", "RD_HOURS"))
     assert (CL._WET, CL._CELLS, CL._HIST, CL._ASUM, CL._ASQ, CL._VBA, CL._KPP, CL._LARGEST, CL._DRY, CL._ABA) == tuple(
         value(m) for m in ("RD_CL_WET", "RD_CL_CELLS", "RD_CL_HIST", "RD_CL_ASUM", "RD_CL_ASQ", "RD_CL_VBA", "RD_CL_KPP", "RD_CL_LARGEST", "RD_CL_DRY",
                            "RD_CL_ABA"))

@@ -135,3 +135,18 @@ def test_upload_or_refusal_once_the_state_exists():
     assert H.to_state_device(t, False, torch.device("cpu")) is t
     with pytest.raises(ValueError, match="lies on cpu, the state on meta"):
         H.to_state_device(t, False, torch.device("meta"))
+
+
+def test_the_numpy_quantiser_against_literals():
+    """tests/hourly_np.quantise, the yardstick of the fixed-point depth in four restatements, pinned to values worked out by hand:
+    the fp32 product rounds ties to even, the range is 0 <= x < 2048 with -0.0 inside it, and NaN and both infinities are bad"""
+    from tests import hourly_np as hn
+    below = np.nextafter(np.float32(2048), np.float32(0))
+    x = np.array([0.5 / 1024, 1.5 / 1024, 2.5 / 1024, below, 2048.0, -0.0, -1e-30, np.nan, np.inf, -np.inf], np.float32)
+    q, bad = hn.quantise(x)
+    assert bad.tolist() == [False, False, False, False, True, False, True, True, True, True]
+    # (2048 - 2^-13) * 1024 = 2^21 - 1/8 is exact in fp32 and rounds up to 2^21
+    assert q[:3].tolist() == [0, 2, 2] and q[5] == 0 and q[3] == 2048 * 1024 and q[bad].tolist() == [0] * 5
+    assert q.dtype == np.int64 and hn.quantise(np.float32(2048.0), 2048 * 24)[1] == False and hn.quantise(np.float32(49152.0), 2048 * 24)[1] == True  # noqa: E712
+    assert hn.levels_q((0.0, 0.00048828125, 0.00146484375, 49152.0)) == [0, 0, 2, 49152 * 1024]        # fp64 product, ties to even
+    assert (hn.UNIT, hn.MAX_DEPTH) == (H.UNIT, H.MAX_DEPTH) == (1024, 2048)

@@ -24,6 +24,8 @@ WANT = {
     "pass_negative": 0, "pass_zero": 0, "pass_below_unit": 0, "pass_one_unit": 1, "pass_below_two": 1, "pass_five": 5,
     "pass_more_than_input": 72, "pass_more_than_max": 65535, "pass_at_max": 65535, "pass_largest_size": 2730,
     "aligned_all": 1, "aligned_one_on_4": 0, "aligned_4_is_enough": 1,
+    # the 16-byte route: x on 16 bytes, the plane (or nx) and the day stride multiples of 4
+    "vec4_aligned": 1, "vec4_off_by_4_bytes": 0, "vec4_plane_not_of_4": 0, "vec4_stride_not_of_4": 0,
 }
 
 

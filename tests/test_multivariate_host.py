@@ -195,9 +195,10 @@ def test_header_and_lib_agree_on_the_entries():
 
 def test_python_constants_are_the_kernel_header_s():
     text = open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", "rdgan_mvscore.hip.h")).read()
+    text += "".join(open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", h)).read() for h in ("rdgan_hourly_host.h", "rdgan_hourly.hip.h"))
     value = lambda name: eval(re.search(r"^#define " + name + r"\s+(\S.*?)\s*(//.*)?$", text, re.M).group(1).replace("L", ""))
     assert (MV.MAX_MEMBERS, MV.MAX_PLANE, MV.MAX_DAYS, MV.MAX_RADIUS, MV.MAX_LAG, MV.NHOURS) == tuple(
-        value(n) for n in ("RD_MV_MAXM", "RD_MV_MAXPLANE", "RD_MV_MAXDAYS", "RD_MV_MAXR", "RD_MV_MAXLAG", "RD_MV_HOURS"))
+        value(n) for n in ("RD_MV_MAXM", "RD_HOURLY_MAXPLANE", "RD_MV_MAXDAYS", "RD_MV_MAXR", "RD_MV_MAXLAG", "RD_HOURS"))
     # the panels of the widest energy kernel (three, two buffers) fit the 64 KB a workgroup gets without asking; rows stay 16-byte aligned
     assert 2 * 3 * value("RD_MV_TILE") * value("RD_MV_LDK") * 4 <= 64 * 1024 and value("RD_MV_LDK") % 4 == 0 and value("RD_MV_LDK") >= value("RD_MV_CHUNK")
     assert value("RD_MV_TILE") * value("RD_MV_CHUNK") == value("RD_MV_STAGE") * value("RD_MV_THREADS")

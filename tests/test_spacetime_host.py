@@ -248,7 +248,8 @@ def test_header_and_lib_agree_on_the_spacetime_entries():
 
 def test_python_constants_are_the_kernel_header_s():
     text = open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", "rdgan_spacetime.hip.h")).read()
+    text += "".join(open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", h)).read() for h in ("rdgan_hourly_host.h", "rdgan_hourly.hip.h"))
     value = lambda name: eval(re.search(r"^#define " + name + r"\s+(\S.*?)\s*(//.*)?$", text, re.M).group(1).replace("L", ""))
     assert (ST.MAX_RADIUS, ST.MAX_LAG, ST.MAX_PLANE, ST.MAX_PASS, ST.MAX_TILE_WORDS, ST.LDS_WORDS, ST.NHOURS) == tuple(
-        value(m) for m in ("RD_ST_MAXR", "RD_ST_MAXK", "RD_ST_MAXPLANE", "RD_ST_MAXPASS", "RD_ST_MAXCW", "RD_ST_LDS_WORDS", "RD_ST_HOURS"))
+        value(m) for m in ("RD_ST_MAXR", "RD_ST_MAXK", "RD_HOURLY_MAXPLANE", "RD_ST_MAXPASS", "RD_ST_MAXCW", "RD_ST_LDS_WORDS", "RD_HOURS"))
     assert value("RD_ST_HPB") * value("RD_ST_GROUPS") == 24 and ST.MAX_PASS % 24 == 0

@@ -227,11 +227,11 @@ def test_tensor_layout_refuses_what_a_stride_cannot_express():
 
 def test_python_constants_are_the_kernel_header_s():
     text = open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", "rdgan_temporal.hip.h")).read()
-    text += open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", "rdgan_verify.hip.h")).read()
+    text += "".join(open(os.path.join(ROOT, "pr_disagg_radar_gan_amd", "csrc", h)).read() for h in ("rdgan_verify.hip.h", "rdgan_hourly_host.h", "rdgan_hourly.hip.h"))
     macro = lambda name: re.search(r"^#define " + name + r"\s+(\S+)", text, re.M).group(1)
     value = lambda name: int(macro(name)) if macro(name).isdigit() else int(macro(macro(name)))
     assert (TS.THREADS, TS.MAX_BLOCKS, TS.MAX_LAG, TS.N_COUNTS, TS.NHOURS) == tuple(
-        value(m) for m in ("RD_TS_THREADS", "RD_TS_MAXBLOCKS", "RD_TS_MAXK", "RD_TS_NC", "RD_TS_HOURS"))
+        value(m) for m in ("RD_TS_THREADS", "RD_TS_MAXBLOCKS", "RD_TS_MAXK", "RD_TS_NC", "RD_HOURS"))
     assert (TS._WH, TS._LW, TS._WS, TS._DS, TS._FW, TS._LAST, TS._TR) == tuple(
         value(m) for m in ("RD_TS_WH", "RD_TS_LW", "RD_TS_WS", "RD_TS_DS", "RD_TS_FW", "RD_TS_LAST", "RD_TS_TR"))
     from pr_disagg_radar_gan_amd import verification as V
