@@ -891,6 +891,36 @@ int rdgan_cascade_generate(const unsigned* model, const int* edge_units, int n_e
                            long first_query, long ny, long nx, int n_members, long first_member, unsigned long long seed, int patch,
                            float* out, int* units_out, void* stream);
 
+/* Extremes of hourly fields (csrc/rdgan_extremes.hip.h): block maxima of the k-hour depths of every pixel, and
+ * the integer sums that give the L-moments of series of such maxima.
+ * The block-maxima entry: hourly, n, day_stride, ny, nx and the size limits as x for rdgan_areal_accumulate (ny nx <= 2^24); q(x) and a
+ * bad pixel-hour as there.  A pixel-day with a bad hour is void.  block [n] ints on the HOST: the block of every day, each in
+ * 0 .. n_blocks - 1 = NB - 1, in any order (1 <= NB <= 2^31).  window_mask: bit w - 1 set for a window of w hours, 1 .. 8 bits
+ * among the low 24, K their number; window i is the i-th set bit from below.  The depth of a good pixel-day for window w is the
+ * largest q[h0] + .. + q[h0 + w - 1] over h0 = 0 .. 24 - w: windows lie within the day and never cross midnight.
+ *   bmax_inout [NB][K][ny nx] 64-bit integers (device): the largest depth of any good day of the block; the caller fills it with -1
+ *     before the first call, and -1 stays where a block has no good day.  NB K ny nx <= 2^31.
+ *   ndays_inout, nvoid_inout [NB][ny nx] 32-bit integers (device): the good and the void pixel-days; zeroed by the caller.
+ * The three ACCUMULATE over any number of calls through integer atomics (max and add), so they do not depend on how the days are
+ * split into calls, on their order or on days_per_run: the days a workgroup walks before it hands over, 1 .. 4096, or 0 for the
+ * entry's choice.
+ * rdgan_lmoment_sums: table [S][B][M] 64-bit integers (device), S = n_series series of B = n_blocks maxima (1 <= B <= 128) at
+ * M = n_positions positions, S B M <= 2^40.  An entry below 0 is left out; with ndays ([S][B][M] 32-bit integers, device, or null)
+ * so is one whose ndays entry is below min_days.  The entries kept must be below 2^40 (the caller checks).  Over their ascending
+ * order statistics x_(1) <= .. <= x_(n):
+ *   sums_out [S][M][3]: A0 = sum x_(j), A1 = sum (j - 1) x_(j), A2 = sum (j - 1)(j - 2) x_(j), each below 2^40 128^3 = 2^61
+ *   n_out [S][M] 32-bit integers: n
+ *   sorted_out: null, or [S][B][M]: x_(1) .. x_(n), then -1 for every entry left out
+ * Written, not added to; invariant under the order of tied values and independent of the launch geometry.
+ * Both asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, n, ny, nx, S, B or M < 1, a size
+ * above the limits, B > 128, a window mask that is 0 or has more than 8 bits or one above bit 23, a block outside 0 .. NB - 1,
+ * day_stride < 24 ny nx, days_per_run outside 0 .. 4096) with nothing launched and no output touched.  All offsets are 64-bit. */
+int rdgan_block_maxima_accumulate(const float* hourly, long n, long day_stride, long ny, long nx, const int* block, long n_blocks,
+                                  unsigned window_mask, int days_per_run, long long* bmax_inout, int* ndays_inout, int* nvoid_inout,
+                                  void* stream);
+int rdgan_lmoment_sums(const long long* table, const int* ndays, int min_days, long n_series, int n_blocks, long n_positions,
+                       long long* sums_out, int* n_out, long long* sorted_out, void* stream);
+
 /* Log-spectral distance, log_spectral_distance.py.  rdgan_spectra_bins: K, the radial bins kept for an nd x nd field
  * (nd 8/16/24/32/48/64: 3/9/15/20/32/43); -2 for an nd the spectra kernel does not cover.
  * rdgan_radial_spectra: compute_radial_spectrum (:59-65) with azimuthal_average (:19-56) -- fields [n][nd][nd] fp32 ->

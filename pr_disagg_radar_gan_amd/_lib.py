@@ -148,6 +148,11 @@ SIGNATURES = {
     "rdgan_cascade_generate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_f32p, ctypes.c_long, ctypes.c_long,
                                               ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_long, ctypes.c_uint64, ctypes.c_int,
                                               c_f32p, ctypes.c_void_p, c_stream]),
+    "rdgan_block_maxima_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,
+                                                     ctypes.c_long, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, c_stream]),
+    "rdgan_lmoment_sums": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_long,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
     "rdgan_spectra_bins": (ctypes.c_int, [ctypes.c_int]),
     "rdgan_radial_spectra": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_stream]),
     "rdgan_lsd_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long]),

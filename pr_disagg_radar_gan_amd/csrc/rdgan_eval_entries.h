@@ -1314,3 +1314,58 @@ extern "C" int rdgan_cascade_generate(const unsigned* model, const int* edge_uni
                        (int)nx, plane, (long)n_members, first_member, seed, patch, nbx, out, units_out);
   return (int)hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------
+// extremes of hourly fields (rdgan_extremes.hip.h): block maxima of the k-hour depths per pixel, L-moment sums of series of maxima
+// ------------------------------------------------------------------------------------
+// the window mask of the peak kernels (rd_peaks_mask): bit w - 1 for a window of w hours, 1 .. RD_EX_MAXK windows of 1 .. 24 hours
+static bool rd_ex_mask_ok(unsigned mask) { return mask != 0u && mask < (1u << RD_HOURS) && __builtin_popcount(mask) <= RD_EX_MAXK; }
+
+// the days of a workgroup's run where the caller leaves the choice: about 2048 workgroups, and RD_EX_MINRUN days at least
+static long rd_ex_run(long n, long groups) {
+  const long even = (n * groups + 2047) / 2048;
+  return std::min<long>(n, std::min<long>(RD_EX_MAXRUN, std::max<long>(RD_EX_MINRUN, even)));
+}
+
+extern "C" int rdgan_block_maxima_accumulate(const float* hourly, long n, long day_stride, long ny, long nx, const int* block, long n_blocks,
+                                             unsigned window_mask, int days_per_run, long long* bmax_inout, int* ndays_inout,
+                                             int* nvoid_inout, void* stream) {
+  if (!hourly || !block || !bmax_inout || !ndays_inout || !nvoid_inout) return -2;
+  if (!rd_aligned(7, bmax_inout) || !rd_aligned(3, ndays_inout, nvoid_inout) || !rd_ar_shape_ok(ny, nx)) return -2;
+  if (!rd_ex_mask_ok(window_mask) || n_blocks < 1 || n_blocks > RD_EX_MAXBLOCKS || days_per_run < 0 || days_per_run > RD_EX_MAXRUN) return -2;
+  const long plane = ny * nx, K = __builtin_popcount(window_mask);
+  if (n_blocks > RD_EX_MAXSTATE / (K * plane)) return -2;
+  if (!rd_hourly_layout_ok(hourly, n, day_stride, RD_HOURS * plane)) return -2;
+  for (long d = 0; d < n; ++d)
+    if (block[d] < 0 || block[d] >= n_blocks) return -2;
+  const bool vec = rd_vec4_ok(hourly, plane, day_stride);
+  const long groups = ((vec ? plane / 4 : plane) + RD_EX_THREADS - 1) / RD_EX_THREADS;
+  const long run = days_per_run ? std::min<long>(days_per_run, n) : rd_ex_run(n, groups);
+  const long runs = (n + run - 1) / run;
+  if (runs > 0x7FFFFFFFL / groups) return -2;                              // (only a days_per_run far below the array's size)
+  hipStream_t st = (hipStream_t)stream;
+  int* dev = nullptr;
+  RD_TRY(rd_field_upload(block, (size_t)n, &dev, st));
+  if (vec)
+    hipLaunchKernelGGL(k_block_maxima<4>, dim3((unsigned)(groups * runs)), dim3(RD_EX_THREADS), 0, st, hourly, n, day_stride, plane,
+                       (const int*)dev, n_blocks, window_mask, (int)run, groups, bmax_inout, ndays_inout, nvoid_inout);
+  else
+    hipLaunchKernelGGL(k_block_maxima<1>, dim3((unsigned)(groups * runs)), dim3(RD_EX_THREADS), 0, st, hourly, n, day_stride, plane,
+                       (const int*)dev, n_blocks, window_mask, (int)run, groups, bmax_inout, ndays_inout, nvoid_inout);
+  hipError_t e = hipGetLastError();
+  hipError_t f = hipFreeAsync(dev, st);
+  return (int)(e != hipSuccess ? e : f);
+}
+
+extern "C" int rdgan_lmoment_sums(const long long* table, const int* ndays, int min_days, long n_series, int n_blocks, long n_positions,
+                                  long long* sums_out, int* n_out, long long* sorted_out, void* stream) {
+  if (!table || !sums_out || !n_out || !rd_aligned(7, table, sums_out, sorted_out) || !rd_aligned(3, ndays, n_out)) return -2;
+  if (n_series < 1 || n_positions < 1 || n_blocks < 1 || n_blocks > RD_EX_MAXB) return -2;
+  if (n_positions > RD_HOURLY_MAXELEMS / n_blocks || n_series > RD_HOURLY_MAXELEMS / (n_blocks * n_positions)) return -2;
+  const long tiles = n_series * ((n_positions + RD_EX_PX - 1) / RD_EX_PX);
+  RD_TRY(ensure_lds(nullptr, (const void*)k_lmoment_sums, RD_EX_LDS_MAX));
+  hipLaunchKernelGGL(k_lmoment_sums, dim3((unsigned)std::min<long>(tiles, 1L << 20)), dim3(RD_EX_THREADS),
+                     RD_EX_LDS_HEAD + (size_t)n_blocks * RD_EX_PX * sizeof(long long), (hipStream_t)stream, table, ndays, min_days, n_series,
+                     n_blocks, n_positions, sums_out, n_out, sorted_out);
+  return (int)hipGetLastError();
+}

@@ -180,6 +180,23 @@ def catchment_rainfall_field(daily, n_scenarios, cmap, windows=(1, 3, 6, 12, 24)
                                                latent_mode=latent_mode, norm_scale=norm_scale)
 
 
+def extremes_field(daily, n_scenarios, block, n_blocks_per_member, windows=(1, 3, 6, 12, 24), min_days=1, return_sorted=False, overlap=4,
+                   latent_mode="shared", scenario_chunk=16):
+    """The extremes of n_scenarios scenarios of a series of daily maps (extremes.extremes_field on the module's ``gen`` and
+    ``norm_scale``): for every scenario, pixel and duration the largest accumulation of each block of days -- block (D,) names the
+    year or season of every day, 0 .. n_blocks_per_member - 1 -- and from those maxima the L-moment sums that give Gumbel and GEV
+    return levels: the intensity-duration-frequency curves of the ensemble.  daily as generate_scenarios_field takes it; windows:
+    the durations in hours, within the day.  Returns an extremes.ExtremeStats on the device, one series per scenario;
+    extremes.compare sets the statistics of observed days against the band the scenarios span.  The latent noise comes from the
+    global numpy RNG as in generate_scenarios_field; the hourly scenarios are produced scenario_chunk at a time and never held
+    together."""
+    from . import extremes
+    daily = _daily_map(daily)
+    return extremes.extremes_field(gen, daily, n_scenarios, block, n_blocks_per_member, windows, min_days=min_days,
+                                   return_sorted=return_sorted, scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode,
+                                   norm_scale=norm_scale)
+
+
 def spacetime_structure_field(daily, n_scenarios, thresholds, radius=4, max_lag=1, overlap=4, latent_mode="shared", scenario_chunk=16):
     """The space-time structure of n_scenarios scenarios of a whole daily map (spacetime.spacetime_structure_field on the module's
     ``gen`` and ``norm_scale``): the wet/dry agreement of hour h at pixel p with hour h + k at pixel p + d, and the displacement
