@@ -100,6 +100,15 @@ def test_two_ranks_different_shards_equal_the_global_batch_on_the_hip_engine(tmp
         want = torch.cat([p.reshape(-1) for p in ps])
         # lr * g / (|g| + eps'): a step of at most 1e-4 * sqrt(1 - 0.9^t)/sqrt(0.1); equal wherever g is not within rounding of 0
         assert float((got.double() - want).abs().mean()) < 1e-8
+    # ... and the update itself, elementwise and without Adam's amplification of gradient noise: on every rank the weights
+    # and second moments are fp64 Adam of the reduced gradient that rank consumed, from the initial weights with v = 0, at
+    # the bound of tests/test_hip_adam.py (1/world is already in the saved slabs; times 0.5 is exact)
+    from tests import adam_np
+    for r, rank in enumerate((r0, r1)):
+        for params, n, t, key in ((d, nd_, 1, "d"), (g, ng_, 2, "g")):
+            adam_np.check_update(rank[key + "params"].numpy(), rank[key + "v"].numpy(), W.flatten(params),
+                                 rank[key + "grad"][:n].numpy(), np.zeros(n, np.float32), t,
+                                 what=f"rank {r} ({exchange}), '{key}' update")
 
 
 def ot_adam(ps, grads, vs, t):
