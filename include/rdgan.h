@@ -806,6 +806,49 @@ int rdgan_analog_apply(const float* lib, long n, long day_stride, long ny, long 
                        long first_query, const int* neighbours, const int* found, int k, int n_members, long first_member,
                        unsigned long long seed, int weights, float* out, int* picks_out, void* stream);
 
+/* Chaining scenarios across midnight: how well every member of one day continues every member of the next,
+ * the cheapest single series through the days, and a greedy matching of the members of neighbouring days.
+ * Everything is an integer.  A value x of an hourly array is GOOD when it is finite and 0 <= x < 2048; a good value has the feature
+ * e = min((int) rintf(x * 32), 65535), a uint16 in units of 1/32 mm (rint to even); a bad value has the feature 0 and sets the bad
+ * bit of its (day, edge, pixel).  Edge 0 of a day is its first_hour, edge 1 its last_hour, both 0 .. 23.  Boundary b joins edge 1 of
+ * day b to edge 0 of day b + shift, b = 0 .. B - 1, B = n_days - shift (shift 1: a seam; shift 0: two hours of the same day).  Pixel p
+ * is MASKED at boundary b when either edge's bad bit is set; n_valid[b] counts the other pixels.  C[b][i][j] is the sum over the
+ * unmasked pixels of |e(day b, member i, edge 1, p) - e(day b + shift, member j, edge 0, p)|, below 2^40; a fully masked boundary
+ * has all costs 0.  key = C << 24 | i << 12 | j is a strict total order of the pairs of a boundary.
+ * Shapes: 1 <= ny nx = P <= 2^24, Ppad = 8 ceil(P / 8), W = ceil(Ppad / 32); 1 <= members <= 4096; 1 <= n_days <= 65535; at most
+ * 2^31 costs per call.  All buffers lie on the device.
+ * rdgan_seq_edges: hourly [n][24][ny][nx] fp32 with the leading stride day_stride >= 24 P (4-byte aligned; 16-byte loads when it is
+ * 16-byte aligned and P and day_stride are multiples of 4); unit u is day u % n_days of member u / n_days, n a multiple of n_days.  Only the
+ * two chosen hours are read.  feat_out [n][2][Ppad] uint16, 16-byte aligned, padding pixels 0.  bad_inout [n_days][2][W] 32-bit
+ * words, bit p % 32 of word p / 32, ORed into: the caller zeroes it before the first call.
+ * rdgan_seq_costs: feat_a [s_a][n_days][2][Ppad] and bad_a, the row ensemble; feat_b [s_b][n_days][2][Ppad] and bad_b, the column
+ * ensemble (the same pointers for one ensemble).  costs_out [B][s_a][s_b] and n_valid_out [B], 64-bit (written, not added to).
+ * pixel_splits: into how many ranges the pixels of a tile of pairs are cut, one workgroup each (at most one per 128 pixels); 0 leaves
+ * the choice to the entry (about 2048 workgroups a launch).  The result does not depend on it, nor on how the kernel cuts the pairs
+ * into tiles: integer sums, 32-bit partial sums added to 64-bit ones every 32768 pixels of a range.
+ * rdgan_seq_minplus: costs [n_boundaries][S][S]; acc_out [n_boundaries + 1][S] 64-bit with acc[0] = 0 and acc[b + 1][j] = min over i
+ * of acc[b][i] + C[b][i][j]; back_out [n_boundaries][S] int32, the smallest i that attains the minimum.  Costs >= 0 whose path sums
+ * stay below 2^62.
+ * rdgan_seq_match: costs [n_boundaries][S][S] with 0 <= C < 2^40; the greedy matching of every boundary -- all pairs walked by
+ * ascending key, a pair taken when neither its row nor its column is taken -- computed as rounds of locally dominant pairs: a free
+ * pair is taken iff its key is the minimum of its row over the free columns and of its column over the free rows.  init = 1 starts
+ * the matchings (perm -1, free_rows S), init = 0 continues them; `rounds` rounds are launched, 0 .. 4096; a round of a complete
+ * matching does nothing.  perm_inout [n_boundaries][S] int32: the column of row i, -1 while free.  free_rows_inout [n_boundaries]
+ * int32.  S rounds complete any matching.  workspace: 8-byte aligned, rdgan_seq_workspace_bytes(S, n_boundaries) bytes (-2 for an
+ * argument out of range), kept by the caller between the calls of one matching.  No workgroup waits for another.
+ * Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, a size or hour outside the limits above,
+ * day_stride below 24 P, n not a multiple of n_days, shift outside 0 .. n_days - 1, pixel_splits < 0, a workspace too small) with nothing launched and
+ * no output touched.  All offsets are 64-bit. */
+long rdgan_seq_workspace_bytes(long n_members, long n_boundaries);
+int rdgan_seq_edges(const float* hourly, long n, long day_stride, long ny, long nx, long n_days, int first_hour, int last_hour,
+                    unsigned short* feat_out, unsigned int* bad_inout, void* stream);
+int rdgan_seq_costs(const unsigned short* feat_a, const unsigned int* bad_a, long s_a, const unsigned short* feat_b,
+                    const unsigned int* bad_b, long s_b, long n_days, long plane, int shift, int pixel_splits, long long* costs_out,
+                    long long* n_valid_out, void* stream);
+int rdgan_seq_minplus(const long long* costs, long n_boundaries, long n_members, long long* acc_out, int* back_out, void* stream);
+int rdgan_seq_match(const long long* costs, long n_boundaries, long n_members, int init, int rounds, int* perm_inout,
+                    int* free_rows_inout, void* workspace, long workspace_bytes, void* stream);
+
 /* Joint-field scores of ensembles of hourly days: the energy score (Gneiting et al. 2008) and the variogram
  * score of order p (Scheuerer & Hamill 2015) of an ensemble of whole days against the observed day, taken as one vector.
  * An ensemble is x [m][24][ny][nx] fp32, every value finite, 1 <= m <= 8192; the observation y [24][ny][nx] fp32.  A position where y

@@ -17,6 +17,8 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
   * ``analog`` -- the analog baseline (method of fragments): the k nearest library days of a daily condition, their scaled fractions
   * ``multivariate`` -- energy and variogram score of ensembles of whole hourly days; the four-method experiment
   * ``cascade`` -- the random-cascade baseline: splits of wet boxes calibrated on hourly data, applied to daily sums 24 h -> 1 h
+  * ``sequence`` -- chaining scenarios across midnight: seam costs between the members of neighbouring days, the cheapest single
+    series, a greedy matching into continuous series
 """
 from .engine import Engine, require_gpu  # noqa: F401
 from . import weights  # noqa: F401

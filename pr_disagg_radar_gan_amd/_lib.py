@@ -136,6 +136,14 @@ SIGNATURES = {
     "rdgan_analog_apply": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, c_f32p, ctypes.c_long,
                                           ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_long,
                                           ctypes.c_uint64, ctypes.c_int, c_f32p, ctypes.c_void_p, c_stream]),
+    "rdgan_seq_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long]),
+    "rdgan_seq_edges": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
+    "rdgan_seq_costs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
+                                       ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
+    "rdgan_seq_minplus": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
+    "rdgan_seq_match": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),
     "rdgan_mv_energy_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_int]),
     "rdgan_mv_energy": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),

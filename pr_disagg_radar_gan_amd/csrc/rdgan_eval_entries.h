@@ -1,6 +1,6 @@
 // The handle-free entry points of include/rdgan.h: input pipeline, CRPS experiment, distribution checks, whole fields, ensemble
 // products, verification, the evaluations of hourly arrays (temporal structure, rain cells, storms, areal extremes, catchment
-// rainfall, space-time structure), analogs, spectra and RainFARM.  They take no rdgan_handle and use nothing of the step engine but RD_TRY,
+// rainfall, space-time structure), analogs, seams between days, spectra and RainFARM.  They take no rdgan_handle and use nothing of the step engine but RD_TRY,
 // ensure_lds(nullptr, ...) and ew_blocks.  Host code, included by rdgan_api.hip at one point, behind the op-level test entries (the
 // library stays one translation unit: one code object for the ISA lint).
 //
@@ -1367,5 +1367,94 @@ extern "C" int rdgan_lmoment_sums(const long long* table, const int* ndays, int 
   hipLaunchKernelGGL(k_lmoment_sums, dim3((unsigned)std::min<long>(tiles, 1L << 20)), dim3(RD_EX_THREADS),
                      RD_EX_LDS_HEAD + (size_t)n_blocks * RD_EX_PX * sizeof(long long), (hipStream_t)stream, table, ndays, min_days, n_series,
                      n_blocks, n_positions, sums_out, n_out, sorted_out);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// chaining scenarios across midnight (rdgan_sequence.hip.h): edge features, seam costs, the min-plus step and the greedy matching
+// ------------------------------------------------------------------------------------
+static bool rd_seq_shape_ok(long s, long n_days, long plane) {
+  return s >= 1 && s <= RD_SEQ_MAXS && n_days >= 1 && n_days <= RD_SEQ_MAXDAYS && plane >= 1 && plane <= RD_HOURLY_MAXPLANE;
+}
+
+extern "C" long rdgan_seq_workspace_bytes(long n_members, long n_boundaries) {
+  if (n_members < 1 || n_members > RD_SEQ_MAXS || n_boundaries < 1 || n_boundaries > RD_SEQ_MAXDAYS) return -2;
+  return n_boundaries * rd_seq_match_bytes(n_members);
+}
+
+extern "C" int rdgan_seq_edges(const float* hourly, long n, long day_stride, long ny, long nx, long n_days, int first_hour, int last_hour,
+                               unsigned short* feat_out, unsigned int* bad_inout, void* stream) {
+  if (!hourly || !feat_out || !bad_inout || !rd_aligned(15, feat_out) || !rd_aligned(3, bad_inout)) return -2;
+  if (ny < 1 || nx < 1 || ny > RD_HOURLY_MAXPLANE || nx > RD_HOURLY_MAXPLANE || ny * nx > RD_HOURLY_MAXPLANE) return -2;
+  if (first_hour < 0 || first_hour >= RD_HOURS || last_hour < 0 || last_hour >= RD_HOURS) return -2;
+  const long plane = ny * nx;
+  if (n_days < 1 || n_days > RD_SEQ_MAXDAYS || !rd_hourly_layout_ok(hourly, n, day_stride, RD_HOURS * plane) || n % n_days != 0) return -2;
+  if (n / n_days > RD_SEQ_MAXS) return -2;
+  const int U = (int)(rd_seq_ppad(plane) / 8), W = (int)rd_seq_words(plane);
+  const long blocks = (n * 2 * U + 255) / 256;
+  if (blocks > 0x7FFFFFFFL) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  if (rd_vec4_ok(hourly, plane, day_stride))
+    hipLaunchKernelGGL(k_seq_edges<true>, dim3((unsigned)blocks), dim3(256), 0, st, hourly, n, day_stride, (int)plane, U, W, n_days, first_hour,
+                       last_hour, (uint4*)feat_out, bad_inout);
+  else
+    hipLaunchKernelGGL(k_seq_edges<false>, dim3((unsigned)blocks), dim3(256), 0, st, hourly, n, day_stride, (int)plane, U, W, n_days, first_hour,
+                       last_hour, (uint4*)feat_out, bad_inout);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_seq_costs(const unsigned short* feat_a, const unsigned int* bad_a, long s_a, const unsigned short* feat_b,
+                               const unsigned int* bad_b, long s_b, long n_days, long plane, int shift, int pixel_splits,
+                               long long* costs_out, long long* n_valid_out, void* stream) {
+  if (!feat_a || !bad_a || !feat_b || !bad_b || !costs_out || !n_valid_out) return -2;
+  if (!rd_aligned(15, feat_a, feat_b) || !rd_aligned(3, bad_a, bad_b) || !rd_aligned(7, costs_out, n_valid_out)) return -2;
+  if (!rd_seq_shape_ok(s_a, n_days, plane) || !rd_seq_shape_ok(s_b, n_days, plane) || shift < 0 || shift >= n_days) return -2;
+  const long B = n_days - shift;
+  if (B * s_a * s_b > RD_SEQ_MAXCOSTS || pixel_splits < 0) return -2;
+  const int U = (int)(rd_seq_ppad(plane) / 8), W = (int)rd_seq_words(plane);
+  const long TA = rd_seq_tiles(s_a), TB = rd_seq_tiles(s_b), nchunks = (U + RD_SEQ_CHUNK - 1) / RD_SEQ_CHUNK;
+  // the pixel chunks are cut into pixel_splits ranges, or, left to the entry (0), into as many as bring the launch to about
+  // RD_SEQ_TARGET_BLOCKS workgroups; never more than there are chunks
+  long nsplit = std::min<long>(nchunks, pixel_splits ? pixel_splits : std::max<long>(1, (RD_SEQ_TARGET_BLOCKS + B * TA * TB - 1) / (B * TA * TB)));
+  const long per_split = (nchunks + nsplit - 1) / nsplit;
+  nsplit = (nchunks + per_split - 1) / per_split;
+  if (B * TA * TB * nsplit > 0x7FFFFFFFL) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY((int)hipMemsetAsync(costs_out, 0, (size_t)(B * s_a * s_b) * 8, st));
+  hipLaunchKernelGGL(k_seq_valid, dim3((unsigned)B), dim3(256), 0, st, bad_a, bad_b, W, shift, plane, n_valid_out);
+  hipLaunchKernelGGL(k_seq_costs, dim3((unsigned)(B * TA * TB * nsplit)), dim3(RD_SEQ_THREADS), 0, st, (const uint4*)feat_a, bad_a, (int)s_a,
+                     (const uint4*)feat_b, bad_b, (int)s_b, n_days, U, W, shift, (int)TA, (int)TB, (int)nsplit, (int)per_split,
+                     (unsigned long long*)costs_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_seq_minplus(const long long* costs, long n_boundaries, long n_members, long long* acc_out, int* back_out, void* stream) {
+  if (!costs || !acc_out || !back_out || !rd_aligned(7, costs, acc_out) || !rd_aligned(3, back_out)) return -2;
+  if (n_members < 1 || n_members > RD_SEQ_MAXS || n_boundaries < 1 || n_boundaries > RD_SEQ_MAXDAYS) return -2;
+  if (n_boundaries * n_members * n_members > RD_SEQ_MAXCOSTS) return -2;
+  const long S = n_members;
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY((int)hipMemsetAsync(acc_out, 0, (size_t)S * 8, st));
+  for (long b = 0; b < n_boundaries; ++b)
+    hipLaunchKernelGGL(k_seq_minplus, dim3((unsigned)((S + 63) / 64)), dim3(256), 0, st, costs + b * S * S, (int)S,
+                       (const long long*)(acc_out + b * S), acc_out + (b + 1) * S, back_out + b * S);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_seq_match(const long long* costs, long n_boundaries, long n_members, int init, int rounds, int* perm_inout,
+                               int* free_rows_inout, void* workspace, long workspace_bytes, void* stream) {
+  if (!costs || !perm_inout || !free_rows_inout || !workspace) return -2;
+  if (!rd_aligned(7, costs, workspace) || !rd_aligned(3, perm_inout, free_rows_inout)) return -2;
+  if (n_members < 1 || n_members > RD_SEQ_MAXS || n_boundaries < 1 || n_boundaries > RD_SEQ_MAXDAYS) return -2;
+  if (n_boundaries * n_members * n_members > RD_SEQ_MAXCOSTS) return -2;
+  if ((init != 0 && init != 1) || rounds < 0 || rounds > RD_SEQ_MAXS || workspace_bytes < n_boundaries * rd_seq_match_bytes(n_members)) return -2;
+  const int S = (int)n_members;
+  const dim3 per_member((unsigned)((S + 255) / 256), (unsigned)n_boundaries), per_rows((unsigned)((S + RD_SEQ_ROWS - 1) / RD_SEQ_ROWS), (unsigned)n_boundaries);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_seq_match_init, per_member, dim3(256), 0, st, S, init, perm_inout, free_rows_inout, workspace);
+  for (int r = 0; r < rounds; ++r) {
+    hipLaunchKernelGGL(k_seq_match_minima, per_rows, dim3(RD_SEQ_THREADS), 0, st, costs, S, r & 1, (const int*)free_rows_inout, workspace);
+    hipLaunchKernelGGL(k_seq_match_take, per_member, dim3(256), 0, st, S, r & 1, perm_inout, free_rows_inout, workspace);
+  }
   return (int)hipGetLastError();
 }
