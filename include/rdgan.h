@@ -1103,6 +1103,65 @@ int rdgan_op_d2_dgrad_slab_t16(const float* gy, const float* w, const float* aux
 int rdgan_op_pixelnorm_lrelu(const float* y, float* h, float* rinv, long npix, int C, void* stream);
 int rdgan_op_pixelnorm_lrelu_bwd(const float* gh, const float* h, const float* rinv, float* dy,
                                  long npix, int C, void* stream);
+/* ---- The step's elementwise kernels one by one (test hooks).  Each launches the production kernel through the launcher the
+ * step functions use (csrc/rdgan_elem_launch.h): same grid, same split.  Raw device pointers, fp32 unless said otherwise; -2 on a
+ * bad argument. ----
+ * Tail of the last generator conv (T:345-350): the remaining tap sums + bias, Softmax over the 24 hours, check_numerics.
+ * out [B,24,H,W]; *flag is OR-ed with 1 when a logit or an output is NaN/Inf, and never cleared.  (The reference checks the softmax
+ * output only; a lone -Inf logit gives p = 0 there and passes.  Flagging it is stricter; finite inputs are unaffected.)  taps by form:
+ *   0  k_colgather_softmax: P[B*24*H*W][32], column t = (kd*3+kh)*3+kw holds h3[pos] . W9[t]; logit(pos) = bias + sum_t P[pos+t-1][t]
+ *   3  k_tapsum_softmax<24,3>: Q[b][d][3][h][w], entry kd = the sum over (kh,kw) of the products plane d sends to plane d+1-kd
+ *      at (h,w); logit(d) = bias + sum_kd Q[d+kd-1][kd]
+ *   9  k_tapsum_softmax<24,9>: Q[b][d][9][h][w], entry (kd,kh) = the sum over kw sent to (d+1-kd, h+1-kh, w);
+ *      logit(d,h) = bias + sum_{kd,kh} Q[d+kd-1][kd*3+kh][h+kh-1]
+ *   12 k_tapsum_softmax12 (H = W = 16): QT[b][item 0..5][tp 0..5][p 0..3][q 0..3][64]; item = planes 4 item .. 4 item + 3, tp = target
+ *      plane 4 item - 1 + tp, p = source parity class, q = target class 2 (y&1) + (x&1) at class position (y>>1)*8 + (x>>1);
+ *      logit(d,y,x) = bias + sum over the items that reach plane d, and over p, of QT[..][q(y,x)][pos(y,x)]
+ * (The tiled variant k_tapsum_softmax12t with k_g9_halo_fold has no entry: the fused-last-conv test ties it to the separate pass.) */
+int rdgan_op_softmax_tail(int form, const float* taps, const float* bias, float* out, int* flag, int B, int H, int W, void* stream);
+/* Softmax backward (k_softmax_bwd): dl = p * (g - sum_d p g) per (sample, h, w) column; p, g, dl [B,24,H,W]. */
+int rdgan_op_softmax_bwd(const float* p, const float* g, float* dl, int B, int H, int W, void* stream);
+/* Gradient-penalty norm (T:238-241; k_gp_norm_part + k_gp_norm_r0): g0 [B][per]; gp_out [B] = ||g0[b]|| - 1; cin_hat_out [B][per][CP],
+ * channel 0 = (10/B) 2 (n-1)/n g0, channels 1..CP-1 = 0.  force_S = 0: the step's choice of workgroups per sample, else that many
+ * (1..64).  A sample of norm 0 gets gp = -1 and NaN in its cin_hat rows (0 * inf, as the gradient of Keras's sqrt). */
+int rdgan_op_gp_norm(const float* g0, int B, int per, int CP, int force_S, float* cin_hat_out, float* gp_out, void* stream);
+/* Loss tails.  mode 0 (k_critic_losses, T:215-216, T:388-392): v [2B] = critic values real | fake, gp [B]; out8 = (total, mean(-v_real),
+ * mean(v_fake), mean(gp^2), flag, 0, 0, 0), total = the second + the third + 10 x the fourth.  mode 1 (k_gen_loss, T:408): v [B];
+ * out8 = (mean(-v), 0, 0, 0, flag, 0, 0, 0).  flag = 1 when the total is NaN/Inf or gflag_in != 0 (the generator's check_numerics). */
+int rdgan_op_loss_tail(int mode, const float* v, const float* gp, int B, int gflag_in, float* out8, void* stream);
+/* The critic's Dense layer (T:303-304; k_critic_dense_fwd) and the top of its input-gradient chain (k_critic_top_bwd) over NB samples
+ * of F features: v_out [NB] = h4 . w + bias; u4_out [NB][F] = gate(h4) w dv(sample), dv = -1/B | +1/B | 1 for the thirds of the 3B
+ * batch (mode 0) or -1/B (mode 1); gate = LeakyReLU' of the stored output (1 where h4 > 0, else 0.2), and with seed != 0 additionally
+ * 0 where h4 is +0.0 (dropped) and 1/0.75 elsewhere.  bf16 != 0: h4 and u4_out are bf16 buffers. */
+int rdgan_op_critic_dense(const void* h4, const float* w, const float* bias, float* v_out, void* u4_out, int NB, int F, int B, int mode,
+                          uint64_t seed, int bf16, void* stream);
+/* Dense weight gradient (k_critic_dense_wgrad + the fold of its row slices): out [F] = sum_b buf[b][:] dv(b) over NB = 3B samples;
+ * slices = 0: the step's choice, else that many row slices (16 at the most).  bf16 != 0: buf is a bf16 buffer. */
+int rdgan_op_critic_dense_wgrad(const void* buf, float* out, int NB, int F, int B, int slices, int bf16, void* stream);
+/* Weight forms of a generator block's kernel W [27][CC] (CC = Cin Cout, CC % 4 == 0) and their adjoints.  which = 0
+ * (k_collapse_weights / k_fold_collapsed_wgrad): out [64 = phase(pd,ph,pw) * 8 + tap(ad,ah,aw)][CC], per axis the sum of the taps
+ * p = 0: {0} | {1,2}, p = 1: {0,1} | {2}.  which = 1 (k_weight_transform / k_weight_transform_adj): out [48 = g * 16 + (ph * 2 + th)
+ * * 4 + (pw * 2 + tw)][CC], along d the groups g = 0: -W0, 1: W0 + W1 + W2, 2: W2, on h and w the collapsed sums.  _adj: dforms
+ * [64 | 48][CC] -> dW [27][CC] = the transposed map. */
+int rdgan_op_weight_forms(int which, const float* W, float* out, long CC, void* stream);
+int rdgan_op_weight_forms_adj(int which, const float* dforms, float* dW, long CC, void* stream);
+/* Critic input (T:275-282, T:221-224; k_build_critic_input[_v4]): real, fake [B][D][HW], cond [B][HW][nc]; out [B | 3B][D][HW][CP]
+ * = (sample | the nc condition channels | zeros).  mode 0: real | fake | alpha real + (1 - alpha) fake with alpha[b] = the uniform
+ * of key (seed, stream 5) at counter alpha_base + b; mode 1: fake only; mode 2: real only.  scalar != 0 forces the one-voxel kernel
+ * where the step would take the four-voxel one (nc = 1, CP = 2, HW % 4 == 0). */
+int rdgan_op_critic_input(const float* real, const float* fake, const float* cond, float* out, int B, int D, int HW, int nc, int CP,
+                          int mode, uint64_t seed, uint32_t alpha_base, int scalar, void* stream);
+/* Gradient wrt the generator's Dense pre-activation (T:326-328).  k_pool_lrelu_bwd: out [B,D,H,W,C] = (sum of the 8 children of
+ * gup [B,2D,2H,2W,C]) * LeakyReLU'(h0); k_lrelu_bwd: out [n] = g * LeakyReLU'(h), n % 4 == 0, bf16 != 0: g and h are bf16 buffers. */
+int rdgan_op_pool_lrelu_bwd(const float* gup, const float* h0, float* out, int B, int D, int H, int W, int C, void* stream);
+int rdgan_op_lrelu_bwd(const void* g, const void* h, float* out, long n, int bf16, void* stream);
+/* Column sums behind every bias gradient (k_colsum_partial / k_colsum_partial_any + the fold), through the handle's partial buffer:
+ * out [C] = sum over rows of src [rows][C].  bf16 != 0 (C in {64, 128, 256}): src is a bf16 buffer. */
+int rdgan_op_colsum(rdgan_handle* h, const void* src, long rows, int C, float* out, int bf16, void* stream);
+/* Hour differences of the shared-centre form and their adjoint (k_diff_d, k_combine_dx), P floats per hour plane (P % 4 == 0):
+ * x [B][D][P] -> E_out [B][D+1][P] = x[j] - x[j-1] (x zero outside); dx_inout [B][D][P] += dE[d] - dE[d+1], dE [B][D+1][P].  Either
+ * pair may be NULL.  bf16 != 0: all four are bf16 buffers. */
+int rdgan_op_diff_combine(const void* x, void* E_out, void* dx_inout, const void* dE, int B, int D, long P, int bf16, void* stream);
 /* Test hook: copies the first n floats of an activation tensor the last forward pass left in the workspace into `out`
  * (device, fp32): which = 0..3 generator h0..h3 [B, D, H, W, C] after LeakyReLU; 4..7 critic layers 1..4 after LeakyReLU
  * and dropout ([B] samples after a generator step or a critic forward; [3B] = real | fake | interpolated after a critic step,

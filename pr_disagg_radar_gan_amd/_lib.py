@@ -195,6 +195,20 @@ SIGNATURES = {
     "rdgan_op_d2_dgrad_slab_t16": (ctypes.c_int, [c_f32p] * 4 + [ctypes.c_int] * 4 + [c_stream]),
     "rdgan_op_pixelnorm_lrelu": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, c_stream]),
     "rdgan_op_pixelnorm_lrelu_bwd": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_long, ctypes.c_int, c_stream]),
+    "rdgan_op_softmax_tail": (ctypes.c_int, [ctypes.c_int, c_f32p, c_f32p, c_f32p, ctypes.c_void_p] + [ctypes.c_int] * 3 + [c_stream]),
+    "rdgan_op_softmax_bwd": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int] * 3 + [c_stream]),
+    "rdgan_op_gp_norm": (ctypes.c_int, [c_f32p] + [ctypes.c_int] * 4 + [c_f32p, c_f32p, c_stream]),
+    "rdgan_op_loss_tail": (ctypes.c_int, [ctypes.c_int, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, c_f32p, c_stream]),
+    "rdgan_op_critic_dense": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p] + [ctypes.c_int] * 4 +
+                              [ctypes.c_uint64, ctypes.c_int, c_stream]),
+    "rdgan_op_critic_dense_wgrad": (ctypes.c_int, [ctypes.c_void_p, c_f32p] + [ctypes.c_int] * 5 + [c_stream]),
+    "rdgan_op_weight_forms": (ctypes.c_int, [ctypes.c_int, c_f32p, c_f32p, ctypes.c_long, c_stream]),
+    "rdgan_op_weight_forms_adj": (ctypes.c_int, [ctypes.c_int, c_f32p, c_f32p, ctypes.c_long, c_stream]),
+    "rdgan_op_critic_input": (ctypes.c_int, [c_f32p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, c_stream]),
+    "rdgan_op_pool_lrelu_bwd": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int] * 5 + [c_stream]),
+    "rdgan_op_lrelu_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_f32p, ctypes.c_long, ctypes.c_int, c_stream]),
+    "rdgan_op_colsum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, c_f32p, ctypes.c_int, c_stream]),
+    "rdgan_op_diff_combine": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, c_stream]),
     "rdgan_debug_activation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_f32p, ctypes.c_long, c_stream]),
     "rdgan_debug_d1_input_grad": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, c_f32p,
                                                  c_stream]),

@@ -280,17 +280,13 @@ static int launch_conv_a16(rdgan_handle* h, const RdPlan& hp, const RdPlan* dp, 
 }
 
 static inline int ew_blocks(long n, int per = 256);
+#include "rdgan_elem_launch.h"   // launchers of the elementwise kernels on raw pointers: shared with the op entries
 // critic input (k_build_critic_input): the four-voxel kernel where the layout allows it
 static void launch_build_critic_input(rdgan_handle* h, const float* real, const float* fake, const float* cond, int B, int mode,
                                       uint32_t akey, uint32_t abase, hipStream_t st) {
   const int D = h->ddim[0][0], HW = h->nd * h->nd;
   const long total = (long)B * D * HW;
-  if (h->nc == 1 && h->CP == 2 && HW % 4 == 0 && total < 0x7FFFFFFFL)
-    hipLaunchKernelGGL(k_build_critic_input_v4, dim3(ew_blocks(total / 4)), dim3(256), 0, st, real, fake, cond, h->cin, B, D, HW, mode,
-                       akey, abase);
-  else
-    hipLaunchKernelGGL(k_build_critic_input, dim3(ew_blocks(total)), dim3(256), 0, st, real, fake, cond, h->cin, B, D, HW, h->nc, h->CP,
-                       mode, akey, abase);
+  launch_critic_input(real, fake, cond, h->cin, B, D, HW, h->nc, h->CP, mode, akey, abase, critic_input_v4_ok(h->nc, h->CP, HW, total), st);
 }
 static inline int ew_blocks(long n, int per) { return (int)std::min<long>((n + per - 1) / per, 8192); }
 
@@ -1126,16 +1122,12 @@ static GenPass gen_pass(const rdgan_handle* h, int B) {
 
 // hour differences E of a block input (shared-centre form): forward, and the backward of a block whose forward ran another form
 static void launch_diff_d(const GenPass& s, const float* x, float* E, int B, int D, long P, hipStream_t st) {
-  const dim3 dg(ew_blocks((long)B * (D + 1) * P / 4));
-  if (s.a16) hipLaunchKernelGGL(k_diff_d<rd_bf16_t>, dg, dim3(256), 0, st, (const rd_bf16_t*)x, (rd_bf16_t*)E, B, D, P);
-  else hipLaunchKernelGGL(k_diff_d<float>, dg, dim3(256), 0, st, x, E, B, D, P);
+  launch_diff_d(s.a16, x, E, B, D, P, st);
 }
 // epilogue of the last conv where the GEMM / streaming kernel has left gq = 3 (9) in-tile tap sums per grid point in P9: the
 // remaining sums, bias, Softmax(axis=1), check_numerics
 static void launch_tapsum_softmax(rdgan_handle* h, int gq, float* out, const float* gp, int B, hipStream_t st) {
-  const dim3 grid((unsigned)(((long)B * h->nd * h->nd + 63) / 64));
-  if (gq == 3) hipLaunchKernelGGL((k_tapsum_softmax<RDGAN_NHOURS, 3>), grid, dim3(256), 0, st, h->P9, gp + h->goff[9], out, B, h->nd, h->nd, h->d_flag);
-  else hipLaunchKernelGGL((k_tapsum_softmax<RDGAN_NHOURS, 9>), grid, dim3(256), 0, st, h->P9, gp + h->goff[9], out, B, h->nd, h->nd, h->d_flag);
+  launch_tapsum_softmax_q(gq, h->P9, gp + h->goff[9], out, B, h->nd, h->nd, h->d_flag, st);
 }
 
 // Weight forms (read only the weights), on `ws`: skipped when the caller vouches that the forms in the workspace were built from
@@ -1160,13 +1152,11 @@ static int gen_build_forms(rdgan_handle* h, const float* gp, hipStream_t st, hip
     const float* Wl = gp + h->goff[2 * l];
     const long cc = (long)h->gch[l - 1] * h->gch[l];
     if (gen_block_fast(h, l, fast_fwd_on(h))) {
-      RdWeightMap wm;
-      fastd_weight_map(wm);
       ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, ws);
-      hipLaunchKernelGGL(k_weight_transform, dim3(ew_blocks(48L * cc / 4)), dim3(256), 0, ws, Wl, h->fU[l], (int)cc, 48, wm);
+      launch_weight_transform(Wl, h->fU[l], cc, ws);
       if (a16) RD_TRY(launch_weights_to_bf16_t(h, h->fU[l], h->bU[l], 48, h->gch[l - 1], h->gch[l], ws));
     } else if (h->collapse) {
-      hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * cc)), dim3(256), 0, ws, Wl, h->GWC[l], (int)cc);
+      launch_collapse_weights(Wl, h->GWC[l], cc, ws);
       if (upconv_slab_on(h, l)) launch_upconv_wimg(h->GWC[l], h->bW3I, ws);
       else if (upconv_slab_t_on(h, l)) launch_upconv_wimg_t(h->GWC[l], h->bW3T, ws);
       else if (upconv2_slab_on(h, l)) launch_upconv2_wimg(h->GWC[l], h->bW2I, ws);
@@ -1319,7 +1309,7 @@ static int gen_last_conv_fwd(rdgan_handle* h, const GenPass& s, const float* gp,
   if (g9_fused_on(h)) {
     // the tap products left the block-3 slab kernel as Q12: the sums over kd and the source classes, bias, softmax
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    hipLaunchKernelGGL((k_tapsum_softmax12<RDGAN_NHOURS>), dim3((unsigned)((ncol / 4 + 63) / 64)), dim3(256), 0, st, h->P9, gp + h->goff[9], out, B, h->d_flag);
+    launch_tapsum_softmax12(h->P9, gp + h->goff[9], out, B, h->d_flag, st);
   } else if (g9_fused_t_on(h)) {
     // the same behind the tiled kernel: main sums per tile + the halo terms of the neighbouring tiles
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
@@ -1373,7 +1363,7 @@ static int gen_last_conv_fwd(rdgan_handle* h, const GenPass& s, const float* gp,
     if (a16) RD_TRY(launch_conv_a16(h, h->plans[PL_G9F], h->d_plans + PL_G9F, B, h->h3, h->W9T, 32, h->P9, e, st, -1, true, false));
     else RD_TRY(launch_conv(h, h->plans[PL_G9F], h->d_plans + PL_G9F, B, h->h3, h->W9T, 32, h->P9, e, st, -1));
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    hipLaunchKernelGGL(k_colgather_softmax, dim3((unsigned)((ncol + 63) / 64)), dim3(64), 0, st, h->P9, gp + h->goff[9], out, B, RDGAN_NHOURS, nd, nd, h->d_flag);
+    launch_colgather_softmax(h->P9, gp + h->goff[9], out, B, nd, nd, h->d_flag, st);
   }
   RD_CHECK(h, hipGetLastError());
   return 0;
@@ -1614,10 +1604,7 @@ static int critic_forward_impl(rdgan_handle* h, const float* dp, int NBt, uint64
     in = h->dh[l];
   }
   ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-  if (a16) hipLaunchKernelGGL(k_critic_dense_fwd<rd_bf16_t>, dim3(NBt), dim3(256), 0, st, (const rd_bf16_t*)h->dh[4], dp + h->doff[8],
-                              dp + h->doff[9], h->v, h->F);
-  else hipLaunchKernelGGL(k_critic_dense_fwd<float>, dim3(NBt), dim3(256), 0, st, (const float*)h->dh[4], dp + h->doff[8],
-                          dp + h->doff[9], h->v, h->F);
+  launch_critic_dense_fwd(a16, h->dh[4], dp + h->doff[8], dp + h->doff[9], h->v, NBt, h->F, st);
   RD_CHECK(h, hipGetLastError());
   return 0;
 }
@@ -1628,11 +1615,7 @@ static int critic_dgrad_chain(rdgan_handle* h, const float* dp, int NBt, int B, 
   const bool a16 = h->a16 != 0;
   {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    const dim3 g(ew_blocks((long)NBt * h->F));
-    if (a16) hipLaunchKernelGGL(k_critic_top_bwd<rd_bf16_t>, g, dim3(256), 0, st, (const rd_bf16_t*)h->dh[4], dp + h->doff[8],
-                                (rd_bf16_t*)h->du[4], NBt, h->F, B, mode, use_drop, rd_make_key(seed, RD_STREAM_D1 + 3));
-    else hipLaunchKernelGGL(k_critic_top_bwd<float>, g, dim3(256), 0, st, (const float*)h->dh[4], dp + h->doff[8],
-                            h->du[4], NBt, h->F, B, mode, use_drop, rd_make_key(seed, RD_STREAM_D1 + 3));
+    launch_critic_top_bwd(a16, h->dh[4], dp + h->doff[8], h->du[4], NBt, h->F, B, mode, seed, st);
   }
   for (int l = 4; l >= 2; --l) {
     int pl = critic_dgrad_plan(h, l, NBt);
@@ -1731,9 +1714,7 @@ static int critic_penalty_input(rdgan_handle* h, const float* dp, const float* u
   ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
   // S blocks per sample when there are few samples of many elements (ndomain 64)
   const int per = (int)h->dL[0];
-  const int S = std::max(1, std::min({(1024 + B - 1) / B, per / 4096, 64}));
-  if (S > 1) hipLaunchKernelGGL(k_gp_norm_part, dim3(B * S), dim3(256), 0, st, h->g0, h->gp_part, per, S);
-  hipLaunchKernelGGL(k_gp_norm_r0, dim3(B * S), dim3(256), 0, st, h->g0, cin_hat, h->gpv, per, B, RD_GP_WEIGHT, h->CP, S, h->gp_part);
+  launch_gp_norm(h->g0, h->gp_part, cin_hat, h->gpv, per, B, h->CP, gp_norm_slices(B, per), st);
   RD_CHECK(h, hipGetLastError());
   return 0;
 }
@@ -1841,14 +1822,9 @@ static int critic_dense_grad_and_losses(rdgan_handle* h, float* grad, int B, hip
   const int NBt = 3 * B;
   {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    const int RS = h->dense_slices > 0 ? std::min(16, h->dense_slices) : std::max(1, std::min(16, NBt / 384));   // row slices of the Dense weight gradient
-    float* dwo = RS > 1 ? h->dw6_part : grad + h->doff[8];
-    const dim3 dg((h->F + 15) / 16, RS);
-    if (h->a16) hipLaunchKernelGGL(k_critic_dense_wgrad<rd_bf16_t>, dg, dim3(256), 0, st, (const rd_bf16_t*)h->dh[4], dwo, NBt, h->F, B);
-    else hipLaunchKernelGGL(k_critic_dense_wgrad<float>, dg, dim3(256), 0, st, (const float*)h->dh[4], dwo, NBt, h->F, B);
-    if (RS > 1) hipLaunchKernelGGL(k_reduce_partials, dim3((h->F + 15) / 16), dim3(256), 0, st, h->dw6_part, RS, h->F, grad + h->doff[8]);
+    launch_critic_dense_wgrad(h->a16 != 0, h->dh[4], grad + h->doff[8], h->dw6_part, NBt, h->F, B, dense_wgrad_slices(h->dense_slices, NBt), st);
     // (grad[doff[9]] = sum of dv over real|fake = 0, cleared by the loss kernel together with the unused loss slots)
-    hipLaunchKernelGGL(k_critic_losses, dim3(1), dim3(256), 0, st, h->v, h->gpv, grad + h->n_critic, B, RD_GP_WEIGHT, h->d_flag, grad + h->doff[9]);
+    launch_critic_losses(h->v, h->gpv, grad + h->n_critic, B, h->d_flag, grad + h->doff[9], st);
   }
   RD_CHECK(h, hipGetLastError());
   return 0;
@@ -1915,8 +1891,7 @@ static int gen_last_conv_bwd(rdgan_handle* h, const GenPass& s, const float* gp,
   const long npix3 = (long)B * h->gpix[3];
   {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    long ncol = (long)B * nd * nd;
-    hipLaunchKernelGGL(k_softmax_bwd, dim3((unsigned)((ncol + 63) / 64)), dim3(64), 0, st, h->fake, h->g0, h->dl, B, RDGAN_NHOURS, nd, nd);
+    launch_softmax_bwd(h->fake, h->g0, h->dl, B, nd, nd, st);
   }
   if (s.a16 && !s.g9_direct) return bad_arg(h, "bf16 storage mode needs the direct backward of the last conv (g9_direct)");
   if (s.g9_direct) {
@@ -1947,8 +1922,7 @@ static int gen_build_dgrad_forms(rdgan_handle* h, const GenPass& s, const float*
   collapsed_dgrad_slice_map(map.src);
   for (int l = 1; l <= 3; ++l) {
     if (gen_block_fast(h, l, fast_bwd_on(h))) continue;
-    if (gen_block_fast(h, l, fast_fwd_on(h))) hipLaunchKernelGGL(k_collapse_weights, dim3(ew_blocks(16L * h->gch[l - 1] * h->gch[l])), dim3(256), 0, st,
-                         gp + h->goff[2 * l], h->GWC[l], h->gch[l - 1] * h->gch[l]);
+    if (gen_block_fast(h, l, fast_fwd_on(h))) launch_collapse_weights(gp + h->goff[2 * l], h->GWC[l], (long)h->gch[l - 1] * h->gch[l], st);
     if (s.a16) continue;              // (bf16 storage: the input gradient reads the bf16 image of Wc re-ordered by tap: gen_block_bwd_collapsed)
     hipLaunchKernelGGL(k_transpose_map, dim3((h->gch[l] + 31) / 32, (h->gch[l - 1] + 31) / 32, 64), dim3(256), 0, st,
                        h->GWC[l], h->GWD[l], h->gch[l - 1], h->gch[l], map);
@@ -1997,13 +1971,11 @@ static int gen_block_bwd_shared_centre(rdgan_handle* h, const GenPass& s, const 
   const int* sd = h->gdim[l - 1];
   const int D = sd[0];
   const long P = (long)sd[1] * sd[2] * h->gch[l - 1];
-  RdWeightMap wm;
-  fastd_weight_map(wm);
   {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
     if (!gen_block_fast(h, l, fast_fwd_on(h))) {      // (otherwise the forward pass has left both)
       launch_diff_d(s, hs[l - 1], h->fE[l], B, D, P, st);
-      hipLaunchKernelGGL(k_weight_transform, dim3(ew_blocks(48L * cc / 4)), dim3(256), 0, st, gp + h->goff[2 * l], h->fU[l], (int)cc, 48, wm);
+      launch_weight_transform(gp + h->goff[2 * l], h->fU[l], cc, st);
     }
   }
   // weight gradients of the three tap groups: E[s] x even planes, x x plane sums, E[s+1] x odd planes
@@ -2017,7 +1989,7 @@ static int gen_block_bwd_shared_centre(rdgan_handle* h, const GenPass& s, const 
       RD_TRY(launch_wgrad16(h, h->plans[pl], h->d_plans + pl, B, wsrc[g], wdy[g], h->fdU, h->wpartial, h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
     } else RD_TRY(launch_wgrad(h, h->plans[pl], h->d_plans + pl, B, wsrc[g], wdy[g], h->fdU, h->wpartial, h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
   }
-  hipLaunchKernelGGL(k_weight_transform_adj, dim3(ew_blocks(27L * cc / 4)), dim3(256), 0, st, h->fdU, grad + h->goff[2 * l], (int)cc, 48, wm);
+  launch_weight_transform_adj(h->fdU, grad + h->goff[2 * l], cc, st);
   RD_TRY(launch_colsum(h, dys[l], (long)B * h->gpix[l], h->gch[l], grad + h->goff[2 * l + 1], side_fork(h, st), a16));   // bias gradient, beside the GEMMs (dys[l] is read-only from here on)
   // input gradients: the shared part from gS, the difference part dE from dy
   const int pbs = PL_F1BS + l - 1, pbe = PL_F1BE + l - 1;
@@ -2045,9 +2017,7 @@ static int gen_block_bwd_shared_centre(rdgan_handle* h, const GenPass& s, const 
   if (!a16 && h->combine_dx_fused && l >= 2) *dE_out = h->fdE;
   else {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    const dim3 cg(ew_blocks((long)B * D * P / 4));
-    if (a16) hipLaunchKernelGGL(k_combine_dx<rd_bf16_t>, cg, dim3(256), 0, st, (rd_bf16_t*)gups[l], (const rd_bf16_t*)h->fdE, B, D, P);
-    else hipLaunchKernelGGL(k_combine_dx<float>, cg, dim3(256), 0, st, gups[l], (const float*)h->fdE, B, D, P);
+    launch_combine_dx(a16, gups[l], h->fdE, B, D, P, st);
   }
   return 0;
 }
@@ -2077,7 +2047,7 @@ static int gen_block_bwd_collapsed(rdgan_handle* h, const GenPass& s, float* gra
     if (wbox) plf = plfx;
     RD_TRY(launch_wgrad(h, h->plans[plf], h->d_plans + plf, B, x, dy, h->dWc, h->wpartial, h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
   }
-  hipLaunchKernelGGL(k_fold_collapsed_wgrad, dim3(ew_blocks(27L * cc / 4)), dim3(256), 0, st, h->dWc, grad + h->goff[2 * l], (int)cc);
+  launch_fold_collapsed_wgrad(h->dWc, grad + h->goff[2 * l], cc, st);
   if (!bias_done)
     RD_TRY(launch_colsum(h, dy, (long)B * h->gpix[l], h->gch[l], grad + h->goff[2 * l + 1], side_fork(h, st), a16));   // bias gradient, beside the GEMMs (dys[l] is read-only from here on)
   if (a16) {      // the collapsed forms re-ordered by tap are already [N = Cin][K = Cout]
@@ -2105,11 +2075,8 @@ static int gen_block_bwd_direct(rdgan_handle* h, const GenPass& s, float* grad, 
 static int gen_dense_bwd(rdgan_handle* h, const GenPass& s, float* grad, int B, hipStream_t st) {
   {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    const dim3 lg(ew_blocks((long)B * h->gpix[0] * 64));
-    if (s.col && s.a16) hipLaunchKernelGGL(k_lrelu_bwd<rd_bf16_t>, lg, dim3(256), 0, st, (const rd_bf16_t*)h->gup1, (const rd_bf16_t*)h->h0, h->ga0,
-                         (long)B * h->gpix[0] * 64);
-    else if (s.col) hipLaunchKernelGGL(k_lrelu_bwd<float>, lg, dim3(256), 0, st, (const float*)h->gup1, (const float*)h->h0, h->ga0, (long)B * h->gpix[0] * 64);
-    else hipLaunchKernelGGL(k_pool_lrelu_bwd, lg, dim3(256), 0, st, h->gup1, h->h0, h->ga0, (long)B * h->gpix[0], h->gdim[0][0], h->gdim[0][1], h->gdim[0][2], 256);
+    if (s.col) launch_lrelu_bwd(s.a16, h->gup1, h->h0, h->ga0, (long)B * h->gpix[0] * 64, st);
+    else launch_pool_lrelu_bwd(h->gup1, h->h0, h->ga0, B, h->gdim[0][0], h->gdim[0][1], h->gdim[0][2], 256, st);
   }
   RD_TRY(launch_wgrad(h, h->plans[PL_GDENSE], h->d_plans + PL_GDENSE, B, h->xcat, h->ga0, grad + h->goff[0], h->wpartial,
                       h->wpartial_cap, st, RDGAN_TAG_GCONV_WGRAD));
@@ -2171,7 +2138,7 @@ extern "C" int rdgan_gen_grad_after(rdgan_handle* h, const float* dp, const floa
   RD_TRY(side_join(h, st, h->ev_join));                // the bias-gradient sums issued on the side stream above
   {
     ProfScope ps(h, RDGAN_TAG_ELEMENTWISE, st);
-    hipLaunchKernelGGL(k_gen_loss, dim3(1), dim3(256), 0, st, h->v, grad + h->n_gen, B, h->d_flag);
+    launch_gen_loss(h->v, grad + h->n_gen, B, h->d_flag, st);
   }
   RD_CHECK(h, hipGetLastError());
   return 0;
@@ -2597,6 +2564,125 @@ extern "C" int rdgan_op_pixelnorm_lrelu_bwd(const float* gh, const float* hh, co
   if (!gh || !hh || !rinv || !dy) return -2;
   RD_TRY(launch_pn_bwd(nullptr, gh, hh, rinv, dy, npix, C, 0, 0, 0, 0, (hipStream_t)stream));
   return (int)hipStreamSynchronize((hipStream_t)stream);
+}
+
+// ---- the step's elementwise kernels one by one (rdgan_elem_launch.h: the launchers the steps use) ----
+extern "C" int rdgan_op_softmax_tail(int form, const float* taps, const float* bias, float* out, int* flag, int B, int H, int W,
+                                     void* stream) {
+  if (!taps || !bias || !out || !flag || B < 1 || H < 1 || W < 1 || (long)B * H * W * RDGAN_NHOURS >= 0x7FFFFFFFL) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  if (form == 0) launch_colgather_softmax(taps, bias, out, B, H, W, flag, st);
+  else if (form == 3 || form == 9) launch_tapsum_softmax_q(form, taps, bias, out, B, H, W, flag, st);
+  else if (form == 12 && H == 16 && W == 16) launch_tapsum_softmax12(taps, bias, out, B, flag, st);
+  else return -2;
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize(st);
+}
+extern "C" int rdgan_op_softmax_bwd(const float* p, const float* g, float* dl, int B, int H, int W, void* stream) {
+  if (!p || !g || !dl || B < 1 || H < 1 || W < 1 || (long)B * H * W * RDGAN_NHOURS >= 0x7FFFFFFFL) return -2;
+  launch_softmax_bwd(p, g, dl, B, H, W, (hipStream_t)stream);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize((hipStream_t)stream);
+}
+extern "C" int rdgan_op_gp_norm(const float* g0, int B, int per, int CP, int force_S, float* cin_hat_out, float* gp_out, void* stream) {
+  if (!g0 || !cin_hat_out || !gp_out || B < 1 || per < 1 || CP < 1 || CP > 4 || force_S < 0 || force_S > 64) return -2;
+  if ((long)B * per * CP >= 0x7FFFFFFFL) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  const int S = force_S ? force_S : gp_norm_slices(B, per);
+  TmpBufs t;
+  float* part = t.floats((size_t)B * S);
+  RD_TRY(t.rc);
+  launch_gp_norm(g0, part, cin_hat_out, gp_out, per, B, CP, S, st);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize(st);
+}
+extern "C" int rdgan_op_loss_tail(int mode, const float* v, const float* gp, int B, int gflag_in, float* out8, void* stream) {
+  if (!v || !out8 || B < 1 || (mode != 0 && mode != 1) || (mode == 0 && !gp)) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  TmpBufs t;
+  int* gflag = (int*)t.bytes(sizeof(int));
+  RD_TRY(t.rc);
+  RD_TRY((int)hipMemcpyAsync(gflag, &gflag_in, sizeof(int), hipMemcpyHostToDevice, st));
+  if (mode == 0) launch_critic_losses(v, gp, out8, B, gflag, nullptr, st);
+  else launch_gen_loss(v, out8, B, gflag, st);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize(st);
+}
+extern "C" int rdgan_op_critic_dense(const void* h4, const float* w, const float* bias, float* v_out, void* u4_out, int NB, int F,
+                                     int B, int mode, uint64_t seed, int bf16, void* stream) {
+  if (!h4 || !w || !bias || !v_out || !u4_out || NB < 1 || F < 1 || B < 1 || (mode != 0 && mode != 1)) return -2;
+  if ((long)NB * F >= 0x7FFFFFFFL) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  launch_critic_dense_fwd(bf16 != 0, h4, w, bias, v_out, NB, F, st);
+  launch_critic_top_bwd(bf16 != 0, h4, w, u4_out, NB, F, B, mode, seed, st);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize(st);
+}
+extern "C" int rdgan_op_critic_dense_wgrad(const void* buf, float* out, int NB, int F, int B, int slices, int bf16, void* stream) {
+  if (!buf || !out || NB < 1 || F < 1 || B < 1 || slices < 0 || (long)NB * F >= 0x7FFFFFFFL) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  const int RS = dense_wgrad_slices(slices, NB);
+  TmpBufs t;
+  float* part = t.floats((size_t)RS * F);
+  RD_TRY(t.rc);
+  launch_critic_dense_wgrad(bf16 != 0, buf, out, part, NB, F, B, RS, st);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize(st);
+}
+extern "C" int rdgan_op_weight_forms(int which, const float* W, float* out, long CC, void* stream) {
+  if (!W || !out || CC < 4 || CC % 4 || CC > (1L << 24) || (which != 0 && which != 1)) return -2;
+  if (which == 0) launch_collapse_weights(W, out, CC, (hipStream_t)stream);
+  else launch_weight_transform(W, out, CC, (hipStream_t)stream);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize((hipStream_t)stream);
+}
+extern "C" int rdgan_op_weight_forms_adj(int which, const float* dforms, float* dW, long CC, void* stream) {
+  if (!dforms || !dW || CC < 4 || CC % 4 || CC > (1L << 24) || (which != 0 && which != 1)) return -2;
+  if (which == 0) launch_fold_collapsed_wgrad(dforms, dW, CC, (hipStream_t)stream);
+  else launch_weight_transform_adj(dforms, dW, CC, (hipStream_t)stream);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize((hipStream_t)stream);
+}
+extern "C" int rdgan_op_critic_input(const float* real, const float* fake, const float* cond, float* out, int B, int D, int HW, int nc,
+                                     int CP, int mode, uint64_t seed, uint32_t alpha_base, int scalar, void* stream) {
+  if (!cond || !out || B < 1 || D < 1 || HW < 1 || nc < 1 || nc > 3 || CP <= nc || CP > 4 || mode < 0 || mode > 2) return -2;
+  if ((mode != 1 && !real) || (mode != 2 && !fake)) return -2;
+  const long total = (long)B * D * HW;
+  if (3 * total * CP >= 0x7FFFFFFFL) return -2;
+  launch_critic_input(real, fake, cond, out, B, D, HW, nc, CP, mode, rd_make_key(seed, RD_STREAM_ALPHA), alpha_base,
+                      !scalar && critic_input_v4_ok(nc, CP, HW, total), (hipStream_t)stream);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize((hipStream_t)stream);
+}
+extern "C" int rdgan_op_pool_lrelu_bwd(const float* gup, const float* h0, float* out, int B, int D, int H, int W, int C, void* stream) {
+  if (!gup || !h0 || !out || B < 1 || D < 1 || H < 1 || W < 1 || C < 4 || C % 4 || 8L * B * D * H * W * C >= 0x7FFFFFFFL) return -2;
+  launch_pool_lrelu_bwd(gup, h0, out, B, D, H, W, C, (hipStream_t)stream);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize((hipStream_t)stream);
+}
+extern "C" int rdgan_op_lrelu_bwd(const void* g, const void* h, float* out, long n, int bf16, void* stream) {
+  if (!g || !h || !out || n < 4 || n % 4) return -2;
+  launch_lrelu_bwd(bf16 != 0, g, h, out, n / 4, (hipStream_t)stream);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize((hipStream_t)stream);
+}
+extern "C" int rdgan_op_colsum(rdgan_handle* h, const void* src, long rows, int C, float* out, int bf16, void* stream) {
+  if (!h) return -2;
+  if (!src || !out || rows < 1 || C < 1) return bad_arg(h, "op_colsum: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ahead_drain(h, st));
+  RD_TRY(launch_colsum(h, (const float*)src, rows, C, out, st, bf16 != 0));
+  return (int)hipStreamSynchronize(st);
+}
+extern "C" int rdgan_op_diff_combine(const void* x, void* E_out, void* dx_inout, const void* dE, int B, int D, long P, int bf16,
+                                     void* stream) {
+  if (B < 1 || D < 1 || P < 4 || P % 4 || (x == nullptr) != (E_out == nullptr) || (dx_inout == nullptr) != (dE == nullptr)) return -2;
+  if (!x && !dx_inout) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  if (x) launch_diff_d(bf16 != 0, x, E_out, B, D, P, st);
+  if (dx_inout) launch_combine_dx(bf16 != 0, dx_inout, dE, B, D, P, st);
+  RD_TRY((int)hipGetLastError());
+  return (int)hipStreamSynchronize(st);
 }
 
 // test hook: the first critic layer's input gradient w.r.t. the sample channel from a given u1 [B][L1][64] (fp32), by the route

@@ -308,7 +308,8 @@ __global__ void k_pool_lrelu_bwd(const float* __restrict__ gup, const float* __r
 
 // G9+G10+G11 (T:345-350): logits[pos] = bias + sum_tap P[pos+tap-1][tap] from the column GEMM
 // P[pos][32] = h3[pos][:] . W9[:, tap]; then softmax over the 24 hours of each grid point.
-// One thread per (sample, h, w) column.  Sets *nonfinite if any output is NaN/Inf.
+// One thread per (sample, h, w) column.  Sets *nonfinite if any logit or output is NaN/Inf (all four tails do: the reference's
+// check_numerics sees the output only, where a lone -Inf logit is a finite p = 0; flagging it is stricter, finite inputs are unaffected).
 __global__ void k_colgather_softmax(const float* __restrict__ P, const float* __restrict__ bias, float* __restrict__ out,
                                     int B, int D, int H, int W, int* __restrict__ nonfinite) {
   const long ncol = (long)B * H * W;
@@ -320,6 +321,7 @@ __global__ void k_colgather_softmax(const float* __restrict__ P, const float* __
   const long hw = (long)H * W;
   float* o = out + b * D * hw + (long)h * W + w;
   float mx = -3.0e38f;
+  bool bad = false;                // a NaN/Inf logit or output (a lone -Inf logit leaves only finite outputs: caught here)
   for (int d = 0; d < D; ++d) {
     float s = bv;
     for (int td = 0; td < 3; ++td) {
@@ -337,11 +339,11 @@ __global__ void k_colgather_softmax(const float* __restrict__ P, const float* __
       }
     }
     o[d * hw] = s;               // raw logit, re-read by this same thread below
+    bad |= !(fabsf(s) <= 3.0e38f);
     mx = fmaxf(mx, s);
   }
   float den = 0.f;
   for (int d = 0; d < D; ++d) { float e = expf(o[d * hw] - mx); o[d * hw] = e; den += e; }
-  bool bad = false;
   for (int d = 0; d < D; ++d) {
     float p = o[d * hw] / den;
     bad |= !(fabsf(p) <= 3.0e38f);
@@ -373,6 +375,7 @@ k_tapsum_softmax(const float* __restrict__ Q, const float* __restrict__ bias, fl
   const float* q = Q + b * D * NQ * hw;
   float lg[DP];
   float mx = -3.0e38f;
+  bool bad = false;                // a NaN/Inf logit or output (a lone -Inf logit leaves only finite outputs: caught here)
 #pragma unroll
   for (int i = 0; i < DP; ++i) {
     const int d = part * DP + i;
@@ -392,6 +395,7 @@ k_tapsum_softmax(const float* __restrict__ Q, const float* __restrict__ bias, fl
       }
     }
     lg[i] = s;
+    bad |= !(fabsf(s) <= 3.0e38f);
     mx = fmaxf(mx, s);
   }
   mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -402,7 +406,6 @@ k_tapsum_softmax(const float* __restrict__ Q, const float* __restrict__ bias, fl
   // (fixed order of the four partial sums: (p0 + p1) + (p2 + p3) on every lane)
   den += __shfl_xor(den, 16, 64);
   den += __shfl_xor(den, 32, 64);
-  bool bad = false;
   float* o = out + b * D * hw + (long)h * W + w;
 #pragma unroll
   for (int i = 0; i < DP; ++i) {
@@ -439,6 +442,7 @@ k_tapsum_softmax12(const float* __restrict__ Q12, const float* __restrict__ bias
   const float* q = Q12 + b * (D / 4 * 6 * 1024) + cidx;
   f32x4 lg[DP];
   f32x4 mx = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+  bool bad = false;                // a NaN/Inf logit or output (a lone -Inf logit leaves only finite outputs: caught here)
 #pragma unroll
   for (int i = 0; i < DP; ++i) {
     const int d = part * DP + i;
@@ -456,7 +460,7 @@ k_tapsum_softmax12(const float* __restrict__ Q12, const float* __restrict__ bias
     }
     lg[i] = s;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) mx[c] = fmaxf(mx[c], s[c]);
+    for (int c = 0; c < 4; ++c) { bad |= !(fabsf(s[c]) <= 3.0e38f); mx[c] = fmaxf(mx[c], s[c]); }
   }
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -473,7 +477,6 @@ k_tapsum_softmax12(const float* __restrict__ Q12, const float* __restrict__ bias
     den[c] += __shfl_xor(den[c], 16, 64);
     den[c] += __shfl_xor(den[c], 32, 64);
   }
-  bool bad = false;
   const long hw = (long)H * W;
   float* o = out + b * D * hw + (long)h * W + w0;
 #pragma unroll
@@ -537,6 +540,10 @@ __global__ void k_dl_im2col(const float* __restrict__ dl, float* __restrict__ co
 // mode 0: out[0:B] = real, out[B:2B] = fake, out[2B:3B] = alpha*real + (1-alpha)*fake, alpha = uniform(key, alpha_base + b)
 // (alpha_base = global index of this rank's first sample, option "sample_offset")
 // mode 1: out[0:B] = fake only (generator step);  mode 2: out[0:B] = real only (critic.predict).
+// x_hat = alpha real + (1 - alpha) fake (T:223-224) with its roundings spelled out -- (1 - a) fake rounded, then one fused a real + that
+// -- so that both kernels below give the same bits: left to the compiler's contraction, the scalar and the four-voxel form differed
+// in the last bit.
+__device__ __forceinline__ float rd_interp(float a, float rl, float fk) { return __fmaf_rn(a, rl, __fmul_rn(1.0f - a, fk)); }
 __global__ void k_build_critic_input(const float* __restrict__ real, const float* __restrict__ fake,
                                      const float* __restrict__ cond, float* __restrict__ out, int B, int D, int HW,
                                      int nc, int CP, int mode, uint32_t alpha_key, uint32_t alpha_base) {
@@ -556,7 +563,7 @@ __global__ void k_build_critic_input(const float* __restrict__ real, const float
     if (mode == 0) {
       float rl = real[f], fk = fake[f];
       float a = rd_uniform(alpha_key, alpha_base + (uint32_t)b);
-      put(f, rl); put(total + f, fk); put(2 * total + f, a * rl + (1.0f - a) * fk);
+      put(f, rl); put(total + f, fk); put(2 * total + f, rd_interp(a, rl, fk));
     } else if (mode == 1) {
       put(f, fake[f]);
     } else {
@@ -583,7 +590,8 @@ __global__ void k_build_critic_input_v4(const float* __restrict__ real, const fl
     if (mode == 0) {
       const f32x4 rl = *(const f32x4*)(real + (long)q * 4), fk = *(const f32x4*)(fake + (long)q * 4);
       const float a = rd_uniform(alpha_key, alpha_base + b);
-      put(q, rl); put((long)total4 + q, fk); put(2L * total4 + q, a * rl + (1.0f - a) * fk);
+      put(q, rl); put((long)total4 + q, fk);
+      put(2L * total4 + q, (f32x4){rd_interp(a, rl.x, fk.x), rd_interp(a, rl.y, fk.y), rd_interp(a, rl.z, fk.z), rd_interp(a, rl.w, fk.w)});
     } else if (mode == 1) {
       put(q, *(const f32x4*)(fake + (long)q * 4));
     } else {

@@ -441,6 +441,7 @@ k_tapsum_softmax12t(const float* __restrict__ Q12, const float* __restrict__ bia
   const float* qb = Q12 + (long)b * 6 * istride + (long)tile * RD_UPT_QITEM + q * 64 + ly * 8 + lx0;
   f32x4 lg[DP];
   f32x4 mx = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+  bool bad = false;                // a NaN/Inf logit or output (a lone -Inf logit leaves only finite outputs: caught here)
 #pragma unroll
   for (int i = 0; i < DP; ++i) {
     const int d = part * DP + i, it = d >> 2, k = d & 3;
@@ -457,7 +458,7 @@ k_tapsum_softmax12t(const float* __restrict__ Q12, const float* __restrict__ bia
     }
     lg[i] = s;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) mx[c] = fmaxf(mx[c], s[c]);
+    for (int c = 0; c < 4; ++c) { bad |= !(fabsf(s[c]) <= 3.0e38f); mx[c] = fmaxf(mx[c], s[c]); }
   }
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -474,7 +475,6 @@ k_tapsum_softmax12t(const float* __restrict__ Q12, const float* __restrict__ bia
     den[c] += __shfl_xor(den[c], 16, 64);
     den[c] += __shfl_xor(den[c], 32, 64);
   }
-  bool bad = false;
   const int Y = 2 * (8 * th + ly) + qh_, X0 = 2 * (8 * tw + lx0) + qw_;          // the four columns: X0, X0 + 2, X0 + 4, X0 + 6
   const long hw = 4L * H * W;
   float* o = out + (long)b * D * hw + (long)Y * (2 * W) + X0;
