@@ -590,6 +590,31 @@ int rdgan_cells_accumulate(const float* x, long n, long day_stride, long ny, lon
                            int connectivity, long long* counts_inout, int* labels_out, int label_threshold, void* workspace,
                            long workspace_bytes, void* stream);
 
+/* Object-based verification of hourly fields: the per-plane records from which SAL (Wernli, Paulat, Hagen
+ * and Frei 2008) -- structure, amplitude, location -- of a generated plane against the observed one is formed on the host.
+ * x, n, day_stride, ny, nx, thresholds, wet and bad pixels, connectivity: as for rdgan_cells_accumulate above; the objects of a
+ * plane at threshold t are its cells there, with the same canonical labels.  The mass of a valid (finite) pixel is
+ * q = (int) rintf(clamp(x, 0, 2048 - 1/1024) * 1024), 0 <= q < 2^21, in units of 2^-10 mm; its coordinates are the integers y, x.
+ * plane_out [n * 24][4] 64-bit integers (device): n_bad, M0 = sum q, Mx = sum q x, My = sum q y over the valid pixels of the plane.
+ * obj_out [n * 24][T][3] 64-bit integers (device): n_objects, n_wet, R = sum_n R_n, where for object n R_n = sum q, Rmax_n = max q,
+ * Sx_n = sum q x, Sy_n = sum q y over its pixels.
+ * vr_out [n * 24][T][2] doubles (device): V = (sum_n R_n (R_n / Rmax_n)) / R and
+ * r = (sum_n R_n hypot(Sx_n / R_n - Mx / M0, Sy_n / R_n - My / M0)) / R, the sums over the objects with R_n > 0; both 0 when R = 0.
+ * The outputs are OVERWRITTEN.  The integers are formed with integer atomics; the fp64 sums run over the objects in a tree fixed by
+ * the pixel index of their labels and by ny nx alone, without floating-point atomics, so every record of a plane is bitwise the
+ * same however the planes are split into calls or passes.
+ * Every sum stays below 2^63 because a plane with 2^21 max(ny, nx) ny nx >= 2^63 is refused (on top of ny nx <= 2^24).
+ * workspace: device memory, 8-byte aligned.  rdgan_sal_workspace_bytes(ny, nx, planes_per_pass) is the size that lets a pass take
+ * planes_per_pass planes (1 .. 65535; 48 bytes per pixel, 40 per 4096 pixels begun and 200 per plane; -2 for an argument out of
+ * range); the entry takes floor(workspace_bytes / rdgan_sal_workspace_bytes(ny, nx, 1)) planes per pass.  Asynchronous on the
+ * stream; 0 = success, -2 = bad argument (a null or misaligned pointer, n, ny or nx < 1, a size above the limits, a threshold list
+ * out of range, connectivity not 4 or 8, day_stride < 24 ny nx, a workspace too small for one plane) with nothing launched and no
+ * output touched.  All offsets are 64-bit. */
+long rdgan_sal_workspace_bytes(long ny, long nx, long planes_per_pass);
+int rdgan_sal_records(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds, int n_thresholds,
+                      int connectivity, long long* plane_out, long long* obj_out, double* vr_out, void* workspace,
+                      long workspace_bytes, void* stream);
+
 /* Storms of hourly fields: wet volumes connected through the day's hours, labelled and counted -- how long
  * a rain system lives, when it starts, and how much of the day's water falls in long-lived systems.
  * x, n, day_stride, ny, nx, thresholds, wet and bad pixels, connectivity, q(x): as for the cells entry above.  A voxel (h, y, x)

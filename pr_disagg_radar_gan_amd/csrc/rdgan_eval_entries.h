@@ -621,6 +621,66 @@ extern "C" int rdgan_cells_accumulate(const float* x, long n, long day_stride, l
 }
 
 // ------------------------------------------------------------------------------------
+// object-based verification (rdgan_sal.hip.h): the per-plane records of SAL on the cells' labels
+// ------------------------------------------------------------------------------------
+// the cells' limits, and every moment below 2^63: 2^21 max(ny, nx) ny nx < 2^63
+static bool rd_sal_shape_ok(long ny, long nx) {
+  return rd_cl_shape_ok(ny, nx) && (long long)std::max(ny, nx) * ny * nx < RD_SAL_MAXMOMENT;
+}
+
+extern "C" long rdgan_sal_workspace_bytes(long ny, long nx, long planes_per_pass) {
+  if (!rd_sal_shape_ok(ny, nx) || planes_per_pass < 1 || planes_per_pass > RD_CL_MAXPASS) return -2;
+  return rd_sal_ws_bytes(ny * nx, planes_per_pass);
+}
+
+extern "C" int rdgan_sal_records(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds, int n_thresholds,
+                                 int connectivity, long long* plane_out, long long* obj_out, double* vr_out, void* workspace,
+                                 long workspace_bytes, void* stream) {
+  rd_thr thr;
+  if (!x || !plane_out || !obj_out || !vr_out || !workspace) return -2;
+  if (!rd_aligned(7, plane_out, obj_out, vr_out, workspace)) return -2;
+  if (!rd_sal_shape_ok(ny, nx) || (connectivity != 4 && connectivity != 8)) return -2;
+  const long plane = ny * nx, day = RD_HOURS * plane;
+  if (!rd_hourly_layout_ok((const void*)x, n, day_stride, day)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  // the planes of a pass: as many as the workspace holds
+  const long n_planes = n * RD_HOURS, chunks = rd_sal_chunks(plane);
+  const long per_pass = rd_pass_units(workspace_bytes, rd_sal_ws_bytes(plane, 1), n_planes, RD_CL_MAXPASS);
+  if (per_pass < 1) return -2;
+  unsigned long long* vol = (unsigned long long*)workspace;
+  unsigned long long* obj = vol + per_pass * plane;
+  unsigned long long* partial = obj + 4 * per_pass * plane;
+  unsigned long long* sink = partial + RD_SAL_NPART * per_pass * chunks;   // wet counts by hour, read by nobody
+  int* parent = (int*)(sink + RD_SAL_SINK * per_pass);
+  unsigned* area = (unsigned*)(parent + per_pass * plane);
+  unsigned* words = area + per_pass * plane;
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ensure_lds(nullptr, (const void*)k_cells_label_tile, RD_CL_LDS_BYTES));
+  hipError_t e = hipMemsetAsync(plane_out, 0, (size_t)n_planes * 4 * sizeof(long long), st);       // the whole-plane sums are added
+  if (e != hipSuccess) return (int)e;
+  const int conn8 = connectivity == 8;
+  const unsigned pblocks = (unsigned)((plane + RD_SAL_THREADS - 1) / RD_SAL_THREADS);
+  for (long p0 = 0; p0 < n_planes; p0 += per_pass) {
+    const unsigned P = (unsigned)std::min<long>(per_pass, n_planes - p0);
+    for (int t = 0; t < n_thresholds; ++t) {
+      rd_cl_label_planes(st, x, day_stride, ny, nx, p0, P, thr.v[t], conn8, 0, sink, sink, vol, parent, area, words);
+      hipLaunchKernelGGL(k_cells_resolve, dim3((unsigned)((plane + RD_CL_THREADS - 1) / RD_CL_THREADS), P), dim3(RD_CL_THREADS), 0, st, plane,
+                         p0, vol, parent, area, (int*)nullptr);
+      hipLaunchKernelGGL(k_sal_clear, dim3(pblocks, P), dim3(RD_SAL_THREADS), 0, st, plane, (const int*)parent, obj);
+      hipLaunchKernelGGL(k_sal_moments, dim3(pblocks, P), dim3(RD_SAL_THREADS), 0, st, x, day_stride, (int)nx, plane, p0, (int)(t == 0),
+                         (const int*)parent, obj, (unsigned long long*)plane_out);
+      hipLaunchKernelGGL(k_sal_plane, dim3((unsigned)chunks, P), dim3(RD_SAL_THREADS), 0, st, plane, p0, (const int*)parent,
+                         (const unsigned*)area, (const unsigned long long*)obj, (const unsigned long long*)plane_out, partial);
+      hipLaunchKernelGGL(k_sal_final, dim3(P), dim3(64), 0, st, chunks, p0, t, n_thresholds, (const unsigned long long*)partial, obj_out,
+                         vr_out);
+      e = hipGetLastError();
+      if (e != hipSuccess) return (int)e;
+    }
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
 // storms of hourly fields (rdgan_storms.hip.h): wet volumes connected through the day's hours, labelled and counted
 // ------------------------------------------------------------------------------------
 static bool rd_sm_shape_ok(long ny, long nx) { return rd_cl_shape_ok(ny, nx) && RD_HOURS * ny * nx <= RD_SM_MAXDAY; }

@@ -110,6 +110,18 @@ def verify_scenarios_field(observed, n_scenarios, thresholds, scales=(1, 3, 5, 9
                                      norm_scale=norm_scale)
 
 
+def sal_scenarios_field(observed, n_scenarios, thresholds, connectivity=8, overlap=4, latent_mode="shared", scenario_chunk=16):
+    """SAL of n_scenarios scenarios of a whole observed day against its hours (sal.sal_field on the module's ``gen`` and
+    ``norm_scale``): per scenario, hour and threshold the structure, amplitude and location components of the object-based
+    verification of Wernli et al. (2008).  observed: ndarray ([n_days,] 24, ny, nx) in mm/h; its daily sums are the condition.
+    thresholds: the wet-pixel events in mm/h.  Returns a sal.SAL (numpy): S, A, L1, L2, L, mask_mismatch and summary().  The latent
+    noise comes from the global numpy RNG as in generate_scenarios_field; the hourly scenarios are produced scenario_chunk at a time
+    and never held together."""
+    from . import sal
+    return sal.sal_field(gen, np.asarray(observed), n_scenarios, thresholds, connectivity=connectivity, scenario_chunk=scenario_chunk,
+                         overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
+
+
 def temporal_structure_field(daily, n_scenarios, thresholds, max_lag=6, overlap=4, latent_mode="shared", scenario_chunk=16):
     """The temporal structure of n_scenarios scenarios of a whole daily map (temporal.temporal_structure_field on the module's
     ``gen`` and ``norm_scale``): wet-spell and dry-spell lengths, wet hours per day, wet/dry transitions by hour, lag correlations.
