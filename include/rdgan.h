@@ -615,6 +615,33 @@ int rdgan_sal_records(const float* x, long n, long day_stride, long ny, long nx,
                       int connectivity, long long* plane_out, long long* obj_out, double* vr_out, void* workspace,
                       long workspace_bytes, void* stream);
 
+/* Scale-separation verification of hourly fields: the integer state of the intensity-scale skill score
+ * (Casati, Ross and Stephenson 2004; Casati 2010) of s member arrays against the observed hours.
+ * members [s][n_days][24][ny][nx] fp32 (device), member m at members + m * member_stride, member_stride >= n_days 24 ny nx;
+ * obs [n_days][24][ny][nx] fp32 (device), dense.  1 <= s <= 4096, ny nx <= 2^24, s n_days 24 ny nx <= 2^40.
+ * thresholds: 1 .. 8 values, as for rdgan_verify_accumulate; the event of a finite value v at threshold u is v > u in fp32.
+ * levels = L, 1 .. 10, 2^L <= min(ny, nx): a tile is a square of side 2^L; the plane is cropped to floor(ny / 2^L) x
+ * floor(nx / 2^L) tiles from (oy, ox) = ((ny mod 2^L) / 2, (nx mod 2^L) / 2), integer divisions.  A pair is one member plane
+ * beside the observed plane of the same day and hour; a tile of a pair is void when any of its pixels is NaN or +-inf in the
+ * member or in the observation, and then contributes nothing.
+ * counts_inout, flat order [t][h][l][3], T x 24 x (L + 1) x 3 64-bit integers (device): summed over the blocks b of side 2^l
+ * (aligned to the tile) of the valid tiles of all pairs of hour h, QX = sum SX_l(b)^2, QO = sum SO_l(b)^2, QXO = sum SX_l(b) SO_l(b),
+ * SX and SO the events of the member and of the observation in b.  tiles_inout [h][2] 64-bit integers: (valid, void) tile-pairs.
+ * Both are ADDED to with 64-bit integer atomics (the caller zeroes them before the first call), so the state does not depend on
+ * how the members are split into calls, on the pass size or on the launch geometry.  One call adds at most
+ * (pixel-pairs of the call) 4^L <= 2^40 2^20 = 2^60 to a counter; the caller keeps (pixel-pairs accumulated) 4^L <= 2^62.
+ * workspace: device memory, 8-byte aligned.  rdgan_iss_workspace_bytes(ny, nx, levels, pairs_per_pass), pairs_per_pass 1 .. 2^30,
+ * is the size that lets a pass hold that many pairs: 8 bytes a pair up to L = 6 (nothing is held), and for L = 7 .. 10
+ * ceil(cy / 64) ceil(cx / 64) (8 x 4 x 20 x 4 + 8) bytes a pair, (cy, cx) the cropped size (-2 for an argument out of range).  The
+ * entry takes floor(workspace_bytes / rdgan_iss_workspace_bytes(ny, nx, levels, 1)) pairs per pass.  Asynchronous on the stream;
+ * 0 = success, -2 = bad argument (a null or misaligned pointer, a size < 1 or above the limits, levels outside 1 .. 10 or
+ * 2^levels > min(ny, nx), a threshold list out of range, s > 4096, member_stride < n_days 24 ny nx, a workspace too small for one
+ * pair) with nothing launched and no output touched.  All offsets are 64-bit. */
+long rdgan_iss_workspace_bytes(long ny, long nx, int levels, long pairs_per_pass);
+int rdgan_iss_accumulate(const float* members, int s, long member_stride, const float* obs, long n_days, long ny, long nx,
+                         const double* thresholds, int n_thresholds, int levels, long long* counts_inout, long long* tiles_inout,
+                         void* workspace, long workspace_bytes, void* stream);
+
 /* Storms of hourly fields: wet volumes connected through the day's hours, labelled and counted -- how long
  * a rain system lives, when it starts, and how much of the day's water falls in long-lived systems.
  * x, n, day_stride, ny, nx, thresholds, wet and bad pixels, connectivity, q(x): as for the cells entry above.  A voxel (h, y, x)

@@ -44,6 +44,7 @@
 #include "rdgan_temporal.hip.h"
 #include "rdgan_cells.hip.h"
 #include "rdgan_sal.hip.h"
+#include "rdgan_iss.hip.h"
 #include "rdgan_storms.hip.h"
 #include "rdgan_areal.hip.h"
 #include "rdgan_catchment.hip.h"

@@ -681,6 +681,75 @@ extern "C" int rdgan_sal_records(const float* x, long n, long day_stride, long n
 }
 
 // ------------------------------------------------------------------------------------
+// scale-separation verification (rdgan_iss.hip.h): the integer state of the intensity-scale skill score
+// ------------------------------------------------------------------------------------
+static bool rd_iss_shape_ok(long ny, long nx, int levels) {
+  return rd_cl_shape_ok(ny, nx) && levels >= 1 && levels <= RD_ISS_MAXL && (1L << levels) <= std::min(ny, nx);
+}
+
+extern "C" long rdgan_iss_workspace_bytes(long ny, long nx, int levels, long pairs_per_pass) {
+  if (!rd_iss_shape_ok(ny, nx, levels) || pairs_per_pass < 1 || pairs_per_pass > (1L << 30)) return -2;
+  return pairs_per_pass * rd_iss_pair_bytes(ny, nx, levels);
+}
+
+// member slices of a launch of k_iss_tiles: enough workgroups to fill the device, at least 8 members each where there are as many
+static unsigned rd_iss_split(long workgroups, int nm) {
+  const long want = (2048 + workgroups - 1) / workgroups, most = (nm + 7) / 8;
+  return (unsigned)std::max<long>(1, std::min<long>(std::min<long>(want, most), RD_ISS_MAXSPLIT));
+}
+
+extern "C" int rdgan_iss_accumulate(const float* members, int s, long member_stride, const float* obs, long n_days, long ny, long nx,
+                                    const double* thresholds, int n_thresholds, int levels, long long* counts_inout,
+                                    long long* tiles_inout, void* workspace, long workspace_bytes, void* stream) {
+  rd_thr thr;
+  if (!members || !obs || !counts_inout || !tiles_inout || !workspace) return -2;
+  if (!rd_aligned(3, members, obs) || !rd_aligned(7, counts_inout, tiles_inout, workspace)) return -2;
+  if (s < 1 || s > RD_ISS_MAXS || n_days < 1 || !rd_iss_shape_ok(ny, nx, levels)) return -2;
+  const long plane = ny * nx;
+  if (n_days > RD_HOURLY_MAXELEMS / (RD_HOURS * plane)) return -2;
+  const long P = n_days * RD_HOURS * plane;
+  if (!rd_hourly_layout_ok((const void*)members, (long)s, member_stride, P)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  const rd_iss_geo g = rd_iss_geometry(ny, nx, levels);
+  const long units = (n_days + g.G - 1) / g.G * RD_HOURS, nblocks = (long)g.nby * g.nbx;
+  const long per_pass = rd_pass_units(workspace_bytes, rd_iss_pair_bytes(ny, nx, levels), (long)s * units, 1L << 30);
+  if (per_pass < 1) return -2;
+  const int T = n_thresholds;
+  unsigned long long* counts = (unsigned long long*)counts_inout;
+  unsigned long long* tiles = (unsigned long long*)tiles_inout;
+  hipStream_t st = (hipStream_t)stream;
+  if (levels <= 6) {                       // nothing is held back: every member in one launch per RD_ISS_MAXUNITS units
+    for (long u0 = 0; u0 < units; u0 += RD_ISS_MAXUNITS) {
+      const unsigned nu = (unsigned)std::min<long>(RD_ISS_MAXUNITS, units - u0);
+      hipLaunchKernelGGL(k_iss_tiles, dim3((unsigned)nblocks, nu, rd_iss_split(nblocks * nu, s)), dim3(RD_ISS_THREADS), 0, st, members,
+                         member_stride, 0, s, obs, n_days, g, thr, T, u0, counts, tiles, (unsigned*)nullptr, (unsigned*)nullptr);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+  }
+  // the pairs of a pass: every member of as many units as the workspace holds, or of one unit as many members as it holds
+  const int nm = (int)std::min<long>(per_pass, s);
+  const long nu_pass = per_pass >= s ? std::min<long>(std::min<long>(per_pass / s, units), RD_ISS_MAXUNITS) : 1;
+  unsigned* held = (unsigned*)workspace;
+  unsigned* flags = held + (long)nm * nu_pass * nblocks * T * 4 * RD_ISS_REC;
+  const unsigned n_tiles = (unsigned)((g.cy >> levels) * (g.cx >> levels));
+  for (long u0 = 0; u0 < units; u0 += nu_pass) {
+    const unsigned nu = (unsigned)std::min<long>(nu_pass, units - u0);
+    for (int m0 = 0; m0 < s; m0 += nm) {
+      const int n = std::min(nm, s - m0);
+      hipLaunchKernelGGL(k_iss_tiles, dim3((unsigned)nblocks, nu, rd_iss_split(nblocks * nu, n)), dim3(RD_ISS_THREADS), 0, st, members,
+                         member_stride, m0, n, obs, n_days, g, thr, T, u0, counts, tiles, held, flags);
+      hipLaunchKernelGGL(k_iss_upper, dim3(n_tiles, nu, (unsigned)n), dim3(RD_ISS_THREADS), 0, st, (const unsigned*)held,
+                         (const unsigned*)flags, g, T, u0, counts, tiles);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return (int)e;
+    }
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
 // storms of hourly fields (rdgan_storms.hip.h): wet volumes connected through the day's hours, labelled and counted
 // ------------------------------------------------------------------------------------
 static bool rd_sm_shape_ok(long ny, long nx) { return rd_cl_shape_ok(ny, nx) && RD_HOURS * ny * nx <= RD_SM_MAXDAY; }

@@ -122,6 +122,20 @@ def sal_scenarios_field(observed, n_scenarios, thresholds, connectivity=8, overl
                          overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
 
+def intensity_scale_scenarios_field(observed, n_scenarios, thresholds, levels=None, overlap=4, latent_mode="shared", scenario_chunk=16):
+    """The intensity-scale skill of n_scenarios scenarios of a whole observed day against its hours
+    (intensity_scale.intensity_scale_field on the module's ``gen`` and ``norm_scale``): per threshold the binary error split by Haar
+    wavelets into spatial scales of 1, 2, 4 ... 2^levels pixels (Casati et al. 2004).  observed: ndarray ([n_days,] 24, ny, nx) in
+    mm/h; its daily sums are the condition.  thresholds: the events in mm/h; levels: the tile is 2^levels pixels wide, by default the
+    largest that fits.  Returns an intensity_scale.IntensityScale (numpy): mse(), skill(), energy(), contingency(), summary().  The
+    latent noise comes from the global numpy RNG as in generate_scenarios_field; the hourly scenarios are produced scenario_chunk at
+    a time and never held together."""
+    from . import intensity_scale
+    return intensity_scale.intensity_scale_field(gen, np.asarray(observed), n_scenarios, thresholds, levels=levels,
+                                                 scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode,
+                                                 norm_scale=norm_scale)
+
+
 def temporal_structure_field(daily, n_scenarios, thresholds, max_lag=6, overlap=4, latent_mode="shared", scenario_chunk=16):
     """The temporal structure of n_scenarios scenarios of a whole daily map (temporal.temporal_structure_field on the module's
     ``gen`` and ``norm_scale``): wet-spell and dry-spell lengths, wet hours per day, wet/dry transitions by hour, lag correlations.
