@@ -642,6 +642,40 @@ int rdgan_iss_accumulate(const float* members, int s, long member_stride, const 
                          const double* thresholds, int n_thresholds, int levels, long long* counts_inout, long long* tiles_inout,
                          void* workspace, long workspace_bytes, void* stream);
 
+/* Distance-map verification of hourly fields: the exact Euclidean distance transform of event sets and the
+ * per-pair records from which Hausdorff distance, mean error distance, Baddeley's Delta and Zhu's measure are formed on the host.
+ * For a threshold u (1 .. 8 values, as for rdgan_verify_accumulate) the set of a plane is its pixels with a finite value v > u in
+ * fp32; a NaN or +-inf pixel is bad and in no set.  d2(x, S) = min over a in S of dy^2 + dx^2, an exact integer, measured in the
+ * plane's own geometry across bad pixels; D(x, S) = isqrt(256 d2(x, S)) = floor(16 sqrt(d2)), the distance in 1/16 pixel, and
+ * 0xFFFF for an empty S.  1 <= ny, nx <= 2048: D <= 46 318.
+ * rdgan_dm_maps: x [n][24][ny][nx] fp32 (device), day i at x + i * day_stride, day_stride >= 24 ny nx, n 24 ny nx <= 2^40.
+ * maps_out [n * 24][T][ny][nx] uint16 (device): D(x, S_t) of every plane and threshold; set_sizes_out [n * 24][T] 64-bit integers
+ * (device): the pixels of each whole set.  Both are OVERWRITTEN.
+ * rdgan_dm_records: members [s][n_days][24][ny][nx] fp32 (device), member m at members + m * member_stride, member_stride >=
+ * n_days 24 ny nx, 1 <= s <= 4096, s n_days 24 ny nx <= 2^40; obs [n_days][24][ny][nx] fp32 (device), dense; obs_maps: the
+ * maps_out of rdgan_dm_maps for obs and the same thresholds.  A pair is one member plane beside the observed plane of the same day
+ * and hour; A is the member's set, B the observation's; a pixel is valid when it is finite on both sides.  cutoff16 = C, 16 ..
+ * 65534, in 1/16 pixel: w(x, S) = min(D(x, S), C).  records_out [s][n_days * 24][T][12] 64-bit integers (device), OVERWRITTEN:
+ *   0 n_valid; 1, 2, 3 nA, nB, nAB, the pixels of A, of B and of both among the valid ones;
+ *   4 sum over valid x in B of D(x, A); 5 sum over valid x in A of D(x, B); 6, 7 the maxima of the same two (the directed Hausdorff
+ *   distances); each of 4 .. 7 is 0 when the other set is empty;
+ *   8, 9, 10 over valid x: sum |wA - wB|, sum (wA - wB)^2, max |wA - wB|;
+ *   11 flags: bit 0 the bad-pixel masks of the two sides differ, bit 1 A empty, bit 2 B empty (the whole sets).
+ * Every sum stays below 2^54 (2^22 pixels times 46 318^2).  Integer atomics only: the records are bitwise independent of how the
+ * members are split into calls, of the pass size and of the launch geometry.
+ * workspace: device memory, 8-byte aligned.  rdgan_dm_workspace_bytes(ny, nx, planes_per_pass), planes_per_pass 1 .. 2^20, is the
+ * size that lets a pass take that many planes: 9 ny ceil(nx / 64) 8 + 64 bytes a plane (-2 for an argument out of range); the
+ * entries take floor(workspace_bytes / rdgan_dm_workspace_bytes(ny, nx, 1)) planes per pass.  Asynchronous on the stream;
+ * 0 = success, -2 = bad argument (a null or misaligned pointer, a size < 1 or above the limits, a side above 2048, a threshold
+ * list out of range, s > 4096, a stride too small, cutoff16 out of range, a workspace too small for one plane) with nothing
+ * launched and no output touched.  All offsets are 64-bit. */
+long rdgan_dm_workspace_bytes(long ny, long nx, long planes_per_pass);
+int rdgan_dm_maps(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds, int n_thresholds,
+                  unsigned short* maps_out, long long* set_sizes_out, void* workspace, long workspace_bytes, void* stream);
+int rdgan_dm_records(const float* members, int s, long member_stride, const float* obs, const unsigned short* obs_maps, long n_days,
+                     long ny, long nx, const double* thresholds, int n_thresholds, int cutoff16, long long* records_out,
+                     void* workspace, long workspace_bytes, void* stream);
+
 /* Storms of hourly fields: wet volumes connected through the day's hours, labelled and counted -- how long
  * a rain system lives, when it starts, and how much of the day's water falls in long-lived systems.
  * x, n, day_stride, ny, nx, thresholds, wet and bad pixels, connectivity, q(x): as for the cells entry above.  A voxel (h, y, x)

@@ -114,6 +114,12 @@ SIGNATURES = {
     "rdgan_iss_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_long, c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long,
                                             ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_long, c_stream]),
+    "rdgan_dm_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_long]),
+    "rdgan_dm_maps": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_int,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),
+    "rdgan_dm_records": (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_long, c_f32p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long,
+                                        ctypes.c_long, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_long, c_stream]),
     "rdgan_storms_state_count": (ctypes.c_long, [ctypes.c_int]),
     "rdgan_storms_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_long]),
     "rdgan_storms_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,

@@ -45,6 +45,7 @@
 #include "rdgan_cells.hip.h"
 #include "rdgan_sal.hip.h"
 #include "rdgan_iss.hip.h"
+#include "rdgan_distmap.hip.h"
 #include "rdgan_storms.hip.h"
 #include "rdgan_areal.hip.h"
 #include "rdgan_catchment.hip.h"

@@ -750,6 +750,96 @@ extern "C" int rdgan_iss_accumulate(const float* members, int s, long member_str
 }
 
 // ------------------------------------------------------------------------------------
+// distance-map verification (rdgan_distmap.hip.h): exact distance transforms of event sets and the records of pairs
+// ------------------------------------------------------------------------------------
+static bool rd_dm_shape_ok(long ny, long nx) { return ny >= 1 && nx >= 1 && ny <= RD_DM_MAXSIDE && nx <= RD_DM_MAXSIDE; }
+
+extern "C" long rdgan_dm_workspace_bytes(long ny, long nx, long planes_per_pass) {
+  if (!rd_dm_shape_ok(ny, nx) || planes_per_pass < 1 || planes_per_pass > RD_DM_MAXPASS) return -2;
+  return planes_per_pass * rd_dm_plane_bytes(ny, nx);
+}
+
+// One pass: pack P planes from plane q0 on and transform them.  maps_out: the maps of the planes (records null), or records: the
+// records of the planes against obs / obs_maps.  sizes: P * T words, zeroed here unless they are the caller's output
+static int rd_dm_pass(hipStream_t st, const rd_dm_geo& g, const float* x, long outer_stride, long per_outer, long q0, long P,
+                      const rd_thr& thr, int T, unsigned long long* masks, unsigned long long* sizes, bool zero_sizes,
+                      unsigned short* maps_out, const float* obs, const unsigned short* obs_maps, int cutoff, unsigned long long* records) {
+  if (zero_sizes) {
+    hipError_t e = hipMemsetAsync(sizes, 0, (size_t)P * T * sizeof(unsigned long long), st);
+    if (e != hipSuccess) return (int)e;
+  }
+  const long items = (long)g.ny * g.W, chunk = 4 * RD_DM_PACK_ITEMS;
+  hipLaunchKernelGGL(k_dm_pack, dim3((unsigned)P, (unsigned)((items + chunk - 1) / chunk)), dim3(RD_DM_THREADS), 0, st, x, outer_stride,
+                     per_outer, q0, g.ny, g.nx, g.W, thr, T, masks, sizes);
+  const dim3 grid((unsigned)((P + g.G - 1) / g.G * g.nstrips), (unsigned)T);
+  if (records)
+    hipLaunchKernelGGL(k_dm_transform<true>, grid, dim3(RD_DM_THREADS), rd_dm_lds_bytes(g), st, g, q0, (int)P, T,
+                       (const unsigned long long*)masks, (const unsigned long long*)sizes, (unsigned short*)nullptr, obs, obs_maps,
+                       per_outer, thr, cutoff, records);
+  else
+    hipLaunchKernelGGL(k_dm_transform<false>, grid, dim3(RD_DM_THREADS), rd_dm_lds_bytes(g), st, g, q0, (int)P, T,
+                       (const unsigned long long*)masks, (const unsigned long long*)sizes, maps_out, (const float*)nullptr,
+                       (const unsigned short*)nullptr, per_outer, thr, 0, (unsigned long long*)nullptr);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_dm_maps(const float* x, long n, long day_stride, long ny, long nx, const double* thresholds, int n_thresholds,
+                             unsigned short* maps_out, long long* set_sizes_out, void* workspace, long workspace_bytes, void* stream) {
+  rd_thr thr;
+  if (!x || !maps_out || !set_sizes_out || !workspace) return -2;
+  if (!rd_aligned(1, maps_out) || !rd_aligned(7, set_sizes_out, workspace) || !rd_dm_shape_ok(ny, nx)) return -2;
+  const long plane = ny * nx;
+  if (!rd_hourly_layout_ok((const void*)x, n, day_stride, RD_HOURS * plane)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  const long n_planes = n * RD_HOURS;
+  const long per_pass = rd_pass_units(workspace_bytes, rd_dm_plane_bytes(ny, nx), n_planes, RD_DM_MAXPASS);
+  if (per_pass < 1) return -2;
+  const rd_dm_geo g = rd_dm_geometry(ny, nx);
+  const int T = n_thresholds;
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ensure_lds(nullptr, (const void*)k_dm_transform<false>, rd_dm_lds_bytes(g)));
+  hipError_t e = hipMemsetAsync(set_sizes_out, 0, (size_t)n_planes * T * sizeof(long long), st);       // the set sizes are added
+  if (e != hipSuccess) return (int)e;
+  for (long q0 = 0; q0 < n_planes; q0 += per_pass) {
+    const long P = std::min<long>(per_pass, n_planes - q0);
+    RD_TRY(rd_dm_pass(st, g, x, day_stride, RD_HOURS, q0, P, thr, T, (unsigned long long*)workspace,
+                      (unsigned long long*)set_sizes_out + q0 * T, false, maps_out, nullptr, nullptr, 0, nullptr));
+  }
+  return 0;
+}
+
+extern "C" int rdgan_dm_records(const float* members, int s, long member_stride, const float* obs, const unsigned short* obs_maps,
+                                long n_days, long ny, long nx, const double* thresholds, int n_thresholds, int cutoff16,
+                                long long* records_out, void* workspace, long workspace_bytes, void* stream) {
+  rd_thr thr;
+  if (!members || !obs || !obs_maps || !records_out || !workspace) return -2;
+  if (!rd_aligned(3, members, obs) || !rd_aligned(1, obs_maps) || !rd_aligned(7, records_out, workspace)) return -2;
+  if (s < 1 || s > RD_DM_MAXS || n_days < 1 || !rd_dm_shape_ok(ny, nx) || cutoff16 < RD_DM_CMIN || cutoff16 > RD_DM_CMAX) return -2;
+  const long plane = ny * nx;
+  if (n_days > RD_HOURLY_MAXELEMS / (RD_HOURS * plane)) return -2;
+  const long per_member = n_days * RD_HOURS;
+  if (!rd_hourly_layout_ok((const void*)members, (long)s, member_stride, per_member * plane)) return -2;
+  if (!rd_thresholds(thresholds, n_thresholds, &thr)) return -2;
+  const long n_planes = (long)s * per_member;
+  const long per_pass = rd_pass_units(workspace_bytes, rd_dm_plane_bytes(ny, nx), n_planes, RD_DM_MAXPASS);
+  if (per_pass < 1) return -2;
+  const rd_dm_geo g = rd_dm_geometry(ny, nx);
+  const int T = n_thresholds;
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY(ensure_lds(nullptr, (const void*)k_dm_transform<true>, rd_dm_lds_bytes(g)));
+  hipError_t e = hipMemsetAsync(records_out, 0, (size_t)n_planes * T * RD_DM_NREC * sizeof(long long), st);
+  if (e != hipSuccess) return (int)e;
+  unsigned long long* masks = (unsigned long long*)workspace;
+  unsigned long long* sizes = masks + per_pass * (1 + RD_THR_MAX) * ny * g.W;
+  for (long q0 = 0; q0 < n_planes; q0 += per_pass) {
+    const long P = std::min<long>(per_pass, n_planes - q0);
+    RD_TRY(rd_dm_pass(st, g, members, member_stride, per_member, q0, P, thr, T, masks, sizes, true, nullptr, obs, obs_maps, cutoff16,
+                      (unsigned long long*)records_out));
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
 // storms of hourly fields (rdgan_storms.hip.h): wet volumes connected through the day's hours, labelled and counted
 // ------------------------------------------------------------------------------------
 static bool rd_sm_shape_ok(long ny, long nx) { return rd_cl_shape_ok(ny, nx) && RD_HOURS * ny * nx <= RD_SM_MAXDAY; }

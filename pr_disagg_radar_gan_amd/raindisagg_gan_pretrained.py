@@ -136,6 +136,20 @@ def intensity_scale_scenarios_field(observed, n_scenarios, thresholds, levels=No
                                                  norm_scale=norm_scale)
 
 
+def distance_scenarios_field(observed, n_scenarios, thresholds, cutoff_px=None, zhu_lambda=0.5, overlap=4, latent_mode="shared",
+                             scenario_chunk=16):
+    """The distance measures of n_scenarios scenarios of a whole observed day against its hours (distmap.distmap_field on the
+    module's ``gen`` and ``norm_scale``): per scenario, hour and threshold how far the scenario's rain is from the observed rain, in
+    pixels -- Hausdorff distance, mean error distances, Baddeley's Delta, Zhu's measure and the critical success index.  observed:
+    ndarray ([n_days,] 24, ny, nx) in mm/h, ny, nx <= 2048; its daily sums are the condition.  thresholds: the events in mm/h;
+    cutoff_px: Baddeley's cutoff in pixels, by default the plane's diagonal.  Returns a distmap.DistanceMeasures (numpy) with
+    summary().  The latent noise comes from the global numpy RNG as in generate_scenarios_field; the hourly scenarios are produced
+    scenario_chunk at a time and never held together."""
+    from . import distmap
+    return distmap.distmap_field(gen, np.asarray(observed), n_scenarios, thresholds, cutoff_px=cutoff_px, zhu_lambda=zhu_lambda,
+                                 scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
+
+
 def temporal_structure_field(daily, n_scenarios, thresholds, max_lag=6, overlap=4, latent_mode="shared", scenario_chunk=16):
     """The temporal structure of n_scenarios scenarios of a whole daily map (temporal.temporal_structure_field on the module's
     ``gen`` and ``norm_scale``): wet-spell and dry-spell lengths, wet hours per day, wet/dry transitions by hour, lag correlations.

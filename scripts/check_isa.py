@@ -51,6 +51,7 @@ NO_SPILL = re.compile(r"k_conv_gemm_f16|k_upconv_slab16|k_upconv2_slab16|k_d2_dg
                       r"k_cells_label_tile|k_cells_merge|k_cells_resolve|k_cells_reduce|k_cells_planes|"
                       r"k_sal_clear|k_sal_moments|k_sal_plane|k_sal_final|"
                       r"k_iss_tiles|k_iss_upper|"
+                      r"k_dm_pack|k_dm_transform|"
                       r"k_st_pack|k_st_correlate|"
                       r"k_storm_lift|k_storm_link|k_storm_resolve|k_storm_reduce|k_storm_days|"
                       r"k_areal_prefix|k_areal_boxes|k_areal_days|"
