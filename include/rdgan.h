@@ -935,6 +935,44 @@ int rdgan_seq_minplus(const long long* costs, long n_boundaries, long n_members,
 int rdgan_seq_match(const long long* costs, long n_boundaries, long n_members, int init, int rounds, int* perm_inout,
                     int* free_rows_inout, void* workspace, long workspace_bytes, void* stream);
 
+/* Scenario reduction: k representative members of an ensemble of hourly days and the weight of each, by fast
+ * forward selection (Heitsch & Roemisch 2003, Algorithm 2.4) under the L1 distance of integer features.
+ * Everything is an integer.  A member is [n_days][24][ny][nx] fp32.  A value x is GOOD when it is finite and 0 <= x < 2048; a good
+ * value has e = min((int) rintf(x * 32), 65535), in units of 1/32 mm (rint to even).  With pool = p in {1, 2, 4, 8} a feature position is
+ * a p x p block of one plane, ceil(ny / p) rows of ceil(nx / p) blocks, a rim block smaller and with its own pixel count n; its feature
+ * is (sum of e + n / 2) / n in integer division, a uint16, and it is BAD (feature 0) when any of its pixels is.  A member has
+ * Pf = n_days 24 ceil(ny / p) ceil(nx / p) positions, padded to Ppad = 8 ceil(Pf / 8) with zeros that are never bad; W = ceil(Ppad / 32).
+ * A position is MASKED when it is bad in any member; the mask is applied when distances are formed, so it does not matter in which
+ * order members and bad values arrive.  Dist[i][j] = sum over the unmasked positions of |e_i - e_j|: symmetric, zero diagonal.
+ * Limits: 1 <= members <= 4096, 1 <= ny nx <= 2^24, a member of at most 2^40 values, Pf 65535 members < 2^52 (so that
+ * key = z << 12 | u of the selection stays inside 64 bits).  All buffers lie on the device.
+ * rdgan_red_features: member m at hourly + m * member_stride, member_stride >= n_days 24 ny nx (4-byte aligned; 16-byte loads at pool 1
+ * when it is 16-byte aligned and member_stride a multiple of 4).  feat_out: member m's Ppad uint16 at feat_out + m * feat_stride,
+ * 16-byte aligned, feat_stride >= Ppad and a multiple of 8, padding 0.  bad_inout [W] 32-bit words, bit f % 32 of word f / 32, ORed
+ * into: the caller zeroes it before the first call and passes it to every call of one ensemble.
+ * rdgan_red_distances: feat as written above for all n_members, bad [W]; dist_out [n_members][n_members] and n_valid_out [1], 64-bit
+ * (written, not added to): n_valid = Pf - the masked positions.  position_splits: into how many ranges the positions of a tile of
+ * pairs are cut, one workgroup each (at most one per 128 positions); 0 leaves the choice to the entry (about 2048 workgroups a
+ * launch).  The result does not depend on it: integer sums, 32-bit partial sums added to 64-bit ones every 32768 positions of a
+ * range.  Only the tiles on and above the diagonal are computed; each sum is written to [i][j] and [j][i].
+ * rdgan_red_select: dist [S][S], symmetric, 0 <= Dist < 2^52 / S (what rdgan_red_distances writes, or a distance of the caller's).
+ * m[j] = +inf; step t = 0 .. k - 1, 1 <= k <= S: z[u] = sum over j of min(m[j], Dist[u][j]) for every u not yet selected, the pick is
+ * the u of the smallest key = z[u] << 12 | u (ties to the smaller index), chosen_out [k] int32 = u, cost_out [k] 64-bit = z[u], then
+ * m[j] = min(m[j], Dist[u][j]).  cost[t] is S times the Kantorovich distance between the ensemble and its reduction to the first
+ * t + 1 picks.  assign_out [S] int32: the chosen u of the smallest Dist[u][j] << 12 | u; counts_out [k] int32: counts[t] members are
+ * assigned to chosen[t], their sum is S; a pick that duplicates a smaller-indexed pick exactly gets 0.  All k steps are enqueued at
+ * once.  workspace: 8-byte aligned, rdgan_red_workspace_bytes(S, k) bytes (-2 for an argument out of range).
+ * Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, a size, pool or k outside the limits
+ * above, a stride too small or no multiple of 8, position_splits < 0, a workspace too small) with nothing launched and no output
+ * touched.  All offsets are 64-bit. */
+long rdgan_red_workspace_bytes(long n_members, long k);
+int rdgan_red_features(const float* hourly, long n_members, long member_stride, long n_days, long ny, long nx, int pool,
+                       unsigned short* feat_out, long feat_stride, unsigned int* bad_inout, void* stream);
+int rdgan_red_distances(const unsigned short* feat, const unsigned int* bad, long n_members, long feat_stride, long n_positions,
+                        int position_splits, long long* dist_out, long long* n_valid_out, void* stream);
+int rdgan_red_select(const long long* dist, long n_members, long k, int* chosen_out, long long* cost_out, int* assign_out,
+                     int* counts_out, void* workspace, long workspace_bytes, void* stream);
+
 /* Joint-field scores of ensembles of hourly days: the energy score (Gneiting et al. 2008) and the variogram
  * score of order p (Scheuerer & Hamill 2015) of an ensemble of whole days against the observed day, taken as one vector.
  * An ensemble is x [m][24][ny][nx] fp32, every value finite, 1 <= m <= 8192; the observation y [24][ny][nx] fp32.  A position where y

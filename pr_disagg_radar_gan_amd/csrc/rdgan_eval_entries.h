@@ -1,6 +1,6 @@
 // The handle-free entry points of include/rdgan.h: input pipeline, CRPS experiment, distribution checks, whole fields, ensemble
 // products, verification, the evaluations of hourly arrays (temporal structure, rain cells, storms, areal extremes, catchment
-// rainfall, space-time structure), analogs, seams between days, spectra and RainFARM.  They take no rdgan_handle and use nothing of the step engine but RD_TRY,
+// rainfall, space-time structure), analogs, seams between days, scenario reduction, spectra and RainFARM.  They take no rdgan_handle and use nothing of the step engine but RD_TRY,
 // ensure_lds(nullptr, ...) and ew_blocks.  Host code, included by rdgan_api.hip at one point, behind the op-level test entries (the
 // library stays one translation unit: one code object for the ISA lint).
 //
@@ -1675,5 +1675,94 @@ extern "C" int rdgan_seq_match(const long long* costs, long n_boundaries, long n
     hipLaunchKernelGGL(k_seq_match_minima, per_rows, dim3(RD_SEQ_THREADS), 0, st, costs, S, r & 1, (const int*)free_rows_inout, workspace);
     hipLaunchKernelGGL(k_seq_match_take, per_member, dim3(256), 0, st, S, r & 1, perm_inout, free_rows_inout, workspace);
   }
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// scenario reduction (rdgan_reduce.hip.h): pooled features, all-pairs distances, forward selection and assignment
+// ------------------------------------------------------------------------------------
+// Pf of a member, or 0 for a shape outside the limits
+static long rd_red_positions(long n_days, long ny, long nx, long pool) {
+  if (pool != 1 && pool != 2 && pool != 4 && pool != RD_RED_MAXPOOL) return 0;
+  if (n_days < 1 || ny < 1 || nx < 1 || ny > RD_HOURLY_MAXPLANE || nx > RD_HOURLY_MAXPLANE || ny * nx > RD_HOURLY_MAXPLANE) return 0;
+  if (n_days > RD_HOURLY_MAXELEMS / (RD_HOURS * ny * nx)) return 0;
+  return n_days * RD_HOURS * rd_red_blocks(ny, pool) * rd_red_blocks(nx, pool);
+}
+// Pf 65535 S < 2^52: a row sum of distances, shifted by 12, stays inside 64 bits
+static bool rd_red_admit(long s, long n_positions) {
+  return s >= 1 && s <= RD_RED_MAXS && n_positions >= 1 && n_positions <= ((1L << RD_RED_KEYBITS) - 1) / ((long)RD_SEQ_FEATMAX * s);
+}
+
+extern "C" long rdgan_red_workspace_bytes(long n_members, long k) {
+  if (n_members < 1 || n_members > RD_RED_MAXS || k < 1 || k > n_members) return -2;
+  return rd_red_select_bytes(n_members, k);
+}
+
+extern "C" int rdgan_red_features(const float* hourly, long n_members, long member_stride, long n_days, long ny, long nx, int pool,
+                                  unsigned short* feat_out, long feat_stride, unsigned int* bad_inout, void* stream) {
+  if (!hourly || !feat_out || !bad_inout || !rd_aligned(15, feat_out) || !rd_aligned(3, bad_inout)) return -2;
+  const long Pf = rd_red_positions(n_days, ny, nx, pool);
+  if (Pf < 1 || !rd_red_admit(n_members, Pf)) return -2;
+  if (!rd_hourly_layout_ok(hourly, n_members, member_stride, n_days * RD_HOURS * ny * nx)) return -2;
+  const long Ppad = rd_seq_ppad(Pf), U = Ppad / 8;
+  if (feat_stride % 8 != 0 || !rd_day_stride_ok(n_members, feat_stride, Ppad)) return -2;
+  const long blocks = (n_members * U + 255) / 256;
+  if (blocks > 0x7FFFFFFFL) return -2;
+  const int by = (int)rd_red_blocks(ny, pool), bx = (int)rd_red_blocks(nx, pool);
+  hipStream_t st = (hipStream_t)stream;
+  if (pool == 1 && rd_aligned(15, hourly) && member_stride % 4 == 0)
+    hipLaunchKernelGGL(k_red_features<true>, dim3((unsigned)blocks), dim3(256), 0, st, hourly, n_members, member_stride, Pf, (int)ny, (int)nx, pool,
+                       by, bx, U, (uint4*)feat_out, feat_stride / 8, bad_inout);
+  else
+    hipLaunchKernelGGL(k_red_features<false>, dim3((unsigned)blocks), dim3(256), 0, st, hourly, n_members, member_stride, Pf, (int)ny, (int)nx, pool,
+                       by, bx, U, (uint4*)feat_out, feat_stride / 8, bad_inout);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_red_distances(const unsigned short* feat, const unsigned int* bad, long n_members, long feat_stride, long n_positions,
+                                   int position_splits, long long* dist_out, long long* n_valid_out, void* stream) {
+  if (!feat || !bad || !dist_out || !n_valid_out) return -2;
+  if (!rd_aligned(15, feat) || !rd_aligned(3, bad) || !rd_aligned(7, dist_out, n_valid_out)) return -2;
+  if (!rd_red_admit(n_members, n_positions) || position_splits < 0) return -2;
+  const long Ppad = rd_seq_ppad(n_positions), U = Ppad / 8, W = rd_seq_words(n_positions), S = n_members;
+  if (feat_stride % 8 != 0 || !rd_day_stride_ok(S, feat_stride, Ppad)) return -2;
+  const long T = rd_seq_tiles(S), tiles = rd_red_tri(T), nchunks = (U + RD_SEQ_CHUNK - 1) / RD_SEQ_CHUNK;
+  // the chunks of positions are cut into position_splits ranges, or, left to the entry (0), into as many as bring the launch to about
+  // RD_RED_TARGET_BLOCKS workgroups; never more than there are chunks
+  long nsplit = std::min<long>(nchunks, position_splits ? position_splits : std::max<long>(1, (RD_RED_TARGET_BLOCKS + tiles - 1) / tiles));
+  const long per_split = (nchunks + nsplit - 1) / nsplit;
+  nsplit = (nchunks + per_split - 1) / per_split;
+  if (tiles * nsplit > 0x7FFFFFFFL) return -2;
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY((int)hipMemsetAsync(dist_out, 0, (size_t)(S * S) * 8, st));
+  RD_TRY((int)hipMemsetAsync(n_valid_out, 0, 8, st));
+  hipLaunchKernelGGL(k_red_valid, dim3((unsigned)std::min<long>((W + 255) / 256, 1024)), dim3(256), 0, st, bad, W, n_positions,
+                     (unsigned long long*)n_valid_out);
+  hipLaunchKernelGGL(k_red_distances, dim3((unsigned)(tiles * nsplit)), dim3(RD_SEQ_THREADS), 0, st, (const uint4*)feat, bad, (int)S, feat_stride / 8,
+                     U, (int)T, (int)nsplit, per_split, (unsigned long long*)dist_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_red_select(const long long* dist, long n_members, long k, int* chosen_out, long long* cost_out, int* assign_out,
+                                int* counts_out, void* workspace, long workspace_bytes, void* stream) {
+  if (!dist || !chosen_out || !cost_out || !assign_out || !counts_out || !workspace) return -2;
+  if (!rd_aligned(7, dist, cost_out, workspace) || !rd_aligned(3, chosen_out, assign_out, counts_out)) return -2;
+  if (n_members < 1 || n_members > RD_RED_MAXS || k < 1 || k > n_members || workspace_bytes < rd_red_select_bytes(n_members, k)) return -2;
+  const int S = (int)n_members;
+  unsigned long long* m = (unsigned long long*)workspace;
+  unsigned long long* slot = m + S;
+  unsigned char* selected = (unsigned char*)(slot + k);
+  hipStream_t st = (hipStream_t)stream;
+  RD_TRY((int)hipMemsetAsync(m, 0xFF, (size_t)(S + k) * 8, st));           // m = +inf, every slot empty
+  RD_TRY((int)hipMemsetAsync(selected, 0, (size_t)S, st));
+  RD_TRY((int)hipMemsetAsync(counts_out, 0, (size_t)k * 4, st));
+  RD_TRY((int)hipMemsetAsync(chosen_out, 0xFF, (size_t)k * 4, st));
+  const dim3 per_rows((unsigned)((S + RD_RED_ROWS - 1) / RD_RED_ROWS)), per_member((unsigned)((S + 255) / 256));
+  for (long t = 0; t < k; ++t) {
+    hipLaunchKernelGGL(k_red_select, per_rows, dim3(256), 0, st, dist, S, (const unsigned long long*)m, (const unsigned char*)selected, slot + t);
+    hipLaunchKernelGGL(k_red_update, per_member, dim3(256), 0, st, dist, S, (const unsigned long long*)(slot + t), m, selected,
+                       chosen_out + t, cost_out + t);
+  }
+  hipLaunchKernelGGL(k_red_assign, per_member, dim3(256), 0, st, dist, S, (int)k, (const int*)chosen_out, assign_out, counts_out);
   return (int)hipGetLastError();
 }

@@ -265,6 +265,21 @@ def chain_scenarios_field(daily, n_scenarios, first_hour=0, last_hour=23, overla
                                 overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
 
+def reduce_scenarios_field(daily, n_scenarios, k, pool=1, return_hourly=False, overlap=4, latent_mode="shared", scenario_chunk=16):
+    """Reduce n_scenarios scenarios of a whole daily map to k representative ones (reduction.reduce_field on the module's ``gen``
+    and ``norm_scale``): fast forward selection under the L1 distance of the hourly fields, pooled over pool x pool pixels, so that
+    the weighted picks stay as close to the whole ensemble as k members can.  daily as generate_scenarios_field takes it.  Returns
+    a reduction.Reduction (numpy): ``chosen`` (k,) the picked scenarios in order, ``weights`` their probabilities, ``assign`` the
+    pick every scenario goes to, ``mean_distance_mm`` the curve on which k is chosen, ``latent`` the latent vectors that make the
+    picks again, and with return_hourly ``hourly`` (k, [D,] 24, ny, nx), the picks themselves on the device.  The latent noise comes
+    from the global numpy RNG as in generate_scenarios_field; the hourly scenarios are produced scenario_chunk at a time and never
+    held together."""
+    from . import reduction
+    daily = _daily_map(daily)
+    return reduction.reduce_field(gen, daily, n_scenarios, k, pool=pool, return_hourly=return_hourly, scenario_chunk=scenario_chunk,
+                                  overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
+
+
 def plot_scenarios(scenarios):
     """reference :68-90: one row per scenario, 24 hourly panels, LogNorm(0.01, 50), gist_earth_r.
     Keeps the reference's indexing ``scenarios[iplot, jplot - 1]`` (the column labelled 00:00 shows

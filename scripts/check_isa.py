@@ -59,7 +59,8 @@ NO_SPILL = re.compile(r"k_conv_gemm_f16|k_upconv_slab16|k_upconv2_slab16|k_d2_dg
                       r"k_analog_features|k_analog_days|k_analog_query|k_analog_search|k_analog_merge|k_analog_apply|"
                       r"k_mv_valid|k_mv_energy|k_mv_energy_reduce|k_mv_variogram|k_mv_variogram_reduce|"
                       r"k_cascade_accumulate|k_cascade_generate|"
-                      r"k_seq_edges|k_seq_valid|k_seq_costs|k_seq_minplus|k_seq_match_init|k_seq_match_minima|k_seq_match_take")
+                      r"k_seq_edges|k_seq_valid|k_seq_costs|k_seq_minplus|k_seq_match_init|k_seq_match_minima|k_seq_match_take|"
+                      r"k_red_features|k_red_valid|k_red_distances|k_red_select|k_red_update|k_red_assign")
 # scratch a NO_SPILL kernel may still use, with the reason (bytes)
 SCRATCH_ALLOWED = {
     r"^k_upconv2_slab16$": 16,     # three per-sample addresses stored in the prologue and reloaded once per sample, outside the K loop
