@@ -935,6 +935,22 @@ int rdgan_seq_minplus(const long long* costs, long n_boundaries, long n_members,
 int rdgan_seq_match(const long long* costs, long n_boundaries, long n_members, int init, int rounds, int* perm_inout,
                     int* free_rows_inout, void* workspace, long workspace_bytes, void* stream);
 
+/* Least-cost assignment of the members of neighbouring days: what the greedy matching above is not.
+ * costs [n_boundaries][S][S] 64-bit with 0 <= C < 2^40 (not checked), the limits of the matching above: 1 <= S <= 4096,
+ * 1 <= n_boundaries <= 65535, at most 2^31 costs per call.  For every boundary b: perm_out [n_boundaries][S] int32, a permutation
+ * that minimises total = sum over i of C[b][i][perm[b][i]]; u_out and v_out [n_boundaries][S] 64-bit, duals with
+ * u[i] + v[j] <= C[b][i][j] for all pairs and equality on the matched ones, so sum u + sum v = total proves the optimum;
+ * total_out [n_boundaries] 64-bit.  Optimal permutations are not unique; the algorithm is the definition: shortest augmenting paths
+ * with dual potentials (the Hungarian method in Jonker-Volgenant form), rows inserted in the order 0 .. S - 1 from u = v = 0, each by
+ * a Dijkstra search over the columns whose next column is the unused one of the smallest (minv[j], j), value first, then the
+ * smaller index.  |u|, |v| < S 2^40 <= 2^52: plain 64-bit integers.  One workgroup solves one boundary from the first row to the
+ * last; no workgroup waits for another, every loop is counted, and the result does not depend on the launch geometry.  Outside
+ * the precondition the result is not the defined one, but every access stays in range.  All buffers lie on the device.
+ * Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, a size outside the limits) with
+ * nothing launched and no output touched.  All offsets are 64-bit. */
+int rdgan_assign(const long long* costs, long n_boundaries, long n_members, int* perm_out, long long* u_out, long long* v_out,
+                 long long* total_out, void* stream);
+
 /* Scenario reduction: k representative members of an ensemble of hourly days and the weight of each, by fast
  * forward selection (Heitsch & Roemisch 2003, Algorithm 2.4) under the L1 distance of integer features.
  * Everything is an integer.  A member is [n_days][24][ny][nx] fp32.  A value x is GOOD when it is finite and 0 <= x < 2048; a good

@@ -158,6 +158,8 @@ SIGNATURES = {
     "rdgan_seq_minplus": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
     "rdgan_seq_match": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),
+    "rdgan_assign": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_void_p, c_stream]),
     "rdgan_red_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long]),
     "rdgan_red_features": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_stream]),

@@ -1679,6 +1679,20 @@ extern "C" int rdgan_seq_match(const long long* costs, long n_boundaries, long n
 }
 
 // ------------------------------------------------------------------------------------
+// least-cost assignment of the members of neighbouring days (rdgan_assign.hip.h): one workgroup solves one boundary
+// ------------------------------------------------------------------------------------
+extern "C" int rdgan_assign(const long long* costs, long n_boundaries, long n_members, int* perm_out, long long* u_out, long long* v_out,
+                            long long* total_out, void* stream) {
+  if (!costs || !perm_out || !u_out || !v_out || !total_out) return -2;
+  if (!rd_aligned(7, costs, u_out, v_out, total_out) || !rd_aligned(3, perm_out)) return -2;
+  if (n_members < 1 || n_members > RD_SEQ_MAXS || n_boundaries < 1 || n_boundaries > RD_SEQ_MAXDAYS) return -2;
+  if (n_boundaries * n_members * n_members > RD_SEQ_MAXCOSTS) return -2;
+  hipLaunchKernelGGL(k_seq_assign, dim3((unsigned)n_boundaries), dim3(RD_ASG_THREADS), 0, (hipStream_t)stream, costs, (int)n_members, perm_out,
+                     u_out, v_out, total_out);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
 // scenario reduction (rdgan_reduce.hip.h): pooled features, all-pairs distances, forward selection and assignment
 // ------------------------------------------------------------------------------------
 // Pf of a member, or 0 for a shape outside the limits

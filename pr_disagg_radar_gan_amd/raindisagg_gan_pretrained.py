@@ -251,18 +251,21 @@ def spacetime_structure_field(daily, n_scenarios, thresholds, radius=4, max_lag=
                                                norm_scale=norm_scale)
 
 
-def chain_scenarios_field(daily, n_scenarios, first_hour=0, last_hour=23, overlap=4, latent_mode="shared", scenario_chunk=16):
+def chain_scenarios_field(daily, n_scenarios, first_hour=0, last_hour=23, overlap=4, latent_mode="shared", scenario_chunk=16,
+                          matching="greedy"):
     """Chain n_scenarios scenarios of a series of daily maps (n_days, ny, nx) across midnight (sequence.chain_field on the module's
     ``gen`` and ``norm_scale``): how well every member of one day continues every member of the next, the cheapest single series,
-    and a greedy matching that orders the members of every day into n_scenarios continuous series.  Returns a sequence.ChainResult
+    and a matching that orders the members of every day into n_scenarios continuous series -- the greedy one, or with
+    matching="optimal" the one of least total seam cost per boundary (sequence.optimal_matching).  Returns a sequence.ChainResult
     (numpy): ``order[d][s]`` is the member of day d in series s, and sequence.reorder applies it to the hourly ensemble that
     generate_scenarios_field returns for the same numpy RNG state; sequence.compare sets the seams against observed ones.  The
     latent noise comes from the global numpy RNG as in generate_scenarios_field; the hourly scenarios are produced scenario_chunk
     at a time and never held together."""
     from . import sequence
+    sequence.check_matching(matching)
     daily = _daily_map(daily)
     return sequence.chain_field(gen, daily, n_scenarios, scenario_chunk=scenario_chunk, first_hour=first_hour, last_hour=last_hour,
-                                overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
+                                overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale, matching=matching)
 
 
 def reduce_scenarios_field(daily, n_scenarios, k, pool=1, return_hourly=False, overlap=4, latent_mode="shared", scenario_chunk=16):

@@ -11,7 +11,8 @@ A day has two edges, its first_hour (0) and its last_hour (23).  Boundary b join
 b + shift (1: a seam; 0: two hours of the same day, a yardstick).  A pixel is masked at b when the bad bit of either edge is set for
 any member; n_valid[b] counts the others.  C[b][i][j] is the sum over the unmasked pixels of |e_i - e_j|, an int64 below 2^40, and
 key = C << 24 | i << 12 | j orders the pairs strictly.  The greedy matching walks all pairs by ascending key and takes a pair when
-neither its row nor its column is taken; it is NOT the assignment of least total cost (Hungarian, auction): that is out of scope.
+neither its row nor its column is taken; it is NOT the assignment of least total cost: that is optimal_matching (DESIGN.md section
+32, csrc/rdgan_assign.hip.h), shortest augmenting paths with dual potentials, which chain* use with matching="optimal".
 
 No CPU fallback: without a visible MI355X the device functions raise RdganError; argument errors are ValueErrors raised before any
 device call."""
@@ -33,6 +34,7 @@ MAX_COSTS = 1 << 31                                                          # R
 MAX_COST = 1 << 40                                                           # a cost lies below it: RD_SEQ_FEATMAX + 1 times MAX_PLANE
 YARDSTICK_HOURS = (11, 12)                                                   # the within-day pair compare() sets beside the seams
 _FIRST_BATCH = 8                                                             # rounds of the first batch of a matching; then doubled
+MATCHINGS = ("greedy", "optimal")                                            # what chain* accept as `matching`
 
 
 def padded_plane(plane):
@@ -219,6 +221,32 @@ def greedy_matching(costs, return_rounds=False):
     return (perm, done) if return_rounds else perm
 
 
+def optimal_matching(costs, return_duals=False):
+    """costs (B, S, S) int64 -> perm (B, S) int32 CUDA, for every boundary a permutation of least total cost sum_i C[b][i][perm[b][i]];
+    with return_duals (perm, total (B,), u (B, S), v (B, S)), int64 CUDA: u[i] + v[j] <= C[i][j] for all pairs with equality on the
+    matched ones, so sum u + sum v == total proves the optimum.  The precondition of greedy_matching, 0 <= C < 2^40, again not
+    checked.  Optimal permutations are not unique; the algorithm (rows inserted in the order 0 .. S - 1 by
+    shortest augmenting paths, the next column the unused one of the smallest (minv[j], j)) is the definition.  One asynchronous
+    launch, one workgroup per boundary, no host wait."""
+    costs, B, S = _check_costs(costs)
+    require_gpu()
+    lib = _lib.load()
+    dev = costs.device
+    with torch.cuda.device(dev):
+        perm = torch.empty((B, S), dtype=torch.int32, device=dev)
+        duals = torch.empty((2, B, S), dtype=torch.int64, device=dev)
+        total = torch.empty(B, dtype=torch.int64, device=dev)
+        rc = lib.rdgan_assign(_p(costs), B, S, _p(perm), _p(duals[0]), _p(duals[1]), _p(total), _stream(costs))
+    _lib.check(rc, None, "rdgan_assign")
+    return (perm, total, duals[0], duals[1]) if return_duals else perm
+
+
+def check_matching(matching):
+    if matching not in MATCHINGS:
+        raise ValueError(f"matching: expected one of {MATCHINGS}, got {matching!r}")
+    return matching
+
+
 def series_order(perm):
     """perm (B, S) -> order (B + 1, S) int64, on perm's device (or numpy for an array): order[0][s] = s, order[d + 1][s] =
     perm[d][order[d][s]]; series s consists of member order[d][s] on day d, and every member of every day is used exactly once"""
@@ -254,7 +282,8 @@ def reorder(x, order):
 
 @dataclass
 class ChainResult:
-    """What chain() found.  order (D, S) int64 and perm (D - 1, S) int32: the matched series (series_order, greedy_matching); path
+    """What chain() found.  order (D, S) int64 and perm (D - 1, S) int32: the matched series (series_order; greedy_matching, or
+    optimal_matching when `matching` is "optimal", and then greedy_matched (D - 1,) is what the greedy matching would have given); path
     (D,) and path_total: the cheapest single series and its cost in 1/32 mm; n_valid (D - 1,); and per boundary, in mm/h per valid
     pixel (cost / (32 n_valid), NaN where n_valid is 0): random -- the mean over all pairs, what pairing at random expects;
     diagonal -- the mean over the pairs (s, s), the pairing by index of a plain concatenation; matched -- the mean over the matched
@@ -274,6 +303,8 @@ class ChainResult:
     plane_shape: tuple = ()
     observed: np.ndarray = None
     observed_within: np.ndarray = None
+    matching: str = "greedy"
+    greedy_matched: np.ndarray = None
 
 
 def _per_pixel(cost, n_valid):
@@ -281,13 +312,17 @@ def _per_pixel(cost, n_valid):
         return np.where(n_valid > 0, np.asarray(cost, dtype=np.float64) / (UNIT * n_valid.astype(np.float64)), np.nan)
 
 
-def chain_edges(edges):
-    """chain() for a SeamEdges that has its members: costs, matching, series order, path and the four seam statistics"""
+def chain_edges(edges, matching="greedy"):
+    """chain() for a SeamEdges that has its members: costs, matching, series order, path and the four seam statistics.  matching:
+    "greedy" (greedy_matching) or "optimal" (optimal_matching: least total seam cost per boundary; the result then also holds
+    greedy_matched, the matched mean of the greedy matching, so the gain is read off one result)"""
     _check_edges(edges, "edges")
+    check_matching(matching)
     if edges.n_days < 2:
         raise ValueError("chaining needs at least 2 days")
     costs, n_valid = seam_costs(edges)
-    perm = greedy_matching(costs)
+    greedy = greedy_matching(costs)
+    perm = optimal_matching(costs) if matching == "optimal" else greedy
     path, total = best_path(costs)
     order = series_order(perm)
     B, S = perm.shape
@@ -295,19 +330,24 @@ def chain_edges(edges):
         c = costs.double()
         matched = torch.gather(c, 2, perm.long()[..., None]).mean(dim=(1, 2))
         steps = torch.from_numpy(np.stack([np.arange(B), path[:-1], path[1:]])).to(costs.device)
-        host = torch.stack([c.mean(dim=(1, 2)), c.diagonal(dim1=1, dim2=2).mean(dim=1), matched,
-                            costs[steps[0], steps[1], steps[2]].double(), n_valid.double()]).cpu().numpy()
+        rows = [c.mean(dim=(1, 2)), c.diagonal(dim1=1, dim2=2).mean(dim=1), matched,
+                costs[steps[0], steps[1], steps[2]].double(), n_valid.double()]
+        if matching == "optimal":
+            rows.append(torch.gather(c, 2, greedy.long()[..., None]).mean(dim=(1, 2)))
+        host = torch.stack(rows).cpu().numpy()
     nv = host[4].astype(np.int64)
     return ChainResult(order=order.cpu().numpy(), perm=perm.cpu().numpy(), path=path, path_total=total, n_valid=nv,
                        random=_per_pixel(host[0], nv), diagonal=_per_pixel(host[1], nv), matched=_per_pixel(host[2], nv),
                        path_cost=_per_pixel(host[3], nv), first_hour=edges.first_hour, last_hour=edges.last_hour,
-                       plane_shape=edges.plane_shape)
+                       plane_shape=edges.plane_shape, matching=matching,
+                       greedy_matched=_per_pixel(host[5], nv) if matching == "optimal" else None)
 
 
-def chain(hourly, first_hour=0, last_hour=23):
+def chain(hourly, first_hour=0, last_hour=23, matching="greedy"):
     """One call for an ensemble that is held: hourly (S, D, 24, ny, nx), D >= 2 -> ChainResult.  reorder(hourly, result.order) is
-    the ensemble as S continuous series."""
-    return chain_edges(SeamEdges(first_hour, last_hour).add(hourly))
+    the ensemble as S continuous series.  matching: as for chain_edges."""
+    check_matching(matching)
+    return chain_edges(SeamEdges(first_hour, last_hour).add(hourly), matching)
 
 
 def compare(result, observed_hourly, consecutive=None):
@@ -337,16 +377,18 @@ def compare(result, observed_hourly, consecutive=None):
 
 
 def chain_field(gen, daily, n_scenarios, scenario_chunk=16, first_hour=0, last_hour=23, overlap=4, latent_mode="shared", seed=None,
-                latent=None, chunk=1024, norm_scale=W.NORM_SCALE):
+                latent=None, chunk=1024, norm_scale=W.NORM_SCALE, matching="greedy"):
     """Disaggregate the daily maps (D, ny, nx), D >= 2, into n_scenarios scenarios and chain them without holding the hourly
     ensemble: the scenario stream of field._stream_scenarios with SeamEdges.add as the sink, which keeps two hours of every day.
     -> ChainResult.  The latent array is drawn once for all scenarios, exactly as field.disaggregate draws it for the same seed,
     latent and numpy RNG state, so member s of day d -- order[d][s'] names it -- is reproduced by disaggregate with the same seed or
     latent (row s of it), and the series themselves by reorder() on that output.  The generator's fp32 output depends in its last
     bits on the batch of tiles it runs in, so against chain(disaggregate(...all scenarios...)[0]) the integers are equal when the
-    batches are the same (`chunk` at most one unit's wet tiles, or one scenario chunk), as _hourly.evaluate_field says."""
+    batches are the same (`chunk` at most one unit's wet tiles, or one scenario chunk), as _hourly.evaluate_field says.  matching: as
+    for chain_edges."""
     S, step = F._check_scenarios(n_scenarios, scenario_chunk, MAX_MEMBERS)
     first_hour, last_hour = check_hour(first_hour, "first_hour"), check_hour(last_hour, "last_hour")
+    check_matching(matching)
     req = F._check_request(gen, daily, S, overlap, latent_mode, latent, chunk, norm_scale)
     if req[1] or req[2] < 2:
         raise ValueError("daily: chaining needs daily maps (D, ny, nx) of at least 2 days")
@@ -354,4 +396,4 @@ def chain_field(gen, daily, n_scenarios, scenario_chunk=16, first_hour=0, last_h
         raise ValueError(f"daily: at most {MAX_DAYS} days of {MAX_PLANE} pixels")
     edges = SeamEdges(first_hour, last_hour)
     F._stream_scenarios(gen, req, req[0], S, step, edges.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
-    return chain_edges(edges)
+    return chain_edges(edges, matching)
