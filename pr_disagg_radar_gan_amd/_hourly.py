@@ -1,6 +1,9 @@
 """What the evaluations of hourly arrays share on the host: how an array (..., 24, ny, nx) is admitted -- kind, shape, layout --
-before any device call, the accumulator they all are (HourlyAccumulator) with its driver for whole daily fields
-(evaluate_field), and the two small quotients their statistics use."""
+before any device call, the accumulator the single-array ones are (HourlyAccumulator) with its driver for whole daily fields
+(evaluate_field), the base of those that hold members against an observation (ObservedVerifier) with theirs (ObservedRequest), and
+the small quotients and summaries their statistics use."""
+import warnings
+
 import numpy as np
 import torch
 
@@ -73,6 +76,24 @@ def member_layout(x):
     return S, P, stride, shape
 
 
+def dense_member_layout(members, from_host):
+    """members (S, *shape) behind admit_array: a host array becomes dense float32 (member stride P), a tensor stays as it is
+    -> (members, S, P, member_stride, shape)"""
+    if from_host:
+        members = np.ascontiguousarray(members, dtype=np.float32)
+    return (members,) + member_layout(torch.from_numpy(members) if from_host else members)
+
+
+def check_pair(ens_shape, obs_shape, what="ens"):
+    """ValueError unless ens_shape is (S,) + obs_shape with 1 .. MAX_MEMBERS members"""
+    if len(ens_shape) < 4:
+        raise ValueError(f"{what}: expected an array or tensor of shape (S, ..., 24, ny, nx)")
+    if not 1 <= int(ens_shape[0]) <= MAX_MEMBERS:
+        raise ValueError(f"the number of members must lie in 1 .. {MAX_MEMBERS}, got {int(ens_shape[0])}")
+    if tuple(ens_shape[1:]) != tuple(obs_shape):
+        raise ValueError(f"{what}: expected shape (S,) + {tuple(obs_shape)}, got {tuple(ens_shape)}")
+
+
 def admit_array(a, what="hourly"):
     """Kind and shape of an hourly input, host code: a float32 CUDA tensor is taken as it is, anything else as a numpy array of
     numbers; a torch tensor on the host is refused.  -> (the tensor or array, from_host, shape)"""
@@ -109,6 +130,21 @@ def to_state_device(a, from_host, device, what="hourly"):
     if a.device != device:
         raise ValueError(f"{what} lies on {a.device}, the state on {device}")
     return a
+
+
+def observation_on_device(obs, from_host):
+    """the first device step of a verification: a host array goes to "cuda" as dense float32, a tensor is used where it lies"""
+    require_gpu()
+    return to_state_device(obs, True, "cuda") if from_host else obs.detach().contiguous()
+
+
+def grow_workspace(owner, nbytes, device):
+    """-> owner._ws if it holds nbytes, else a new int64 buffer of that size in its place.  It takes the owner, not the buffer: only
+    the owner can drop the old buffer before the new one is allocated, so that the two never coexist."""
+    if owner._ws is None or owner._ws.numel() * 8 < nbytes:
+        owner._ws = None
+        owner._ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    return owner._ws
 
 
 def check_out_tensor(t, name, dtype, shape):
@@ -178,10 +214,8 @@ class HourlyAccumulator:
         self.plane_shape = shape[-2:]
         with torch.cuda.device(device):
             nbytes = workspace_bytes(self.lib, self.workspace_entry, *self._workspace_args(n, ny, nx))
-            if self._ws is None or self._ws.numel() * 8 < nbytes:
-                self._ws = None
-                self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
-            rc = getattr(self.lib, self.entry)(_p(hourly), n, stride, *self._entry_args(ny, nx, out, *extra), _p(self._ws), nbytes,
+            ws = grow_workspace(self, nbytes, device)
+            rc = getattr(self.lib, self.entry)(_p(hourly), n, stride, *self._entry_args(ny, nx, out, *extra), _p(ws), nbytes,
                                                _stream(self.counts))
         _lib.check(rc, None, self.entry)
         return self
@@ -209,9 +243,89 @@ def evaluate_field(acc, gen, daily, n_scenarios, scenario_chunk, overlap, latent
     return acc.result()
 
 
+class ObservedVerifier:
+    """What the verifiers of members against an observation share: the observation (..., 24, ny, nx) on the device, and the head of
+    add(members).  A subclass calls _admit_obs in its __init__, _admit_members first in its add, and overrides _check_members."""
+    _ws = None                                   # the workspace of a subclass that has one (grow_workspace)
+
+    def _admit_obs(self, obs, check_obs=lambda shape: None):
+        """sets shape, ny, nx, P, n_days, then runs the subclass's host checks check_obs(shape), and only then the device: obs, lib"""
+        obs, from_host, self.shape = admit_array(obs, "obs")
+        self.ny, self.nx = self.shape[-2:]
+        self.P = int(np.prod(self.shape, dtype=np.int64))
+        self.n_days = self.P // (NHOURS * self.ny * self.nx)
+        check_obs(self.shape)
+        self.obs = observation_on_device(obs, from_host)
+        self.lib = _lib.load()
+
+    def _check_members(self, s):
+        """ValueError if s more members cannot be taken; host code that must not need the device state"""
+
+    def _admit_members(self, members):
+        """the head of add(members): every step before the last, the move to the observation's device, reads self.shape alone (and
+        what _check_members reads).  -> (members on the device, s, member_stride)"""
+        members, from_host, _ = admit_array(members, "members")
+        members, s, P, stride, shape = dense_member_layout(members, from_host)
+        if shape != self.shape:
+            raise ValueError(f"members: expected shape (s,) + {self.shape}, got {tuple(members.shape)}")
+        if s * P > MAX_ELEMS:
+            raise ValueError(f"members: more than {MAX_ELEMS} values in one call")
+        self._check_members(s)
+        return to_state_device(members, from_host, self.obs.device, "members"), s, stride
+
+
+class ObservedRequest:
+    """The host half of a `*_field` verification against the observed hours: every check of `observed`, `daily` and the scenario
+    arguments, before any device call.  observed ([D,] 24, ny, nx): a numpy array, a float32 CUDA tensor or a DeviceDataset (its
+    hourly tensor and daily plane are used where they lie); daily: the condition ([D,] ny, nx) or None; check_obs(shape): the
+    module's own ValueErrors for the observation; S: the scenarios.  Holds obs and from_host, what admit_array made of `observed`."""
+
+    def __init__(self, gen, observed, daily, check_obs, S, overlap, latent_mode, latent, chunk, norm_scale):
+        self._dataset = observed if hasattr(observed, "daily_plane") else None
+        self.obs, self.from_host, shape = admit_array(observed if self._dataset is None else observed.data, "observed")
+        if len(shape) not in (3, 4):
+            raise ValueError(f"observed must have shape (24, ny, nx) or (n_days, 24, ny, nx), got {shape}")
+        check_obs(shape)
+        day_shape = shape[:-3] + shape[-2:]
+        if daily is not None and not isinstance(daily, torch.Tensor):
+            daily = np.asarray(daily)
+        if daily is not None and tuple(daily.shape) != day_shape:
+            raise ValueError(f"daily: expected shape {day_shape}, got {tuple(daily.shape)}")
+        # the checks of disaggregate on a stand-in of the daily map's shape: nothing has touched the device so far
+        self._req = F._check_request(gen, np.broadcast_to(np.float32(0), day_shape), S, overlap, latent_mode, latent, chunk, norm_scale)
+        self._daily, self._args = daily, (gen, S, overlap, latent_mode, latent, chunk, norm_scale)
+
+    def stream(self, obs, scenario_chunk, sink, seed):
+        """Disaggregate under the device of obs, the observation once it lies there, and hand every chunk of scenarios to sink
+        (field._stream_scenarios).  The default daily is the dataset's daily plane, or the sum of the observed hours."""
+        gen, S, overlap, latent_mode, latent, chunk, norm_scale = self._args
+        with torch.cuda.device(obs.device):
+            daily = self._daily
+            if daily is None:
+                daily = obs.sum(dim=-3) if self._dataset is None else self._dataset.daily_plane()
+            F._stream_scenarios(gen, self._req, daily, S, scenario_chunk, sink, overlap, latent_mode, seed, latent, chunk, norm_scale)
+
+
 def div(a, b):
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(np.asarray(b) != 0, np.asarray(a, dtype=np.float64) / np.asarray(b, dtype=np.float64), np.nan)
+
+
+def quantile_summary(a, axis, mean_abs=False):
+    """dict of median, q25, q75 and undefined (the share of NaN) of a over the pairs along axis -- with mean_abs, the mean of |a|
+    too; NaN where nothing is defined"""
+    with np.errstate(invalid="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)                      # (an all-NaN slice: its quantile is NaN, as wanted)
+        q25, med, q75 = np.nanquantile(a, [0.25, 0.5, 0.75], axis=axis)
+        out = dict(median=med, q25=q25, q75=q75, undefined=np.mean(np.isnan(a), axis=axis))
+        if mean_abs:
+            out["mean_abs"] = np.nanmean(np.abs(a), axis=axis)
+    return out
+
+
+def summary_differences(a, b, names):
+    """{name: {k: a[name][k] - b[name][k]}} of two summaries, dicts of dicts of arrays"""
+    return {name: {k: a[name][k] - b[name][k] for k in a[name]} for name in names}
 
 
 def tv(a, b):

@@ -18,7 +18,6 @@ planes into passes.  measures_from_records is host code on numpy and needs no GP
 No CPU fallback: without a visible MI355X the device functions raise RdganError; argument errors are ValueErrors raised before any
 device call."""
 import math
-import warnings
 from dataclasses import dataclass
 
 import numpy as np
@@ -28,7 +27,8 @@ from . import _lib
 from . import field as F
 from . import weights as W
 from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import MAX_ELEMS, MAX_MEMBERS, NHOURS, admit, admit_array, member_layout, to_state_device
+from ._hourly import (MAX_ELEMS, MAX_MEMBERS, NHOURS, ObservedRequest, ObservedVerifier, admit, admit_array, check_pair, div,
+                      grow_workspace, quantile_summary, summary_differences, to_state_device)
 from .engine import require_gpu
 from .verification import check_event_thresholds
 
@@ -73,7 +73,7 @@ def _pass_bytes(lib, ny, nx, planes_per_pass, n_planes):
     return workspace_bytes(lib, "rdgan_dm_workspace_bytes", ny, nx, per_pass)
 
 
-def _maps(lib, hourly, n, stride, shape, thr, planes_per_pass, ws=None):
+def _maps(lib, hourly, n, stride, shape, thr, planes_per_pass):
     """the library call of distance_maps on a device tensor -> (maps, set_sizes, workspace)"""
     ny, nx = shape[-2:]
     T, dev = len(thr), hourly.device
@@ -81,8 +81,7 @@ def _maps(lib, hourly, n, stride, shape, thr, planes_per_pass, ws=None):
         maps = torch.empty(shape[:-2] + (T, ny, nx), dtype=torch.uint16, device=dev)
         sizes = torch.empty(shape[:-2] + (T,), dtype=torch.int64, device=dev)
         nbytes = _pass_bytes(lib, ny, nx, planes_per_pass, n * NHOURS)
-        if ws is None or ws.numel() * 8 < nbytes:
-            ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
         rc = lib.rdgan_dm_maps(_p(hourly), n, stride, ny, nx, _hp(thr), T, _p(maps), _p(sizes), _p(ws), nbytes, _stream(maps))
     _lib.check(rc, None, "rdgan_dm_maps")
     return maps, sizes, ws
@@ -117,13 +116,6 @@ class PairRecords:
     nx: int
 
 
-def _ratio(num, den):
-    """num / den in fp64, one division each, NaN where den is 0"""
-    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.where(den != 0, num / den, np.nan)
-
-
 @dataclass
 class DistanceMeasures:
     """What measures_from_records returns, numpy on the host, each (S, n_days, 24, T) float64 in pixels unless said otherwise:
@@ -146,9 +138,9 @@ class DistanceMeasures:
         r = self.records.records
         n = r[..., 0]
         if p == 1:
-            return _ratio(r[..., 8], UNIT * n)
+            return div(r[..., 8], UNIT * n)
         if p == 2:
-            return np.sqrt(_ratio(r[..., 9], UNIT * UNIT * n))
+            return np.sqrt(div(r[..., 9], UNIT * UNIT * n))
         if p in (np.inf, "inf"):
             return np.where(n != 0, r[..., 10] / float(UNIT), np.nan)
         raise ValueError(f"p must be 1, 2 or inf, got {p!r}")
@@ -164,12 +156,7 @@ class DistanceMeasures:
         out = dict(thresholds=self.records.thresholds, cutoff_px=self.records.cutoff16 / UNIT, mask_mismatch=float(np.mean(self.flags & 1)))
         for name in MEASURES:
             a = getattr(self, name)
-            T = a.shape[-1]
-            hours = np.moveaxis(a, -2, 0).reshape(NHOURS, -1, T)
-            with np.errstate(invalid="ignore"), warnings.catch_warnings():
-                warnings.simplefilter("ignore", RuntimeWarning)              # (an all-NaN slice: its quantile is NaN, as wanted)
-                q25, med, q75 = np.nanquantile(hours, [0.25, 0.5, 0.75], axis=1)
-            out[name] = dict(median=med, q25=q25, q75=q75, undefined=np.mean(np.isnan(hours), axis=1))
+            out[name] = quantile_summary(np.moveaxis(a, -2, 0).reshape(NHOURS, -1, a.shape[-1]), 1)
         return out
 
 
@@ -186,12 +173,12 @@ def measures_from_records(records, zhu_lambda=0.5):
     lam = float(zhu_lambda)
     n, nA, nB, nAB, flags = r[..., 0], r[..., 1], r[..., 2], r[..., 3], r[..., 11]
     both = (flags & 6) == 0                                                  # neither whole set is empty
-    med_ab = np.where(both, _ratio(r[..., 4], UNIT * nB), np.nan)
-    med_ba = np.where(both, _ratio(r[..., 5], UNIT * nA), np.nan)
+    med_ab = np.where(both, div(r[..., 4], UNIT * nB), np.nan)
+    med_ba = np.where(both, div(r[..., 5], UNIT * nA), np.nan)
     haus = np.where(both & (nA > 0) & (nB > 0), np.maximum(r[..., 6], r[..., 7]) / float(UNIT), np.nan)
-    zhu = lam * np.sqrt(_ratio(nA + nB - 2 * nAB, n)) + (1.0 - lam) * med_ab
+    zhu = lam * np.sqrt(div(nA + nB - 2 * nAB, n)) + (1.0 - lam) * med_ab
     return DistanceMeasures(records, lam, hausdorff=haus, med_model_to_obs=med_ab, med_obs_to_model=med_ba, zhu=zhu,
-                            csi=_ratio(nAB, nA + nB - nAB), flags=flags.copy())
+                            csi=div(nAB, nA + nB - nAB), flags=flags.copy())
 
 
 def compare(a, b):
@@ -202,10 +189,7 @@ def compare(a, b):
         raise ValueError("compare takes two DistanceMeasures or two summaries")
     if tuple(a["thresholds"]) != tuple(b["thresholds"]) or a["cutoff_px"] != b["cutoff_px"]:
         raise ValueError(f"the two summaries differ in thresholds or cutoff: {a['thresholds']}, {a['cutoff_px']} and {b['thresholds']}, {b['cutoff_px']}")
-    out = dict(thresholds=tuple(a["thresholds"]), cutoff_px=a["cutoff_px"])
-    for name in MEASURES:
-        out[name] = {k: a[name][k] - b[name][k] for k in a[name]}
-    return out
+    return dict(thresholds=tuple(a["thresholds"]), cutoff_px=a["cutoff_px"], **summary_differences(a, b, MEASURES))
 
 
 def _check_obs(shape, n_thresholds, max_map_bytes, what="obs"):
@@ -221,7 +205,7 @@ def _check_obs(shape, n_thresholds, max_map_bytes, what="obs"):
     return nbytes
 
 
-class DistanceMapVerifier:
+class DistanceMapVerifier(ObservedVerifier):
     """The observation and its distance maps on the device.  obs (..., 24, ny, nx), ny, nx <= 2048: a numpy array or a float32 CUDA
     tensor (used where it lies); thresholds: the events, in the unit of obs; cutoff_px: Baddeley's cutoff in pixels, 1 .. 4095.875
     -- None: the plane's diagonal, so that an empty set is "everything is a diagonal away"; planes_per_pass: how many planes the
@@ -230,16 +214,13 @@ class DistanceMapVerifier:
 
     def __init__(self, obs, thresholds, cutoff_px=None, planes_per_pass=None, max_map_bytes=2 << 30):
         self.thr = check_event_thresholds(thresholds)
-        obs, from_host, self.shape = admit_array(obs, "obs")
-        self.ny, self.nx = self.shape[-2:]
-        _check_obs(self.shape, len(self.thr), max_map_bytes)
-        self.cutoff16 = cutoff16(cutoff_px, self.ny, self.nx)
-        self.planes_per_pass = check_planes_per_pass(planes_per_pass)
-        require_gpu()
-        self.lib = _lib.load()
-        self.obs = to_state_device(obs, True, "cuda", "obs") if from_host else obs.detach().contiguous()
-        self.P = int(np.prod(self.shape, dtype=np.int64))
-        self.n_days = self.P // (NHOURS * self.ny * self.nx)
+
+        def check_obs(shape):
+            _check_obs(shape, len(self.thr), max_map_bytes)
+            self.cutoff16 = cutoff16(cutoff_px, shape[-2], shape[-1])
+            self.planes_per_pass = check_planes_per_pass(planes_per_pass)
+
+        self._admit_obs(obs, check_obs)
         self.maps, self.set_sizes, self._ws = _maps(self.lib, self.obs, self.n_days, NHOURS * self.ny * self.nx, self.shape, self.thr,
                                                     self.planes_per_pass)
         self._parts = []
@@ -247,25 +228,14 @@ class DistanceMapVerifier:
     def add(self, members):
         """members (s, *obs.shape) float32, s <= 4096: a CUDA tensor, whose member axis may have any stride >= prod(obs.shape) (a
         view of a wider buffer), or a numpy array.  Appends the records of these members; returns self."""
-        members, from_host, _ = admit_array(members, "members")
-        if from_host:
-            members = np.ascontiguousarray(members, dtype=np.float32)                                 # dense: member stride P
-        s, P, stride, shape = member_layout(torch.from_numpy(members) if from_host else members)
-        if shape != self.shape:
-            raise ValueError(f"members: expected shape (s,) + {self.shape}, got {tuple(members.shape)}")
-        if s * P > MAX_ELEMS:
-            raise ValueError(f"members: more than {MAX_ELEMS} values in one call")
-        dev = self.obs.device
-        members = to_state_device(members, from_host, dev, "members")
-        T = len(self.thr)
+        members, s, stride = self._admit_members(members)
+        T, dev = len(self.thr), self.obs.device
         with torch.cuda.device(dev):
             rec = torch.empty((s, self.n_days, NHOURS, T, NREC), dtype=torch.int64, device=dev)
             nbytes = _pass_bytes(self.lib, self.ny, self.nx, self.planes_per_pass, s * self.n_days * NHOURS)
-            if self._ws is None or self._ws.numel() * 8 < nbytes:
-                self._ws = None
-                self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+            ws = grow_workspace(self, nbytes, dev)
             rc = self.lib.rdgan_dm_records(_p(members), s, stride, _p(self.obs), _p(self.maps), self.n_days, self.ny, self.nx,
-                                           _hp(self.thr), T, self.cutoff16, _p(rec), _p(self._ws), nbytes, _stream(rec))
+                                           _hp(self.thr), T, self.cutoff16, _p(rec), _p(ws), nbytes, _stream(rec))
         _lib.check(rc, None, "rdgan_dm_records")
         self._parts.append(rec)
         return self
@@ -277,21 +247,12 @@ class DistanceMapVerifier:
         return PairRecords(torch.cat(self._parts, dim=0).cpu().numpy(), tuple(float(t) for t in self.thr), self.cutoff16, self.ny, self.nx)
 
 
-def _check_pair(ens_shape, obs_shape, what="ens"):
-    if len(ens_shape) < 4:
-        raise ValueError(f"{what}: expected an array or tensor of shape (S, ..., 24, ny, nx)")
-    if not 1 <= int(ens_shape[0]) <= MAX_MEMBERS:
-        raise ValueError(f"the number of members must lie in 1 .. {MAX_MEMBERS}, got {int(ens_shape[0])}")
-    if tuple(ens_shape[1:]) != tuple(obs_shape):
-        raise ValueError(f"{what}: expected shape (S,) + {tuple(obs_shape)}, got {tuple(ens_shape)}")
-
-
 def distmap_hourly(ens, obs, thresholds, cutoff_px=None, planes_per_pass=None, max_map_bytes=2 << 30, zhu_lambda=0.5):
     """One call for an ensemble that is held: ens (S, *obs.shape), obs (..., 24, ny, nx), each a float32 CUDA tensor or a numpy
     array.  -> DistanceMeasures of shape (S, n_days, 24, T); its .records are the PairRecords"""
     thr, planes_per_pass = check_event_thresholds(thresholds), check_planes_per_pass(planes_per_pass)
     obs, ens = admit_array(obs, "obs")[0], admit_array(ens, "ens")[0]
-    _check_pair(tuple(ens.shape), tuple(obs.shape))
+    check_pair(ens.shape, obs.shape)
     _check_obs(tuple(obs.shape), len(thr), max_map_bytes)
     cutoff16(cutoff_px, obs.shape[-2], obs.shape[-1])
     measures_from_records(PairRecords(np.zeros((0, NREC), np.int64), (), MIN_CUTOFF, 1, 1), zhu_lambda)        # (zhu_lambda, before the device)
@@ -310,24 +271,13 @@ def distmap_field(gen, observed, n_scenarios, thresholds, cutoff_px=None, planes
     (_hourly.evaluate_field says when they are).  -> DistanceMeasures of shape (S, D, 24, T)"""
     thr, planes_per_pass = check_event_thresholds(thresholds), check_planes_per_pass(planes_per_pass)
     S, step = F._check_scenarios(n_scenarios, scenario_chunk, MAX_MEMBERS)
-    dataset = hasattr(observed, "daily_plane")
-    obs = observed.data if dataset else observed
-    obs, _, shape = admit_array(obs, "observed")
-    if len(shape) not in (3, 4):
-        raise ValueError(f"observed must have shape (24, ny, nx) or (n_days, 24, ny, nx), got {shape}")
-    _check_obs(shape, len(thr), max_map_bytes, "observed")
-    cutoff16(cutoff_px, shape[-2], shape[-1])
     measures_from_records(PairRecords(np.zeros((0, NREC), np.int64), (), MIN_CUTOFF, 1, 1), zhu_lambda)
-    day_shape = shape[:-3] + shape[-2:]
-    if daily is not None and not isinstance(daily, torch.Tensor):
-        daily = np.asarray(daily)
-    if daily is not None and tuple(daily.shape) != day_shape:
-        raise ValueError(f"daily: expected shape {day_shape}, got {tuple(daily.shape)}")
-    # the checks of disaggregate on a stand-in of the daily map's shape: nothing has touched the device so far
-    req = F._check_request(gen, np.broadcast_to(np.float32(0), day_shape), S, overlap, latent_mode, latent, chunk, norm_scale)
-    ver = DistanceMapVerifier(obs, thr, cutoff_px, planes_per_pass, max_map_bytes)
-    with torch.cuda.device(ver.obs.device):
-        if daily is None:
-            daily = observed.daily_plane() if dataset else ver.obs.sum(dim=-3)
-        F._stream_scenarios(gen, req, daily, S, step, ver.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
+
+    def check_obs(shape):
+        _check_obs(shape, len(thr), max_map_bytes, "observed")
+        cutoff16(cutoff_px, shape[-2], shape[-1])
+
+    request = ObservedRequest(gen, observed, daily, check_obs, S, overlap, latent_mode, latent, chunk, norm_scale)
+    ver = DistanceMapVerifier(request.obs, thr, cutoff_px, planes_per_pass, max_map_bytes)
+    request.stream(ver.obs, step, ver.add, seed)
     return measures_from_records(ver.records(), zhu_lambda)

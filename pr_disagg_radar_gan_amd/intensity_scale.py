@@ -25,8 +25,8 @@ from . import _lib
 from . import field as F
 from . import weights as W
 from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import MAX_ELEMS, MAX_MEMBERS, MAX_PLANE, NHOURS, admit_array, member_layout, to_state_device
-from .engine import require_gpu
+from ._hourly import (MAX_ELEMS, MAX_MEMBERS, MAX_PLANE, NHOURS, ObservedRequest, ObservedVerifier, admit_array, check_pair,
+                      grow_workspace)
 from .verification import check_event_thresholds
 
 MAX_LEVELS = 10                                                              # RD_ISS_MAXL
@@ -54,7 +54,7 @@ def crop(ny, nx, levels):
     return (ny % side) // 2, (nx % side) // 2, ny // side * side, nx // side * side
 
 
-def _ratio(num, den):
+def _exact_ratio(num, den):
     """num / den elementwise for arrays of Python integers: one correctly rounded division each, NaN where den is 0"""
     return np.frompyfunc(lambda n, d: n / d if d else float("nan"), 2, 1)(num, den).astype(np.float64)
 
@@ -96,7 +96,7 @@ class IntensityScale:
         """the MSE of the binary error field per component, (T, L + 1) -- or (T, 24, L + 1); the components sum to the binary MSE
         QZ_0 / N; NaN without a valid tile"""
         q, n = self._q(by_hour)
-        return _ratio(*self._components(q[..., 0] - 2 * q[..., 2] + q[..., 1], n))
+        return _exact_ratio(*self._components(q[..., 0] - 2 * q[..., 2] + q[..., 1], n))
 
     def skill(self, by_hour=False, bias_corrected=False):
         """ISS_j = 1 - (L + 1) MSE_j / MSE_random, (T, L + 1) -- or (T, 24, L + 1).  MSE_random = 2 e (1 - e) with the base rate
@@ -110,7 +110,7 @@ class IntensityScale:
         if bias_corrected:
             r = np.where(o0 == 0, 0, r)
         d = den * r
-        return _ratio(d - (self.levels + 1) * num * n * n, d)
+        return _exact_ratio(d - (self.levels + 1) * num * n * n, d)
 
     def energy(self, by_hour=False):
         """(En^X, En^O, relative difference), each (T, L + 1) -- or (T, 24, L + 1): the components' mean squares of the member's and
@@ -118,7 +118,7 @@ class IntensityScale:
         q, n = self._q(by_hour)
         nx_, den = self._components(q[..., 0], n)
         no_, _ = self._components(q[..., 1], n)
-        return _ratio(nx_, den), _ratio(no_, den), _ratio(nx_ - no_, np.where(n == 0, 0, nx_ + no_))
+        return _exact_ratio(nx_, den), _exact_ratio(no_, den), _exact_ratio(nx_ - no_, np.where(n == 0, 0, nx_ + no_))
 
     def contingency(self, by_hour=False):
         """(hits, false alarms, misses, correct negatives) over the pixel-pairs of the valid tiles, (T, 4) -- or (T, 24, 4) int64"""
@@ -132,7 +132,7 @@ class IntensityScale:
         q, n = self._q(False)
         enx, eno, rel = self.energy()
         return dict(thresholds=self.thresholds, levels=self.levels, scales_px=self.scales_px, valid_tiles=int(self.tiles[:, 0].sum()),
-                    void_tiles=int(self.tiles[:, 1].sum()), base_rate=_ratio(q[..., 0, 1], n), bias=_ratio(q[..., 0, 0], q[..., 0, 1]),
+                    void_tiles=int(self.tiles[:, 1].sum()), base_rate=_exact_ratio(q[..., 0, 1], n), bias=_exact_ratio(q[..., 0, 0], q[..., 0, 1]),
                     mse=self.mse(), skill=self.skill(), skill_bias_corrected=self.skill(bias_corrected=True), energy_model=enx,
                     energy_obs=eno, energy_rel_diff=rel, skill_by_hour=self.skill(by_hour=True))
 
@@ -163,7 +163,7 @@ def _check_obs(shape, levels, what="obs"):
     return check_levels(levels, ny, nx)
 
 
-class IntensityScaleVerifier:
+class IntensityScaleVerifier(ObservedVerifier):
     """The state of an intensity-scale verification on the device.  obs (..., 24, ny, nx): a numpy array or a float32 CUDA tensor
     (used where it lies); thresholds: the events, in the unit of obs; levels: L, the tile is 2^L pixels wide -- None:
     min(10, floor(log2(min(ny, nx)))); pairs_per_pass: how many (member plane, observed plane) pairs the workspace of L > 6 holds at
@@ -171,48 +171,36 @@ class IntensityScaleVerifier:
 
     def __init__(self, obs, thresholds, levels=None, pairs_per_pass=None):
         self.thr = check_event_thresholds(thresholds)
-        obs, from_host, self.shape = admit_array(obs, "obs")
-        self.levels = _check_obs(self.shape, levels)
-        self.pairs_per_pass = _check_pairs_per_pass(pairs_per_pass)
-        require_gpu()
-        self.lib = _lib.load()
-        self.obs = to_state_device(obs, True, "cuda", "obs") if from_host else obs.detach().contiguous()
+
+        def check_obs(shape):
+            self.levels = _check_obs(shape, levels)
+            self.pairs_per_pass = _check_pairs_per_pass(pairs_per_pass)
+
+        self._admit_obs(obs, check_obs)
         dev = self.obs.device
-        self.ny, self.nx = self.shape[-2:]
-        self.P = int(np.prod(self.shape, dtype=np.int64))
-        self.n_days = self.P // (NHOURS * self.ny * self.nx)
         _, _, cy, cx = crop(self.ny, self.nx, self.levels)
         self._pairs_of_a_member = self.n_days * NHOURS * cy * cx                # pixel-pairs one member adds
         self.n_members = 0
         self.counts = torch.zeros((len(self.thr), NHOURS, self.levels + 1, 3), dtype=torch.int64, device=dev)
         self.tiles = torch.zeros((NHOURS, 2), dtype=torch.int64, device=dev)
-        self._ws = None
+
+    def _check_members(self, s):
+        if (self.n_members + s) * self._pairs_of_a_member * 4 ** self.levels > MAX_COUNT:
+            raise ValueError(f"{self.n_members + s} members of {self._pairs_of_a_member} pixel-pairs each at levels={self.levels} could "
+                             "overflow the 64-bit state (pixel-pairs * 4^levels must stay at or below 2^62)")
 
     def add(self, members):
         """members (s, *obs.shape) float32, s <= 4096: a CUDA tensor, whose member axis may have any stride >= prod(obs.shape) (a
         view of a wider buffer), or a numpy array.  Returns self."""
-        members, from_host, _ = admit_array(members, "members")
-        if from_host:
-            members = np.ascontiguousarray(members, dtype=np.float32)                                 # dense: member stride P
-        s, P, stride, shape = member_layout(torch.from_numpy(members) if from_host else members)
-        if shape != self.shape:
-            raise ValueError(f"members: expected shape (s,) + {self.shape}, got {tuple(members.shape)}")
-        if s * P > MAX_ELEMS:
-            raise ValueError(f"members: more than {MAX_ELEMS} values in one call")
-        if (self.n_members + s) * self._pairs_of_a_member * 4 ** self.levels > MAX_COUNT:
-            raise ValueError(f"{self.n_members + s} members of {self._pairs_of_a_member} pixel-pairs each at levels={self.levels} could "
-                             "overflow the 64-bit state (pixel-pairs * 4^levels must stay at or below 2^62)")
-        members = to_state_device(members, from_host, self.obs.device, "members")
+        members, s, stride = self._admit_members(members)
         L = self.levels
         with torch.cuda.device(self.obs.device):
             one = workspace_bytes(self.lib, "rdgan_iss_workspace_bytes", self.ny, self.nx, L, 1)
             pairs = self.pairs_per_pass or max(1, min(s * self.n_days * NHOURS, _DEFAULT_PASS_BYTES // one))
             nbytes = workspace_bytes(self.lib, "rdgan_iss_workspace_bytes", self.ny, self.nx, L, pairs)
-            if self._ws is None or self._ws.numel() * 8 < nbytes:
-                self._ws = None
-                self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.obs.device)
+            ws = grow_workspace(self, nbytes, self.obs.device)
             rc = self.lib.rdgan_iss_accumulate(_p(members), s, stride, _p(self.obs), self.n_days, self.ny, self.nx, _hp(self.thr),
-                                               len(self.thr), L, _p(self.counts), _p(self.tiles), _p(self._ws), nbytes,
+                                               len(self.thr), L, _p(self.counts), _p(self.tiles), _p(ws), nbytes,
                                                _stream(self.obs))
         _lib.check(rc, None, "rdgan_iss_accumulate")
         self.n_members += s
@@ -235,13 +223,7 @@ def intensity_scale_hourly(ens, obs, thresholds, levels=None):
     array.  -> IntensityScale"""
     thr = check_event_thresholds(thresholds)
     obs, ens = admit_array(obs, "obs")[0], admit_array(ens, "ens")[0]
-    if len(ens.shape) < 4:
-        raise ValueError("ens: expected an array or tensor of shape (S, ..., 24, ny, nx)")
-    S = int(ens.shape[0])
-    if not 1 <= S <= MAX_MEMBERS:
-        raise ValueError(f"the number of members must lie in 1 .. {MAX_MEMBERS}, got {S}")
-    if tuple(ens.shape[1:]) != tuple(obs.shape):
-        raise ValueError(f"ens: expected shape (S,) + {tuple(obs.shape)}, got {tuple(ens.shape)}")
+    check_pair(ens.shape, obs.shape)
     levels = _check_obs(tuple(obs.shape), levels)
     return IntensityScaleVerifier(obs, thr, levels).add(ens).result()
 
@@ -257,22 +239,8 @@ def intensity_scale_field(gen, observed, n_scenarios, thresholds, levels=None, d
     (_hourly.evaluate_field says when they are).  -> IntensityScale"""
     thr = check_event_thresholds(thresholds)
     S, step = F._check_scenarios(n_scenarios, scenario_chunk, MAX_MEMBERS)
-    dataset = hasattr(observed, "daily_plane")
-    obs = observed.data if dataset else observed
-    obs, _, shape = admit_array(obs, "observed")
-    if len(shape) not in (3, 4):
-        raise ValueError(f"observed must have shape (24, ny, nx) or (n_days, 24, ny, nx), got {shape}")
-    levels = _check_obs(shape, levels, "observed")
-    day_shape = shape[:-3] + shape[-2:]
-    if daily is not None and not isinstance(daily, torch.Tensor):
-        daily = np.asarray(daily)
-    if daily is not None and tuple(daily.shape) != day_shape:
-        raise ValueError(f"daily: expected shape {day_shape}, got {tuple(daily.shape)}")
-    # the checks of disaggregate on a stand-in of the daily map's shape: nothing has touched the device so far
-    req = F._check_request(gen, np.broadcast_to(np.float32(0), day_shape), S, overlap, latent_mode, latent, chunk, norm_scale)
-    ver = IntensityScaleVerifier(obs, thr, levels)
-    with torch.cuda.device(ver.obs.device):
-        if daily is None:
-            daily = observed.daily_plane() if dataset else ver.obs.sum(dim=-3)
-        F._stream_scenarios(gen, req, daily, S, step, ver.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
+    request = ObservedRequest(gen, observed, daily, lambda shape: _check_obs(shape, levels, "observed"), S, overlap, latent_mode, latent,
+                              chunk, norm_scale)
+    ver = IntensityScaleVerifier(request.obs, thr, levels)
+    request.stream(ver.obs, step, ver.add, seed)
     return ver.result()

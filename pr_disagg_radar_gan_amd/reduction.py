@@ -32,7 +32,7 @@ from . import _lib
 from . import field as F
 from . import weights as W
 from ._dev import ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import MAX_ELEMS, MAX_MEMBERS, MAX_PLANE, admit_array, member_layout, to_state_device
+from ._hourly import MAX_ELEMS, MAX_MEMBERS, MAX_PLANE, admit_array, dense_member_layout, to_state_device
 from .engine import require_gpu
 
 UNIT = 32                                                                    # RD_SEQ_UNIT: features are integers in 1 / UNIT mm
@@ -102,9 +102,7 @@ class ScenarioFeatures:
             raise ValueError(f"members: a plane of {ny * nx} pixels and a member of {P} values; the limits are {MAX_PLANE} and {MAX_ELEMS}")
         pf = n_positions(mshape, self.pool)
         check_admission(self.n_members + s, pf, self.max_feature_bytes)
-        if from_host:
-            members = np.ascontiguousarray(members, dtype=np.float32)                                 # dense: member stride P
-        stride = member_layout(torch.from_numpy(members) if from_host else members)[2]
+        members, _, _, stride, _ = dense_member_layout(members, from_host)
         if self.lib is None:
             require_gpu()
             self.lib = _lib.load()

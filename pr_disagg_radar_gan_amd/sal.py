@@ -11,7 +11,6 @@ into passes or calls.  sal_from_records is host code on numpy and needs no GPU.
 
 No CPU fallback: without a visible MI355X the device functions raise RdganError; argument errors are ValueErrors raised before any
 device call."""
-import warnings
 from dataclasses import dataclass
 
 import numpy as np
@@ -21,7 +20,8 @@ from . import _lib
 from . import field as F
 from . import weights as W
 from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, workspace_bytes
-from ._hourly import MAX_MEMBERS, MAX_PLANE, NHOURS, admit, admit_array, to_state_device
+from ._hourly import (MAX_MEMBERS, MAX_PLANE, NHOURS, ObservedRequest, admit, check_pair, div, observation_on_device,
+                      quantile_summary, summary_differences, to_state_device)
 from .cells import MAX_PASS, check_connectivity, check_planes_per_pass
 from .engine import require_gpu
 from .verification import check_event_thresholds
@@ -124,19 +124,8 @@ class SAL:
             a = getattr(self, c)
             T = a.shape[-1]
             flat, hours = a.reshape(-1, T), np.moveaxis(a, -2, 0).reshape(NHOURS, -1, T)
-            with np.errstate(invalid="ignore"), warnings.catch_warnings():
-                warnings.simplefilter("ignore", RuntimeWarning)              # (an all-NaN slice: its quantile is NaN, as wanted)
-                q25, med, q75 = np.nanquantile(flat, [0.25, 0.5, 0.75], axis=0)
-                out[c] = dict(median=med, q25=q25, q75=q75, mean_abs=np.nanmean(np.abs(flat), axis=0),
-                              undefined=np.mean(np.isnan(flat), axis=0), by_hour=np.nanquantile(hours, 0.5, axis=1))
+            out[c] = dict(quantile_summary(flat, 0, mean_abs=True), by_hour=quantile_summary(hours, 1)["median"])
         return out
-
-
-def _ratio(a, b):
-    """a / b in fp64, NaN where b is 0"""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.where(b != 0, a / b, np.nan)
 
 
 def sal_from_records(model, obs):
@@ -162,11 +151,11 @@ def sal_from_records(model, obs):
         raise ValueError(f"the two records do not broadcast: {m.plane.shape[:-1]} and {o.plane.shape[:-1]}") from None
     ny, nx = m.ny, m.nx
     d = np.sqrt(np.float64(ny * ny + nx * nx))
-    Dm, Do = _ratio(m.M0, ny * nx - m.n_bad), _ratio(o.M0, ny * nx - o.n_bad)
-    A = 2.0 * _ratio(Dm - Do, Dm + Do)
-    L1 = np.hypot(_ratio(m.Mx, m.M0) - _ratio(o.Mx, o.M0), _ratio(m.My, m.M0) - _ratio(o.My, o.M0)) / d
+    Dm, Do = div(m.M0, ny * nx - m.n_bad), div(o.M0, ny * nx - o.n_bad)
+    A = 2.0 * div(Dm - Do, Dm + Do)
+    L1 = np.hypot(div(m.Mx, m.M0) - div(o.Mx, o.M0), div(m.My, m.M0) - div(o.My, o.M0)) / d
     both = (m.n_objects > 0) & (o.n_objects > 0)
-    S = np.where(both, 2.0 * _ratio(m.V - o.V, m.V + o.V), np.nan)
+    S = np.where(both, 2.0 * div(m.V - o.V, m.V + o.V), np.nan)
     L2 = np.where(both, 2.0 * np.abs(m.r - o.r) / d, np.nan)
     T = len(m.thresholds)
     wide = lambda a: np.broadcast_to(a[..., None], lead + (T,)).copy()
@@ -183,19 +172,7 @@ def compare(a, b):
         raise ValueError("compare takes two SAL or two summaries")
     if tuple(a["thresholds"]) != tuple(b["thresholds"]):
         raise ValueError(f"the two summaries have different thresholds: {a['thresholds']} and {b['thresholds']}")
-    out = dict(thresholds=tuple(a["thresholds"]))
-    for c in COMPONENTS:
-        out[c] = {k: a[c][k] - b[c][k] for k in a[c]}
-    return out
-
-
-def _check_pair(ens_shape, obs_shape, what="ens"):
-    if len(ens_shape) < 4:
-        raise ValueError(f"{what}: expected an array or tensor of shape (S, ..., 24, ny, nx)")
-    if not 1 <= int(ens_shape[0]) <= MAX_MEMBERS:
-        raise ValueError(f"the number of members must lie in 1 .. {MAX_MEMBERS}, got {int(ens_shape[0])}")
-    if tuple(ens_shape[1:]) != tuple(obs_shape):
-        raise ValueError(f"{what}: expected shape (S,) + {tuple(obs_shape)}, got {tuple(ens_shape)}")
+    return dict(thresholds=tuple(a["thresholds"]), **summary_differences(a, b, COMPONENTS))
 
 
 def sal_hourly(ens, obs, thresholds, connectivity=8, planes_per_pass=None):
@@ -203,7 +180,7 @@ def sal_hourly(ens, obs, thresholds, connectivity=8, planes_per_pass=None):
     array.  -> SAL of shape (S, ..., 24, T)"""
     thr, connectivity, planes_per_pass = _check_request(thresholds, connectivity, planes_per_pass)
     obs_shape, ens_shape = admit(obs)[2], admit(ens)[2]
-    _check_pair(ens_shape, obs_shape)
+    check_pair(ens_shape, obs_shape)
     check_plane(*obs_shape[-2:])
     return sal_from_records(plane_records(ens, thr, connectivity, planes_per_pass).cpu(),
                             plane_records(obs, thr, connectivity, planes_per_pass).cpu())
@@ -220,28 +197,12 @@ def sal_field(gen, observed, n_scenarios, thresholds, connectivity=8, planes_per
     -> SAL of shape (S, [D,] 24, T)"""
     thr, connectivity, planes_per_pass = _check_request(thresholds, connectivity, planes_per_pass)
     S, step = F._check_scenarios(n_scenarios, scenario_chunk, MAX_MEMBERS)
-    dataset = hasattr(observed, "daily_plane")
-    obs = observed.data if dataset else observed
-    obs, from_host, shape = admit_array(obs, "observed")
-    if len(shape) not in (3, 4):
-        raise ValueError(f"observed must have shape (24, ny, nx) or (n_days, 24, ny, nx), got {shape}")
-    check_plane(shape[-2], shape[-1], "observed")
-    day_shape = shape[:-3] + shape[-2:]
-    if daily is not None and not isinstance(daily, torch.Tensor):
-        daily = np.asarray(daily)
-    if daily is not None and tuple(daily.shape) != day_shape:
-        raise ValueError(f"daily: expected shape {day_shape}, got {tuple(daily.shape)}")
-    # the checks of disaggregate on a stand-in of the daily map's shape: nothing has touched the device so far
-    req = F._check_request(gen, np.broadcast_to(np.float32(0), day_shape), S, overlap, latent_mode, latent, chunk, norm_scale)
-    require_gpu()
-    obs = to_state_device(obs, True, "cuda", "observed") if from_host else obs.detach().contiguous()
+    request = ObservedRequest(gen, observed, daily, lambda shape: check_plane(shape[-2], shape[-1], "observed"), S, overlap, latent_mode,
+                              latent, chunk, norm_scale)
+    obs = observation_on_device(request.obs, request.from_host)
     obs_rec = plane_records(obs, thr, connectivity, planes_per_pass).cpu()
     parts = []
-    with torch.cuda.device(obs.device):
-        if daily is None:
-            daily = observed.daily_plane() if dataset else obs.sum(dim=-3)
-        F._stream_scenarios(gen, req, daily, S, step, lambda buf: parts.append(plane_records(buf, thr, connectivity, planes_per_pass).cpu()),
-                            overlap, latent_mode, seed, latent, chunk, norm_scale)
+    request.stream(obs, step, lambda buf: parts.append(plane_records(buf, thr, connectivity, planes_per_pass).cpu()), seed)
     model = PlaneRecords(*(np.concatenate([getattr(p, k) for p in parts], axis=0) for k in ("plane", "objects", "vr")), obs_rec.ny, obs_rec.nx,
                          obs_rec.thresholds, connectivity)
     return sal_from_records(model, obs_rec)

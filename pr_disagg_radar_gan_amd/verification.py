@@ -23,8 +23,7 @@ from . import _lib
 from . import field as F
 from . import weights as W
 from ._dev import host_ptr as _hp, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import MAX_MEMBERS, admit_array, member_layout, to_state_device
-from .engine import require_gpu
+from ._hourly import MAX_MEMBERS, ObservedRequest, ObservedVerifier, admit_array, check_pair
 
 MAX_THRESHOLDS, MAX_SCALES, MAX_BINS = 8, 8, 64                             # RD_VF_MAXT, RD_VF_MAXW, RD_VF_MAXBINS (MAX_MEMBERS: RD_VF_MAXS)
 MAX_BOX_MEMBERS = 1 << 26                                                   # S * w_max^2 stays below this
@@ -129,39 +128,30 @@ class Verification:
             return np.where(f[..., 1] > 0, 1.0 - f[..., 0] / f[..., 1], np.nan)
 
 
-class EnsembleVerifier:
+class EnsembleVerifier(ObservedVerifier):
     """The state of a verification on the device.  obs (..., 24, ny, nx): a numpy array or a float32 CUDA tensor (used where it
     lies); thresholds: the events, in the unit of obs."""
 
     def __init__(self, obs, thresholds):
         self.thr = check_event_thresholds(thresholds)
-        obs, from_host, self.shape = admit_array(obs, "obs")
-        require_gpu()
-        self.lib = _lib.load()
-        self.obs = to_state_device(obs, True, "cuda", "obs") if from_host else obs.detach().contiguous()
+        self._admit_obs(obs)
         dev = self.obs.device
-        self.P = int(np.prod(self.shape, dtype=np.int64))
-        self.ny, self.nx = self.shape[-2], self.shape[-1]
         self.n_members = 0
         self.exceed = torch.zeros((len(self.thr),) + self.shape, dtype=torch.int32, device=dev)
         self.below = torch.zeros(self.shape, dtype=torch.int32, device=dev)
         self.equal = torch.zeros(self.shape, dtype=torch.int32, device=dev)
         self.bad = torch.isnan(self.obs).to(torch.uint8)
 
+    def _check_members(self, s):
+        if self.n_members + s > MAX_MEMBERS:
+            raise ValueError(f"a verification holds at most {MAX_MEMBERS} members: {self.n_members} held, {s} more offered")
+
     def add(self, members):
         """members (s, *obs.shape) float32: a CUDA tensor, whose member axis may have any stride >= prod(obs.shape) (a view of a
         wider buffer, as member_stats_device accepts it), or a numpy array.  Returns self."""
-        members, from_host, _ = admit_array(members, "members")
-        if from_host:
-            members = np.ascontiguousarray(members, dtype=np.float32)                                 # dense: member stride P
-        s, P, stride, shape = member_layout(torch.from_numpy(members) if from_host else members)
-        if shape != self.shape:
-            raise ValueError(f"members: expected shape (s,) + {self.shape}, got {tuple(members.shape)}")
-        if self.n_members + s > MAX_MEMBERS:
-            raise ValueError(f"a verification holds at most {MAX_MEMBERS} members: {self.n_members} held, {s} more offered")
-        members = to_state_device(members, from_host, self.obs.device, "members")
+        members, s, stride = self._admit_members(members)
         with torch.cuda.device(self.obs.device):
-            rc = self.lib.rdgan_verify_accumulate(_p(members), s, stride, P, _p(self.obs), _hp(self.thr), len(self.thr),
+            rc = self.lib.rdgan_verify_accumulate(_p(members), s, stride, self.P, _p(self.obs), _hp(self.thr), len(self.thr),
                                                   _p(self.exceed), _p(self.below), _p(self.equal), _p(self.bad),
                                                   _stream(self.obs))
         _lib.check(rc, None, "rdgan_verify_accumulate")
@@ -180,7 +170,6 @@ class EnsembleVerifier:
             raise ValueError("no member has been added")
         wd, n_bins, seed = check_scales(scales, S), _check_bins(n_bins, S), _check_seed(seed)
         T, Wn, dev = len(self.thr), len(wd), self.obs.device
-        n_days = self.P // (W.NHOURS * self.ny * self.nx)
         with torch.cuda.device(dev):
             rank = torch.empty((W.NHOURS, S + 1), dtype=torch.int64, device=dev)
             rel = torch.empty((T, W.NHOURS, n_bins, 3), dtype=torch.int64, device=dev)
@@ -193,7 +182,7 @@ class EnsembleVerifier:
             _lib.check(rc, None, "rdgan_verify_reduce")
             nbytes = workspace_bytes(self.lib, "rdgan_verify_fss_workspace_bytes", self.ny, self.nx, T, Wn)
             ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-            rc = self.lib.rdgan_verify_fss(_p(self.obs), _p(self.exceed), _p(self.bad), n_days, self.ny, self.nx, S,
+            rc = self.lib.rdgan_verify_fss(_p(self.obs), _p(self.exceed), _p(self.bad), self.n_days, self.ny, self.nx, S,
                                            _hp(self.thr), T, _hp(wd), Wn, _p(fss), _p(ws), nbytes, st)
             _lib.check(rc, None, "rdgan_verify_fss")
             rank, rel, brier, fss = rank.cpu().numpy(), rel.cpu().numpy(), brier.cpu().numpy(), fss.cpu().numpy()
@@ -206,13 +195,8 @@ def verify_hourly(ens, obs, thresholds, **result_kw):
     EnsembleVerifier.result.  -> Verification"""
     thr = check_event_thresholds(thresholds)
     obs, ens = admit_array(obs, "obs")[0], admit_array(ens, "ens")[0]
-    if len(ens.shape) < 4:
-        raise ValueError("ens: expected an array or tensor of shape (S, ..., 24, ny, nx)")
+    check_pair(ens.shape, obs.shape)
     S = int(ens.shape[0])
-    if not 1 <= S <= MAX_MEMBERS:
-        raise ValueError(f"the number of members must lie in 1 .. {MAX_MEMBERS}, got {S}")
-    if tuple(ens.shape[1:]) != tuple(obs.shape):
-        raise ValueError(f"ens: expected shape (S,) + {tuple(obs.shape)}, got {tuple(ens.shape)}")
     unknown = set(result_kw) - {"scales", "n_bins", "seed"}
     if unknown:
         raise ValueError(f"unknown arguments {sorted(unknown)}")
@@ -234,21 +218,7 @@ def verify_field(gen, observed, n_scenarios, thresholds, scales=DEFAULT_SCALES, 
     thr = check_event_thresholds(thresholds)
     S, step = F._check_scenarios(n_scenarios, scenario_chunk, MAX_MEMBERS)
     wd, n_bins, rank_seed = check_scales(scales, S), _check_bins(n_bins, S), _check_seed(rank_seed)
-    dataset = hasattr(observed, "daily_plane")
-    obs = observed.data if dataset else observed
-    obs, _, shape = admit_array(obs, "observed")
-    if len(shape) not in (3, 4):
-        raise ValueError(f"observed must have shape (24, ny, nx) or (n_days, 24, ny, nx), got {shape}")
-    day_shape = shape[:-3] + shape[-2:]
-    if daily is not None and not isinstance(daily, torch.Tensor):
-        daily = np.asarray(daily)
-    if daily is not None and tuple(daily.shape) != day_shape:
-        raise ValueError(f"daily: expected shape {day_shape}, got {tuple(daily.shape)}")
-    # the checks of disaggregate on a stand-in of the daily map's shape: nothing has touched the device so far
-    req = F._check_request(gen, np.broadcast_to(np.float32(0), day_shape), S, overlap, latent_mode, latent, chunk, norm_scale)
-    ver = EnsembleVerifier(obs, thr)
-    with torch.cuda.device(ver.obs.device):
-        if daily is None:
-            daily = observed.daily_plane() if dataset else ver.obs.sum(dim=-3)
-        F._stream_scenarios(gen, req, daily, S, step, ver.add, overlap, latent_mode, seed, latent, chunk, norm_scale)
+    request = ObservedRequest(gen, observed, daily, lambda shape: None, S, overlap, latent_mode, latent, chunk, norm_scale)
+    ver = EnsembleVerifier(request.obs, thr)
+    request.stream(ver.obs, step, ver.add, seed)
     return ver.result(scales=wd, n_bins=n_bins, seed=rank_seed)
