@@ -1022,6 +1022,37 @@ long rdgan_mv_variogram_workspace_bytes(long n_days, long ny, long nx, int radiu
 int rdgan_mv_variogram(const float* ens, const float* obs, long m, long n_days, long ny, long nx, int shared, double p, int radius,
                        int max_lag, double* sq_out, long long* count_out, void* workspace, long workspace_bytes, void* stream);
 
+/* Multivariate rank histograms: the pre-ranks of the observed day among the members of an ensemble of whole
+ * hourly days -- average rank and band depth (Thorarinsdottir, Scheuerer & Heinz 2016) and the leave-one-out minimum spanning tree
+ * (Smith & Hansen 2004; Wilks 2004).  Everything is an integer.
+ * A case is z_0 = the observation y [24][ny][nx] and z_1 .. z_m = the members x [m][24][ny][nx], fp32, N = m + 1, 1 <= m <= 4095.  A
+ * position is VALID when all N values are finite there (a NaN or an infinity of the observation or of any member leaves it out).
+ * Per valid position and per i, comparing in fp32 (-0.0 == 0.0): lt_i = the number of j with z_j < z_i, gt_i those with z_j > z_i.
+ * shared = 0: ens [n_days][m][24][ny][nx]; shared = 1: ens [m][24][ny][nx], one ensemble for all days.  obs [n_days][24][ny][nx].
+ * 1 <= n_days <= 2^20, 1 <= ny nx <= 2^24, N 24 ny nx <= 2^40 and at most 2^40 ensemble values per call.  All buffers lie on the
+ * device, dense; ens and obs 4-byte aligned, the outputs and the workspace 8-byte aligned.
+ * rdgan_mvr_ranks: sums_out [n_days][24][N][2], 64-bit, index 0 of N the observation: per hour h, [i][0] = the sum over the hour's
+ * valid positions of lt_i - gt_i + N + 1 (twice the mid-rank of z_i, so ties need no randomness) and [i][1] = the sum of
+ * (N - 1)(N - 2) - lt_i (lt_i - 1) - gt_i (gt_i - 1) (twice the number of pairs of the other vectors whose closed interval holds
+ * z_i: the band depth; low is outlying).  n_valid_out [n_days][24], 64-bit: the hour's valid positions.  Both are written, not added
+ * to; the caller adds the hours for the day.  A position whose N values are all equal adds N + 1 and (N - 1)(N - 2) to every i in
+ * closed form; the result is the same with and without that shortcut.  position_runs: into how many runs the tiles of positions
+ * of a plane are cut, one workgroup each; 0 leaves the choice to the entry (about 2048 workgroups a launch).  The result does not
+ * depend on it: integer sums met by 64-bit integer atomics.  workspace: 8-byte aligned, rdgan_mvr_ranks_workspace_bytes(m, n_days,
+ * shared) bytes (-2 for an argument out of range); nothing is kept in it today.
+ * rdgan_mvr_mst: dist [n][n] 64-bit, symmetric, 0 <= entries < 2^40 (what rdgan_red_distances writes for Pf 65535 < 2^40; the
+ * caller checks), 1 <= n <= 4096.  len_out [n], 64-bit: len[i] = the length of the minimum spanning tree of the n - 1 vertices other
+ * than i (Prim's algorithm, one workgroup per i); 0 for n <= 2.  The weights are integers, so the length does not depend on the
+ * order in which equal edges are taken.  Outside the precondition the result is not the defined one, but every access stays in
+ * range.
+ * Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, a size outside the limits above, shared
+ * not 0 or 1, position_runs < 0, a workspace too small, more than 2^31 - 1 workgroups) with nothing launched and no output touched.
+ * All offsets are 64-bit. */
+long rdgan_mvr_ranks_workspace_bytes(long m, long n_days, int shared);
+int rdgan_mvr_ranks(const float* ens, const float* obs, long m, long n_days, long ny, long nx, int shared, int position_runs,
+                    long long* sums_out, long long* n_valid_out, void* workspace, long workspace_bytes, void* stream);
+int rdgan_mvr_mst(const long long* dist, long n, long long* len_out, void* stream);
+
 /* Random-cascade baseline: the microcanonical multiplicative cascade (Olsson 1998; Guentner et al. 2001) with
  * the three-way first split of a 24-hour day (Mueller & Haberlandt 2015).  rdgan_cascade_accumulate counts, over observed hourly
  * data, how a wet box of rain splits into its parts; the caller turns the counts into a table of thresholds; rdgan_cascade_generate

@@ -16,6 +16,8 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
   * ``catchments`` -- catchment rainfall: the hyetograph of every basin of a map and its largest k-hour accumulation per day
   * ``analog`` -- the analog baseline (method of fragments): the k nearest library days of a daily condition, their scaled fractions
   * ``multivariate`` -- energy and variogram score of ensembles of whole hourly days; the four-method experiment
+  * ``multivariate_ranks`` -- multivariate rank histograms of such ensembles: average-rank, band-depth and minimum-spanning-tree
+    pre-ranks of the observed day, the observation's rank and the reliability index
   * ``cascade`` -- the random-cascade baseline: splits of wet boxes calibrated on hourly data, applied to daily sums 24 h -> 1 h
   * ``sequence`` -- chaining scenarios across midnight: seam costs between the members of neighbouring days, the cheapest single
     series, a greedy matching into continuous series
@@ -25,3 +27,4 @@ from . import weights  # noqa: F401
 from . import field_products  # noqa: F401
 from . import verification  # noqa: F401
 from . import multivariate  # noqa: F401
+from . import multivariate_ranks  # noqa: F401

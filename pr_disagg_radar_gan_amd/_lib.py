@@ -167,6 +167,10 @@ SIGNATURES = {
                                            ctypes.c_void_p, ctypes.c_void_p, c_stream]),
     "rdgan_red_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),
+    "rdgan_mvr_ranks_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_int]),
+    "rdgan_mvr_ranks": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),
+    "rdgan_mvr_mst": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_stream]),
     "rdgan_mv_energy_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_int]),
     "rdgan_mv_energy": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),

@@ -1780,3 +1780,61 @@ extern "C" int rdgan_red_select(const long long* dist, long n_members, long k, i
   hipLaunchKernelGGL(k_red_assign, per_member, dim3(256), 0, st, dist, S, (int)k, (const int*)chosen_out, assign_out, counts_out);
   return (int)hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------
+// multivariate rank histograms (rdgan_mvrank.hip.h): the sums behind the average-rank and band-depth pre-ranks, leave-one-out MST lengths
+// ------------------------------------------------------------------------------------
+// N = m + 1 vectors (the observation and the members) of 24 ny nx values: N 24 ny nx within RD_HOURLY_MAXELEMS
+static bool rd_mvr_shape_ok(long m, long n_days, long ny, long nx, int shared) {
+  if (m < 1 || m > RD_MVR_MAXM || n_days < 1 || n_days > RD_MVR_MAXDAYS || (shared != 0 && shared != 1)) return false;
+  if (ny < 1 || nx < 1 || ny > RD_HOURLY_MAXPLANE || nx > RD_HOURLY_MAXPLANE || ny * nx > RD_HOURLY_MAXPLANE) return false;
+  if (m + 1 > RD_HOURLY_MAXELEMS / (RD_HOURS * ny * nx)) return false;
+  return (shared ? 1 : n_days) * m <= RD_HOURLY_MAXELEMS / (RD_HOURS * ny * nx);
+}
+
+// nothing is kept between the launches of a call today: the size is the least a caller may pass
+extern "C" long rdgan_mvr_ranks_workspace_bytes(long m, long n_days, int shared) {
+  if (!rd_mvr_shape_ok(m, n_days, 1, 1, shared)) return -2;
+  return 8;
+}
+
+template <int TP>
+static int rd_mvr_ranks_launch(const float* ens, const float* obs, long N, long n_days, long P, int shared, int position_runs,
+                               long long* sums_out, long long* n_valid_out, hipStream_t st) {
+  const long planes = n_days * RD_HOURS, tiles = (P + TP - 1) / TP;
+  // the tiles of a plane are cut into position_runs runs, or, left to the entry (0), into as many as bring the launch to about
+  // RD_MVR_TARGET_BLOCKS workgroups; never more than there are tiles
+  long runs = std::min<long>(tiles, position_runs ? position_runs : std::max<long>(1, (RD_MVR_TARGET_BLOCKS + planes - 1) / planes));
+  const long per_run = (tiles + runs - 1) / runs;
+  runs = (tiles + per_run - 1) / per_run;
+  if (planes * runs > 0x7FFFFFFFL) return -2;
+  const size_t lds = (size_t)rd_mvr_lds_bytes(N);
+  RD_TRY(ensure_lds(nullptr, (const void*)k_mvr_ranks<TP>, lds));
+  RD_TRY((int)hipMemsetAsync(sums_out, 0, (size_t)(planes * N * 2) * 8, st));
+  RD_TRY((int)hipMemsetAsync(n_valid_out, 0, (size_t)planes * 8, st));
+  hipLaunchKernelGGL(k_mvr_ranks<TP>, dim3((unsigned)(planes * runs)), dim3(RD_MVR_THREADS), lds, st, ens, obs, (int)N,
+                     shared ? 0L : (N - 1) * RD_HOURS * P, P, tiles, (int)runs, per_run, (unsigned long long*)sums_out,
+                     (unsigned long long*)n_valid_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rdgan_mvr_ranks(const float* ens, const float* obs, long m, long n_days, long ny, long nx, int shared, int position_runs,
+                               long long* sums_out, long long* n_valid_out, void* workspace, long workspace_bytes, void* stream) {
+  if (!ens || !obs || !sums_out || !n_valid_out || !workspace) return -2;
+  if (!rd_aligned(3, ens, obs) || !rd_aligned(7, sums_out, n_valid_out, workspace)) return -2;
+  if (!rd_mvr_shape_ok(m, n_days, ny, nx, shared) || position_runs < 0 || workspace_bytes < 8) return -2;
+  const long N = m + 1, P = ny * nx;
+  hipStream_t st = (hipStream_t)stream;
+  switch (rd_mvr_tp(N)) {
+    case 64: return rd_mvr_ranks_launch<64>(ens, obs, N, n_days, P, shared, position_runs, sums_out, n_valid_out, st);
+    case 32: return rd_mvr_ranks_launch<32>(ens, obs, N, n_days, P, shared, position_runs, sums_out, n_valid_out, st);
+    case 16: return rd_mvr_ranks_launch<16>(ens, obs, N, n_days, P, shared, position_runs, sums_out, n_valid_out, st);
+    default: return rd_mvr_ranks_launch<8>(ens, obs, N, n_days, P, shared, position_runs, sums_out, n_valid_out, st);
+  }
+}
+
+extern "C" int rdgan_mvr_mst(const long long* dist, long n, long long* len_out, void* stream) {
+  if (!dist || !len_out || !rd_aligned(7, dist, len_out) || n < 1 || n > RD_MVR_MAXN) return -2;
+  hipLaunchKernelGGL(k_mvr_mst, dim3((unsigned)n), dim3(RD_MVR_THREADS), 0, (hipStream_t)stream, dist, (int)n, len_out);
+  return (int)hipGetLastError();
+}
