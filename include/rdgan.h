@@ -759,6 +759,38 @@ int rdgan_areal_accumulate(const float* x, long n, long day_stride, long ny, lon
                            const int* widths, int n_widths, const double* levels, int n_levels, long long* counts_inout,
                            long long* depths_out, void* workspace, long workspace_bytes, void* stream);
 
+/* Scaling of hourly fields: how the variability of rain changes with the scale it is looked at -- moments and
+ * histograms of box sums over dyadic boxes and aligned windows of the day.
+ * hourly, n, day_stride, ny, nx and the size limits: as x for the areal entry above (ny nx <= 2^24); q(x) and the bad pixel-hours as
+ * there.  space_levels = A, 0 <= A <= 6 and 2^A <= min(ny, nx).  Space level a = 0 .. A: boxes of 2^a x 2^a pixels on the dyadic grid
+ * anchored at pixel (0, 0), only those wholly inside the plane (a rim narrower than 2^a is left out at level a and at no other).
+ * Time level b = 0 .. 4: the aligned windows of T = 1, 2, 4, 8, 24 hours of the day.  For a day, a level pair, a box and a window, R is
+ * the sum of q over the box and the window, R <= 24 * 2^33 < 2^38; a box-window that holds a bad pixel-hour is void.
+ * counts_inout [(A + 1) * 5 * 296 + 2] 64-bit integers (device); the record of (a, b) lies at (a * 5 + b) * 296 +
+ *     0       n_boxes: the valid box-windows
+ *     1       n_void: the void box-windows
+ *     2       n_wet: the valid box-windows with R > 0
+ *     3       sum1: the sum of R over the valid box-windows
+ *     4       sum2_hh: with R = h * 2^19 + l, l < 2^19, the sum of h^2
+ *     5       sum2_hl: the sum of h l
+ *     6       sum2_ll: the sum of l^2 (the second moment is 2^38 sum2_hh + 2^20 sum2_hl + sum2_ll, in integers of any width)
+ *     7       max_R: the largest R seen (a running maximum, not a sum)
+ *     8       hist[288]: valid box-windows by the bin of R -- bin 0: R = 0; R = 1 .. 7: bin R; otherwise, e = floor(log2 R),
+ *             bin 8 + 8 (e - 3) + ((R >> (e - 3)) & 7), which covers [(8 + m) << (e - 3), (9 + m) << (e - 3)); the last is 287
+ * then n_days_total at (A + 1) * 5 * 296 and n_bad, the bad pixel-hours of the planes (rims included), behind it; the state-count
+ * entry returns (A + 1) * 5 * 296 + 2, or -2 for A out of range.  The array ACCUMULATES over any number of calls; the caller zeroes
+ * it before the first.  Everything is an integer merged with integer atomics, so the state does not depend on how the days are split
+ * into calls, on the launch geometry or on whether the array admits 16-byte loads.
+ * workspace: device memory, 8-byte aligned; nothing is held in it, the workspace-bytes entry returns 8 (-2 for a shape or A out of
+ * range) and the accumulate entry asks for that much.
+ * Asynchronous on the stream; 0 = success, -2 = bad argument (a null or misaligned pointer, n, ny or nx < 1, a size above the
+ * limits, day_stride < 24 ny nx, A outside 0 .. 6 or 2^A > min(ny, nx), a workspace below 8 bytes) with nothing launched and no
+ * output touched.  All offsets are 64-bit. */
+long rdgan_scaling_state_count(int space_levels);
+long rdgan_scaling_workspace_bytes(long ny, long nx, int space_levels);
+int rdgan_scaling_accumulate(const float* hourly, long n, long day_stride, long ny, long nx, int space_levels, long long* counts_inout,
+                             void* workspace, long workspace_bytes, void* stream);
+
 /* Catchment rainfall of hourly fields: the areal rainfall of every basin of a map, hour by hour, its largest
  * k-hour accumulation per day, and statistics of those maxima over the days.
  * hourly, n, day_stride, ny, nx and the size limits: as x for rdgan_areal_accumulate above (ny nx <= 2^24); q(x) and the bad

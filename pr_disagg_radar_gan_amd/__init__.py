@@ -18,6 +18,8 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
   * ``multivariate`` -- energy and variogram score of ensembles of whole hourly days; the four-method experiment
   * ``multivariate_ranks`` -- multivariate rank histograms of such ensembles: average-rank, band-depth and minimum-spanning-tree
     pre-ranks of the observed day, the observation's rank and the reliability index
+  * ``scaling`` -- box moments over space and time: wet fraction, moments and histograms of the rain summed over dyadic boxes and
+    aligned windows, their scaling exponents and the box-counting dimension
   * ``cascade`` -- the random-cascade baseline: splits of wet boxes calibrated on hourly data, applied to daily sums 24 h -> 1 h
   * ``sequence`` -- chaining scenarios across midnight: seam costs between the members of neighbouring days, the cheapest single
     series, a greedy matching into continuous series

@@ -130,6 +130,10 @@ SIGNATURES = {
     "rdgan_areal_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,
                                               ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),
+    "rdgan_scaling_state_count": (ctypes.c_long, [ctypes.c_int]),
+    "rdgan_scaling_workspace_bytes": (ctypes.c_long, [ctypes.c_long, ctypes.c_long, ctypes.c_int]),
+    "rdgan_scaling_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_int,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_stream]),
     "rdgan_catchment_state_count": (ctypes.c_long, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "rdgan_catchment_workspace_bytes": (ctypes.c_long, [ctypes.c_int, ctypes.c_long]),
     "rdgan_catchment_accumulate": (ctypes.c_int, [c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,

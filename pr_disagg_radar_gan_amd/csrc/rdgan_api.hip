@@ -58,6 +58,7 @@
 #include "rdgan_assign.hip.h"
 #include "rdgan_reduce.hip.h"
 #include "rdgan_mvrank.hip.h"
+#include "rdgan_scaling.hip.h"
 #include "rdgan_handle.h"           // struct rdgan_handle by concern; RD_CHECK / RD_TRY, side_fork / side_join, ensure_lds, the profiling scopes
 #include "rdgan_slab_launch.h"      // one launcher per slab kernel of the bf16 storage mode
 

@@ -1044,6 +1044,42 @@ extern "C" int rdgan_catchment_accumulate(const float* hourly, long n, long day_
 }
 
 // ------------------------------------------------------------------------------------
+// scaling of hourly fields (rdgan_scaling.hip.h): moments and histograms of box sums over dyadic boxes and aligned windows
+// ------------------------------------------------------------------------------------
+static bool rd_sc_args_ok(long ny, long nx, int space_levels) {
+  return rd_ar_shape_ok(ny, nx) && space_levels >= 0 && space_levels <= RD_SC_MAXA && (1L << space_levels) <= std::min(ny, nx);
+}
+
+extern "C" long rdgan_scaling_state_count(int space_levels) {
+  if (space_levels < 0 || space_levels > RD_SC_MAXA) return -2;
+  return rd_sc_state_count(space_levels);
+}
+
+extern "C" long rdgan_scaling_workspace_bytes(long ny, long nx, int space_levels) {
+  return rd_sc_args_ok(ny, nx, space_levels) ? RD_SC_WORKSPACE : -2;
+}
+
+extern "C" int rdgan_scaling_accumulate(const float* hourly, long n, long day_stride, long ny, long nx, int space_levels,
+                                        long long* counts_inout, void* workspace, long workspace_bytes, void* stream) {
+  if (!hourly || !counts_inout || !workspace || !rd_aligned(7, counts_inout, workspace)) return -2;
+  if (!rd_sc_args_ok(ny, nx, space_levels) || workspace_bytes < RD_SC_WORKSPACE) return -2;
+  if (!rd_hourly_layout_ok(hourly, n, day_stride, RD_HOURS * ny * nx)) return -2;
+  const rd_sc_geo g = rd_sc_geometry(ny, nx, space_levels);
+  const long units = (n + g.G - 1) / g.G * g.nby * g.nbx;
+  // a side of 64 or more fills more than half of its blocks' side, a shorter one more than half of its share: the units of a call
+  // hold fewer than 4 pixels for each of the array's (the last collage apart), a workgroup's share stays below RD_SC_MAXUNITS
+  static_assert(4 * (RD_HOURLY_MAXELEMS / (RD_HOURS * RD_SC_TILE * RD_SC_TILE)) / RD_SC_MINGRID + 2 <= RD_SC_MAXUNITS, "32-bit LDS counters");
+  const unsigned blocks = (unsigned)std::min<long>(units, RD_SC_MINGRID);
+  if (rd_vec4_ok(hourly, nx, day_stride))
+    hipLaunchKernelGGL(k_scaling_tiles<4>, dim3(blocks), dim3(RD_SC_THREADS), 0, (hipStream_t)stream, hourly, n, day_stride, g, units,
+                       (unsigned long long*)counts_inout);
+  else
+    hipLaunchKernelGGL(k_scaling_tiles<1>, dim3(blocks), dim3(RD_SC_THREADS), 0, (hipStream_t)stream, hourly, n, day_stride, g, units,
+                       (unsigned long long*)counts_inout);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
 // space-time structure of hourly fields (rdgan_spacetime.hip.h): displaced wet/dry agreement and the best shift of hour pairs
 // ------------------------------------------------------------------------------------
 static bool rd_st_params_ok(int n_thresholds, int radius, int max_lag) {

@@ -203,6 +203,20 @@ def areal_extremes_field(daily, n_scenarios, windows=(1, 3, 6, 12, 24), widths=(
                                       scenario_chunk=scenario_chunk, overlap=overlap, latent_mode=latent_mode, norm_scale=norm_scale)
 
 
+def scaling_scenarios_field(daily, n_scenarios, space_levels=None, overlap=4, latent_mode="shared", scenario_chunk=16):
+    """The scaling structure of n_scenarios scenarios of a whole daily map (scaling.scaling_structure_field on the module's ``gen``
+    and ``norm_scale``): the moments, wet fraction and histogram of the rain summed over dyadic boxes of 1 .. 2^space_levels pixels a
+    side and aligned windows of 1, 2, 4, 8, 24 hours -- whether the generator's fields scale as radar fields do, or are too
+    intermittent at one hour or too smooth at a few pixels.  daily as generate_scenarios_field takes it; space_levels: 0 .. 6 (None:
+    the largest the map admits).  Returns a scaling.ScalingStats (numpy); scaling.compare sets it against the same statistics of
+    observed days.  The latent noise comes from the global numpy RNG as in generate_scenarios_field; the hourly scenarios are produced
+    scenario_chunk at a time and never held together."""
+    from . import scaling
+    daily = _daily_map(daily)
+    return scaling.scaling_structure_field(gen, daily, n_scenarios, space_levels, scenario_chunk=scenario_chunk, overlap=overlap,
+                                           latent_mode=latent_mode, norm_scale=norm_scale)
+
+
 def catchment_rainfall_field(daily, n_scenarios, cmap, windows=(1, 3, 6, 12, 24), levels=None, return_series=False, overlap=4,
                              latent_mode="shared", scenario_chunk=16):
     """The catchment rainfall of n_scenarios scenarios of a whole daily map (catchments.catchment_rainfall_field on the module's

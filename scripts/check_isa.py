@@ -56,6 +56,7 @@ NO_SPILL = re.compile(r"k_conv_gemm_f16|k_upconv_slab16|k_upconv2_slab16|k_d2_dg
                       r"k_storm_lift|k_storm_link|k_storm_resolve|k_storm_reduce|k_storm_days|"
                       r"k_areal_prefix|k_areal_boxes|k_areal_days|"
                       r"k_catch_sums|k_catch_days|"
+                      r"k_scaling_tiles|"
                       r"k_analog_features|k_analog_days|k_analog_query|k_analog_search|k_analog_merge|k_analog_apply|"
                       r"k_mv_valid|k_mv_energy|k_mv_energy_reduce|k_mv_variogram|k_mv_variogram_reduce|"
                       r"k_cascade_accumulate|k_cascade_generate|"
