@@ -15,7 +15,7 @@ Host-side mirror of the reference's Python surface over hand-written HIP kernels
   * ``areal`` -- depth-area-duration: the largest k-hour accumulation over any w x w box per day, and the areal reduction factor
   * ``catchments`` -- catchment rainfall: the hyetograph of every basin of a map and its largest k-hour accumulation per day
   * ``analog`` -- the analog baseline (method of fragments): the k nearest library days of a daily condition, their scaled fractions
-  * ``multivariate`` -- energy and variogram score of ensembles of whole hourly days; the four-method experiment
+  * ``multivariate`` -- energy and variogram score of ensembles of whole hourly days; their experiment over the roster of competing methods
   * ``multivariate_ranks`` -- multivariate rank histograms of such ensembles: average-rank, band-depth and minimum-spanning-tree
     pre-ranks of the observed day, the observation's rank and the reliability index
   * ``scaling`` -- box moments over space and time: wet fraction, moments and histograms of the rain summed over dyadic boxes and

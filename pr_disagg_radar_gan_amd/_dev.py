@@ -1,5 +1,5 @@
 """Host-side plumbing every module that calls the library shares: pointers and streams for ctypes, arrays brought to the device,
-workspace sizes, whole-number arguments.  Host code; nothing here touches the device but device_f32's upload."""
+workspace sizes, whole-number and flag arguments.  Host code; nothing here touches the device but device_f32's upload."""
 import ctypes
 
 import numpy as np
@@ -50,3 +50,10 @@ def whole_number(value, lo, hi, what, whole_floats=False):
     if not (ok and lo <= int(value) <= hi):
         raise ValueError(f"{what} must be a whole number in {lo} .. {hi}, got {value!r}")
     return int(value)
+
+
+def flag(value, name):
+    """bool(value) for a bool or numpy bool; ValueError otherwise"""
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"{name} must be True or False, got {value!r}")
+    return bool(value)

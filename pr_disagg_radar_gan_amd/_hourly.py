@@ -1,7 +1,8 @@
 """What the evaluations of hourly arrays share on the host: how an array (..., 24, ny, nx) is admitted -- kind, shape, layout --
 before any device call, the accumulator the single-array ones are (HourlyAccumulator) with its driver for whole daily fields
-(evaluate_field), the base of those that hold members against an observation (ObservedVerifier) with theirs (ObservedRequest), and
-the small quotients and summaries their statistics use."""
+(evaluate_field), the base of those that hold members against an observation (ObservedVerifier) with theirs (ObservedRequest), how an ensemble of
+whole days is admitted against observed days (admit_ensemble, the joint-field scores and ranks), and the small quotients and
+summaries their statistics use."""
 import warnings
 
 import numpy as np
@@ -9,7 +10,7 @@ import torch
 
 from . import _lib
 from . import field as F
-from ._dev import ptr as _p, stream as _stream, workspace_bytes
+from ._dev import device_f32, ptr as _p, stream as _stream, workspace_bytes
 from .engine import require_gpu
 
 NHOURS = 24                                                                  # RD_HOURS
@@ -136,6 +137,62 @@ def observation_on_device(obs, from_host):
     """the first device step of a verification: a host array goes to "cuda" as dense float32, a tensor is used where it lies"""
     require_gpu()
     return to_state_device(obs, True, "cuda") if from_host else obs.detach().contiguous()
+
+
+def shape_of(a, name):
+    """the shape of an input device_f32 will convert: a floating-point CUDA tensor or a numpy array of numbers (admit_array asks more)"""
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda:
+            raise ValueError(f"{name}: expected a CUDA tensor or a numpy array, got a torch tensor on the host")
+        if not a.dtype.is_floating_point:
+            raise ValueError(f"{name}: expected floating-point values")
+        return tuple(int(v) for v in a.shape)
+    a = np.asarray(a)
+    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"{name}: expected an array of numbers")
+    return tuple(int(v) for v in a.shape)
+
+
+def check_reals(reals, name="reals"):
+    """-> the shape of the observed days (D, 24, ny, nx) that a per-day loop runs over"""
+    shape = shape_of(reals, name)
+    if len(shape) != 4 or shape[1] != NHOURS or min(shape) < 1:
+        raise ValueError(f"{name}: expected shape (D, {NHOURS}, ny, nx) with no empty axis, got {shape}")
+    return shape
+
+
+def admit_ensemble(ens, obs, max_members, max_days, obs_is_a_vector=False):
+    """The shapes of an ensemble of whole days against observed days, host code: ens (m, 24, ny, nx) with obs (24, ny, nx) or
+    (D, 24, ny, nx) -- one shared ensemble -- or ens (D, m, 24, ny, nx) with obs (D, 24, ny, nx).  obs_is_a_vector: m + 1 vectors and
+    the call's members must stay within MAX_ELEMS values (otherwise the entry alone holds the members to it).  -> (m, D, ny, nx, shared)"""
+    es, os_ = shape_of(ens, "ens"), shape_of(obs, "obs")
+    if len(es) not in (4, 5) or es[-3] != NHOURS or min(es) < 1:
+        raise ValueError(f"ens: expected shape (m, {NHOURS}, ny, nx) or (D, m, {NHOURS}, ny, nx) with no empty axis, got {es}")
+    if len(os_) not in (3, 4) or min(os_) < 1 or os_[-3:] != es[-3:]:
+        raise ValueError(f"obs: expected shape ({NHOURS}, {es[-2]}, {es[-1]}) or (D, {NHOURS}, {es[-2]}, {es[-1]}), got {os_}")
+    m, ny, nx = es[-4], es[-2], es[-1]
+    D, shared = os_[0] if len(os_) == 4 else 1, len(es) == 4
+    if not shared and (len(os_) != 4 or es[0] != D):
+        raise ValueError(f"ens holds {es[0]} days, obs must have shape ({es[0]}, {NHOURS}, {ny}, {nx}), got {os_}")
+    if m > max_members:
+        raise ValueError(f"at most {max_members} members, got {m}")
+    if ny * nx > MAX_PLANE:
+        raise ValueError(f"a plane has {ny * nx} pixels, the limit is {MAX_PLANE}")
+    if D > max_days:
+        raise ValueError(f"at most {max_days} days per call, got {D}")
+    if obs_is_a_vector and max(m + 1, (1 if shared else D) * m) * NHOURS * ny * nx > MAX_ELEMS:
+        raise ValueError(f"{m} members of {NHOURS} x {ny} x {nx} values: at most {MAX_ELEMS} values per call")
+    return m, D, ny, nx, shared
+
+
+def ensemble_on_device(ens, obs):
+    """the first device step behind admit_ensemble: both as float32 on one device, a numpy array going where the other lies"""
+    require_gpu()
+    ens = device_f32(ens, "ens", obs.device if isinstance(obs, torch.Tensor) else None)
+    obs = device_f32(obs, "obs", ens.device)
+    if obs.device != ens.device:
+        raise ValueError(f"ens lies on {ens.device}, obs on {obs.device}")
+    return ens, obs
 
 
 def grow_workspace(owner, nbytes, device):

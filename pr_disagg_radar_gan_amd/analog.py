@@ -90,7 +90,7 @@ def _check_plane(ny, nx, what):
         raise ValueError(f"{what}: a plane has {ny * nx} pixels, the limit is {MAX_PLANE}")
 
 
-def _gather_tiles(dataset, ixs):
+def gather_tiles(dataset, ixs):
     """the raw mm/h tiles (n, 24, nd, nd) of the valid-tile rows ixs, as rainfarm.random_tiles gathers them, and their day indices"""
     nd, dev = dataset.ndomain, dataset.data.device
     ar, hours = torch.arange(nd, device=dev), torch.arange(NHOURS, device=dev)
@@ -146,7 +146,7 @@ class AnalogLibrary:
             ixs = np.random.randint(dataset.n_samples, size=whole_number(n, 1, MAX_LIBRARY, "n, unless None,"))
         if len(ixs) > MAX_LIBRARY:
             raise ValueError(f"the data set has {len(ixs)} valid tiles, a library holds {MAX_LIBRARY}")
-        tiles, days = _gather_tiles(dataset, ixs)
+        tiles, days = gather_tiles(dataset, ixs)
         return cls(tiles, groups=days)
 
     # ---- queries

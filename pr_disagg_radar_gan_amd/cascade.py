@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._dev import device_f32, host_ptr, ptr as _p, stream as _stream, whole_number
-from .analog import _gather_tiles
+from ._dev import device_f32, flag, host_ptr, ptr as _p, stream as _stream, whole_number
+from .analog import gather_tiles
 from ._hourly import MAX_ELEMS, MAX_PLANE, NHOURS, UNIT, HourlyAccumulator, admit, to_state_device
 from .engine import require_gpu
 from .ensemble import crps_ensemble_device
@@ -157,7 +157,7 @@ class CascadeModel:
             ixs = np.random.randint(dataset.n_samples, size=whole_number(n, 1, 1 << 40, "n, unless None,"))
         cal = CascadeCalibrator(edges)
         for i in range(0, len(ixs), 1 << 16):                                # (the gathered tiles of a chunk are held at once)
-            cal.add(_gather_tiles(dataset, ixs[i:i + (1 << 16)])[0])
+            cal.add(gather_tiles(dataset, ixs[i:i + (1 << 16)])[0])
         return cal.result()
 
     def save(self, path):
@@ -205,8 +205,7 @@ class CascadeModel:
         seed = whole_number(seed, 0, (1 << 64) - 1, "seed")
         first_member = whole_number(first_member, 0, 1 << 62, "first_member")
         patch = whole_number(patch, 1, MAX_PLANE, "patch")
-        if not isinstance(return_units, (bool, np.bool_)):
-            raise ValueError(f"return_units must be True or False, got {return_units!r}")
+        return_units = flag(return_units, "return_units")
         Q, ny, nx = self._check_cond(cond)
         first_query = whole_number(first_query, 0, (1 << 32) - Q, "first_query")
         if Q * S * NHOURS * ny * nx > MAX_ELEMS:

@@ -119,7 +119,7 @@ def rainfarm_crps_for_days(reals_precip, alpha, beta, n_members=1000, seed=None)
     rainfarm.crps_for_day(reals_precip[0], alpha, beta, n_members, seed) bit for bit; without one the phases come from the global
     numpy RNG in R's order."""
     shape = _check_days(reals_precip, "reals_precip")
-    rainfarm._check_nd(shape[2])
+    rainfarm.check_nd(shape[2])
     if int(n_members) < 1 or int(n_members) > MAX_MEMBERS:
         raise ValueError(f"1 .. {MAX_MEMBERS} members per day, got {n_members}")
     require_gpu()

@@ -1238,11 +1238,7 @@ extern "C" int rdgan_analog_apply(const float* lib, long n, long day_stride, lon
 // ------------------------------------------------------------------------------------
 // joint-field scores (rdgan_mvscore.hip.h): the sums of the energy score and the tables of the variogram score
 // ------------------------------------------------------------------------------------
-static bool rd_mv_shape_ok(long m, long n_days, long ny, long nx, int shared) {
-  if (m < 1 || m > RD_MV_MAXM || n_days < 1 || n_days > RD_MV_MAXDAYS || (shared != 0 && shared != 1)) return false;
-  if (ny < 1 || nx < 1 || ny > RD_HOURLY_MAXPLANE || nx > RD_HOURLY_MAXPLANE || ny * nx > RD_HOURLY_MAXPLANE) return false;
-  return (shared ? 1 : n_days) * m <= RD_HOURLY_MAXELEMS / (RD_HOURS * ny * nx);
-}
+static bool rd_mv_shape_ok(long m, long D, long ny, long nx, int shared) { return rd_ensemble_shape_ok(m, D, ny, nx, shared, RD_MV_MAXM, RD_MV_MAXDAYS, 0); }
 // workgroups of the largest launch of an energy call
 static long rd_mv_energy_blocks(long m, long n_days, int shared) {
   if (!shared) return n_days * rd_mv_tile_pairs(rd_mv_tiles(m + 1));
@@ -1821,12 +1817,7 @@ extern "C" int rdgan_red_select(const long long* dist, long n_members, long k, i
 // multivariate rank histograms (rdgan_mvrank.hip.h): the sums behind the average-rank and band-depth pre-ranks, leave-one-out MST lengths
 // ------------------------------------------------------------------------------------
 // N = m + 1 vectors (the observation and the members) of 24 ny nx values: N 24 ny nx within RD_HOURLY_MAXELEMS
-static bool rd_mvr_shape_ok(long m, long n_days, long ny, long nx, int shared) {
-  if (m < 1 || m > RD_MVR_MAXM || n_days < 1 || n_days > RD_MVR_MAXDAYS || (shared != 0 && shared != 1)) return false;
-  if (ny < 1 || nx < 1 || ny > RD_HOURLY_MAXPLANE || nx > RD_HOURLY_MAXPLANE || ny * nx > RD_HOURLY_MAXPLANE) return false;
-  if (m + 1 > RD_HOURLY_MAXELEMS / (RD_HOURS * ny * nx)) return false;
-  return (shared ? 1 : n_days) * m <= RD_HOURLY_MAXELEMS / (RD_HOURS * ny * nx);
-}
+static bool rd_mvr_shape_ok(long m, long D, long ny, long nx, int shared) { return rd_ensemble_shape_ok(m, D, ny, nx, shared, RD_MVR_MAXM, RD_MVR_MAXDAYS, 1); }
 
 // nothing is kept between the launches of a call today: the size is the least a caller may pass
 extern "C" long rdgan_mvr_ranks_workspace_bytes(long m, long n_days, int shared) {

@@ -1,7 +1,7 @@
 // What the evaluations of an hourly array (..., 24, ny, nx) share on the host: the plain constants (rdgan_hourly.hip.h adds the
 // device helpers on top of them), and what the accumulate entries (rdgan_eval_entries.h: temporal, cells, storms, areal, catchment,
 // space-time, cascade) check and size the same way: the layout of the array, the 16-byte route, the levels in units, the units of a
-// pass.  Host-only and free of HIP: a plain C++ compiler builds this header on its own (tests/test_hourly_host.py does).
+// pass; and how the joint-field scores and the rank histograms admit an ensemble against observed days.  Host-only and free of HIP: a plain C++ compiler builds this header on its own (tests/test_hourly_host.py does).
 #pragma once
 #include <math.h>
 
@@ -26,6 +26,15 @@ static bool rd_day_stride_ok(long n, long day_stride, long day_elems) {
 // the array an accumulate entry reads: x on 4 bytes, 1 <= n days of day_elems >= 1 elements each, at most RD_HOURLY_MAXELEMS in all
 static bool rd_hourly_layout_ok(const void* x, long n, long day_stride, long day_elems) {
   return rd_aligned(3, x) && day_elems >= 1 && n >= 1 && n <= RD_HOURLY_MAXELEMS / day_elems && rd_day_stride_ok(n, day_stride, day_elems);
+}
+
+// an ensemble of 1 <= m <= max_m members against 1 <= n_days <= max_days observed days of 24 ny nx values, shared by the days or one
+// per day: the call's members, and m + extra vectors (the ranks count the observation in: 1), within RD_HOURLY_MAXELEMS
+static bool rd_ensemble_shape_ok(long m, long n_days, long ny, long nx, int shared, long max_m, long max_days, long extra) {
+  if (m < 1 || m > max_m || n_days < 1 || n_days > max_days || (shared != 0 && shared != 1)) return false;
+  if (ny < 1 || nx < 1 || ny > RD_HOURLY_MAXPLANE || nx > RD_HOURLY_MAXPLANE || ny * nx > RD_HOURLY_MAXPLANE) return false;
+  const long held = RD_HOURLY_MAXELEMS / (RD_HOURS * ny * nx);
+  return m + extra <= held && (shared ? 1 : n_days) * m <= held;
 }
 
 // 16-byte loads of four adjacent values (rd_load<4>): every row of every day starts on 16 bytes, rows being `row` elements apart

@@ -15,13 +15,10 @@ from typing import Dict
 import numpy as np
 import torch
 
-from . import _lib, crps_experiment, ensemble, rainfarm
-from . import weights as W
-from ._dev import device_f32, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from .analog import AnalogLibrary
-from ._hourly import MAX_PLANE, NHOURS
-from .cascade import CascadeModel
-from .engine import require_gpu
+from . import _lib, crps_experiment
+from ._dev import flag, ptr as _p, stream as _stream, whole_number, workspace_bytes
+from ._experiment import competing_methods, for_each_day, gan_ensemble     # noqa: F401 (gan_ensemble is public here)
+from ._hourly import MAX_PLANE, NHOURS, admit_ensemble, ensemble_on_device  # noqa: F401 (the two limits are public here)
 
 MAX_MEMBERS = crps_experiment.MAX_MEMBERS                                    # RD_MV_MAXM
 MAX_DAYS = 1 << 20                                                           # RD_MV_MAXDAYS
@@ -83,48 +80,9 @@ def check_weights(weights, radius, max_lag):
     return w * (default_weights(r, L) > 0)
 
 
-def _shape_of(a, name):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError(f"{name}: expected a CUDA tensor or a numpy array, got a torch tensor on the host")
-        if not a.dtype.is_floating_point:
-            raise ValueError(f"{name}: expected floating-point values")
-        return tuple(int(v) for v in a.shape)
-    a = np.asarray(a)
-    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
-        raise ValueError(f"{name}: expected an array of numbers")
-    return tuple(int(v) for v in a.shape)
-
-
 def admit(ens, obs):
-    """The shapes of a call, host code: ens (m, 24, ny, nx) with obs (24, ny, nx) or (D, 24, ny, nx) -- one shared ensemble -- or
-    ens (D, m, 24, ny, nx) with obs (D, 24, ny, nx).  -> (m, D, ny, nx, shared)"""
-    es, os_ = _shape_of(ens, "ens"), _shape_of(obs, "obs")
-    if len(es) not in (4, 5) or es[-3] != NHOURS or min(es) < 1:
-        raise ValueError(f"ens: expected shape (m, {NHOURS}, ny, nx) or (D, m, {NHOURS}, ny, nx) with no empty axis, got {es}")
-    if len(os_) not in (3, 4) or min(os_) < 1 or os_[-3:] != es[-3:]:
-        raise ValueError(f"obs: expected shape ({NHOURS}, {es[-2]}, {es[-1]}) or (D, {NHOURS}, {es[-2]}, {es[-1]}), got {os_}")
-    m, ny, nx = es[-4], es[-2], es[-1]
-    D = os_[0] if len(os_) == 4 else 1
-    shared = len(es) == 4
-    if not shared and (len(os_) != 4 or es[0] != D):
-        raise ValueError(f"ens holds {es[0]} days, obs must have shape ({es[0]}, {NHOURS}, {ny}, {nx}), got {os_}")
-    if m > MAX_MEMBERS:
-        raise ValueError(f"at most {MAX_MEMBERS} members, got {m}")
-    if ny * nx > MAX_PLANE:
-        raise ValueError(f"a plane has {ny * nx} pixels, the limit is {MAX_PLANE}")
-    if D > MAX_DAYS:
-        raise ValueError(f"at most {MAX_DAYS} days per call, got {D}")
-    return m, D, ny, nx, shared
-
-
-def _on_device(ens, obs):
-    require_gpu()
-    ens = device_f32(ens, "ens", obs.device if isinstance(obs, torch.Tensor) else None)
-    obs = device_f32(obs, "obs", ens.device)
-    if obs.device != ens.device:
-        raise ValueError(f"ens lies on {ens.device}, obs on {obs.device}")
-    return ens, obs
+    """_hourly.admit_ensemble with the limits of the scores: at most 8192 members, 2^20 days.  -> (m, D, ny, nx, shared)"""
+    return admit_ensemble(ens, obs, MAX_MEMBERS, MAX_DAYS)
 
 
 def _workspace(lib, dev, entry, *args):
@@ -141,7 +99,7 @@ def energy_terms(ens, obs):
     every day of obs, its member distances computed once -- or (D, m, 24, ny, nx); obs (24, ny, nx) or (D, 24, ny, nx); numpy or
     CUDA.  Two calls agree bit for bit; a day's sums do not depend on the other days of the call."""
     m, D, ny, nx, shared = admit(ens, obs)
-    ens, obs = _on_device(ens, obs)
+    ens, obs = ensemble_on_device(ens, obs)
     lib, dev = _lib.load(), ens.device
     obs_sum = torch.empty(D, dtype=torch.float64, device=dev)
     pair_sum = torch.empty(D, dtype=torch.float64, device=dev)
@@ -161,11 +119,9 @@ def energy_from_terms(obs_sum, pair_sum, m, fair=False):
 
 def energy_score(ens, obs, fair=False):
     """The energy score per day, a float64 CUDA tensor (D,); arguments as energy_terms.  NaN for a day without a valid position."""
-    if not isinstance(fair, (bool, np.bool_)):
-        raise ValueError(f"fair must be True or False, got {fair!r}")
-    m = admit(ens, obs)[0]
+    fair, m = flag(fair, "fair"), admit(ens, obs)[0]
     obs_sum, pair_sum = energy_terms(ens, obs)
-    return energy_from_terms(obs_sum, pair_sum, m, bool(fair))
+    return energy_from_terms(obs_sum, pair_sum, m, fair)
 
 
 def variogram_score(ens, obs, p=0.5, radius=2, max_lag=1, weights=None, normalised=False, return_tables=False):
@@ -178,7 +134,7 @@ def variogram_score(ens, obs, p=0.5, radius=2, max_lag=1, weights=None, normalis
     p, r, L = check_order(p), check_radius(radius), check_max_lag(max_lag)
     w = check_weights(weights, r, L)
     m, D, ny, nx, shared = admit(ens, obs)
-    ens, obs = _on_device(ens, obs)
+    ens, obs = ensemble_on_device(ens, obs)
     lib, dev = _lib.load(), ens.device
     side = 2 * r + 1
     sq = torch.empty((D, L + 1, side, side), dtype=torch.float64, device=dev)
@@ -198,33 +154,15 @@ def variogram_score(ens, obs, p=0.5, radius=2, max_lag=1, weights=None, normalis
 # ---------------------------------------------------------------------------------------------------------------------------------
 # many days, one ensemble in memory at a time
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _check_reals(reals, name="reals"):
-    shape = _shape_of(reals, name)
-    if len(shape) != 4 or shape[1] != NHOURS or min(shape) < 1:
-        raise ValueError(f"{name}: expected shape (D, {NHOURS}, ny, nx) with no empty axis, got {shape}")
-    return shape
-
-
 def scores_for_days(make_ensemble, reals, fair=False, p=0.5, radius=2, max_lag=1, weights=None, normalised=False):
     """reals (D, 24, ny, nx), numpy or CUDA; make_ensemble(d) -> day d's (m, 24, ny, nx) ensemble, which is scored against
     reals[d] and dropped before the next one is made: the m 24 ny nx floats exist for one day at a time.  -> (es, vs), numpy
     float64 (D,)."""
-    if not callable(make_ensemble):
-        raise ValueError("make_ensemble must be callable")
-    if not isinstance(fair, (bool, np.bool_)):
-        raise ValueError(f"fair must be True or False, got {fair!r}")
-    shape = _check_reals(reals)
-    p, r, L = check_order(p), check_radius(radius), check_max_lag(max_lag)
+    fair, p, r, L = flag(fair, "fair"), check_order(p), check_radius(radius), check_max_lag(max_lag)
     w = check_weights(weights, r, L)
-    require_gpu()
-    reals = device_f32(reals, "reals")
-    es, vs = [], []
-    for d in range(shape[0]):
-        ens = make_ensemble(d)
-        es.append(energy_score(ens, reals[d], fair=fair))
-        vs.append(variogram_score(ens, reals[d], p=p, radius=r, max_lag=L, weights=w, normalised=normalised))
-        del ens
-    return torch.cat(es).cpu().numpy(), torch.cat(vs).cpu().numpy()
+    days = for_each_day(make_ensemble, reals, lambda d, ens, real: (
+        energy_score(ens, real, fair=fair), variogram_score(ens, real, p=p, radius=r, max_lag=L, weights=w, normalised=normalised)))
+    return tuple(torch.cat(part).cpu().numpy() for part in zip(*days))
 
 
 @dataclass
@@ -250,65 +188,17 @@ class MultivariateExperimentResult:
         return out
 
 
-def gan_ensemble(gen, real, n_members, seed=None, norm_scale=W.NORM_SCALE):
-    """The generator's ensemble for one real day (24, nd, nd) on the host, in mm/h: the fractions of
-    ensemble.generate_ensemble_device times the condition, as crps_experiment.crps_for_days scales them"""
-    dsum = real.sum(0)
-    fractions = ensemble.generate_ensemble_device(gen, (dsum / norm_scale).numpy()[..., None], n_members, seed=seed)
-    return fractions * (dsum / norm_scale * norm_scale).to(fractions.device)
-
-
 def multivariate_experiment(gen, reals_precip, climatology, slopes=None, library=None, n_members=1000, seed=0, fair=False, p=0.5,
                             radius=2, max_lag=1, weights=None, normalised=False, k=10, analog_weights="rank", query_groups=None, cascade=None,
                             cascade_patch=1):
     """Energy and variogram score per real day for the competing methods.  reals_precip (D, 24, nd, nd) mm/h; climatology
-    (n, 24, nd, nd), e.g. crps_experiment.climatology_sample(dataset), scored in the shared form.  Seed rules, those of the CRPS
-    experiment: the GAN's day d uses the device generator seeded seed + d (crps_experiment.crps_for_days); RainFARM, with slopes =
-    (alpha, beta), draws the members d n_members .. (d + 1) n_members - 1 of the counter RNG (rainfarm_crps_for_days); the analog
-    baseline, with library = an AnalogLibrary, is library.generate(daily sum of day d, n_members, k, seed, analog_weights,
-    first_query=d), query_groups (D,) leaving the library's days of the same group out; the random cascade, with cascade = a
-    cascade.CascadeModel, is cascade.generate(daily sum of day d, n_members, seed, first_query=d, patch=cascade_patch) and adds
-    es["cascade"] and vs["cascade"].  -> MultivariateExperimentResult."""
-    shape = _check_reals(reals_precip, "reals_precip")
-    cs = _check_reals(climatology, "climatology")
-    if shape[2] != shape[3] or cs[1:] != shape[1:] or cs[0] > MAX_MEMBERS:
-        raise ValueError(f"reals_precip (D, {NHOURS}, nd, nd) and climatology (n <= {MAX_MEMBERS}, {NHOURS}, nd, nd) expected, got {shape} and {cs}")
-    if slopes is not None:
-        if len(slopes) != 2:
-            raise ValueError("slopes must be (alpha, beta)")
-        rainfarm._check_nd(shape[2])
-    if library is not None and (not isinstance(library, AnalogLibrary) or tuple(library.plane_shape) != shape[2:]):
-        raise ValueError(f"library: expected an AnalogLibrary of planes {shape[2:]}")
-    if query_groups is not None and (library is None or len(query_groups) != shape[0]):
-        raise ValueError(f"query_groups: {shape[0]} groups and a library expected")
-    if cascade is not None and not isinstance(cascade, CascadeModel):
-        raise ValueError("cascade: expected a cascade.CascadeModel")
-    cascade_patch = whole_number(cascade_patch, 1, MAX_PLANE, "cascade_patch")
-    m = whole_number(n_members, 1, MAX_MEMBERS, "n_members")
-    seed = whole_number(seed, 0, (1 << 62), "seed")
-    score = dict(fair=fair, p=check_order(p), radius=check_radius(radius), max_lag=check_max_lag(max_lag),
-                 weights=check_weights(weights, radius, max_lag), normalised=normalised)
-    if not isinstance(fair, (bool, np.bool_)):
-        raise ValueError(f"fair must be True or False, got {fair!r}")
-    require_gpu()
-    reals = device_f32(reals_precip, "reals_precip")
-    reals_host = reals.cpu()                                                 # the GAN's daily sums are taken on the host, as crps_for_days does
-    res = MultivariateExperimentResult()
-    res.es["gan"], res.vs["gan"] = scores_for_days(lambda d: gan_ensemble(gen, reals_host[d], m, seed=seed + d), reals, **score)
-    clim = device_f32(climatology, "climatology", reals.device)
-    vs_score = {key: v for key, v in score.items() if key != "fair"}
-    res.es["random"] = energy_score(clim, reals, fair=fair).cpu().numpy()
-    res.vs["random"] = variogram_score(clim, reals, **vs_score).cpu().numpy()
-    if slopes is not None:
-        alpha, beta = float(slopes[0]), float(slopes[1])
-        res.es["rainfarm"], res.vs["rainfarm"] = scores_for_days(
-            lambda d: rainfarm.downscale_device(reals[d].sum(0), alpha, beta, n_members=m, seed=seed, first_member=d * m), reals, **score)
-    if library is not None:
-        groups = None if query_groups is None else np.asarray(query_groups)
-        res.es["analog"], res.vs["analog"] = scores_for_days(
-            lambda d: library.generate(reals[d:d + 1].sum(1), m, k=k, seed=seed, weights=analog_weights, first_query=d,
-                                       query_groups=None if groups is None else groups[d:d + 1])[0], reals, **score)
-    if cascade is not None:
-        res.es["cascade"], res.vs["cascade"] = scores_for_days(
-            lambda d: cascade.generate(reals[d:d + 1].sum(1), m, seed=seed, first_query=d, patch=cascade_patch)[0], reals, **score)
-    return res
+    (n, 24, nd, nd), e.g. crps_experiment.climatology_sample(dataset), scored in the shared form as es["random"]; es["gan"] always,
+    es["rainfarm"] / es["analog"] / es["cascade"] with slopes / a library / a cascade model; vs likewise.  The methods' arguments
+    and the seed rules that make day d's ensemble are _experiment.competing_methods'.  -> MultivariateExperimentResult."""
+    fair, p, r, L = flag(fair, "fair"), check_order(p), check_radius(radius), check_max_lag(max_lag)
+    score = dict(p=p, radius=r, max_lag=L, weights=check_weights(weights, r, L), normalised=normalised)
+    roster = competing_methods(gen, reals_precip, climatology, max_members=MAX_MEMBERS, slopes=slopes, library=library, n_members=n_members,
+                               seed=seed, k=k, analog_weights=analog_weights, query_groups=query_groups, cascade=cascade, cascade_patch=cascade_patch)
+    both = roster.run(lambda make: scores_for_days(make, roster.reals, fair=fair, **score),
+                      lambda clim, reals: (energy_score(clim, reals, fair=fair).cpu().numpy(), variogram_score(clim, reals, **score).cpu().numpy()))
+    return MultivariateExperimentResult({name: es for name, (es, _) in both.items()}, {name: vs for name, (_, vs) in both.items()})

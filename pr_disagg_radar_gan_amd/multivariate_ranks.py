@@ -33,12 +33,11 @@ from typing import Dict, Tuple
 import numpy as np
 import torch
 
-from . import _lib, multivariate as MV, rainfarm
+from . import _lib
 from . import reduction as R
-from ._dev import device_f32, ptr as _p, stream as _stream, whole_number, workspace_bytes
-from ._hourly import MAX_ELEMS, MAX_PLANE, NHOURS
-from .analog import AnalogLibrary
-from .cascade import CascadeModel
+from ._dev import device_f32, flag, ptr as _p, stream as _stream, whole_number, workspace_bytes
+from ._experiment import competing_methods, for_each_day
+from ._hourly import MAX_ELEMS, MAX_PLANE, NHOURS, admit_ensemble, ensemble_on_device, shape_of  # noqa: F401 (the limits are public here)
 from .engine import require_gpu
 
 MAX_VECTORS = 4096                                                           # RD_MVR_MAXN: the observation and the members
@@ -52,13 +51,8 @@ KINDS = ("average", "band_depth", "mst")
 # host: arguments
 # ---------------------------------------------------------------------------------------------------------------------------------
 def admit(ens, obs):
-    """multivariate.admit with the limits of the ranks: at most 4095 members, N 24 ny nx <= 2^40.  -> (m, D, ny, nx, shared)"""
-    m, D, ny, nx, shared = MV.admit(ens, obs)
-    if m > MAX_MEMBERS:
-        raise ValueError(f"at most {MAX_MEMBERS} members, got {m}")
-    if (m + 1) * NHOURS * ny * nx > MAX_ELEMS or (1 if shared else D) * m * NHOURS * ny * nx > MAX_ELEMS:
-        raise ValueError(f"{m} members of {NHOURS} x {ny} x {nx} values: at most {MAX_ELEMS} values per call")
-    return m, D, ny, nx, shared
+    """_hourly.admit_ensemble with the limits of the ranks: at most 4095 members, 2^20 days, N 24 ny nx <= 2^40.  -> (m, D, ny, nx, shared)"""
+    return admit_ensemble(ens, obs, MAX_MEMBERS, MAX_DAYS, obs_is_a_vector=True)
 
 
 def check_kinds(kinds, by_hour=False):
@@ -72,12 +66,6 @@ def check_kinds(kinds, by_hour=False):
     return kinds
 
 
-def _flag(value, name):
-    if not isinstance(value, (bool, np.bool_)):
-        raise ValueError(f"{name} must be True or False, got {value!r}")
-    return bool(value)
-
-
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the pre-ranks
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -87,10 +75,10 @@ def prerank_sums(ens, obs, by_hour=False, position_runs=None):
     for every day of obs -- or (D, m, 24, ny, nx); obs (24, ny, nx) (D = 1) or (D, 24, ny, nx); numpy or CUDA; members may hold NaN.
     position_runs: None, or into how many runs the tiles of positions of a plane are cut, one workgroup each; the result does not
     depend on it."""
-    by_hour = _flag(by_hour, "by_hour")
+    by_hour = flag(by_hour, "by_hour")
     runs = 0 if position_runs is None else whole_number(position_runs, 1, (1 << 31) - 1, "position_runs, unless None,")
     m, D, ny, nx, shared = admit(ens, obs)
-    ens, obs = MV._on_device(ens, obs)
+    ens, obs = ensemble_on_device(ens, obs)
     lib, dev = _lib.load(), ens.device
     with torch.cuda.device(dev):
         sums = torch.empty((D, NHOURS, m + 1, 2), dtype=torch.int64, device=dev)
@@ -116,7 +104,7 @@ def mst_leave_one_out(dist, check=True):
     """dist (N, N) int64 CUDA, symmetric, 0 <= entries < 2^40 -> (N,) int64 CUDA: entry i is the length of the minimum spanning tree of
     the vertices other than i; 0 for N <= 2.  check: the range of the entries is read back from the device first and a ValueError
     raised outside it; mst_preranks, whose features bound the distances by arithmetic, turns it off."""
-    check = _flag(check, "check")
+    check = flag(check, "check")
     dist, N = _check_dist(dist)
     require_gpu()
     lib, dev = _lib.load(), dist.device
@@ -144,7 +132,7 @@ def mst_preranks(ens_day, obs_day, pool=1):
     observation; n_valid, a 0-d int64 CUDA tensor).  The members and then the observation go through reduction.ScenarioFeatures at
     this pool (the observation is added last and read back as index 0), reduction.member_distances and the MST kernel."""
     pool = R.check_pool(pool)
-    es, os_ = MV._shape_of(ens_day, "ens_day"), MV._shape_of(obs_day, "obs_day")
+    es, os_ = shape_of(ens_day, "ens_day"), shape_of(obs_day, "obs_day")
     if len(es) != 4 or es[1] != NHOURS or min(es) < 1 or os_ != es[1:]:
         raise ValueError(f"ens_day (m, {NHOURS}, ny, nx) and obs_day ({NHOURS}, ny, nx) expected, got {es} and {os_}")
     m = es[0]
@@ -273,12 +261,12 @@ def multivariate_ranks(ens, obs, kinds=KINDS, by_hour=False, pool=1):
     """The observation's ranks for the D cases of a call -> MultivariateRanks.  ens and obs as prerank_sums.  by_hour: every (day,
     hour) is a case of its own (below, equal, n_valid of shape (D, 24)); the MST is of the whole day only, and asking for it with
     by_hour is a ValueError.  pool: of the MST's features."""
-    by_hour = _flag(by_hour, "by_hour")
+    by_hour = flag(by_hour, "by_hour")
     kinds, pool = check_kinds(kinds, by_hour), R.check_pool(pool)
     m, D, ny, nx, shared = admit(ens, obs)
     if "mst" in kinds:
         check_mst_admission(m + 1, R.n_positions((NHOURS, ny, nx), pool))
-    ens, obs = MV._on_device(ens, obs)
+    ens, obs = ensemble_on_device(ens, obs)
     return _collect(kinds, m, [_case_ranks(ens, obs, kinds, by_hour, pool, m, D, shared)])
 
 
@@ -286,65 +274,29 @@ def ranks_for_days(make_ensemble, reals, kinds=KINDS, by_hour=False, pool=1):
     """reals (D, 24, ny, nx), numpy or CUDA; make_ensemble(d) -> day d's (m, 24, ny, nx) ensemble, which is ranked against reals[d]
     and dropped before the next one is made, as multivariate.scores_for_days does: one ensemble is alive at a time.  Every day
     must bring the same number of members.  -> MultivariateRanks."""
-    if not callable(make_ensemble):
-        raise ValueError("make_ensemble must be callable")
-    by_hour = _flag(by_hour, "by_hour")
+    by_hour = flag(by_hour, "by_hour")
     kinds, pool = check_kinds(kinds, by_hour), R.check_pool(pool)
-    shape = MV._check_reals(reals)
-    require_gpu()
-    reals = device_f32(reals, "reals")
-    parts, m = [], None
-    for d in range(shape[0]):
-        ens = make_ensemble(d)
-        one = multivariate_ranks(ens, reals[d], kinds, by_hour, pool)
-        if m is not None and one.n_members != m:
-            raise ValueError(f"make_ensemble({d}) brought {one.n_members} members, the days before it {m}")
-        m = one.n_members
-        parts.append({k: (one.below[k], one.equal[k], one.n_valid[k]) for k in kinds})
-        del ens
-    return _collect(kinds, m, parts)
+    members = []
+
+    def per_day(d, ens, real):
+        one = multivariate_ranks(ens, real, kinds, by_hour, pool)
+        if members and one.n_members != members[-1]:
+            raise ValueError(f"make_ensemble({d}) brought {one.n_members} members, the days before it {members[-1]}")
+        members.append(one.n_members)
+        return {k: (one.below[k], one.equal[k], one.n_valid[k]) for k in kinds}
+
+    parts = for_each_day(make_ensemble, reals, per_day)
+    return _collect(kinds, members[0], parts)
 
 
 def multivariate_rank_experiment(gen, reals_precip, climatology, slopes=None, library=None, n_members=1000, seed=0, kinds=KINDS,
                                  by_hour=False, pool=1, k=10, analog_weights="rank", query_groups=None, cascade=None, cascade_patch=1):
     """The rank histograms of the competing methods over the real days: {method: MultivariateRanks} with "gan", "random" (the fixed
     climatological ensemble, ranked in the shared form) and "rainfarm" / "analog" / "cascade" where the experiment has slopes / a
-    library / a cascade model.  The arguments and the seed rules are those of multivariate.multivariate_experiment, the GAN's
-    ensemble multivariate.gan_ensemble: the two experiments see the same members.  n_members and the climatology: at most 4095."""
-    shape = MV._check_reals(reals_precip, "reals_precip")
-    cs = MV._check_reals(climatology, "climatology")
-    if shape[2] != shape[3] or cs[1:] != shape[1:] or cs[0] > MAX_MEMBERS:
-        raise ValueError(f"reals_precip (D, {NHOURS}, nd, nd) and climatology (n <= {MAX_MEMBERS}, {NHOURS}, nd, nd) expected, got {shape} and {cs}")
-    if slopes is not None:
-        if len(slopes) != 2:
-            raise ValueError("slopes must be (alpha, beta)")
-        rainfarm._check_nd(shape[2])
-    if library is not None and (not isinstance(library, AnalogLibrary) or tuple(library.plane_shape) != shape[2:]):
-        raise ValueError(f"library: expected an AnalogLibrary of planes {shape[2:]}")
-    if query_groups is not None and (library is None or len(query_groups) != shape[0]):
-        raise ValueError(f"query_groups: {shape[0]} groups and a library expected")
-    if cascade is not None and not isinstance(cascade, CascadeModel):
-        raise ValueError("cascade: expected a cascade.CascadeModel")
-    cascade_patch = whole_number(cascade_patch, 1, MAX_PLANE, "cascade_patch")
-    m = whole_number(n_members, 1, MAX_MEMBERS, "n_members")
-    seed = whole_number(seed, 0, (1 << 62), "seed")
-    by_hour = _flag(by_hour, "by_hour")
+    library / a cascade model.  The competitors, their arguments and their seed rules are those of _experiment.competing_methods, as in
+    multivariate.multivariate_experiment: the two experiments see the same members.  n_members and the climatology: at most 4095."""
+    by_hour = flag(by_hour, "by_hour")
     rank = dict(kinds=check_kinds(kinds, by_hour), by_hour=by_hour, pool=R.check_pool(pool))
-    require_gpu()
-    reals = device_f32(reals_precip, "reals_precip")
-    reals_host = reals.cpu()                                                 # the GAN's daily sums are taken on the host, as crps_for_days does
-    res = {"gan": ranks_for_days(lambda d: MV.gan_ensemble(gen, reals_host[d], m, seed=seed + d), reals, **rank)}
-    res["random"] = multivariate_ranks(device_f32(climatology, "climatology", reals.device), reals, **rank)
-    if slopes is not None:
-        alpha, beta = float(slopes[0]), float(slopes[1])
-        res["rainfarm"] = ranks_for_days(
-            lambda d: rainfarm.downscale_device(reals[d].sum(0), alpha, beta, n_members=m, seed=seed, first_member=d * m), reals, **rank)
-    if library is not None:
-        groups = None if query_groups is None else np.asarray(query_groups)
-        res["analog"] = ranks_for_days(
-            lambda d: library.generate(reals[d:d + 1].sum(1), m, k=k, seed=seed, weights=analog_weights, first_query=d,
-                                       query_groups=None if groups is None else groups[d:d + 1])[0], reals, **rank)
-    if cascade is not None:
-        res["cascade"] = ranks_for_days(
-            lambda d: cascade.generate(reals[d:d + 1].sum(1), m, seed=seed, first_query=d, patch=cascade_patch)[0], reals, **rank)
-    return res
+    roster = competing_methods(gen, reals_precip, climatology, max_members=MAX_MEMBERS, slopes=slopes, library=library, n_members=n_members,
+                               seed=seed, k=k, analog_weights=analog_weights, query_groups=query_groups, cascade=cascade, cascade_patch=cascade_patch)
+    return roster.run(lambda make: ranks_for_days(make, roster.reals, **rank), lambda clim, reals: multivariate_ranks(clim, reals, **rank))

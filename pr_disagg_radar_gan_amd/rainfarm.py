@@ -21,7 +21,7 @@ N_TCLASS = 13                   # |m| = 0 .. 12 of the 24-point DFT
 MAX_N = 1 << 24                 # samples / members per kernel call
 
 
-def _check_nd(nd):
+def check_nd(nd):
     if int(nd) not in ND_SUPPORTED:
         raise ValueError(f"ndomain {nd} is not covered by the RainFARM kernels {ND_SUPPORTED}")
     return int(nd)
@@ -33,7 +33,7 @@ def _check_nd(nd):
 def spectral_amplitudes(alpha, beta, nd, ds_t_factor=NHOURS):
     """(24, nd, nd) complex128: R:94-113's sqrt(om^-beta * k_sqr^-alpha/2) with om = 2 pi fftfreq(24) taken as complex (negative
     om, Nyquist included, on numpy's principal branch: phase wrap(-pi beta) / 2), zero on the om = 0 plane and at k = 0."""
-    nd = _check_nd(nd)
+    nd = check_nd(nd)
     if ds_t_factor != NHOURS:
         raise ValueError(f"ds_t_factor must be {NHOURS}, got {ds_t_factor}")
     ki = np.fft.fftfreq(nd)
@@ -51,7 +51,7 @@ def spectral_amplitudes(alpha, beta, nd, ds_t_factor=NHOURS):
 def class_abscissae(nd):
     """(x_spatial (nd/2+1, nd/2+1), x_temporal (13,)): log of R's wavenumber for every class, by R's own float64 expressions
     (R:68-72 and R:39-41), so every point of a class has exactly the x R gives it.  Class (0, 0) and m = 0 are -inf (never kept)."""
-    nd = _check_nd(nd)
+    nd = check_nd(nd)
     h = nd // 2 + 1
     ki = np.fft.fftfreq(nd)
     k = np.sqrt(ki[:h, None] ** 2 + ki[None, :h] ** 2)     # index |a| of fftfreq: +|a|/nd, or -1/2 at nd/2 (same square)
@@ -110,7 +110,7 @@ def slope_statistics(p_samples):
     shape = tuple(x.shape)
     if len(shape) != 4 or shape[1] != NHOURS or shape[2] != shape[3]:
         raise ValueError(f"p_samples must have shape (n, {NHOURS}, nd, nd), got {shape}")
-    nd = _check_nd(shape[2])
+    nd = check_nd(shape[2])
     n = shape[0]
     if not 1 <= n <= MAX_N:
         raise ValueError(f"p_samples: 1 .. {MAX_N} samples per call, got {n}")
@@ -157,7 +157,7 @@ def random_tiles(dataset, n):
     numpy RNG) and their raw mm/h tiles (n, 24, nd, nd) gathered from dataset.data on the device (:80-81)."""
     if dataset.indices is None:
         raise ValueError("dataset has no valid-tile indices (set_indices)")
-    nd = _check_nd(dataset.ndomain)
+    nd = check_nd(dataset.ndomain)
     dev = dataset.data.device
     ar = torch.arange(nd, device=dev)
     hours = torch.arange(NHOURS, device=dev)
@@ -174,7 +174,7 @@ def calibrate(dataset, n_calib=5000, n_repeat=10):
     from dataset.data on the device (:80-81), and (alpha, beta) estimated.  Returns the list of (alpha, beta)."""
     if dataset.indices is None:
         raise ValueError("dataset has no valid-tile indices (set_indices)")
-    _check_nd(dataset.ndomain)
+    check_nd(dataset.ndomain)
     return [estimate_slopes(random_tiles(dataset, n_calib)) for _ in range(n_repeat)]
 
 
@@ -202,7 +202,7 @@ def downscale_device(precip, alpha, beta, n_members=None, seed=None, uniforms=No
         raise ValueError(f"precip must have shape (nd, nd) or (n, nd, nd), got {shape}")
     if shape[-1] != shape[-2]:
         raise ValueError(f"precip fields must be square, got {shape}")
-    nd = _check_nd(shape[-1])
+    nd = check_nd(shape[-1])
     n = int(n_members)
     if not 1 <= n <= MAX_N:
         raise ValueError(f"1 .. {MAX_N} members per call, got {n}")
@@ -242,7 +242,7 @@ def downscale_spatiotemporal(precip, alpha, beta, ds_t_factor):
     pr = np.asarray(precip)
     if pr.ndim != 2 or pr.shape[0] != pr.shape[1]:
         raise ValueError(f"precip must have shape (nd, nd), got {pr.shape}")
-    _check_nd(pr.shape[0])
+    check_nd(pr.shape[0])
     require_gpu()
     u = np.random.rand(NHOURS, pr.shape[0], pr.shape[1])
     return downscale_device(pr, alpha, beta, uniforms=u[None]).cpu().numpy()[0]
@@ -264,7 +264,7 @@ def crps_for_day(real_precip, alpha, beta, n_members=1000, seed=None):
     shape = tuple(real_precip.shape)
     if len(shape) != 3 or shape[0] != NHOURS or shape[1] != shape[2]:
         raise ValueError(f"real_precip must have shape ({NHOURS}, nd, nd), got {shape}")
-    _check_nd(shape[1])
+    check_nd(shape[1])
     require_gpu()
     real = device_f32(real_precip, "real_precip")
     ens = downscale_device(real.sum(0), alpha, beta, n_members=n_members, seed=seed)
@@ -276,5 +276,5 @@ def _check_days(real_precip):
     shape = tuple(real_precip.shape)
     if len(shape) != 4 or shape[1] != NHOURS or shape[2] != shape[3]:
         raise ValueError(f"real_precip must have shape (n, {NHOURS}, nd, nd), got {shape}")
-    _check_nd(shape[2])
+    check_nd(shape[2])
     return real_precip

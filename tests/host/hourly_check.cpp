@@ -1,6 +1,6 @@
 // csrc/rdgan_hourly_host.h compiled WITHOUT HIP and with the address and undefined-behaviour sanitizers
-// (tests/test_hourly_host.py): one line "name value" per probe of rd_hourly_layout_ok, rd_pass_units, rd_aligned and rd_vec4_ok at
-// their edges; the test holds the expected values.
+// (tests/test_hourly_host.py): one line "name value" per probe of rd_hourly_layout_ok, rd_pass_units, rd_aligned, rd_vec4_ok and
+// rd_ensemble_shape_ok at their edges; the test holds the expected values.
 #include <stdio.h>
 #include "../../pr_disagg_radar_gan_amd/csrc/rdgan_hourly_host.h"
 
@@ -47,5 +47,40 @@ int main() {
   printf("vec4_off_by_4_bytes %d\n", rd_vec4_ok((const char*)buf + 4, 4 * 8, 24 * 32 + 4));
   printf("vec4_plane_not_of_4 %d\n", rd_vec4_ok(x, 5 * 7, 24 * 35));
   printf("vec4_stride_not_of_4 %d\n", rd_vec4_ok(x, 4 * 8, 24 * 32 + 2));
+  // an ensemble against observed days: the scores (8192 members, no extra vector) and the ranks (4095, the observation as one more),
+  // 2^20 days either; a plane of 4096 x 4096 leaves room for 2730 vectors of 24 planes
+  const long days = 1L << 20;
+  auto scores = [&](long m, long D, long ny, long nx, int shared) { return (int)rd_ensemble_shape_ok(m, D, ny, nx, shared, 8192, days, 0); };
+  auto ranks = [&](long m, long D, long ny, long nx, int shared) { return (int)rd_ensemble_shape_ok(m, D, ny, nx, shared, 4095, days, 1); };
+  printf("ens_scores_good %d\n", scores(5, 2, 3, 5, 0));
+  printf("ens_scores_most %d\n", scores(8192, days, 1, 1, 0));
+  printf("ens_scores_m0 %d\n", scores(0, 2, 3, 5, 0));
+  printf("ens_scores_m_over %d\n", scores(8193, 2, 3, 5, 0));
+  printf("ens_scores_days0 %d\n", scores(5, 0, 3, 5, 0));
+  printf("ens_scores_days_over %d\n", scores(5, days + 1, 3, 5, 0));
+  printf("ens_scores_ny0 %d\n", scores(5, 2, 0, 5, 0));
+  printf("ens_scores_nx0 %d\n", scores(5, 2, 3, 0, 0));
+  printf("ens_scores_plane_over %d\n", scores(5, 2, 4097, 4097, 0));
+  printf("ens_scores_side_over %d\n", scores(5, 2, (1L << 24) + 1, 1, 0));
+  printf("ens_scores_shared2 %d\n", scores(5, 2, 3, 5, 2));
+  printf("ens_scores_shared_negative %d\n", scores(5, 2, 3, 5, -1));
+  printf("ens_scores_fill_the_cap %d\n", scores(2730, 1, 4096, 4096, 0));
+  printf("ens_scores_one_over_the_cap %d\n", scores(2731, 1, 4096, 4096, 0));
+  printf("ens_ranks_good %d\n", ranks(5, 2, 3, 5, 0));
+  printf("ens_ranks_most %d\n", ranks(4095, days, 1, 1, 1));
+  printf("ens_ranks_m0 %d\n", ranks(0, 2, 3, 5, 0));
+  printf("ens_ranks_m_over %d\n", ranks(4096, 2, 3, 5, 0));
+  printf("ens_ranks_days0 %d\n", ranks(5, 0, 3, 5, 0));
+  printf("ens_ranks_days_over %d\n", ranks(5, days + 1, 3, 5, 0));
+  printf("ens_ranks_ny0 %d\n", ranks(5, 2, 0, 5, 0));
+  printf("ens_ranks_nx0 %d\n", ranks(5, 2, 3, 0, 0));
+  printf("ens_ranks_plane_over %d\n", ranks(5, 2, 4097, 4097, 0));
+  printf("ens_ranks_shared2 %d\n", ranks(5, 2, 3, 5, 2));
+  printf("ens_ranks_shared_negative %d\n", ranks(5, 2, 3, 5, -1));
+  printf("ens_ranks_vectors_over_the_cap %d\n", ranks(4095, 2, 4096, 4096, 0));
+  printf("ens_ranks_observation_fits %d\n", ranks(2729, 1, 4096, 4096, 0));
+  printf("ens_ranks_observation_is_one_too_many %d\n", ranks(2730, 1, 4096, 4096, 0));
+  printf("ens_ranks_per_day_members_over_the_cap %d\n", ranks(2048, days, 64, 64, 0));
+  printf("ens_ranks_shared_members_fit %d\n", ranks(2048, days, 64, 64, 1));
   return 0;
 }

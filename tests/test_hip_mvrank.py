@@ -186,3 +186,59 @@ def test_ranks_of_the_observation_end_to_end():
     assert np.array_equal(hourly.below["band_depth"][2], b) and np.array_equal(hourly.equal["band_depth"][2], e)
     assert np.array_equal(hourly.n_valid["average"][2], nv)
     assert set(MR.compare(res, hourly, n_bins=2)) == {"average", "band_depth"}
+
+
+def test_rank_experiment_equals_the_ranks_called_by_hand():
+    """the twin of test_hip_multivariate.test_experiment_equals_the_scores_called_by_hand, on its inputs: every method's members
+    built by hand by the seed rules, ranked by multivariate_ranks, equal the experiment's -- and, scored by energy_score, equal
+    multivariate_experiment's on the same arguments: the two experiments see the same members"""
+    MR = _mr()
+    from pr_disagg_radar_gan_amd import cascade, ensemble, multivariate as mv, rainfarm, weights as W
+    from pr_disagg_radar_gan_amd import gan_train_cwgangp_pixelnorm as T
+    from pr_disagg_radar_gan_amd.analog import AnalogLibrary
+    T.configure(ndomain=8)
+    gen = T.create_generator(seed=2)
+    rng = np.random.default_rng(21)
+    reals = (rng.gamma(0.3, 2.0, (3, 24, 8, 8)) + 1e-3).astype(np.float32)
+    clim = rain(rng, (40, 24, 8, 8))
+    days = rain(rng, (12, 24, 8, 8), dry=0.4)
+    library, model = AnalogLibrary(days), cascade.calibrate(days)
+    m, seed, slopes = 16, 5, (2.2, 1.3)
+    args = dict(slopes=slopes, library=library, n_members=m, seed=seed, cascade=model, cascade_patch=8)
+    res = MR.multivariate_rank_experiment(gen, reals, clim, kinds=MR.KINDS, pool=2, **args)
+    order = ["gan", "random", "rainfarm", "analog", "cascade"]
+    assert list(res) == order
+    rd = torch.from_numpy(reals).cuda()
+    by_hand = {name: [] for name in order if name != "random"}
+    for d in range(3):
+        dsum = torch.from_numpy(reals[d]).sum(0)
+        frac = ensemble.generate_ensemble_device(gen, (dsum / W.NORM_SCALE).numpy()[..., None], m, seed=seed + d)
+        by_hand["gan"].append(frac * (dsum / W.NORM_SCALE * W.NORM_SCALE).to(frac.device))
+        by_hand["rainfarm"].append(rainfarm.downscale_device(rd[d].sum(0), *slopes, n_members=m, seed=seed, first_member=d * m))
+        by_hand["analog"].append(library.generate(rd[d:d + 1].sum(1), m, k=10, seed=seed, weights="rank", first_query=d)[0])
+        by_hand["cascade"].append(model.generate(rd[d:d + 1].sum(1), m, seed=seed, first_query=d, patch=8)[0])
+
+    def same(got, want, at=slice(None)):
+        assert got.kinds == want.kinds and got.n_members == want.n_members
+        for kind in want.kinds:
+            for f in ("below", "equal", "n_valid"):
+                assert np.array_equal(getattr(got, f)[kind][at], getattr(want, f)[kind]), (kind, f)
+
+    for name, members in by_hand.items():
+        assert res[name].n_members == m
+        for d in range(3):
+            same(res[name], MR.multivariate_ranks(members[d], rd[d], kinds=MR.KINDS, pool=2), slice(d, d + 1))
+    same(res["random"], MR.multivariate_ranks(clim, reals, kinds=MR.KINDS, pool=2))
+    assert res["random"].n_members == 40 and all(res[name].below[k].shape == (3,) for name in order for k in MR.KINDS)
+    hourly = MR.multivariate_rank_experiment(gen, reals, clim, n_members=m, seed=seed, by_hour=True, kinds=("average", "band_depth"))
+    assert list(hourly) == ["gan", "random"]
+    for d in range(3):
+        same(hourly["gan"], MR.multivariate_ranks(by_hand["gan"][d], rd[d], kinds=("average", "band_depth"), by_hour=True), slice(d, d + 1))
+    same(hourly["random"], MR.multivariate_ranks(clim, reals, kinds=("average", "band_depth"), by_hour=True))
+    assert hourly["gan"].below["average"].shape == (3, 24)
+    scores = mv.multivariate_experiment(gen, reals, clim, **args)                          # the same members, scored
+    assert list(scores.es) == list(scores.vs) == order
+    for name, members in by_hand.items():
+        for d in range(3):
+            assert scores.es[name][d] == mv.energy_score(members[d], rd[d]).item(), (name, d)
+    assert np.array_equal(scores.es["random"], mv.energy_score(clim, reals).cpu().numpy())

@@ -2,7 +2,8 @@
 rd_hourly_layout_ok, rd_pass_units, rd_aligned) checked without a GPU: tests/host/hourly_check.cpp, a stand-alone program built
 by the host C++ compiler from that header alone with the address and undefined-behaviour sanitizers, prints each helper at its
 edges, and the output equals the table below, which restates the checks the entries held inline: x on 4 bytes, n >= 1,
-n day_elems <= 2^40, day_elems <= day_stride <= 2^50 / n; min(min(max(workspace_bytes, 0) / unit, n_units), max_units)."""
+n day_elems <= 2^40, day_elems <= day_stride <= 2^50 / n; min(min(max(workspace_bytes, 0) / unit, n_units), max_units).  So is
+rd_ensemble_shape_ok, the one admission of an ensemble against observed days behind the joint-field scores and the ranks."""
 import os
 import shutil
 import subprocess
@@ -26,6 +27,16 @@ WANT = {
     "aligned_all": 1, "aligned_one_on_4": 0, "aligned_4_is_enough": 1,
     # the 16-byte route: x on 16 bytes, the plane (or nx) and the day stride multiples of 4
     "vec4_aligned": 1, "vec4_off_by_4_bytes": 0, "vec4_plane_not_of_4": 0, "vec4_stride_not_of_4": 0,
+    # rd_ensemble_shape_ok as the joint-field scores call it (m <= 8192, D <= 2^20, the members within 2^40 values) and as the
+    # ranks do (m <= 4095, and m + 1 vectors within 2^40 too): the refusals of the two test_cabi_argument_checks tables for shape
+    # and limits; 5 members, 2 days of 3 x 5 unless the name says otherwise; 4096 x 4096 pixels hold 2730 vectors
+    "ens_scores_good": 1, "ens_scores_most": 1, "ens_scores_m0": 0, "ens_scores_m_over": 0, "ens_scores_days0": 0, "ens_scores_days_over": 0,
+    "ens_scores_ny0": 0, "ens_scores_nx0": 0, "ens_scores_plane_over": 0, "ens_scores_side_over": 0, "ens_scores_shared2": 0,
+    "ens_scores_shared_negative": 0, "ens_scores_fill_the_cap": 1, "ens_scores_one_over_the_cap": 0,
+    "ens_ranks_good": 1, "ens_ranks_most": 1, "ens_ranks_m0": 0, "ens_ranks_m_over": 0, "ens_ranks_days0": 0, "ens_ranks_days_over": 0,
+    "ens_ranks_ny0": 0, "ens_ranks_nx0": 0, "ens_ranks_plane_over": 0, "ens_ranks_shared2": 0, "ens_ranks_shared_negative": 0,
+    "ens_ranks_vectors_over_the_cap": 0, "ens_ranks_observation_fits": 1, "ens_ranks_observation_is_one_too_many": 0,
+    "ens_ranks_per_day_members_over_the_cap": 0, "ens_ranks_shared_members_fit": 1,
 }
 
 
